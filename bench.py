@@ -12,7 +12,8 @@ SURVEY.md 8d config D states it -- nothing about a query is on the device before
   -> batched RANSAC(3000, adaptive) + ICP(20) registration of all B x 20 (query, candidate) jobs in one
      launch sequence (gloc_reg_batch_multi) -> lowest-rank successful candidate -> query scan released.
 5 of every 20 consecutive places carry a scan of a DIFFERENT world (true negatives, SURVEY cfg C).
-The K timed steps are repeated `--reps` (5) times; `value` is the median repetition.
+The K timed steps run once (`--reps R`: R repetitions of them, `value` = the median repetition).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 N = 1  BASELINE.json configs[3]: KITTI-00-sized database, 4541 places x 4096-D, ~123k-point scans;
        20 steps x 25 queries = the 500-query stream.
@@ -405,6 +406,25 @@ def emit(out, stream=None, detail_path=None):
     return final
 
 
+def dump_outputs(out_dir, q_ids, cand, d2, tables, sels):
+    """What the last timed step handed its caller, one .npy per array (float32 as computed; ids and counts as float64,
+    exact): the step's query stream ids, the top-k place ids and squared distances, every candidate's registration
+    (pose, rmse, RANSAC inliers, ok) and the selected candidate's retrieval rank (-1: none).  A few KB per step."""
+    os.makedirs(out_dir, exist_ok=True)
+    tables = np.asarray(tables, np.float32)
+    arrays = {"query_id": np.asarray(q_ids, np.float64),
+              "knn_index": np.asarray(cand, np.int64).astype(np.float64),
+              "knn_d2": np.asarray(d2, np.float32),
+              "reg_T": np.ascontiguousarray(tables[..., :16].reshape(tables.shape[:-1] + (4, 4))),
+              "reg_rmse": np.ascontiguousarray(tables[..., 16]),
+              "reg_inliers": tables[..., 17].astype(np.float64),
+              "reg_ok": tables[..., 18].astype(np.float64),
+              "selected_rank": np.asarray(sels, np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without torchrun's environment: start the N ranks as a CHILD process tree
     (nothing here has touched the GPU, torch is not imported: no exec of a GPU-initialised process), pass its
@@ -426,7 +446,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5, help="timed repetitions of the K steps; value = median")
+    ap.add_argument("--reps", type=int, default=1, help="timed repetitions of the K steps; value = median (default 1: --steps "
+                                                         "is the number of timed steps)")
     ap.add_argument("--batch", type=int, default=25, help="queries per step per GPU (registered in one batch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--places", type=int, default=N_PLACES_1GPU,
@@ -474,6 +495,9 @@ def main():
                     help="override gloc_reg_params.ransac_confidence (0: score all 3000 hypotheses)")
     ap.add_argument("--no-target-index", action="store_true",
                     help="leave the database scans in curve order (A/B of gloc_scan_store_build_target_index)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (retrieval, registration, selection) "
+                         "as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--min-success", type=float, default=0.9,
                     help="the run fails (exit code 3) when the stream's registration success rate is below this (0.95 in rounds 1-5, "
                          "whose different-world places were rigid copies of views at unrelated poses; a different world cast from the "
@@ -767,6 +791,7 @@ def main():
                                     gather=capi_knn.all_gather_tables if capi_knn is not None else None)
     qreg = sharded.QueryParallelRegistrar(rank, world, None, comm_device=comm_dev)
     stage = {"prep_wait": 0.0, "h2d_index": 0.0, "knn": 0.0, "register": 0.0}
+    last_d2 = [None]            # the latest step's top-k distances (device tensor, kept for --dump-outputs)
     work_pairs = []
 
     # ---- one step -----------------------------------------------------------------------------
@@ -820,6 +845,7 @@ def main():
         t1 = time.time()
         torch.cuda.current_stream().synchronize()   # the descriptors' H2D
         idx, d2 = knn.search(qd, TOP_K)
+        last_d2[0] = d2
         cand = idx.cpu().numpy()                          # [queries of the step, 20] global place ids, retrieval order
         t2 = time.time()
         a, b = my_slice(i, Bq)
@@ -892,6 +918,7 @@ def main():
             t_b = time.time()
             torch.cuda.current_stream().synchronize()       # the descriptors' H2D
             idx, d2 = knn.search(qd, TOP_K)
+            last_d2[0] = d2
             cand = idx.cpu().numpy()
             t_c = time.time()
             mine = cand[rank * len(ids):(rank + 1) * len(ids)]          # this rank's queries of the step
@@ -947,6 +974,13 @@ def main():
         rep_s.append(elapsed)
         sels, cands_last, tabs_last = rsel, rc_, rt_
     elapsed = float(np.median(rep_s))
+    if args.dump_outputs and rank == 0 and tabs_last:
+        # the last timed step's results, before the legs below run other steps
+        n_last = tabs_last[-1].shape[0]
+        q_last = (n_steps - 1) * per_step
+        names = dump_outputs(args.dump_outputs, np.arange(q_last, q_last + cands_last[-1].shape[0]), cands_last[-1],
+                             last_d2[0].cpu().numpy(), tabs_last[-1], sels[-n_last:])
+        log(f"outputs of the last timed step: {', '.join(names)} in {args.dump_outputs}")
 
     # ---- accuracy of the timed stream (the last repetition's results; every repetition computes the same) ----
     all_cand = np.concatenate(cands_last) if cands_last else np.zeros((0, TOP_K), np.int64)

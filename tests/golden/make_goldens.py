@@ -65,6 +65,34 @@ def crc(a):
     return np.uint64(int(np.ascontiguousarray(a, np.float32).view(np.uint32).sum(dtype=np.uint64)))
 
 
+def knn_live_inputs():
+    """tests/test_oracle_knn.py::test_oracle_matches_reference_live: 16 x 2000 x 128, top-20."""
+    return synth.descriptors_iid(91, 0, 2000, 128), synth.descriptors_iid(92, 0, 16, 128), 20
+
+
+def reg_refnn_inputs():
+    """tests/test_oracle_reg.py::test_nn3_full_size_matches_reference_golden: the full-size pair thinned, registered
+    by the restatement with the reference's kd-tree as its 1-NN search."""
+    src, tgt, _ = nn3_fullsize_inputs()
+    return np.ascontiguousarray(src[::8]), np.ascontiguousarray(tgt[::4])
+
+
+def make_knn_live():
+    db, q, k = knn_live_inputs()
+    idx, d2 = oracle.ref_knn_search(db, q, k)
+    np.savez_compressed(os.path.join(HERE, "knn_live_d128_q16_iid.npz"), idx=idx, d2_bits=d2.view(np.uint32),
+                        q_crc=crc(q), db_crc=crc(db))
+    print("knn_live_d128_q16_iid", idx.shape)
+
+
+def make_reg_refnn():
+    s, t = reg_refnn_inputs()
+    b = oracle.reg_one(s, t, ransac_iters=200, icp_iters=5, ref_nn=True)
+    np.savez_compressed(os.path.join(HERE, "reg_refnn_fullsize.npz"), T=b["T"], inliers=np.uint32(b["inliers"]),
+                        src_crc=crc(s), tgt_crc=crc(t))
+    print("reg_refnn_fullsize", s.shape, t.shape, "inliers", b["inliers"])
+
+
 def main():
     oracle.build(ref=True)
     for case in KNN_CASES:
@@ -90,6 +118,8 @@ def main():
     np.savez_compressed(os.path.join(HERE, "nn3_fullsize.npz"), idx=idx, d2_bits=d2.view(np.uint32),
                         src_crc=crc(src), tgt_crc=crc(tgt), T=T)
     print("nn3_fullsize", src.shape, tgt.shape, os.path.getsize(os.path.join(HERE, "nn3_fullsize.npz")))
+    make_knn_live()
+    make_reg_refnn()
 
 
 if __name__ == "__main__":

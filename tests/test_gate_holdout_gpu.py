@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 def test_suggested_final_step_on_unseen_worlds():
     import gate_holdout as gh
-    views = gh.build_views("/tmp/gloc3d_gate_holdout_views.npz", workers=0)     # (no fork: the GPU may be in use already)
+    views = gh.build_views(None, workers=0)     # (no cache outside the checkout; no fork: the GPU may be in use already)
     res = gh.run(views)
     off, at = res["thresholds"]["off"], res["thresholds"]["0.03"]
     assert res["queries"] == 8 and res["candidates_per_query"] == 20

@@ -1,8 +1,10 @@
 """CPU: the kNN oracle against the reference's golden vectors and (where built) the reference itself."""
+import os
+
 import numpy as np
 import pytest
 
-from util import KNN_CASES, bits, load_knn_case
+from util import GOLDEN, KNN_CASES, bits, load_knn_case, make_goldens
 
 
 @pytest.mark.parametrize("case", KNN_CASES)
@@ -14,14 +16,16 @@ def test_oracle_matches_reference_goldens(oracle_mod, case):
 
 
 def test_oracle_matches_reference_live(oracle_mod):
-    if not oracle_mod.have_ref():
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    from gloc3d_amd import synth
-    db = synth.descriptors_iid(91, 0, 2000, 128)
-    q = synth.descriptors_iid(92, 0, 16, 128)
-    a = oracle_mod.knn_search(db, q, 20)
-    b = oracle_mod.ref_knn_search(db, q, 20)
-    assert (a[0] == b[0]).all() and (bits(a[1]) == bits(b[1])).all()
+    """Against the reference's output stored in tests/golden (knn_live_d128_q16_iid.npz) and, where oracle/_ref is
+    built, against the reference library itself."""
+    db, q, k = make_goldens.knn_live_inputs()
+    g = np.load(os.path.join(GOLDEN, "knn_live_d128_q16_iid.npz"))
+    assert make_goldens.crc(q) == g["q_crc"] and make_goldens.crc(db) == g["db_crc"]
+    a = oracle_mod.knn_search(db, q, k)
+    assert (a[0] == g["idx"]).all() and (bits(a[1]) == g["d2_bits"]).all()
+    if oracle_mod.have_ref():
+        b = oracle_mod.ref_knn_search(db, q, k)
+        assert (a[0] == b[0]).all() and (bits(a[1]) == bits(b[1])).all()
 
 
 def test_l2_eval_order_and_tail(oracle_mod):

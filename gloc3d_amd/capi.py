@@ -49,6 +49,12 @@ class RegParams(C.Structure):
                 ("ransac_confidence", C.c_float), ("max_rmse", C.c_float), ("max_final_step", C.c_float)]
 
 
+class NdtParams(C.Structure):
+    _fields_ = [("source_leaf", C.c_float), ("resolution", C.c_float), ("step_size", C.c_float), ("trans_eps", C.c_float),
+                ("max_iters", C.c_uint32), ("outlier_ratio", C.c_float), ("min_points_per_cell", C.c_uint32),
+                ("min_covar_eigvalue_mult", C.c_float)]
+
+
 class BevParams(C.Structure):
     _fields_ = [("resolution", C.c_float), ("max_range", C.c_float), ("out_width", C.c_uint32),
                 ("out_height", C.c_uint32), ("format", C.c_uint32), ("pad_bgr", C.c_uint8 * 3),
@@ -172,6 +178,11 @@ _PROTOS = [
     ("gloc_reg_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
     ("gloc_reg_profile_reset", _i, [_vp]),
     ("gloc_reg_nn_stats", _i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    ("gloc_ndt_default_params", None, [C.POINTER(NdtParams)]),
+    ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
+    ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
+    ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
+    ("gloc_scan_store_add_approx_voxel", _i, [_vp, _u32, C.c_float, C.POINTER(_u32)]),
     ("gloc_vlad_create", _i, [_i, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)]),
     ("gloc_vlad_set_gating", _i, [_vp, _vp, _vp, _vp]),
     ("gloc_vlad_destroy", _i, [_vp]),
@@ -445,6 +456,15 @@ def default_reg_params(**over):
     return p
 
 
+def default_ndt_params(**over):
+    """gloc_ndt_params with the reference's constants (ndt_match_3d) and PCL's defaults for the rest, then `over`."""
+    p = NdtParams()
+    lib().gloc_ndt_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
 class ScanStore:
     """Resident scans + their search index, shared by any number of Registrars."""
 
@@ -564,6 +584,12 @@ class ScanStore:
         n = C.c_size_t()
         check(lib().gloc_scan_store_points(self._h, int(scan_id), C.byref(n)))
         return n.value
+
+    def add_approx_voxel(self, base_id, leaf=0.2):
+        """A new scan: the approximate voxel filter of scan base_id (NDT's source filter).  Returns its id."""
+        sid = C.c_uint32()
+        check(lib().gloc_scan_store_add_approx_voxel(self._h, int(base_id), float(leaf), C.byref(sid)))
+        return sid.value
 
     def download(self, scan_id):
         n = self.points(scan_id)
@@ -702,6 +728,41 @@ class Registrar:
                                        None if it is None else _np_ptr(it), C.byref(prm),
                                        _np_ptr(T), _np_ptr(rmse), _np_ptr(inl), _np_ptr(ok)))
         return dict(T=T, rmse=rmse, inliers=inl, ok=ok.astype(bool))
+
+    def ndt_batch(self, src_id, tgt_ids, init_T=None, params=None):
+        """NDT of scan src_id against each of tgt_ids (gloc_reg_ndt_batch_ids): returns T [n, 4, 4] float32, trans
+        probability [n] float64, iterations [n], converged [n] bool."""
+        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
+        n = ids.shape[0]
+        prm = params or default_ndt_params()
+        it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
+        T = np.empty((n, 4, 4), np.float32)
+        prob, iters, conv = np.empty(n, np.float64), np.empty(n, np.uint32), np.empty(n, np.int32)
+        check(lib().gloc_reg_ndt_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
+                                           C.byref(prm), _np_ptr(T), _np_ptr(prob), _np_ptr(iters), _np_ptr(conv)))
+        return T, prob, iters, conv.astype(bool)
+
+    def ndt_derivatives(self, src_id, tgt_id, p6, params=None):
+        """score, gradient [6], Hessian [6, 6] of the filtered source against the target's cells at p6."""
+        p = np.ascontiguousarray(p6, np.float64).reshape(6)
+        prm = params or default_ndt_params()
+        s, g, H = C.c_double(), np.empty(6, np.float64), np.empty((6, 6), np.float64)
+        check(lib().gloc_reg_ndt_derivatives(self._h, int(src_id), int(tgt_id), _np_ptr(p), C.byref(prm), C.byref(s),
+                                             _np_ptr(g), _np_ptr(H)))
+        return s.value, g, H
+
+    def ndt_cells(self, scan_id, params=None):
+        """The valid NDT cells of a scan, sorted by key: dict(key3 [m, 3] int32, count [m], mean [m, 3], icov [m, 3, 3])."""
+        prm = params or default_ndt_params()
+        m = C.c_size_t()
+        check(lib().gloc_reg_ndt_cells(self._h, int(scan_id), C.byref(prm), 0, None, None, None, None, C.byref(m)))
+        k = m.value
+        key, cnt = np.empty((k, 3), np.int32), np.empty(k, np.uint32)
+        mean, icov = np.empty((k, 3), np.float64), np.empty((k, 3, 3), np.float64)
+        if k:
+            check(lib().gloc_reg_ndt_cells(self._h, int(scan_id), C.byref(prm), k, _np_ptr(key), _np_ptr(cnt), _np_ptr(mean),
+                                           _np_ptr(icov), C.byref(m)))
+        return dict(key3=key, count=cnt, mean=mean, icov=icov)
 
     def first_success_multi(self, q_ids, cand_ids, init_T=None, params=None):
         """The reference's stop-at-the-first-success loop for several queries: returns rank [Q] (-1: none),

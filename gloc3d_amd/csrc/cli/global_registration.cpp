@@ -7,11 +7,14 @@
 // "err_pos, err_rot" (:1417), then the success rate (<1 m and <5 deg) and mean/std (:1432-1442).
 // The reference composes a 2-D SURF match with ground alignment and optionally refines with PCL ICP
 // (:1342-1398, use_icp=false :1222); here the pair goes through the 3-D RANSAC-SVD + ICP hot path.
+// GLOC_REFINE=ndt: the RANSAC stage alone gives the guess and NDT refines it (gloc_reg_ndt_batch_ids), the slot
+// ndt_match_3d takes behind the reference's use_icp branch (:1388-1398); unset or "icp": RANSAC + ICP as before.
 // No GUI windows are opened.  Scans: the reference reads NCLT raw records unconditionally (:1239,1304) although
 // its comments say KITTI (:1224-1226); here the optional third argument (or GLOC_SCAN_FORMAT) names the format,
 // and "auto" (default) decides by CONTENT -- never by file size: an NCLT file with an even number of 8-byte
 // records is a multiple of 16 bytes as well (host/gloc_io.hpp: looks_like_kitti).
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <memory>
 
@@ -42,6 +45,15 @@ int main(int argc, char* argv[]) {
   }
   gloc_reg_params prm;
   gloc_reg_default_params(&prm);
+  const char* refine = getenv("GLOC_REFINE");
+  const bool ndt = refine && std::strcmp(refine, "ndt") == 0;
+  if (refine && *refine && !ndt && std::strcmp(refine, "icp") != 0) {
+    std::fprintf(stderr, "GLOC_REFINE must be icp or ndt, not %s\n", refine);
+    return 2;
+  }
+  gloc_ndt_params nprm;
+  gloc_ndt_default_params(&nprm);
+  if (ndt) prm.icp_iters = 0;  // the 3-D RANSAC estimate is NDT's guess
   const size_t ndb = vs.db_files.size();
   int all_tests = 0, succeed = 0;
   std::vector<double> rot_err, pos_err;
@@ -68,6 +80,14 @@ int main(int argc, char* argv[]) {
                            nullptr) != GLOC_OK) {
       std::fprintf(stderr, "fatal: %s\n", gloc_last_error());
       return 1;
+    }
+    if (ndt) {
+      const std::vector<float> guess(T);
+      if (gloc_reg_ndt_batch_ids(reg, qid, ids.data(), ids.size(), guess.data(), &nprm, T.data(), nullptr, nullptr,
+                                 nullptr) != GLOC_OK) {
+        std::fprintf(stderr, "fatal: %s\n", gloc_last_error());
+        return 1;
+      }
     }
     for (size_t c = 0; c < ids.size(); ++c) {
       const size_t j = vs.pos_idx[i][c];

@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include <future>
 
+#include "ndt.hpp"
 #include "nn_compact.hpp"
 #include "reg_kernels.hpp"
 #include "scan_store.hpp"
@@ -99,6 +100,7 @@ struct gloc_reg {
   size_t last_ld = 0;      // shape of the last batch (gloc_reg_debug_corr)
   uint32_t last_jobs = 0;
   Profiler prof;
+  gloc::ndt::Ws* ndt = nullptr;  // NDT workspace (ndt.hip), made on first use
 };
 
 namespace {
@@ -904,6 +906,7 @@ int gloc_reg_destroy(gloc_reg* h) {
   h->store = nullptr;
   if (h->own_store) (void)gloc_scan_store_destroy(h->own_store);
   h->prof.destroy();
+  gloc::ndt::ws_free(h->ndt);
   for (DevBuf* b : {&h->jobs, &h->states, &h->corr, &h->d2, &h->pairs, &h->Rt, &h->valid, &h->inliers,
                     &h->partials, &h->export_idx, &h->export_d2, &h->counters, &h->trace, &h->split_zero, &h->split_ff, &h->alive, &h->heavy_buf})
     b->release();
@@ -1481,6 +1484,40 @@ int gloc_reg_debug_trace(gloc_reg* h, int enable, uint32_t* out, size_t cap_wave
     GLOC_HIP(hipStreamSynchronize(h->stream));
   }
   return GLOC_OK;
+}
+
+int gloc_reg_ndt_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                           const gloc_ndt_params* prm, float* out_T, double* out_prob, uint32_t* out_iters,
+                           int* out_converged) {
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  const gloc::ndt::Ctx x{h->store, h->stream, &h->prof, &h->ndt};
+  return gloc::ndt::run(x, src_scan_id, tgt_scan_ids, n, init_T, nullptr, prm, out_T, out_prob, out_iters, out_converged,
+                        nullptr);
+}
+
+int gloc_reg_ndt_derivatives(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const double p6[6],
+                             const gloc_ndt_params* prm, double* out_score, double* out_grad6, double* out_hess36) {
+  GLOC_REQUIRE(h && p6 && out_score && out_grad6 && out_hess36, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  const gloc::ndt::Ctx x{h->store, h->stream, &h->prof, &h->ndt};
+  double s[43];
+  GLOC_TRY(gloc::ndt::run(x, src_scan_id, &tgt_scan_id, 1, nullptr, p6, prm, nullptr, nullptr, nullptr, nullptr, s));
+  *out_score = s[0];
+  for (int i = 0; i < 6; ++i) out_grad6[i] = s[1 + i];
+  for (int i = 0; i < 36; ++i) out_hess36[i] = s[7 + i];
+  return GLOC_OK;
+}
+
+int gloc_reg_ndt_cells(gloc_reg* h, uint32_t scan_id, const gloc_ndt_params* prm, size_t capacity, int32_t* out_key3,
+                       uint32_t* out_count, double* out_mean3, double* out_icov9, size_t* n_cells) {
+  GLOC_REQUIRE(h && n_cells, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  const gloc::ndt::Ctx x{h->store, h->stream, &h->prof, &h->ndt};
+  return gloc::ndt::cells(x, scan_id, prm, capacity, out_key3, out_count, out_mean3, out_icov9, n_cells);
 }
 
 int gloc_reg_profile(gloc_reg* h, const char* kernel, double* total_ms, uint64_t* launches) {

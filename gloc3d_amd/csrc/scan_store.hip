@@ -944,6 +944,8 @@ int add_common(gloc_scan_store* st, const float* pts, size_t n, size_t stride, b
 
 }  // namespace
 
+int gloc::reg::store_insert_scan(gloc_scan_store* st, const DevScan& s, uint32_t* id) { return store_insert(st, s, id); }
+
 extern "C" {
 
 int gloc_scan_store_create(int device, gloc_scan_store** out) {

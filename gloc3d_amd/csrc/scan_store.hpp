@@ -67,6 +67,8 @@ int store_make_scan(gloc_scan_store* st, const float* pts, size_t n, size_t stri
 int store_make_scans(gloc_scan_store* st, size_t count, const float* const* pts, const size_t* n, size_t stride,
                      bool device_src, DevScan* out);
 void store_free_scan(gloc_scan_store* st, DevScan& s, bool cache_block);
+// Give a scan made by store_make_scan an id (a recycled one first).  Caller holds store->mu.
+int store_insert_scan(gloc_scan_store* st, const DevScan& s, uint32_t* id);
 // Re-sort an indexed scan into kd order (target index) and rebuild everything that depends on the order.
 // Caller holds store->mu; nothing may be reading the scan; returns after the work has completed.
 int store_build_target_index(gloc_scan_store* st, DevScan& s);

@@ -415,6 +415,50 @@ int gloc_reg_profile_reset(gloc_reg* h);
  * 1-NN launches since the last gloc_reg_profile_reset. */
 int gloc_reg_nn_stats(gloc_reg* h, uint64_t* pairs_evaluated, uint64_t* launches);
 
+/* ---- NDT scan registration ---------------------------------------------------------------------------- *
+ * Replaces ndt_match_3d (registration/global_registration.cpp:250-330): the source thinned by an approximate voxel grid
+ * (pcl::ApproximateVoxelGrid, 0.2 m), the unfiltered target modelled by normal distributions in 0.5 m cells
+ * (pcl::VoxelGridCovariance), Newton iterations with a More-Thuente line search from the caller's guess
+ * (pcl::NormalDistributionsTransform: step 0.1, epsilon 0.01, 35 iterations).  The executable contract is the float64
+ * restatement tests/ndt_ref.py; parity with PCL itself is unpinned.  A refinement behind a 3-D
+ * RANSAC guess, in the slot the reference's use_icp branch gives ICP or NDT (:1388-1398). */
+typedef struct gloc_ndt_params {
+  float source_leaf;             /* 0.2 m (:256); <= 0: no filter (the finite points of the source) */
+  float resolution;              /* 0.5 m cells (:271) */
+  float step_size;               /* 0.1: the line search's largest step (:268) */
+  float trans_eps;               /* 0.01: stop once a step is shorter (:266); the line search's shortest step is half of it */
+  uint32_t max_iters;            /* 35 (:274) */
+  float outlier_ratio;           /* 0.55 [upstream default] */
+  uint32_t min_points_per_cell;  /* 6 [upstream default] */
+  float min_covar_eigvalue_mult; /* 0.01 [upstream default]: eigenvalues below this x the largest are raised to it */
+} gloc_ndt_params;
+
+void gloc_ndt_default_params(gloc_ndt_params* p);
+
+/* Refine n candidates: the source scan against each target scan (ids of the handle's store), from init_T (n x 16
+ * row-major floats, source -> target, NULL = identity).  The source is filtered once per call.  Outputs per candidate
+ * (any may be NULL except out_T): the pose (n x 16), trans_probability = score / filtered source size, the iteration
+ * count, and converged = the loop stopped because a step was shorter than trans_eps (or was zero) -- stricter than
+ * PCL's hasConverged(), which is also true when the iteration cap stops it.  A target with no cell in reach of the
+ * source returns its guess after 0 iterations with probability 0.  Every candidate's result is independent of the
+ * batch it is in, bit for bit.  GLOC_ERR_INVALID: null arguments, an unknown id, resolution <= 0, max_iters = 0, an empty
+ * filtered source; GLOC_ERR_STATE: a batch in flight on the handle. */
+int gloc_reg_ndt_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                           const gloc_ndt_params* prm, float* out_T, double* out_prob, uint32_t* out_iters,
+                           int* out_converged);
+/* One evaluation at p6 = [tx, ty, tz, rx, ry, rz] (T = Trans Rx Ry Rz) of the score, gradient and Hessian (6 x 6 row-major)
+ * of the filtered source against the target's cells (tests and callers that drive the optimiser themselves). */
+int gloc_reg_ndt_derivatives(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const double p6[6],
+                             const gloc_ndt_params* prm, double* out_score, double* out_grad6, double* out_hess36);
+/* The valid cells of a scan at prm->resolution, sorted by (kx, ky, kz): integer cell index, point count, mean, inverse
+ * covariance (3 x 3 row-major).  n_cells: how many there are (the arrays may be NULL to ask). */
+int gloc_reg_ndt_cells(gloc_reg* h, uint32_t scan_id, const gloc_ndt_params* prm, size_t capacity, int32_t* out_key3,
+                       uint32_t* out_count, double* out_mean3, double* out_icov9, size_t* n_cells);
+/* A new resident scan: the approximate voxel filter (pcl::ApproximateVoxelGrid: 512 hash slots, a slot taken by another
+ * cell is flushed first) of scan base_id at `leaf` -- the NDT source filter on its own, e.g. to thin a source before ICP.
+ * Rows come out in (slot, first point) order. */
+int gloc_scan_store_add_approx_voxel(gloc_scan_store* st, uint32_t base_id, float leaf, uint32_t* new_id);
+
 /* ============================ NetVLAD-FC pooling head ("next" row N2) ===================== *
  * Replaces NetVLAD.forward of the reference (model/netvlad_fc.py:73-109, built without gating at
  * main.py:594) -- the tail of the TorchScript module RpyPCLoopDetector::get_place_feature runs

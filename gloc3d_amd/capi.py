@@ -72,6 +72,19 @@ class BevInfo(C.Structure):
 
 
 BEV_U8_HWC3, BEV_F32_CHW = 0, 1
+
+
+class PillarParams(C.Structure):
+    _fields_ = [("xbound", C.c_float * 3), ("ybound", C.c_float * 3), ("zbound", C.c_float * 3),
+                ("num_points", C.c_uint32), ("mask_mode", C.c_uint32)]
+
+    def grid(self):
+        """(gx, gy, gz) as the library and voxel.py:40-45 compute them."""
+        return tuple(int((float(b[1]) - float(b[0])) / float(b[2])) for b in (self.xbound, self.ybound, self.zbound))
+
+
+PILLAR_MASK_INPUT, PILLAR_MASK_VALID = 0, 1   # include/gloc3d.h GLOC_PILLAR_MASK_*
+PILLAR_FEATURES = 64
 GROUND_OPT_KNN_EXHAUSTIVE = 1
 
 
@@ -202,6 +215,19 @@ _PROTOS = [
     ("gloc_bev_set_profile", _i, [_vp, _i]),
     ("gloc_bev_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
     ("gloc_bev_device_flags", _i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)]),
+    ("gloc_pillar_default_params", _i, [C.POINTER(PillarParams)]),
+    ("gloc_pillar_create", _i, [_i, C.POINTER(_vp)]),
+    ("gloc_pillar_destroy", _i, [_vp]),
+    ("gloc_pillar_set_stream", _i, [_vp, _vp]),
+    ("gloc_pillar_synchronize", _i, [_vp]),
+    ("gloc_pillar_set_pointnet", _i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float]),
+    ("gloc_pillar_inputs", _i, [_vp, _vp, _vp, _sz, _sz, C.POINTER(PillarParams), _vp]),
+    ("gloc_pillar_inputs_device", _i, [_vp, _vp, _vp, _sz, _sz, C.POINTER(PillarParams), _vp]),
+    ("gloc_pillar_canvas", _i, [_vp, _vp, _vp, _sz, _sz, C.POINTER(PillarParams), _vp]),
+    ("gloc_pillar_canvas_device", _i, [_vp, _vp, _vp, _sz, _sz, C.POINTER(PillarParams), _vp]),
+    ("gloc_pillar_set_profile", _i, [_vp, _i]),
+    ("gloc_pillar_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
+    ("gloc_pillar_profile_reset", _i, [_vp]),
     ("gloc_coarse_default_params", _i, [_vp]),
     ("gloc_coarse_create", _i, [_i, C.POINTER(_vp)]),
     ("gloc_coarse_destroy", _i, [_vp]),
@@ -999,6 +1025,111 @@ class BevProjector:
         ms, n = C.c_double(), C.c_uint64()
         check(lib().gloc_bev_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+def default_pillar_params(**over):
+    """gloc_pillar_params with the reference's grid and P (gen_libtorch_pointpillar.py:25-34), then `over`
+    (xbound / ybound / zbound as [lo, hi, res])."""
+    p = PillarParams()
+    check(lib().gloc_pillar_default_params(C.byref(p)))
+    for k, v in over.items():
+        if k in ("xbound", "ybound", "zbound"):
+            for i in range(3):
+                getattr(p, k)[i] = v[i]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _scan_batch(scans):
+    """A scan [n, >=4] or a list of them -> (points [sum n, stride] float32, offsets [B + 1] uint64)."""
+    if isinstance(scans, np.ndarray) and scans.ndim == 2:
+        scans = [scans]
+    arrs = [np.asarray(s, np.float32).reshape(-1, np.shape(s)[-1] if np.ndim(s) == 2 else 4) for s in scans]
+    stride = max([a.shape[1] for a in arrs] + [4])
+    assert all(a.shape[1] == stride for a in arrs if a.shape[0]), "scans of one batch share their row width"
+    off = np.zeros(len(arrs) + 1, np.uint64)
+    off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    pts = np.ascontiguousarray(np.concatenate([a.reshape(-1, stride) for a in arrs]) if arrs else np.zeros((0, stride)),
+                               np.float32)
+    return pts, off
+
+
+class PillarEncoder:
+    """PointPillar scan front end: points_to_voxels + the traced model's [P, 16] input (model/voxel.py:23-133,
+    gen_libtorch_pointpillar.py:47-62) and the PointNet + scatter-mean canvas [64, gx * gy * gz]
+    (model/s2s_merged.py:113-127,204-218)."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        self.device = device
+        check(lib().gloc_pillar_create(device, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().gloc_pillar_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_pointnet(self, w, bn_weight, bn_bias, bn_mean, bn_var, eps=1e-5):
+        """w [64, 14] (or the Conv1d's [64, 14, 1]); BatchNorm1d weight, bias, running mean, running var [64]."""
+        a = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in (w, bn_weight, bn_bias, bn_mean, bn_var)]
+        assert a[0].size == PILLAR_FEATURES * 14 and all(x.size == PILLAR_FEATURES for x in a[1:])
+        check(lib().gloc_pillar_set_pointnet(self._h, *[_np_ptr(x) for x in a], float(eps)))
+
+    def inputs(self, scans, params=None):
+        """A scan [n, 4+] or a list of them -> [B, P, 16] float32."""
+        p = params or default_pillar_params()
+        pts, off = _scan_batch(scans)
+        out = np.empty((len(off) - 1, p.num_points, 16), np.float32)
+        check(lib().gloc_pillar_inputs(self._h, _np_ptr(pts), _np_ptr(off), len(off) - 1, pts.shape[1], C.byref(p),
+                                       _np_ptr(out)))
+        return out
+
+    def canvas(self, scans, params=None):
+        """A scan [n, 4+] or a list of them -> [B, 64, gx * gy * gz] float32."""
+        p = params or default_pillar_params()
+        pts, off = _scan_batch(scans)
+        gx, gy, gz = p.grid()
+        out = np.empty((len(off) - 1, PILLAR_FEATURES, gx * gy * gz), np.float32)
+        check(lib().gloc_pillar_canvas(self._h, _np_ptr(pts), _np_ptr(off), len(off) - 1, pts.shape[1], C.byref(p),
+                                       _np_ptr(out)))
+        return out
+
+    def inputs_device(self, pts_ptr, offsets, stride_floats, out_ptr, params=None):
+        """Device buffers on the handle's stream: scans back to back at pts_ptr, host `offsets` (B + 1, in points)."""
+        p = params or default_pillar_params()
+        off = np.ascontiguousarray(offsets, np.uint64)
+        check(lib().gloc_pillar_inputs_device(self._h, C.c_void_p(pts_ptr), _np_ptr(off), off.shape[0] - 1,
+                                              stride_floats, C.byref(p), C.c_void_p(out_ptr)))
+
+    def canvas_device(self, pts_ptr, offsets, stride_floats, out_ptr, params=None):
+        p = params or default_pillar_params()
+        off = np.ascontiguousarray(offsets, np.uint64)
+        check(lib().gloc_pillar_canvas_device(self._h, C.c_void_p(pts_ptr), _np_ptr(off), off.shape[0] - 1,
+                                              stride_floats, C.byref(p), C.c_void_p(out_ptr)))
+
+    def set_stream(self, stream_ptr):
+        check(lib().gloc_pillar_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    def synchronize(self):
+        check(lib().gloc_pillar_synchronize(self._h))
+
+    def set_profile(self, on=True):
+        check(lib().gloc_pillar_set_profile(self._h, 1 if on else 0))
+
+    def profile(self, kernel):
+        ms, n = C.c_double(), C.c_uint64()
+        check(lib().gloc_pillar_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def profile_reset(self):
+        check(lib().gloc_pillar_profile_reset(self._h))
 
 
 def default_coarse_params(**over):

@@ -1,0 +1,325 @@
+// pillar.hip -- C ABI of the PointPillar scan front end (include/gloc3d.h, "PointPillar-NetVLAD scan descriptor").
+// Replaces points_to_voxels + the input packing of the traced scan model (model/voxel.py:23-133,
+// s2s_libtorch/gen_libtorch_pointpillar.py:47-62; the C++ demo's per-point loop, i2i_feature_extract.cpp:41-137) and the
+// PointNet + scatter-mean at the head of PointPillarTest.forward (model/s2s_merged.py:113-127,204-222).
+#include <algorithm>
+#include <cmath>
+#include <new>
+
+#include "common.hpp"
+#include "pillar_kernels.hpp"
+#include "seg_sort.hpp"
+
+using namespace gloc;
+using namespace gloc::pillar;
+
+struct gloc_pillar {
+  int device = 0;
+  hipStream_t own_stream = nullptr, stream = nullptr;
+  DevBuf keys[2], vals[2], flags, hist, segs, offsets, vrange, vcent, vcnt, inputs, part, pn;
+  DevBuf stage_in, stage_out;             // host-pointer API staging
+  std::vector<segsort::Seg> h_segs;       // kept alive until the next call (the uploads are asynchronous)
+  std::vector<uint64_t> h_offsets;
+  bool have_pn = false;
+  Profiler prof;
+};
+
+namespace {
+
+int make_grid(const gloc_pillar_params* p, Grid* g) {
+  GLOC_REQUIRE(p, GLOC_ERR_INVALID, "params is NULL");
+  const float* b[3] = {p->xbound, p->ybound, p->zbound};
+  uint64_t nv = 1;
+  for (int k = 0; k < 3; ++k) {
+    GLOC_REQUIRE(std::isfinite(b[k][0]) && std::isfinite(b[k][1]) && std::isfinite(b[k][2]) && b[k][2] > 0.f &&
+                     b[k][1] > b[k][0],
+                 GLOC_ERR_INVALID, "bound %d must be finite [lo, hi, res] with hi > lo and res > 0", k);
+    // the grid size from the bounds widened to double and truncated, as voxel.py:40-45 does with numpy
+    const double cells = ((double)b[k][1] - (double)b[k][0]) / (double)b[k][2];
+    GLOC_REQUIRE(cells >= 1.0 && cells < 16777216.0, GLOC_ERR_INVALID, "bound %d gives %.0f cells", k, cells);
+    g->off[k] = b[k][0];
+    g->res[k] = b[k][2];
+    g->size[k] = (int)cells;
+    nv *= (uint64_t)g->size[k];
+  }
+  // the index goes through float channel 14: exact below 2^24
+  GLOC_REQUIRE(nv <= (1u << 24), GLOC_ERR_INVALID, "%llu voxels exceed 2^24", (unsigned long long)nv);
+  GLOC_REQUIRE(p->num_points >= 1 && p->num_points <= (1u << 24), GLOC_ERR_INVALID, "num_points must be in [1, 2^24]");
+  GLOC_REQUIRE(p->mask_mode == GLOC_PILLAR_MASK_INPUT || p->mask_mode == GLOC_PILLAR_MASK_VALID, GLOC_ERR_INVALID,
+               "unknown mask_mode %u", p->mask_mode);
+  g->nv = (uint32_t)nv;
+  return GLOC_OK;
+}
+
+int check_batch(const float* d_pts, const uint64_t* offsets, size_t n_scans, size_t stride, const gloc_pillar_params* p,
+                const void* d_out) {
+  GLOC_REQUIRE(stride >= 4 && stride <= 64, GLOC_ERR_INVALID, "stride_floats must be in [4, 64]");
+  GLOC_REQUIRE(n_scans > 0 && n_scans <= 65535, GLOC_ERR_INVALID, "n_scans must be in [1, 65535]");
+  GLOC_REQUIRE(offsets && d_out, GLOC_ERR_INVALID, "NULL argument");
+  GLOC_REQUIRE(((uintptr_t)d_out & 15) == 0, GLOC_ERR_INVALID, "output must be 16-byte aligned");
+  for (size_t i = 0; i < n_scans; ++i)
+    GLOC_REQUIRE(offsets[i + 1] >= offsets[i], GLOC_ERR_INVALID, "offsets must be non-decreasing");
+  GLOC_REQUIRE(offsets[n_scans] == 0 || d_pts, GLOC_ERR_INVALID, "points pointer is NULL");
+  GLOC_REQUIRE((uint64_t)n_scans * p->num_points <= (1ull << 31), GLOC_ERR_INVALID,
+               "n_scans x num_points exceeds 2^31 rows");
+  return GLOC_OK;
+}
+
+// classify -> sort -> runs -> voxel -> gather into d_out [n_scans][P][16]; leaves the sorted order, flags and voxel
+// ranges in the handle for the canvas.  Returns the index of the sorted key / row buffers in *cur.
+int front(gloc_pillar* h, const float* d_pts, const uint64_t* offsets, size_t n_scans, size_t stride,
+          const gloc_pillar_params* p, const Grid& g, float* d_out, int* cur) {
+  GLOC_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const uint32_t P = p->num_points, B = (uint32_t)n_scans;
+  const size_t rows = (size_t)B * P;
+  for (DevBuf* k : {&h->keys[0], &h->keys[1], &h->vals[0], &h->vals[1], &h->flags}) GLOC_TRY(k->ensure(rows * 4, s));
+  GLOC_TRY(h->hist.ensure(segsort::scratch_bytes(B, P), s));
+  GLOC_TRY(h->segs.ensure(sizeof(segsort::Seg) * B, s));
+  GLOC_TRY(h->offsets.ensure(sizeof(uint64_t) * (B + 1), s));
+  GLOC_TRY(h->vrange.ensure(sizeof(uint2) * B * g.nv, s));
+  GLOC_TRY(h->vcent.ensure(sizeof(float4) * B * g.nv, s));
+  GLOC_TRY(h->vcnt.ensure(sizeof(float) * B * g.nv, s));
+  h->h_segs.resize(B);
+  for (uint32_t b = 0; b < B; ++b) h->h_segs[b] = segsort::Seg{b * P, P};
+  h->h_offsets.assign(offsets, offsets + n_scans + 1);
+  GLOC_HIP(hipMemcpyAsync(h->offsets.p, h->h_offsets.data(), sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->segs.p, h->h_segs.data(), sizeof(segsort::Seg) * B, hipMemcpyHostToDevice, s));
+  const float* pts = offsets[n_scans] ? d_pts : h->keys[0].as<float>();  // any valid pointer: no point is read
+  const dim3 rgrid((P + 255) / 256, B), vgrid((g.nv + 255) / 256, B);
+  {
+    ProfScope ps(h->prof, "pillar_classify", s);
+    hipLaunchKernelGGL(pillar_classify_kernel, rgrid, dim3(256), 0, s, pts, h->offsets.as<uint64_t>(), (int)stride, P, g,
+                       h->keys[0].as<uint32_t>(), h->vals[0].as<uint32_t>(), h->flags.as<uint32_t>());
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "pillar_sort", s);
+    int bits = 0;
+    while (bits < 32 && ((g.nv - 1) >> bits)) ++bits;
+    const int end_bit = std::max(8, (bits + 7) / 8 * 8);  // 11 200 voxels: two 8-bit passes
+    *cur = segsort::sort_pairs<uint32_t, 8>(s, h->keys[0].as<uint32_t>(), h->keys[1].as<uint32_t>(),
+                                            h->vals[0].as<uint32_t>(), h->vals[1].as<uint32_t>(),
+                                            h->segs.as<segsort::Seg>(), B, P, 0, end_bit, h->hist.as<uint32_t>());
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "pillar_runs", s);
+    GLOC_HIP(hipMemsetAsync(h->vrange.p, 0, sizeof(uint2) * B * g.nv, s));
+    hipLaunchKernelGGL(pillar_runs_kernel, rgrid, dim3(256), 0, s, h->keys[*cur].as<uint32_t>(), P, g.nv,
+                       h->vrange.as<uint2>());
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "pillar_voxel", s);
+    hipLaunchKernelGGL(pillar_voxel_kernel, vgrid, dim3(256), 0, s, pts, h->offsets.as<uint64_t>(), (int)stride, P, g.nv,
+                       h->vals[*cur].as<uint32_t>(), h->flags.as<uint32_t>(), h->vrange.as<uint2>(),
+                       h->vcent.as<float4>(), h->vcnt.as<float>());
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "pillar_gather", s);
+    hipLaunchKernelGGL(pillar_gather_kernel, rgrid, dim3(256), 0, s, pts, h->offsets.as<uint64_t>(), (int)stride, P, g,
+                       h->vcent.as<float4>(), h->vcnt.as<float>(), reinterpret_cast<float4*>(d_out));
+    GLOC_HIP(hipGetLastError());
+  }
+  return GLOC_OK;
+}
+
+int inputs_device(gloc_pillar* h, const float* d_pts, const uint64_t* offsets, size_t n_scans, size_t stride,
+                  const gloc_pillar_params* p, float* d_out) {
+  Grid g;
+  GLOC_TRY(make_grid(p, &g));
+  GLOC_TRY(check_batch(d_pts, offsets, n_scans, stride, p, d_out));
+  int cur = 0;
+  return front(h, d_pts, offsets, n_scans, stride, p, g, d_out, &cur);
+}
+
+int canvas_device(gloc_pillar* h, const float* d_pts, const uint64_t* offsets, size_t n_scans, size_t stride,
+                  const gloc_pillar_params* p, float* d_out) {
+  Grid g;
+  GLOC_TRY(make_grid(p, &g));
+  GLOC_TRY(check_batch(d_pts, offsets, n_scans, stride, p, d_out));
+  GLOC_REQUIRE(h->have_pn, GLOC_ERR_STATE, "no PointNet weights: call gloc_pillar_set_pointnet first");
+  const uint32_t P = p->num_points, B = (uint32_t)n_scans;
+  hipStream_t s = h->stream;
+  GLOC_HIP(hipSetDevice(h->device));
+  GLOC_TRY(h->inputs.ensure(sizeof(float) * 16 * B * (size_t)P, s));
+  int cur = 0;
+  GLOC_TRY(front(h, d_pts, offsets, n_scans, stride, p, g, h->inputs.as<float>(), &cur));
+  const uint32_t n_tiles = (P + TILE - 1) / TILE;
+  GLOC_TRY(h->part.ensure(sizeof(double) * 2 * FEAT * n_tiles * B, s));
+  const bool valid = p->mask_mode == GLOC_PILLAR_MASK_VALID;
+  {
+    ProfScope ps(h->prof, "pillar_partial", s);
+    const dim3 grid((n_tiles + 3) / 4, B);
+    auto k = valid ? pillar_partial_kernel<1> : pillar_partial_kernel<0>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, h->inputs.as<float>(), h->keys[cur].as<uint32_t>(),
+                       h->vals[cur].as<uint32_t>(), h->flags.as<uint32_t>(), P, n_tiles, h->pn.as<Pn>(),
+                       h->part.as<double>());
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "pillar_canvas", s);
+    const dim3 grid((g.nv + 63) / 64, B);
+    auto k = valid ? pillar_canvas_kernel<1> : pillar_canvas_kernel<0>;
+    hipLaunchKernelGGL(k, grid, dim3(1024), 0, s, h->inputs.as<float>(), h->vals[cur].as<uint32_t>(),
+                       h->flags.as<uint32_t>(), h->vrange.as<uint2>(), P, g.nv, n_tiles, h->pn.as<Pn>(),
+                       h->part.as<double>(), d_out);
+    GLOC_HIP(hipGetLastError());
+  }
+  return GLOC_OK;
+}
+
+// host buffers: stage the points, run the device call, copy `out_floats_per_scan` floats per scan back
+template <typename F>
+int host_call(gloc_pillar* h, const float* pts, const uint64_t* offsets, size_t n_scans, size_t stride,
+              const gloc_pillar_params* p, float* out, size_t out_floats, F&& dev) {
+  GLOC_REQUIRE(h && p && out && offsets, GLOC_ERR_INVALID, "NULL argument");
+  GLOC_REQUIRE(n_scans > 0 && n_scans <= 65535, GLOC_ERR_INVALID, "n_scans must be in [1, 65535]");
+  GLOC_REQUIRE(stride >= 4 && stride <= 64, GLOC_ERR_INVALID, "stride_floats must be in [4, 64]");
+  GLOC_REQUIRE(offsets[n_scans] == 0 || pts, GLOC_ERR_INVALID, "points pointer is NULL");
+  GLOC_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t in_bytes = sizeof(float) * offsets[n_scans] * stride, out_bytes = sizeof(float) * out_floats;
+  GLOC_TRY(h->stage_in.ensure(std::max<size_t>(in_bytes, 16), s));
+  GLOC_TRY(h->stage_out.ensure(out_bytes, s));
+  if (in_bytes) GLOC_HIP(hipMemcpyAsync(h->stage_in.p, pts, in_bytes, hipMemcpyHostToDevice, s));
+  GLOC_TRY(dev(h, h->stage_in.as<float>(), offsets, n_scans, stride, p, h->stage_out.as<float>()));
+  GLOC_HIP(hipMemcpyAsync(out, h->stage_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipStreamSynchronize(s));
+  return GLOC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gloc_pillar_default_params(gloc_pillar_params* p) {
+  GLOC_REQUIRE(p, GLOC_ERR_INVALID, "params is NULL");
+  std::memset(p, 0, sizeof(*p));
+  const float xb[3] = {-35.f, 35.f, 0.5f}, yb[3] = {-20.f, 20.f, 0.5f}, zb[3] = {-10.f, 10.f, 20.f};
+  std::memcpy(p->xbound, xb, sizeof(xb));  // gen_libtorch_pointpillar.py:27
+  std::memcpy(p->ybound, yb, sizeof(yb));  // :28
+  std::memcpy(p->zbound, zb, sizeof(zb));  // :29
+  p->num_points = 122480;                  // dataset/kitti_s2s.py:222-227, s2s_libtorch/s2s_feature_extract.cpp:143
+  p->mask_mode = GLOC_PILLAR_MASK_INPUT;   // the traced model: input channel 15 (model/s2s_merged.py:204-206)
+  return GLOC_OK;
+}
+
+int gloc_pillar_create(int device, gloc_pillar** out) {
+  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is NULL");
+  GLOC_TRY(select_device(device));
+  gloc_pillar* h = new (std::nothrow) gloc_pillar();
+  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "out of host memory");
+  h->device = device;
+  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    delete h;
+    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
+    return GLOC_ERR_HIP;
+  }
+  h->stream = h->own_stream;
+  *out = h;
+  return GLOC_OK;
+}
+
+int gloc_pillar_destroy(gloc_pillar* h) {
+  if (!h) return GLOC_OK;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);
+  h->prof.destroy();
+  for (DevBuf* b : {&h->keys[0], &h->keys[1], &h->vals[0], &h->vals[1], &h->flags, &h->hist, &h->segs, &h->offsets,
+                    &h->vrange, &h->vcent, &h->vcnt, &h->inputs, &h->part, &h->pn, &h->stage_in, &h->stage_out})
+    b->release();
+  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+  delete h;
+  return GLOC_OK;
+}
+
+int gloc_pillar_set_stream(gloc_pillar* h, void* hip_stream) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
+  GLOC_HIP(hipSetDevice(h->device));
+  GLOC_HIP(hipStreamSynchronize(h->stream));
+  h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
+  return GLOC_OK;
+}
+
+int gloc_pillar_synchronize(gloc_pillar* h) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
+  GLOC_HIP(hipSetDevice(h->device));
+  GLOC_HIP(hipStreamSynchronize(h->stream));
+  return GLOC_OK;
+}
+
+int gloc_pillar_set_pointnet(gloc_pillar* h, const float* w, const float* bn_weight, const float* bn_bias,
+                             const float* bn_mean, const float* bn_var, float eps) {
+  GLOC_REQUIRE(h && w && bn_weight && bn_bias && bn_mean && bn_var, GLOC_ERR_INVALID, "NULL argument");
+  GLOC_REQUIRE(eps >= 0.f && std::isfinite(eps), GLOC_ERR_INVALID, "eps must be finite and >= 0");
+  Pn pn;
+  for (int c = 0; c < FEAT; ++c) {
+    for (int k = 0; k < IN_CH; ++k) pn.w[c][k] = w[c * IN_CH + k];
+    // BatchNorm1d in eval mode folded into one scale and shift per channel (in double, then rounded once)
+    const double sc = (double)bn_weight[c] / std::sqrt((double)bn_var[c] + (double)eps);
+    pn.scale[c] = (float)sc;
+    pn.shift[c] = (float)((double)bn_bias[c] - (double)bn_mean[c] * sc);
+  }
+  GLOC_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  GLOC_TRY(h->pn.ensure(sizeof(Pn), s));
+  GLOC_HIP(hipMemcpyAsync(h->pn.p, &pn, sizeof(Pn), hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipStreamSynchronize(s));  // pn lives on this stack frame
+  h->have_pn = true;
+  return GLOC_OK;
+}
+
+int gloc_pillar_inputs(gloc_pillar* h, const float* pts, const uint64_t* offsets, size_t n_scans, size_t stride_floats,
+                       const gloc_pillar_params* p, float* out) {
+  GLOC_REQUIRE(p, GLOC_ERR_INVALID, "params is NULL");
+  return host_call(h, pts, offsets, n_scans, stride_floats, p, out, n_scans * (size_t)p->num_points * 16, inputs_device);
+}
+
+int gloc_pillar_inputs_device(gloc_pillar* h, const float* d_pts, const uint64_t* offsets, size_t n_scans,
+                              size_t stride_floats, const gloc_pillar_params* p, float* d_out) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
+  return inputs_device(h, d_pts, offsets, n_scans, stride_floats, p, d_out);
+}
+
+int gloc_pillar_canvas(gloc_pillar* h, const float* pts, const uint64_t* offsets, size_t n_scans, size_t stride_floats,
+                       const gloc_pillar_params* p, float* out) {
+  Grid g;
+  GLOC_TRY(make_grid(p, &g));
+  return host_call(h, pts, offsets, n_scans, stride_floats, p, out, n_scans * (size_t)FEAT * g.nv, canvas_device);
+}
+
+int gloc_pillar_canvas_device(gloc_pillar* h, const float* d_pts, const uint64_t* offsets, size_t n_scans,
+                              size_t stride_floats, const gloc_pillar_params* p, float* d_out) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
+  return canvas_device(h, d_pts, offsets, n_scans, stride_floats, p, d_out);
+}
+
+int gloc_pillar_set_profile(gloc_pillar* h, int enable) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
+  h->prof.enabled = enable != 0;
+  return GLOC_OK;
+}
+
+int gloc_pillar_profile(gloc_pillar* h, const char* kernel, double* total_ms, uint64_t* launches) {
+  GLOC_REQUIRE(h && kernel, GLOC_ERR_INVALID, "NULL argument");
+  GLOC_HIP(hipSetDevice(h->device));
+  GLOC_TRY(h->prof.collect(h->stream));
+  auto it = h->prof.fam.find(kernel);
+  if (total_ms) *total_ms = it == h->prof.fam.end() ? 0.0 : it->second.total_ms;
+  if (launches) *launches = it == h->prof.fam.end() ? 0 : it->second.launches;
+  return GLOC_OK;
+}
+
+int gloc_pillar_profile_reset(gloc_pillar* h) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
+  GLOC_HIP(hipSetDevice(h->device));
+  GLOC_TRY(h->prof.collect(h->stream));
+  h->prof.reset();
+  return GLOC_OK;
+}
+
+}  // extern "C"

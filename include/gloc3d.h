@@ -542,6 +542,61 @@ int gloc_bev_set_profile(gloc_bev* h, int enable);
 /* kernel families: "bev_clear", "bev_mark", "bev_flag", "bev_image" */
 int gloc_bev_profile(gloc_bev* h, const char* kernel, double* total_ms, uint64_t* launches);
 
+/* ============================ PointPillar scan front end ================================= *
+ * The non-CNN head of the reference's scan descriptor PointPillarVLAD (exported by
+ * s2s_libtorch/gen_libtorch_pointpillar.py, timed by s2s_libtorch/s2s_feature_extract.cpp):
+ *  - gloc_pillar_inputs*: points_to_voxels and the traced model's input (model/voxel.py:23-133,
+ *    gen_libtorch_pointpillar.py:47-62), [P][16] per scan: x y z i, the voxel's count of unpadded rows,
+ *    p - centroid, centroid, p - voxel centre, voxel index (as a float), mask.  Bit for bit the reference
+ *    module's on the CPU (tests/pillar_ref.py).  The index is x-major, x*gy*gz + y*gz + z
+ *    (raval_index, voxel.py:14-20), not the C++ demo's layout.
+ *  - gloc_pillar_canvas*: the PointNet (Conv1d 14 -> 64, BatchNorm1d eval, ReLU) times the row mask, and its
+ *    mean per voxel over every row of the voxel (model/s2s_merged.py:113-127,204-218): [64][nv] per scan,
+ *    nv = gx*gy*gz, empty voxels 0.  Sums in fp64 in a fixed order: the same bits on every run.
+ * A scan is its first num_points points, then zero rows with mask 0 (pad_or_trim_to_np, dataset/kitti_s2s.py:
+ * 222-227).  Points are x y z i, stride_floats >= 4 apart; a batch is n_scans scans back to back with host
+ * offsets in points, as the BEV calls.  Outputs are scans back to back, 16-byte aligned. */
+typedef struct gloc_pillar gloc_pillar;
+
+enum {
+  GLOC_PILLAR_MASK_INPUT = 0, /* features times input channel 15, the caller's mask (the traced model, s2s_merged.py:204-206) */
+  GLOC_PILLAR_MASK_VALID = 1  /* features times 1 - padding (the training forward, model/pointpillar.py:199) */
+};
+
+typedef struct gloc_pillar_params {
+  float xbound[3];     /* lo, hi, res: -35, 35, 0.5 m (gen_libtorch_pointpillar.py:27) */
+  float ybound[3];     /* -20, 20, 0.5 m (:28) */
+  float zbound[3];     /* -10, 10, 20 m (:29): one cell */
+  uint32_t num_points; /* P = 122480 rows per scan (dataset/kitti_s2s.py:222-227, s2s_feature_extract.cpp:143) */
+  uint32_t mask_mode;  /* GLOC_PILLAR_MASK_INPUT (default) or GLOC_PILLAR_MASK_VALID; canvas only */
+} gloc_pillar_params;
+
+int gloc_pillar_default_params(gloc_pillar_params* p);
+int gloc_pillar_create(int device, gloc_pillar** out);
+int gloc_pillar_destroy(gloc_pillar* h);
+int gloc_pillar_set_stream(gloc_pillar* h, void* hip_stream);
+int gloc_pillar_synchronize(gloc_pillar* h);
+/* PointNet weights: w [64][14] (pn.pointnet.0.weight), BatchNorm1d weight, bias, running mean and variance [64],
+ * eps (1e-5, torch's default).  Needed by the canvas calls (GLOC_ERR_STATE without). */
+int gloc_pillar_set_pointnet(gloc_pillar* h, const float* w, const float* bn_weight, const float* bn_bias,
+                             const float* bn_mean, const float* bn_var, float eps);
+/* Host buffers: out [n_scans][num_points][16]. */
+int gloc_pillar_inputs(gloc_pillar* h, const float* pts, const uint64_t* offsets, size_t n_scans, size_t stride_floats,
+                       const gloc_pillar_params* p, float* out);
+/* Device buffers on the handle's stream, no synchronisation. */
+int gloc_pillar_inputs_device(gloc_pillar* h, const float* d_pts, const uint64_t* offsets, size_t n_scans,
+                              size_t stride_floats, const gloc_pillar_params* p, float* d_out);
+/* Host buffers: out [n_scans][64][gx*gy*gz]. */
+int gloc_pillar_canvas(gloc_pillar* h, const float* pts, const uint64_t* offsets, size_t n_scans, size_t stride_floats,
+                       const gloc_pillar_params* p, float* out);
+int gloc_pillar_canvas_device(gloc_pillar* h, const float* d_pts, const uint64_t* offsets, size_t n_scans,
+                              size_t stride_floats, const gloc_pillar_params* p, float* d_out);
+int gloc_pillar_set_profile(gloc_pillar* h, int enable);
+/* kernel families: "pillar_classify", "pillar_sort", "pillar_runs", "pillar_voxel", "pillar_gather",
+ * "pillar_partial", "pillar_canvas" */
+int gloc_pillar_profile(gloc_pillar* h, const char* kernel, double* total_ms, uint64_t* launches);
+int gloc_pillar_profile_reset(gloc_pillar* h);
+
 /* ============================ coarse global (x, y, yaw) match (row a-12) =================== *
  * Replaces RpyPCLoopDetector::match(q_grid, db_idx, xy_yaw, scale) (registration/loop_detector.cpp:186-288):
  * the coarse pose of the query in a database place's frame from their two BEV occupancy images,

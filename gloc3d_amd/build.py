@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgloc3d.so")
-SOURCES = ["common.hip", "comm.hip", "knn.hip", "scan_store.hip", "reg.hip", "vlad.hip", "bev.hip", "ground.hip", "coarse.hip", "ndt.hip", "pillar.hip"]
+SOURCES = ["common.hip", "comm.hip", "knn.hip", "scan_store.hip", "reg.hip", "vlad.hip", "bev.hip", "ground.hip", "coarse.hip", "ndt.hip", "pillar.hip", "vgg.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the exact kernels must reproduce the reference's un-fused fp32 arithmetic
 EXTRA = os.environ.get("GLOC3D_EXTRA_FLAGS", "").split()
@@ -22,7 +22,7 @@ FLAGS = EXTRA + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-co
 # totals every 64 k, and from AGPRs that is a v_accvgpr_read per register and step (measured: 121 of the main loop's
 # ~330 vector instructions); without AGPRs the kernel also fits three work-groups per CU (161 registers, not 192)
 MFMA_VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
-PER_SOURCE = {"knn.hip": MFMA_VGPR_FORM}
+PER_SOURCE = {"knn.hip": MFMA_VGPR_FORM, "vgg.hip": MFMA_VGPR_FORM}
 _probe = {}
 
 

@@ -228,6 +228,18 @@ _PROTOS = [
     ("gloc_pillar_set_profile", _i, [_vp, _i]),
     ("gloc_pillar_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
     ("gloc_pillar_profile_reset", _i, [_vp]),
+    ("gloc_vgg_create", _i, [_i, C.POINTER(_vp)]),
+    ("gloc_vgg_destroy", _i, [_vp]),
+    ("gloc_vgg_set_stream", _i, [_vp, _vp]),
+    ("gloc_vgg_synchronize", _i, [_vp]),
+    ("gloc_vgg_layer_shape", _i, [_i, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_i), C.POINTER(_i)]),
+    ("gloc_vgg_set_layer", _i, [_vp, _i, _vp, _vp]),
+    ("gloc_vgg_forward", _i, [_vp, _vp, _sz, _u32, _u32, _vp]),
+    ("gloc_vgg_forward_device", _i, [_vp, _vp, _sz, _u32, _u32, _vp]),
+    ("gloc_vgg_forward_layer", _i, [_vp, _i, _vp, _sz, _u32, _u32, _vp]),
+    ("gloc_vgg_set_profile", _i, [_vp, _i]),
+    ("gloc_vgg_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
+    ("gloc_vgg_profile_reset", _i, [_vp]),
     ("gloc_coarse_default_params", _i, [_vp]),
     ("gloc_coarse_create", _i, [_i, C.POINTER(_vp)]),
     ("gloc_coarse_destroy", _i, [_vp]),
@@ -937,6 +949,9 @@ class NetVladFC:
     def forward_device(self, feat_ptr, n, hw, out_ptr):
         check(lib().gloc_vlad_forward_device(self._h, C.c_void_p(feat_ptr), n, hw, C.c_void_p(out_ptr)))
 
+    def set_stream(self, stream_ptr):
+        check(lib().gloc_vlad_set_stream(self._h, C.c_void_p(stream_ptr)))
+
     def set_profile(self, on=True):
         check(lib().gloc_vlad_set_profile(self._h, 1 if on else 0))
 
@@ -1130,6 +1145,85 @@ class PillarEncoder:
 
     def profile_reset(self):
         check(lib().gloc_pillar_profile_reset(self._h))
+
+
+VGG_LAYERS = 13
+
+
+def vgg_layer_shape(layer):
+    """(Cin, Cout, relu, pool) of encoder layer `layer` (0..12), from the library's own table."""
+    ci, co, r, p = C.c_uint32(), C.c_uint32(), C.c_int(), C.c_int()
+    check(lib().gloc_vgg_layer_shape(layer, C.byref(ci), C.byref(co), C.byref(r), C.byref(p)))
+    return ci.value, co.value, bool(r.value), bool(p.value)
+
+
+class VggEncoder:
+    """VGG16 features[:-2], the i2i model's encoder (s2s_libtorch/gen_libtorch_i2i.py:36-60): [n, 3, H, W] ->
+    [n, 512, H / 16, W / 16], fp32 NCHW in and out (split-bf16 matrix cores inside, include/gloc3d.h)."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        self.device = device
+        check(lib().gloc_vgg_create(device, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().gloc_vgg_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_layer(self, layer, w, b):
+        """w [Cout, Cin, 3, 3] (torch's Conv2d weight), b [Cout]."""
+        ci, co, _, _ = vgg_layer_shape(layer)
+        wa = np.ascontiguousarray(w, np.float32)
+        ba = np.ascontiguousarray(b, np.float32)
+        assert wa.shape == (co, ci, 3, 3) and ba.shape == (co,), (layer, wa.shape, ba.shape)
+        check(lib().gloc_vgg_set_layer(self._h, layer, _np_ptr(wa), _np_ptr(ba)))
+
+    def set_layers(self, layers):
+        """layers: 13 (w, b) pairs in network order."""
+        assert len(layers) == VGG_LAYERS
+        for i, (w, b) in enumerate(layers):
+            self.set_layer(i, w, b)
+
+    def forward(self, images):
+        """Host [n, 3, H, W] (or [3, H, W]) -> [n, 512, H / 16, W / 16]."""
+        x = np.ascontiguousarray(images, np.float32)
+        if x.ndim == 3:
+            x = x[None]
+        n, _, H, W = x.shape
+        out = np.empty((n, 512, H // 16, W // 16), np.float32)
+        check(lib().gloc_vgg_forward(self._h, _np_ptr(x), n, H, W, _np_ptr(out)))
+        return out
+
+    def forward_device(self, images_ptr, n, H, W, out_ptr):
+        check(lib().gloc_vgg_forward_device(self._h, C.c_void_p(images_ptr), n, H, W, C.c_void_p(out_ptr)))
+
+    def forward_layer_device(self, layer, in_ptr, n, H, W, out_ptr):
+        """One layer with its epilogue on device buffers, NCHW [n, Cin, H, W] -> [n, Cout, Ho, Wo]."""
+        check(lib().gloc_vgg_forward_layer(self._h, layer, C.c_void_p(in_ptr), n, H, W, C.c_void_p(out_ptr)))
+
+    def set_stream(self, stream_ptr):
+        check(lib().gloc_vgg_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    def synchronize(self):
+        check(lib().gloc_vgg_synchronize(self._h))
+
+    def set_profile(self, on=True):
+        check(lib().gloc_vgg_set_profile(self._h, 1 if on else 0))
+
+    def profile(self, kernel):
+        ms, n = C.c_double(), C.c_uint64()
+        check(lib().gloc_vgg_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def profile_reset(self):
+        check(lib().gloc_vgg_profile_reset(self._h))
 
 
 def default_coarse_params(**over):

@@ -1,13 +1,18 @@
 // global_localization -- drop-in for the reference's evaluator
 // (registration/global_localization.cpp:577-600):
 //
-//   global_localization VALSET POSES DESCRIPTORS [x]
+//   global_localization VALSET POSES MODEL [x]
 //
 // Same argv positions and the same report: recall@{1,5,10,20}, success rate, rot/pos error
 // mean +/- std, failed_detect_indices.txt and failed_registration_indices.txt in the CWD.
-// argv[3] is the descriptor file that stands in for the TorchScript model (the CNN is out of the
-// hot path's scope): "GLOCDESC" u32 n u32 dim, then db descriptors followed by query descriptors in
-// valset order.  A 4th argument selects ground alignment as in the reference (:584-588): every db
+// argv[3] is either
+//   * the i2i model's weights, exported from the reference's TorchScript module or checkpoint by
+//     tools/export_i2i_weights.py ("GLOCI2IW"): the database scans are described in batches in construct_db
+//     and each query on its own, BEV -> VGG16 -> NetVLAD-FC on the GPU (loop_detector.cpp:137-172), or
+//   * a descriptor file ("GLOCDESC" u32 n u32 dim, then db descriptors followed by query descriptors in
+//     valset order), descriptors computed elsewhere.
+// In MODEL mode with the 4th argument the descriptors are those of the ground-aligned scans, as the reference's.
+// GLOC_DUMP_DESCRIPTORS=FILE writes the descriptors retrieval used as a GLOCDESC file.  A 4th argument selects ground alignment as in the reference (:584-588): every db
 // and query scan is pre-aligned by gloc_ground_estimate (:431-436, :495-499), registration runs on
 // the aligned clouds and the pose is carried back with Tdb_l2g^-1 * T * Tq_l2g (:527-541).
 //
@@ -37,6 +42,7 @@ struct GlocEvaluator {
   std::vector<float> desc;
   size_t n_desc = 0, dim = 0;
   std::unique_ptr<RpyPCLoopDetector> det;
+  std::unique_ptr<I2iModel> model;  // MODEL mode: descriptors computed here
   std::vector<std::vector<size_t>> queried_idx;
   std::vector<std::pair<size_t, Mat4>> located;  // {db idx, pose in db}
   double time_sum_match = 0, times_call_match = 0;
@@ -99,19 +105,37 @@ struct GlocEvaluator {
   void construct_db() {  // :419-449
     det.reset(new RpyPCLoopDetector(dim, device));
     if (comm) det->attach_comm(comm);
-    double t_add = 0, t_align = 0;
-    for (size_t i = 0; i < vs.db_files.size(); ++i) {
-      std::vector<float> scan = read_lidar_kitti(vs.db_files[i]);
-      std::vector<float> d(desc.begin() + i * dim, desc.begin() + (i + 1) * dim);
-      if (align_ground) {
-        const double ta = now_ms();
-        db_rpz_estimates.push_back(align(scan));
-        t_align += now_ms() - ta;
+    double t_add = 0, t_align = 0, t_desc = 0;
+    const size_t ndb = vs.db_files.size();
+    // In batches of I2iModel::kBatch scans: read, ground-align (the reference describes and stores the aligned
+    // cloud, :431-440, add_keyframe -> get_place_feature, loop_detector.cpp:10-14), describe (MODEL mode), add.
+    for (size_t i0 = 0; i0 < ndb; i0 += I2iModel::kBatch) {
+      const size_t i1 = std::min(ndb, i0 + I2iModel::kBatch);
+      std::vector<std::vector<float>> scans;
+      for (size_t i = i0; i < i1; ++i) {
+        scans.push_back(read_lidar_kitti(vs.db_files[i]));
+        if (align_ground) {
+          const double ta = now_ms();
+          db_rpz_estimates.push_back(align(scans.back()));
+          t_align += now_ms() - ta;
+        }
       }
-      const double t0 = now_ms();
-      det->add_keyframe(d, scan.data(), scan.size() / 4);
-      t_add += now_ms() - t0;
+      if (model) {
+        std::vector<const std::vector<float>*> ptrs;
+        for (const auto& sc : scans) ptrs.push_back(&sc);
+        const double t0 = now_ms();
+        model->describe(ptrs, det->projection_params(), desc);
+        t_desc += now_ms() - t0;
+      }
+      for (size_t i = i0; i < i1; ++i) {
+        const std::vector<float>& scan = scans[i - i0];
+        std::vector<float> d(desc.begin() + i * dim, desc.begin() + (i + 1) * dim);
+        const double t0 = now_ms();
+        det->add_keyframe(d, scan.data(), scan.size() / 4);
+        t_add += now_ms() - t0;
+      }
     }
+    if (model) std::printf("time cost for the db descriptors: %f ms.\n", t_desc / std::max<size_t>(1, ndb));
     if (align_ground)
       std::printf("time cost for align to ground: %f ms.\n", t_align / std::max<size_t>(1, vs.db_files.size()));
     std::printf("time cost for add_keyframe (upload + index): %f ms.\n", t_add / std::max<size_t>(1, vs.db_files.size()));
@@ -123,6 +147,21 @@ struct GlocEvaluator {
     queried_idx.clear();
     located.assign(vs.q_files.size(), {ndb + 1, identity4()});
     for (size_t q = 0; q < vs.q_files.size(); ++q) {
+      // the query scan, ground-aligned with the 4th argument (:495-499); read once, where it is needed
+      std::vector<float> scan;
+      Mat4 Tq_l2g = identity4();
+      bool loaded = false;
+      auto load = [&]() {
+        if (loaded) return;
+        scan = read_lidar_kitti(vs.q_files[q]);
+        if (align_ground) Tq_l2g = align(scan);
+        loaded = true;
+      };
+      if (model) {  // the query's descriptor, from the scan detect() is given (:495-499)
+        load();
+        desc.resize((ndb + q) * dim);
+        model->describe({&scan}, det->projection_params(), desc);
+      }
       std::vector<float> d(desc.begin() + (ndb + q) * dim, desc.begin() + (ndb + q + 1) * dim);
       std::vector<size_t> idx;
       std::vector<float> d2;
@@ -132,9 +171,7 @@ struct GlocEvaluator {
       queried_idx.push_back(idx);
       if (idx.empty()) continue;
       if ((int)(q % (size_t)world) != rank) continue;  // registered by another rank
-      std::vector<float> scan = read_lidar_kitti(vs.q_files[q]);
-      Mat4 Tq_l2g = identity4();
-      if (align_ground) Tq_l2g = align(scan);
+      load();
       Mat4 pose = identity4();
       // Without alignment the registration starts from the identity (sensor frames alike).  The same
       // prior expressed between the ground frames is Tdb_l2g * Tq_l2g^-1; it also carries the half
@@ -241,7 +278,7 @@ struct GlocEvaluator {
 
 int main(int argc, char* argv[]) {
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s VALSET POSES DESCRIPTORS [x]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s VALSET POSES MODEL [x]\n", argv[0]);
     return 2;
   }
   GlocEvaluator g;
@@ -250,20 +287,26 @@ int main(int argc, char* argv[]) {
   std::printf("db_num and db_files: %zu\nq_num and q_files: %zu\nq_num and q_pos_index: %zu\n", g.vs.db_files.size(),
               g.vs.q_files.size(), g.vs.pos_idx.size());
   std::printf("Read poses with size: %zu\n", g.poses_db_q.size());
-  if (!read_descriptors(argv[3], g.desc, g.n_desc, g.dim)) {
+  const bool model_mode = I2iModel::is_weights_file(argv[3]);
+  if (!model_mode && !read_descriptors(argv[3], g.desc, g.n_desc, g.dim)) {
     std::fprintf(stderr,
-                 "%s is not a descriptor file (GLOCDESC header).  The reference loads a TorchScript model here; the "
-                 "descriptor network is upstream of this build's hot path -- export its outputs for the valset's db "
-                 "then query scans and pass that file instead.\n", argv[3]);
-    return 1;
-  }
-  if (g.n_desc != g.vs.db_files.size() + g.vs.q_files.size() ||
-      g.poses_db_q.size() != g.vs.db_files.size() + g.vs.q_files.size()) {
-    std::fprintf(stderr, "descriptor/pose count does not match the valset\n");
+                 "%s is neither an i2i weights file (GLOCI2IW header) nor a descriptor file (GLOCDESC header).  The "
+                 "reference loads a TorchScript model here: export its weights with tools/export_i2i_weights.py MODEL "
+                 "OUT and pass OUT instead.\n", argv[3]);
     return 1;
   }
   try {
     g.init_comm();
+    if (model_mode) {
+      g.model.reset(new I2iModel(argv[3], g.device));
+      g.dim = g.model->out_dim();
+      g.n_desc = g.vs.db_files.size() + g.vs.q_files.size();
+    }
+    if (g.n_desc != g.vs.db_files.size() + g.vs.q_files.size() ||
+        g.poses_db_q.size() != g.vs.db_files.size() + g.vs.q_files.size()) {
+      std::fprintf(stderr, "descriptor/pose count does not match the valset\n");
+      return 1;
+    }
     g.construct_db();
     g.locate_all_query();
   } catch (const std::exception& e) {
@@ -273,6 +316,13 @@ int main(int argc, char* argv[]) {
   if (g.rank == 0) {  // the report (and the two failure files) once
     g.recognition_recalls();
     g.registration_recalls();
+    // GLOC_DUMP_DESCRIPTORS=FILE: the descriptors retrieval used, db then queries, as a GLOCDESC file
+    if (const char* dump = std::getenv("GLOC_DUMP_DESCRIPTORS")) {
+      if (!write_descriptors(dump, g.desc, g.n_desc, g.dim)) {
+        std::fprintf(stderr, "cannot write %s\n", dump);
+        return 1;
+      }
+    }
   }
   return 0;
 }

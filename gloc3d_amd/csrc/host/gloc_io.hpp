@@ -232,6 +232,14 @@ inline bool read_descriptors(const std::string& path, std::vector<float>& data, 
   return (bool)f.read(reinterpret_cast<char*>(data.data()), (std::streamsize)(data.size() * sizeof(float)));
 }
 
+inline bool write_descriptors(const std::string& path, const std::vector<float>& data, size_t n, size_t dim) {
+  std::ofstream f(path, std::ofstream::out | std::ofstream::binary);
+  const uint32_t hdr[2] = {(uint32_t)n, (uint32_t)dim};
+  return f.is_open() && f.write("GLOCDESC", 8) && f.write(reinterpret_cast<const char*>(hdr), 8) &&
+         data.size() >= n * dim &&
+         f.write(reinterpret_cast<const char*>(data.data()), (std::streamsize)(n * dim * sizeof(float)));
+}
+
 inline void mean_std(const std::vector<double>& v, double& mean, double& stdev) {  // :185-196 (n-1)
   double sum = 0;
   for (double d : v) sum += d;

@@ -1,15 +1,18 @@
 // loop_detector.hpp -- host-side mirror of the reference's RpyPCLoopDetector
 // (registration/loop_detector.h:41-119) for the hot path: same method names, argument meaning and
 // guards, over the C ABI (include/gloc3d.h).  Differences, all forced by scope:
-//   * the descriptor comes from the caller (the CNN backbone is upstream of the hot path);
-//     get_projected_grid / get_place_input are the BEV projection in front of it;
+//   * the descriptor comes from the caller; get_projected_grid / get_place_input are the BEV projection in front
+//     of it, and I2iModel (below) is the i2i network behind it, read from an exported weights file;
 //   * match(scan, db_idx, xy_yaw, scale) is the coarse 2-D match on the BEV grids (an exhaustive yaw x shift
 //     search instead of SURF + FLANN + RANSAC-affine); the batched match() is the 3-D registration
 //     (RANSAC-SVD + ICP) of north_star, seeded by it.
 // Not thread-safe; single caller thread, like the reference.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <fstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -256,6 +259,7 @@ class RpyPCLoopDetector {
     return chw;
   }
 
+  gloc_bev_params projection_params() const { return bev_params(); }  // the BEV settings of get_place_input
   gloc_reg_params& registration_params() { return reg_params_; }
   size_t size() const { return db_size_; }
   size_t top_k() const { return top_k_; }
@@ -307,6 +311,107 @@ class RpyPCLoopDetector {
   int device_ = 0;
   gloc_reg_params reg_params_{};
   std::vector<uint32_t> db_scan_ids_;
+};
+
+// The i2i descriptor network from a GLOCI2IW weights file (tools/export_i2i_weights.py), in place of the TorchScript
+// module get_place_feature runs (loop_detector.cpp:137-172): BEV [3][768][768] (gloc_bev) -> VGG16 features[:-2]
+// (gloc_vgg) -> NetVLAD-FC (gloc_vlad), up to kBatch scans per pass through the host-pointer entry points.
+// File: "GLOCI2IW", u32 version (1), u32 layers (13), per layer u32 cout, u32 cin, w [cout][cin][3][3], b [cout];
+// then u32 clusters, dim, out_dim, has_bias, conv_w [clusters][dim], conv_b [clusters] if has_bias,
+// centroids [clusters][dim], fc_w [clusters * dim][out_dim]; little-endian fp32.
+class I2iModel {
+ public:
+  static constexpr size_t kBatch = 8;
+  static bool is_weights_file(const std::string& path) {
+    std::ifstream f(path, std::ifstream::in | std::ifstream::binary);
+    char magic[8];
+    return f.is_open() && f.read(magic, 8) && std::memcmp(magic, "GLOCI2IW", 8) == 0;
+  }
+
+  I2iModel(const std::string& path, int device = 0) {
+    std::ifstream f(path, std::ifstream::in | std::ifstream::binary);
+    char magic[8];
+    uint32_t hdr[2];
+    if (!f.is_open() || !f.read(magic, 8) || std::memcmp(magic, "GLOCI2IW", 8) != 0 || !read(f, hdr, 2) ||
+        hdr[0] != 1 || hdr[1] != 13)
+      throw std::runtime_error(path + ": not a GLOCI2IW version 1 file of 13 layers");
+    try {
+      check(gloc_vgg_create(device, &vgg_));
+      for (int l = 0; l < 13; ++l) {
+        uint32_t shape[2], cin = 0, cout = 0;
+        if (!read(f, shape, 2)) throw std::runtime_error(path + ": truncated");
+        check(gloc_vgg_layer_shape(l, &cin, &cout, nullptr, nullptr));
+        if (shape[0] != cout || shape[1] != cin) throw std::runtime_error(path + ": layer shapes differ from VGG16");
+        std::vector<float> w((size_t)cout * cin * 9), b(cout);
+        if (!read(f, w.data(), w.size()) || !read(f, b.data(), b.size())) throw std::runtime_error(path + ": truncated");
+        check(gloc_vgg_set_layer(vgg_, l, w.data(), b.data()));
+      }
+      uint32_t head[4];
+      if (!read(f, head, 4)) throw std::runtime_error(path + ": truncated");
+      const size_t K = head[0], D = head[1];
+      out_dim_ = head[2];
+      if (D != 512) throw std::runtime_error(path + ": the encoder gives 512 channels");
+      std::vector<float> conv_w(K * D), conv_b(head[3] ? K : 0), cent(K * D), fc(K * D * out_dim_);
+      if (!read(f, conv_w.data(), conv_w.size()) || !read(f, conv_b.data(), conv_b.size()) ||
+          !read(f, cent.data(), cent.size()) || !read(f, fc.data(), fc.size()))
+        throw std::runtime_error(path + ": truncated");
+      check(gloc_vlad_create(device, D, K, out_dim_, conv_w.data(), head[3] ? conv_b.data() : nullptr, cent.data(),
+                             fc.data(), 1, &vlad_));
+      check(gloc_bev_create(device, &bev_));
+    } catch (...) {
+      release();
+      throw;
+    }
+  }
+  ~I2iModel() { release(); }
+  I2iModel(const I2iModel&) = delete;
+  I2iModel& operator=(const I2iModel&) = delete;
+
+  size_t out_dim() const { return out_dim_; }
+
+  // scans (x y z i rows) -> descriptors [n][out_dim], appended to `out`; bev: the reference's projection settings
+  void describe(const std::vector<const std::vector<float>*>& scans, const gloc_bev_params& bev, std::vector<float>& out) {
+    gloc_bev_params p = bev;
+    p.format = GLOC_BEV_F32_CHW;
+    const size_t H = p.out_height, W = p.out_width, img = 3 * H * W, hw = (H / 16) * (W / 16);
+    for (size_t i0 = 0; i0 < scans.size(); i0 += kBatch) {
+      const size_t n = std::min(kBatch, scans.size() - i0);
+      images_.resize(n * img);
+      for (size_t i = 0; i < n; ++i) {
+        gloc_bev_info info;
+        const std::vector<float>& s = *scans[i0 + i];
+        check(gloc_bev_project(bev_, s.data(), s.size() / 4, 4, &p, images_.data() + i * img, &info));
+        if (info.empty) throw std::runtime_error("no point of the scan lies within range");  // the reference aborts
+      }
+      feat_.resize(n * 512 * hw);
+      check(gloc_vgg_forward(vgg_, images_.data(), n, (uint32_t)H, (uint32_t)W, feat_.data()));
+      const size_t o = out.size();
+      out.resize(o + n * out_dim_);
+      check(gloc_vlad_forward(vlad_, feat_.data(), n, hw, out.data() + o));
+    }
+  }
+
+ private:
+  template <class T>
+  static bool read(std::ifstream& f, T* p, size_t count) {
+    return count == 0 || (bool)f.read(reinterpret_cast<char*>(p), (std::streamsize)(count * sizeof(T)));
+  }
+  static void check(int rc) {
+    if (rc != GLOC_OK) throw std::runtime_error(gloc_last_error());
+  }
+  void release() {
+    gloc_bev_destroy(bev_);
+    gloc_vgg_destroy(vgg_);
+    gloc_vlad_destroy(vlad_);
+    bev_ = nullptr;
+    vgg_ = nullptr;
+    vlad_ = nullptr;
+  }
+  gloc_bev* bev_ = nullptr;
+  gloc_vgg* vgg_ = nullptr;
+  gloc_vlad* vlad_ = nullptr;
+  size_t out_dim_ = 0;
+  std::vector<float> images_, feat_;
 };
 
 }  // namespace gloc_host

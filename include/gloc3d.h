@@ -484,6 +484,40 @@ int gloc_vlad_set_profile(gloc_vlad* h, int enable);
 /* kernel families: "vlad_tile", "vlad_cluster", "vlad_fc", "vlad_gate" */
 int gloc_vlad_profile(gloc_vlad* h, const char* kernel, double* total_ms, uint64_t* launches);
 
+/* ============================ VGG16 place-descriptor encoder ============================= *
+ * The encoder of the reference's i2i model, VGG16 features[:-2] (s2s_libtorch/gen_libtorch_i2i.py:36-60,
+ * main.py:531-541): 13 3x3 convolutions (pad 1, stride 1, bias) with ReLU and four 2x2 max-pools, the last
+ * convolution (conv5_3) without ReLU or pool.  Its input is the BEV tensor (gloc_bev, GLOC_BEV_F32_CHW) and its output
+ * feeds gloc_vlad_forward_device (dim 512) as it is: together the TorchScript module RpyPCLoopDetector::get_place_feature
+ * runs (registration/loop_detector.cpp:137-172).  Layers 0..12: Cin -> Cout = 3 -> 64, 64 -> 64 (pool), 64 -> 128,
+ * 128 -> 128 (pool), 128 -> 256, 256 -> 256, 256 -> 256 (pool), 256 -> 512, 512 -> 512, 512 -> 512 (pool), 3 x 512 -> 512.
+ * fp32 in and out.  Inside, each convolution is an implicit GEMM on the bf16 matrix cores with both operands split in
+ * two bf16 halves (hi + lo, three products; the weights are split when they are set).  Contract for arbitrary fp32
+ * input: max|out - fp32 reference| <= 1e-4 max|reference| per layer and for the whole encoder.
+ * Each output has a fixed summation order: a batch gives the same bits as single calls. */
+typedef struct gloc_vgg gloc_vgg;
+int gloc_vgg_create(int device, gloc_vgg** out);
+int gloc_vgg_destroy(gloc_vgg* h);
+int gloc_vgg_set_stream(gloc_vgg* h, void* hip_stream);
+int gloc_vgg_synchronize(gloc_vgg* h);
+/* Cin, Cout, ReLU and pool of layer `layer` (0..12); needs no handle and no device.  Any pointer may be NULL. */
+int gloc_vgg_layer_shape(int layer, uint32_t* cin, uint32_t* cout, int* relu, int* pool);
+/* w [Cout][Cin][3][3] (torch's Conv2d layout), b [Cout], host fp32; copied and re-laid on the device before this
+ * returns.  Every forward call needs the weights of the layers it runs (GLOC_ERR_STATE without). */
+int gloc_vgg_set_layer(gloc_vgg* h, int layer, const float* w, const float* b);
+/* images [n][3][H][W] -> out [n][512][H/16][W/16], NCHW fp32; H and W multiples of 16 (GLOC_ERR_INVALID otherwise).
+ * Host buffers, synchronous. */
+int gloc_vgg_forward(gloc_vgg* h, const float* images, size_t n, uint32_t H, uint32_t W, float* out);
+/* The same on device buffers, on the handle's stream, without synchronisation. */
+int gloc_vgg_forward_device(gloc_vgg* h, const float* d_images, size_t n, uint32_t H, uint32_t W, float* d_out);
+/* One layer with its own epilogue (ReLU, pool) on device buffers: d_in [n][Cin][H][W] -> d_out [n][Cout][Ho][Wo],
+ * NCHW fp32, Ho, Wo = H/2, W/2 for a pooled layer (which needs even H and W), else H, W.  Any H, W in [1, 8192]. */
+int gloc_vgg_forward_layer(gloc_vgg* h, int layer, const float* d_in, size_t n, uint32_t H, uint32_t W, float* d_out);
+int gloc_vgg_set_profile(gloc_vgg* h, int enable);
+/* kernel families: "vgg_conv0" .. "vgg_conv12" (one per layer), "vgg_layout" (forward_layer's NCHW -> NHWC) */
+int gloc_vgg_profile(gloc_vgg* h, const char* kernel, double* total_ms, uint64_t* launches);
+int gloc_vgg_profile_reset(gloc_vgg* h);
+
 /* ============================ BEV occupancy projection ("next" row N1) ==================== *
  * Replaces RpyPCLoopDetector::get_projected_grid + crop_pad_occupancy + the tensor packing of
  * get_place_feature (registration/loop_detector.cpp:83-106,122-151): one scan inserted into a fresh

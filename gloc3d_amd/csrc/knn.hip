@@ -4,7 +4,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
-#include <cstdlib>
 #include <vector>
 #include <new>
 
@@ -36,7 +35,6 @@ struct gloc_knn {
   DevBuf keys2;     // rerank output [nq][k]
   DevBuf qnorm;     // [nq]
   DevBuf qsplit;    // [nq][dim / 8][8 bf16 h, 8 bf16 m]: the queries of the split-bf16 coarse pass
-  DevBuf dev_trace; // developer aid: phase stamps of the fused select + re-rank kernel (null unless enabled)
   DevBuf flags;     // [nq] int
   DevBuf redo_tickets;  // [nq] u32: flagged_redo_kernel's tickets (0 between searches)
   DevBuf bmin;          // [nq][blocks of 32 rows]: the coarse kernel's block minima (large windows, one K-split)
@@ -125,7 +123,7 @@ int launch_dist_exact(gloc_knn* h, const float* d_q, int nq, size_t first, int n
   ProfScope ps(h->prof, "dist_exact", h->stream);
   const int QT = only_flagged ? 1 : (nq >= 8 ? 8 : (nq >= 4 ? 4 : (nq >= 2 ? 2 : 1)));
   const int qgroups = (nq + QT - 1) / QT;
-  if (nq <= 2 && !getenv("GLOC3D_KNN_NO_SMALL")) {
+  if (nq <= 2) {
     // one or two queries: the streaming form (one wave per work-group, all group sums before the chains);
     // measured against the general kernel at 4541 x 4096: Q = 1 18.6 vs 33 us, Q = 2 equal, Q = 4 / 8 slower
     const int G = (int)h->dim >> 2, Gs = std::min(G, EXS_G);
@@ -173,8 +171,6 @@ struct SlicePlan {
   int S, L;
 };
 bool plan_slices(int n_range, int nq, int K, SlicePlan* out) {
-  static const bool off = getenv("GLOC3D_KNN_NO_SLICES") != nullptr;  // developer switch: the chunked form
-  if (off) return false;
   long long s = ((long long)n_range + SELQ_MAX_ROWS - 1) / SELQ_MAX_ROWS;
   while (s * nq < 512 && n_range / (s * 2) >= 4096 && s * 2 * K <= SELQ_MAX_ROWS) s *= 2;
   const int L = (int)((((long long)n_range + s - 1) / s + 63) & ~63ll);
@@ -211,8 +207,7 @@ int run_select(gloc_knn* h, const float* d_q, int nq, int K, size_t first, int n
                const FinalOut& fo = FinalOut{nullptr, nullptr, 0, 1}, bool* finalized = nullptr) {
   if (finalized) *finalized = false;
   ProfScope ps(h->prof, "select", h->stream);
-  static const bool no_selq = getenv("GLOC3D_KNN_NO_SELECT_QUERY") != nullptr;  // developer switch: the chunked form
-  if (n_range <= SELQ_MAX_ROWS && K <= 64 && !no_selq) {  // one launch, one work-group per query
+  if (n_range <= SELQ_MAX_ROWS && K <= 64) {  // one launch, one work-group per query
     hipLaunchKernelGGL(select_query_kernel<MODE>, dim3(nq), dim3(SELQ_THREADS), 0, h->stream, h->dist.as<float>(), ld,
                        strideP, n_splits, h->qnorm.as<float>(), d_q, (int)h->dim, h->norms.as<float>(), first, n_range,
                        K, d_keys_out, only_flagged, fo);
@@ -221,7 +216,7 @@ int run_select(gloc_knn* h, const float* d_q, int nq, int K, size_t first, int n
     return GLOC_OK;
   }
   SlicePlan sl;
-  if (K <= 64 && !no_selq && plan_slices(n_range, nq, K, &sl)) {  // two launches: slices, then their lists
+  if (K <= 64 && plan_slices(n_range, nq, K, &sl)) {  // two launches: slices, then their lists
     GLOC_TRY(launch_slices<MODE>(h, d_q, nq, K, first, n_range, ld, strideP, n_splits, sl, only_flagged));
     hipLaunchKernelGGL(select_query_kernel<2>, dim3(nq), dim3(SELQ_THREADS), 0, h->stream,
                        reinterpret_cast<const float*>(h->klists.as<uint64_t>()), (size_t)2 * sl.S * K, (size_t)0, 1,
@@ -279,29 +274,19 @@ int run_exact(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_
 // ---- MFMA path -------------------------------------------------------------------------------
 struct MfmaPlan {
   int WQ, NT, KS, BQ, BN;
-  int t32 = 0;  // 1: the 32 x 32 x 2 tiles (dist_mfma32_kernel: BQ = 64, BN = 64 * NT)
-  int b3 = 0;   // 1: the split-bf16 form (dist_bf16x3_kernel: BQ = 64, BN = 64 * NT)
+  int t32 = 0;  // 1: the 32 x 32 x 2 tiles (dist_mfma32_kernel: BQ = 64, BN = 128, one plan)
+  int b3 = 0;   // 1: the split-bf16 form (dist_bf16x3_tiled_kernel: BQ = 64, BN = 64 * NT)
 };
 
 MfmaPlan plan_mfma(int nq, int n_range, int dim, bool fp32_only) {
   // The split-bf16 coarse pass (round 4): the matrix cores stop being the bound, the rows' stream from HBM is.  Tiles of
   // 64 queries x 128 rows when those alone fill the CUs twice, 64 rows otherwise; K split until ~512 work-groups.
-  static const bool no_b3 = getenv("GLOC3D_KNN_NO_BF16X3") != nullptr;  // developer switch
-  if (!fp32_only && !no_b3 && dim % 8 == 0 && dim >= 8) {
+  if (!fp32_only && dim % 8 == 0 && dim >= 8) {
     const int qblocks = (nq + 63) / 64;
-    int nt = ((long long)((n_range + 127) / 128) * qblocks >= 512) ? 2 : 1;
-    int ks = 1;
-    if (const char* e = getenv("GLOC3D_KNN_B3")) {  // developer override: "NT,KS"
-      int a = 0, b = 0;
-      if (sscanf(e, "%d,%d", &a, &b) == 2 && (a == 1 || a == 2) && b >= 1 && b <= 16) nt = a, ks = -b;
-    }
+    const int nt = ((long long)((n_range + 127) / 128) * qblocks >= 512) ? 2 : 1;
     const long long tiles = (long long)((n_range + 64 * nt - 1) / (64 * nt)) * qblocks;
-    if (ks < 0) {
-      ks = -ks;
-      while (ks > 1 && !((dim % (64 * ks)) == 0 && dim / ks >= 128)) ks /= 2;
-    } else {
-      while (tiles * ks < 512 && ks < 16 && (dim % (64 * ks * 2)) == 0 && dim / (ks * 2) >= 128) ks *= 2;
-    }
+    int ks = 1;
+    while (tiles * ks < 512 && ks < 16 && (dim % (64 * ks * 2)) == 0 && dim / (ks * 2) >= 128) ks *= 2;
     MfmaPlan b{4, nt, ks, 64, 64 * nt};
     b.b3 = 1;
     return b;
@@ -322,8 +307,7 @@ MfmaPlan plan_mfma(int nq, int n_range, int dim, bool fp32_only) {
     int KS = 1;
     // (one block of queries over >= 64 row tiles: two work-groups per CU overlap each other's LDS hand-offs;
     // measured at 64 x 10 000 and 25 x 4541 x 4096: -4 / -3 us; 128 x 16 000 and 32 x 2000: +4 us, so not there)
-    static const long long wgs_env = getenv("GLOC3D_MFMA_WGS") ? atoll(getenv("GLOC3D_MFMA_WGS")) : 0;  // developer override
-    const long long want_wgs = wgs_env ? wgs_env : ((qblocks == 1 && tiles >= 64) ? 400 : 200);
+    const long long want_wgs = (qblocks == 1 && tiles >= 64) ? 400 : 200;
     while (tiles * KS < want_wgs && KS < 16 && (dim % (64 * KS * 2)) == 0 && dim / (KS * 2) >= 128) KS *= 2;
     const int klen = (dim + KS - 1) / KS;
     const long long wgs = tiles * KS;
@@ -340,24 +324,9 @@ MfmaPlan plan_mfma(int nq, int n_range, int dim, bool fp32_only) {
   // per flop.  Measured at 64 x 125 000 x 4096: 794 us against 922 with the 16 x 16 x 4 tiles (BN = 128, K-step 32, three
   // work-groups per CU).  At 64 x 10 000 the launch is ONE round of work-groups and the tile that divides 10 000 rows
   // into 500 of them (BN = 80, split-K 4) wins: 82 us against 92 - 116 for every 32-wide plan.
-  static const bool no_t32 = getenv("GLOC3D_MFMA_NO_T32") != nullptr;
-  if (nq > 32 && !no_t32 && (long long)((n_range + 127) / 128) * ((nq + 63) / 64) >= 3 * 256) {
+  if (nq > 32 && (long long)((n_range + 127) / 128) * ((nq + 63) / 64) >= 3 * 256) {
     best = MfmaPlan{4, 2, 1, 64, 128};
     best.t32 = 1;
-  }
-  // developer override: GLOC3D_MFMA_T32="NT,KS" -- the 32 x 32 x 2 tiles with NT tiles per wave and KS splits of K
-  if (const char* e = getenv("GLOC3D_MFMA_T32")) {
-    int nt = 0, ks = 0;
-    if (sscanf(e, "%d,%d", &nt, &ks) == 2 && (nt == 1 || nt == 2) && ks > 0 && nq > 32) {
-      best = MfmaPlan{4, nt, ks, 64, 64 * nt};
-      best.t32 = 1;
-    }
-  }
-  // developer override: GLOC3D_MFMA_PLAN="NT,KS"
-  if (const char* e = getenv("GLOC3D_MFMA_PLAN")) {
-    int nt = 0, ks = 0;
-    if (sscanf(e, "%d,%d", &nt, &ks) == 2 && nt > 0 && ks > 0)
-      best = MfmaPlan{WQ, nt, ks, BQ, 16 * nt * (4 / WQ)};
   }
   return best;
 }
@@ -368,8 +337,7 @@ void launch_mfma_inst(gloc_knn* h, const MfmaPlan& p, const float* d_q, int nq, 
   dim3 grid((unsigned)((n_range + p.BN - 1) / p.BN), (unsigned)((nq + p.BQ - 1) / p.BQ),
             (unsigned)p.KS);
   const int kps = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
-  static const int bk = getenv("GLOC3D_MFMA_BK") ? atoi(getenv("GLOC3D_MFMA_BK")) : 64;
-  if (bk == 32 || kps < 128)
+  if (kps < 128)
     hipLaunchKernelGGL((dist_mfma_kernel<WQ, NT, 8>), grid, dim3(256), 0, h->stream,
                        h->rows.as<float>(), d_q, h->dist.as<float>(), (int)h->dim, first, n_range,
                        nq, kps, ld, strideP);
@@ -377,6 +345,37 @@ void launch_mfma_inst(gloc_knn* h, const MfmaPlan& p, const float* d_q, int nq, 
     hipLaunchKernelGGL((dist_mfma_kernel<WQ, NT, 16>), grid, dim3(256), 0, h->stream,
                        h->rows.as<float>(), d_q, h->dist.as<float>(), (int)h->dim, first, n_range,
                        nq, kps, ld, strideP);
+}
+
+// The split-bf16 coarse pass over the mirror.  Its LDS image may exceed the 48-KB default, and the attribute that allows
+// more belongs to the device's copy of the kernel: set once per kernel and device.
+template <auto KERNEL>
+int allow_lds(int device, int bytes) {
+  static std::atomic<uint64_t> done{0};  // bit d: set on device d
+  const uint64_t bit = 1ull << (device & 63);
+  if (bytes > 48 * 1024 && !(done.load(std::memory_order_relaxed) & bit)) {
+    GLOC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.fetch_or(bit, std::memory_order_relaxed);
+  }
+  return GLOC_OK;
+}
+template <int NT, bool QRAW>
+int launch_bf16x3(gloc_knn* h, dim3 grid, const float* qsrc, size_t first, int n_range, int nq, int kps, size_t ld,
+                  size_t strideP, bool use_bmin, int n_blocks) {
+  constexpr int lds_bytes = b3_lds_bytes<NT>();
+  if (use_bmin) {
+    GLOC_TRY((allow_lds<dist_bf16x3_tiled_kernel<NT, QRAW, true>>(h->device, lds_bytes)));
+    hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT, QRAW, true>), grid, dim3(256), lds_bytes, h->stream, h->mirror.as<u32x4>(),
+                       qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps, ld, strideP, h->norms.as<float>(),
+                       h->bmin.as<float>(), n_blocks);
+  } else {
+    GLOC_TRY((allow_lds<dist_bf16x3_tiled_kernel<NT, QRAW>>(h->device, lds_bytes)));
+    hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT, QRAW>), grid, dim3(256), lds_bytes, h->stream, h->mirror.as<u32x4>(),
+                       qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps, ld, strideP, (const float*)nullptr,
+                       (float*)nullptr, 0);
+  }
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
 }
 
 // *finalized: the result (indices, distances) has been written through `fo` already -- no finalize launch
@@ -400,9 +399,8 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
   int n_blocks = 0;
   if (p.b3) {
     // few work-groups: each splits its queries itself; many: once, ahead of the launch
-    dim3 grid((unsigned)((n_range + p.BN - 1) / p.BN), (unsigned)((nq + p.BQ - 1) / p.BQ), (unsigned)p.KS);
-    static const int qraw_env = getenv("GLOC3D_KNN_B3_QRAW") ? atoi(getenv("GLOC3D_KNN_B3_QRAW")) : -1;  // developer switch
-    const bool qraw = qraw_env >= 0 ? qraw_env != 0 : (long long)grid.x * grid.y * grid.z <= 768;  // (64 x 125 000, 977 work-groups: 456 us split ahead, 461 in-kernel)
+    const dim3 grid((unsigned)((n_range + p.BN - 1) / p.BN), (unsigned)((nq + p.BQ - 1) / p.BQ), (unsigned)p.KS);
+    const bool qraw = (long long)grid.x * grid.y * grid.z <= 768;  // (64 x 125 000, 977 work-groups: 456 us split ahead, 461 in-kernel)
     const float* qsrc = d_q;
     if (!qraw) {
       ProfScope ps(h->prof, "split_queries", h->stream);
@@ -413,94 +411,25 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
       qsrc = h->qsplit.as<float>();
     }
     ProfScope ps(h->prof, "dist_mfma", h->stream);
+    // the rows from their tiled, pre-split mirror (round 6), which every add keeps when dim % 8 == 0
+    GLOC_REQUIRE(h->mirror.p, GLOC_ERR_STATE, "internal: the split-bf16 coarse pass without the rows' mirror");
     const int kps3 = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
-    static const bool no_mirror = getenv("GLOC3D_KNN_NO_MIRROR") != nullptr;  // developer switch: the row-major kernel
-    if (!no_mirror && h->mirror.p) {
-      // the rows from their tiled, pre-split mirror: contiguous 8-KB runs per tile and step (round 6)
-      const dim3 tgrid((unsigned)((first % MIR_ROWS + (size_t)n_range + p.BN - 1) / p.BN), grid.y, grid.z);
-      // a large window in one K-split: the epilogue leaves block minima for the selection (select_blocks_body)
-      static const bool no_bmin = getenv("GLOC3D_KNN_NO_BLOCKMIN") != nullptr;  // developer switch: the slices
-      n_blocks = (int)tgrid.x * (p.BN / 32);
-      use_bmin = !no_bmin && n_range > SELQ_MAX_ROWS && p.KS == 1 && n_blocks <= SELQ_MAX_ROWS && KC <= SRR_KC &&
-                 (int)h->dim <= 4 * SRR_G && !getenv("GLOC3D_KNN_NO_FUSED_RERANK");
-      if (use_bmin) {
-        GLOC_TRY(h->bmin.ensure((size_t)nq * n_blocks * sizeof(float), h->stream));
-      }
-#define B3T(NT_, QR_)                                                                                                  \
-  do {                                                                                                                \
-    constexpr int lds_bytes = b3_lds_bytes<NT_, 4>();                                                                 \
-    static std::atomic<uint64_t> attr_set{0};                                                                         \
-    const uint64_t dev_bit = 1ull << (h->device & 63);                                                                \
-    if (lds_bytes > 48 * 1024 && !(attr_set.load(std::memory_order_relaxed) & dev_bit)) {                            \
-      GLOC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dist_bf16x3_tiled_kernel<NT_, QR_>),                \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));                          \
-      attr_set.fetch_or(dev_bit, std::memory_order_relaxed);                                                          \
-    }                                                                                                                 \
-    if (use_bmin) {                                                                                                   \
-      static std::atomic<uint64_t> attr_set_b{0};                                                                     \
-      if (lds_bytes > 48 * 1024 && !(attr_set_b.load(std::memory_order_relaxed) & dev_bit)) {                         \
-        GLOC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dist_bf16x3_tiled_kernel<NT_, QR_, true>),        \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));                        \
-        attr_set_b.fetch_or(dev_bit, std::memory_order_relaxed);                                                      \
-      }                                                                                                               \
-      hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT_, QR_, true>), tgrid, dim3(256), lds_bytes, h->stream,          \
-                         h->mirror.as<u32x4>(), qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps3, ld, \
-                         strideP, h->norms.as<float>(), h->bmin.as<float>(), n_blocks);                               \
-    } else {                                                                                                          \
-      hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT_, QR_>), tgrid, dim3(256), lds_bytes, h->stream,                \
-                         h->mirror.as<u32x4>(), qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps3, ld, \
-                         strideP, (const float*)nullptr, (float*)nullptr, 0);                                         \
-    }                                                                                                                 \
-  } while (0)
-      if (p.NT == 1) { if (qraw) B3T(1, true); else B3T(1, false); }
-      else { if (qraw) B3T(2, true); else B3T(2, false); }
+    const dim3 tgrid((unsigned)((first % MIR_ROWS + (size_t)n_range + p.BN - 1) / p.BN), grid.y, grid.z);
+    // a large window in one K-split: the epilogue leaves block minima for the selection (select_blocks_body)
+    n_blocks = (int)tgrid.x * (p.BN / 32);
+    use_bmin = n_range > SELQ_MAX_ROWS && p.KS == 1 && n_blocks <= SELQ_MAX_ROWS && KC <= SRR_KC && (int)h->dim <= 4 * SRR_G;
+    if (use_bmin) GLOC_TRY(h->bmin.ensure((size_t)nq * n_blocks * sizeof(float), h->stream));
+#define B3T(NT_, QR_) launch_bf16x3<NT_, QR_>(h, tgrid, qsrc, first, n_range, nq, kps3, ld, strideP, use_bmin, n_blocks)
+    if (p.NT == 1) GLOC_TRY(qraw ? B3T(1, true) : B3T(1, false));
+    else GLOC_TRY(qraw ? B3T(2, true) : B3T(2, false));
 #undef B3T
-      GLOC_HIP(hipGetLastError());
-    } else {
-    static const int phase = getenv("GLOC3D_KNN_B3_PHASE") ? atoi(getenv("GLOC3D_KNN_B3_PHASE")) : 5;  // developer switch
-#define B3(NT_, QR_, KO_)                                                                                             \
-  do {                                                                                                                \
-    constexpr int lds_bytes = b3_lds_bytes<NT_, KO_>();                                                               \
-    static std::atomic<uint64_t> attr_set{0}; /* bit d: done on device d (the attribute belongs to the device's copy) */ \
-    const uint64_t dev_bit = 1ull << (h->device & 63);                                                                \
-    if (lds_bytes > 48 * 1024 && !(attr_set.load(std::memory_order_relaxed) & dev_bit)) {                            \
-      GLOC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dist_bf16x3_kernel<NT_, QR_, KO_>),                 \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));                          \
-      attr_set.fetch_or(dev_bit, std::memory_order_relaxed);                                                          \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((dist_bf16x3_kernel<NT_, QR_, KO_>), grid, dim3(256), lds_bytes, h->stream,                    \
-                       h->rows.as<float>(), qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps3, ld,     \
-                       strideP, phase);                                                                               \
-  } while (0)
-#define B3Q(NT_, KO_)          \
-  do {                         \
-    if (qraw)                  \
-      B3(NT_, true, KO_);      \
-    else                       \
-      B3(NT_, false, KO_);     \
-  } while (0)
-    // (steps of 64 k -- KO = 8, 256 contiguous bytes of a row per step -- measured no faster at either size: 444 / 479 us
-    // against 456 / 448 at 64 x 125 000, and slower at 64 x 10 000; only the 32-k instances are built)
-    if (p.NT == 1) B3Q(1, 4);
-    else B3Q(2, 4);
-#undef B3Q
-#undef B3
-    GLOC_HIP(hipGetLastError());
-    }
   } else if (p.t32) {
     ProfScope ps(h->prof, "dist_mfma", h->stream);
+    // (plan_mfma's one 32 x 32 plan: NT = 2, and steps of 32 k)
     dim3 grid((unsigned)((n_range + p.BN - 1) / p.BN), (unsigned)((nq + p.BQ - 1) / p.BQ), (unsigned)p.KS);
     const int kps32 = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
-    static const int bk32 = getenv("GLOC3D_MFMA_BK") ? atoi(getenv("GLOC3D_MFMA_BK")) : 32;
-#define MF32(NT_, KQ_)                                                                                             \
-  hipLaunchKernelGGL((dist_mfma32_kernel<NT_, KQ_>), grid, dim3(256), 0, h->stream, h->rows.as<float>(), d_q,      \
-                     h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps32, ld, strideP)
-    if (bk32 == 32 || kps32 < 128) {
-      if (p.NT == 1) MF32(1, 8); else MF32(2, 8);
-    } else {
-      if (p.NT == 1) MF32(1, 16); else MF32(2, 16);
-    }
-#undef MF32
+    hipLaunchKernelGGL((dist_mfma32_kernel<2, 8>), grid, dim3(256), 0, h->stream, h->rows.as<float>(), d_q,
+                       h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps32, ld, strideP);
     GLOC_HIP(hipGetLastError());
   } else {
     ProfScope ps(h->prof, "dist_mfma", h->stream);
@@ -521,15 +450,13 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
   const float u = 5.9604645e-8f;
   const int kps = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
   const float eps_rel_d = 1.05f * u * (float)(h->dim / 4 + 4);
-  static const float eps_scale = getenv("GLOC3D_KNN_EPS_SCALE") ? (float)atof(getenv("GLOC3D_KNN_EPS_SCALE")) : 1.f;  // dev
   //   split-bf16 form: the dropped product terms 3.03 * 2^-16 = 776 u (knn_kernels.hpp), and its chains are 3 x 64
   //   products long with the accumulation inside an MFMA priced as truncating adds (2 u each): 384 for the 64
   const float chain_u = p.b3 ? 776.f + 384.f : 64.f;
-  const float eps_rel_n = eps_scale * 1.05f * u * (chain_u + (float)((kps + 63) / 64 + p.KS + h->dim / 64 + 6 + 3 + 4));
-  static const bool no_fused = getenv("GLOC3D_KNN_NO_FUSED_RERANK") != nullptr;  // developer switch: the three launches
+  const float eps_rel_n = 1.05f * u * (chain_u + (float)((kps + 63) / 64 + p.KS + h->dim / 64 + 6 + 3 + 4));
   const bool large = n_range > SELQ_MAX_ROWS;  // slices first; an incomplete query is flagged for the host
   SlicePlan sl{1, 0};
-  const bool fused = (!large || use_bmin || plan_slices(n_range, nq, KC, &sl)) && KC <= SRR_KC && (int)h->dim <= 4 * SRR_G && !no_fused;
+  const bool fused = (!large || use_bmin || plan_slices(n_range, nq, KC, &sl)) && KC <= SRR_KC && (int)h->dim <= 4 * SRR_G;
   if (fused) {
     // select + re-rank + completeness check in one launch, one work-group per query
     if (large && use_bmin) {  // round 6: from the coarse kernel's block minima -- 32 x KC partial dots per query, not the window's:
@@ -544,7 +471,7 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
   dim3(nq), dim3(SELQ_THREADS), 0, h->stream, h->dist.as<float>(), ld, strideP, p.KS, d_q, (int)h->dim,                  \
       h->norms.as<float>(), first, n_range, KC, k, h->rows.as<float>(), h->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n, \
       h->qnorm.as<float>(), d_keys_out, h->flags.as<int>(), h->n_incomplete.as<unsigned long long>(), fo,                \
-      h->dist.as<float>(), h->dev_trace.as<unsigned long long>()
+      h->dist.as<float>()
     if (large)
       hipLaunchKernelGGL(select_rerank_kernel<true>, SRR_ARGS, h->klists.as<uint64_t>(), use_bmin ? SELB_LIST : sl.S * KC,
                          use_bmin ? h->bmin.as<float>() : (const float*)nullptr, n_blocks, h->klists.as<uint64_t>());
@@ -594,8 +521,7 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
     // behind a host synchronisation, ~35 us of a 460-us search over a 125 000-row shard).
     // (The coarse partial dots in h->dist are dead by now: the exact distances of the flagged queries
     // reuse the buffer, row q at q * ld.)
-    static const bool no_redo1 = getenv("GLOC3D_KNN_NO_REDO1") != nullptr;  // developer switch: the three launches
-    if (fused && large && k <= 64 && !no_redo1) {
+    if (fused && large && k <= 64) {
       // ONE launch (round 6): every work-group walks the flags and leaves when none is set; a flagged query's exact
       // distances, slice selections and final selection happen inside it (flagged_redo_kernel)
       int S = std::max(1, (n_range + 2047) / 2048);
@@ -677,9 +603,8 @@ int search_device_impl(gloc_knn* h, const float* d_q, size_t nq, size_t k, size_
     size_t qblk = (size_t)(2ull << 30) / (ld * sizeof(float) * 4);
     qblk = std::min<size_t>(1024, std::max<size_t>(64, qblk / 64 * 64));
     // the coarse form of this search (see h_inc): look at the last tracked search's count if its copy has landed
-    static const bool no_adapt = getenv("GLOC3D_KNN_NO_ADAPT") != nullptr;  // developer switch
     bool tracked = false;
-    if (algo == GLOC_KNN_ALGO_MFMA && !no_adapt) {
+    if (algo == GLOC_KNN_ALGO_MFMA) {
       if (h->inc_pending && hipEventQuery(h->inc_ev) == hipSuccess) {
         const unsigned long long now = *h->h_inc, delta = now - h->inc_seen;
         h->inc_seen = now;
@@ -799,7 +724,6 @@ int gloc_knn_destroy(gloc_knn* h) {
   h->keys2.release();
   h->qnorm.release();
   h->qsplit.release();
-  h->dev_trace.release();
   h->flags.release();
   h->redo_tickets.release();
   h->bmin.release();
@@ -819,23 +743,6 @@ int gloc_knn_set_stream(gloc_knn* h, void* hip_stream) {
   GLOC_HIP(hipSetDevice(h->device));
   GLOC_HIP(hipStreamSynchronize(h->stream));
   h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
-  return GLOC_OK;
-}
-
-// Developer aid (not part of include/gloc3d.h): phase stamps [nq][16] of the LAST fused select + re-rank launch.
-int gloc_knn_debug_trace(gloc_knn* h, int enable_nq, unsigned long long* out, size_t n_words) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  if (out && h->dev_trace.p) {
-    GLOC_HIP(hipMemcpyAsync(out, h->dev_trace.p, n_words * 8, hipMemcpyDeviceToHost, h->stream));
-    GLOC_HIP(hipStreamSynchronize(h->stream));
-  }
-  if (enable_nq > 0) {
-    GLOC_TRY(h->dev_trace.ensure((size_t)enable_nq * 128, h->stream));
-  } else if (enable_nq < 0) {
-    GLOC_HIP(hipStreamSynchronize(h->stream));
-    h->dev_trace.release();
-  }
   return GLOC_OK;
 }
 

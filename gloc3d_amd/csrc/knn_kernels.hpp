@@ -582,8 +582,8 @@ __global__ __launch_bounds__(256) void dist_mfma32_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------
 // K1 (split-bf16 form; round 4): the partial dots on the bf16 matrix cores (16 x the fp32 MFMA rate), so that the
 // coarse pass is bound by the stream of the rows from HBM and not by v_mfma_f32_32x32x2_f32 (64 x 125 000 x 4096:
-// 417 us of fp32 MFMA at its peak against 256 us of HBM).  Every fp32 operand x is cut in two bf16 values on its way
-// into LDS, h = bf16(x) and m = bf16(x - h) (x - h is exact in fp32; both conversions round to nearest), and a
+// 417 us of fp32 MFMA at its peak against 256 us of HBM).  Every fp32 operand x is cut in two bf16 values,
+// h = bf16(x) and m = bf16(x - h) (x - h is exact in fp32; both conversions round to nearest), and a
 // product is taken as  qh dh + qh dm + qm dh  -- three v_mfma_f32_32x32x16_bf16 (32 cycles each for K = 16) in place of
 // eight v_mfma_f32_32x32x2_f32 (64 cycles each).  What is dropped, qm dm + (q - qh - qm) d + (qh + qm)(d - dh - dm), is
 // at most 3.03 * 2^-16 |q_i| |d_i| per term (|x - h| <= 2^-8 |x|, |x - h - m| <= 2^-16 |x|): the coarse distance stays a
@@ -591,9 +591,7 @@ __global__ __launch_bounds__(256) void dist_mfma32_kernel(const float* __restric
 // is every bit of the result.  Products of two bf16 values are exact in fp32; the accumulation inside an MFMA is
 // priced as K sequential truncating adds (two units in the last place each), flushed every 64 k as in the fp32 forms.
 // The queries are split once per search (split_queries_kernel: [q][k / 8][8 bf16 h | 8 bf16 m], the fp32 row's own
-// addressing); the rows are split by the work-group that streams them (3 VALU operations per element).
-// Work-group = 4 waves, 2 along the queries (64) x 2 along the rows (BN = 64 NT); LDS image [h | m][k / 8][row][16 B]:
-// one ds_read_b128 is a lane's whole K = 16 fragment half (lane l: row l % 32, k = 8 (l / 32) + j).
+// addressing) or by the work-group that loads them; the rows once, when they are added (mirror_rows_kernel, below).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -630,200 +628,16 @@ __global__ __launch_bounds__(256) void split_queries_kernel(const float* __restr
   o[1] = m;
 }
 
-// QRAW: `qsplit` holds the fp32 queries themselves and the work-group splits them as it does the rows (a launch of few
-// work-groups: cheaper than the split kernel's launch ahead of it).
-// KO: planes of 8 k per step (4: steps of 32 k, 128 contiguous bytes of a row per step; 8: steps of 64 k, 256 bytes).
-// LDS is dynamic: 2 buffers x [h | m] x KO planes x PLANE slots of 16 B.
-template <int NT, int KO>
-constexpr int b3_lds_bytes() {
-  return 2 * 2 * KO * (64 + 64 * NT + 2) * 16;
-}
-template <int NT, bool QRAW, int KO>
-__global__ __launch_bounds__(256) void dist_bf16x3_kernel(const float* __restrict__ db,
-                                                          const float* __restrict__ qsplit /* split_queries_kernel */,
-                                                          float* __restrict__ P, int dim, size_t first_row, int n_range,
-                                                          int nq, int k_per_split, size_t ldP, size_t strideP,
-                                                          int phase /* groups of 64 k per row tile, 0: none */) {
-  constexpr int BQ = 64;
-  constexpr int BN = 64 * NT;
-  constexpr int ROWS = BQ + BN;
-  // 16-B slots per k / 8 plane, = 2 mod 8: the eight lanes of a ds_write_b128 group (two rows x four planes) fall on
-  // eight different slots of the 128-B bank row (PLANE = ROWS + 1: two-way, a third of all LDS cycles by the counters)
-  constexpr int PLANE = ROWS + 2;
-  constexpr int BK = 8 * KO;
-  static_assert(KO == 4 || KO == 8, "steps of 32 or 64 k");
-  constexpr int NQ = BQ * KO / 256;  // 8-float chunks per thread and step: of the queries,
-  constexpr int ND = BN * KO / 256;  // of the rows
-  extern __shared__ u32x4 lds[];     // [buffer][h | m][plane][row]
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wq = w & 1, wn = w >> 1;
-  const int n0 = blockIdx.x * BN;
-  const int q0 = blockIdx.y * BQ;
-  const int kbeg = blockIdx.z * k_per_split;
-  const int kend = (kbeg + k_per_split) < dim ? (kbeg + k_per_split) : dim;
-  // Every work-group starts its walk over k at another group of 64 k and wraps around (rows are 16 KB apart: work-groups
-  // that walk in step ask for the same offset of every row at the same time, and the addresses of one moment differ in
-  // their upper bits only -- measured with loads alone: 5.5 TB/s in step, 6.4 TB/s out of step).  The groups' sums are
-  // added in the rotated order: the same number of additions, the same bound.  (Only when the split is whole groups.)
-  const int klen = kend - kbeg;
-  const int rot = (phase > 0 && klen % 64 == 0) ? (int)(((unsigned)blockIdx.x * (unsigned)phase) % (unsigned)(klen / 64)) * 64 : 0;
-
-  // slot = (row, plane): thread tid holds plane tid % KO of the tile rows (tid + 256 i) / KO -- queries first
-  const int ko8 = (tid % KO) * 8;
-  const float* qsrc[NQ];  // never null: rows outside the window (queries past nq) read the first one
-  const float* dsrc[ND];
-#pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-    const int qq = q0 + (tid + 256 * i) / KO;
-    qsrc[i] = qsplit + (size_t)(qq < nq ? qq : 0) * dim;
-  }
-#pragma unroll
-  for (int i = 0; i < ND; ++i) {
-    const int jj = n0 + (tid + 256 * i) / KO;
-    dsrc[i] = db + (first_row + (size_t)(jj < n_range ? jj : 0)) * dim;
-  }
-  struct Pre {
-    f32x4 q[NQ][2], d[ND][2];
-  };
-  // (the loads are left raw -- no select on a loaded value before its stage is stored, or the wait for it lands right
-  // behind the load and the two stages in flight are none: rows outside the window compute garbage nobody stores, and
-  // the chunks that can lie beyond kend, when the split's length is no multiple of the step, are zeroed at the store)
-  auto gload = [&](Pre& pre, int k) {
-    int kr = k + rot;  // (steps never straddle the wrap: rot and the steps are multiples of the step)
-    kr = kr >= kend ? kr - klen : kr;
-    const int kk = kr + ko8;
-    const int kc = kk < dim - 8 ? kk : dim - 8;
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      const f4u a = *reinterpret_cast<const f4u*>(qsrc[i] + kc), b = *reinterpret_cast<const f4u*>(qsrc[i] + kc + 4);
-      pre.q[i][0] = f32x4{a.x, a.y, a.z, a.w};
-      pre.q[i][1] = f32x4{b.x, b.y, b.z, b.w};
-    }
-#pragma unroll
-    for (int i = 0; i < ND; ++i) {
-      const f4u a = *reinterpret_cast<const f4u*>(dsrc[i] + kc), b = *reinterpret_cast<const f4u*>(dsrc[i] + kc + 4);
-      pre.d[i][0] = f32x4{a.x, a.y, a.z, a.w};
-      pre.d[i][1] = f32x4{b.x, b.y, b.z, b.w};
-    }
-  };
-  auto lstore = [&](const Pre& pre, int buf, int k) {
-    u32x4* Lh = lds + buf * 2 * KO * PLANE;
-    u32x4* Lm = Lh + KO * PLANE;
-    const int pl = (tid % KO) * PLANE;
-    const bool tail = k + BK > kend;             // uniform
-    const bool out = tail && k + ko8 >= kend;    // (kend - kbeg and dim are multiples of 8: a chunk is in or out whole)
-    const u32x4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      const int row = (tid + 256 * i) / KO;
-      if constexpr (QRAW) {
-        u32x4 h, m;
-        bf16_split8(pre.q[i][0], pre.q[i][1], h, m);
-        Lh[pl + row] = out ? z : h;
-        Lm[pl + row] = out ? z : m;
-      } else {
-        Lh[pl + row] = out ? z : __builtin_bit_cast(u32x4, pre.q[i][0]);
-        Lm[pl + row] = out ? z : __builtin_bit_cast(u32x4, pre.q[i][1]);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < ND; ++i) {
-      u32x4 h, m;
-      bf16_split8(pre.d[i][0], pre.d[i][1], h, m);
-      const int row = BQ + (tid + 256 * i) / KO;
-      Lh[pl + row] = out ? z : h;
-      Lm[pl + row] = out ? z : m;
-    }
-  };
-
-  // acc: the chain of one group of 64 k (its first MFMA takes a literal zero as C: nothing to clear), added to tot at the
-  // group's end.  The loop below walks two steps per turn, buffer 0 then buffer 1: with steps of 32 k buffer 0 opens
-  // a group and buffer 1 ends it; with steps of 64 k every step is a group.
-  f32x16 acc[NT], tot[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tot[t][r] = 0.f;
-  const int a_row = wq * 32 + (lane & 31);
-  const int b_row0 = BQ + wn * NT * 32 + (lane & 31);
-  auto compute = [&](int buf, auto opens) {
-    const u32x4* Lh = lds + buf * 2 * KO * PLANE;
-    const u32x4* Lm = Lh + KO * PLANE;
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) {
-      const int pl = (ks * 2 + (lane >> 5)) * PLANE;
-      const bf16x8 ah = __builtin_bit_cast(bf16x8, Lh[pl + a_row]), am = __builtin_bit_cast(bf16x8, Lm[pl + a_row]);
-      bf16x8 bh[NT], bm[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        bh[t] = __builtin_bit_cast(bf16x8, Lh[pl + b_row0 + t * 32]);
-        bm[t] = __builtin_bit_cast(bf16x8, Lm[pl + b_row0 + t * 32]);
-      }
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm[t], (decltype(opens)::value && ks == 0) ? zero : acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh[t], acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[t], acc[t], 0, 0, 0);
-    }
-  };
-  auto flush = [&]() {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) tot[t] += acc[t];
-  };
-  constexpr bool STEP_IS_GROUP = BK == 64;
-
-  Pre preA, preB;
-  gload(preA, kbeg);
-  lstore(preA, 0, kbeg);
-  gload(preA, kbeg + BK);
-  gload(preB, kbeg + 2 * BK);
-  __syncthreads();
-  for (int k = kbeg; k < kend; k += 2 * BK) {
-    compute(0, std::true_type{});
-    if constexpr (STEP_IS_GROUP) flush();
-    if (k + BK < kend) {
-      lstore(preA, 1, k + BK);
-      gload(preA, k + 3 * BK);
-      __syncthreads();
-      compute(1, std::integral_constant<bool, STEP_IS_GROUP>{});
-      if constexpr (STEP_IS_GROUP) flush();
-      if (k + 2 * BK < kend) {
-        lstore(preB, 0, k + 2 * BK);
-        gload(preB, k + 4 * BK);
-        __syncthreads();
-      }
-    }
-    if constexpr (!STEP_IS_GROUP) flush();  // the group's 64 k (fewer at the end of the split)
-  }
-  // C/D map of the 32x32 forms: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-  float* Pz = P + (size_t)blockIdx.z * strideP;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int j = n0 + (wn * NT + t) * 32 + (lane & 31);
-    if (j < n_range) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qq = q0 + wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        Pz[(size_t)qq * ldP + j] = tot[t][r];  // rows q >= nq land in the padded part of P
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Round 6 -- the coarse pass reads a MIRROR of the database: the rows already split into their two bf16 values and laid
 // out by TILES of 64 rows,  [tile][k / 8][h | m][row in tile][16 B = 8 bf16],  so that what a work-group needs for a step
 // of 32 k -- four planes of its tile -- is ONE contiguous run of 8 KB instead of 64 pieces of 128 B from rows 16 KB apart.
-// Why: the row-major kernel streams 5.0 - 5.3 TB/s however it walks (tools/dev_stream_pattern.hip, round 4: 128 rows per
-// work-group 5.1 - 5.6 TB/s whatever the piece per row, 8 rows per work-group 6.4 - 6.5): 768 resident work-groups x 128
+// Why: a kernel that streams the rows row-major gets 5.0 - 5.3 TB/s however it walks (tools/dev_stream_pattern.hip, round 4:
+// 128 rows per work-group 5.1 - 5.6 TB/s whatever the piece per row, 8 rows per work-group 6.4 - 6.5): 768 resident work-groups x 128
 // row streams are ~100 000 open rows against the stacks' ~10 000 banks, 768 contiguous streams are not.  The mirror
 // costs the database's size again in HBM (16 GB at a million rows of 288 GB) and is kept current by every add
-// (mirror_rows_kernel); the fp32 rows stay what the exact kernels and the re-rank read.  The split (3 VALU per element per
-// SEARCH in the row-major kernel) moves to the add as well.
+// (mirror_rows_kernel); the fp32 rows stay what the exact kernels and the re-rank read.  The rows are split once, at the
+// add, not by every search (3 VALU operations per element).
 constexpr int MIR_ROWS = 64;  // rows per tile
 __host__ __device__ __forceinline__ size_t mirror_tile_u32x4(int dim) { return (size_t)(dim / 8) * 2 * MIR_ROWS; }  // 16-B slots per tile
 
@@ -844,15 +658,22 @@ __global__ __launch_bounds__(256) void mirror_rows_kernel(const float* __restric
   t[MIR_ROWS] = m;
 }
 
-// The coarse pass over the mirror: the arithmetic, the LDS image and the MFMA sequence of dist_bf16x3_kernel; only where
-// the rows come from differs.  Tiles are aligned to ABSOLUTE row numbers: a window that starts inside a tile computes the
-// tile's leading rows too and stores nothing for them (row - first_row < 0).
+// The coarse pass over the mirror.  Work-group = 4 waves, 2 along the queries (64) x 2 along the rows (BN = 64 NT: NT tiles),
+// steps of 32 k; LDS image [buffer][h | m][k / 8][row][16 B]: one ds_read_b128 is a lane's whole K = 16 fragment half (lane
+// l: row l % 32, k = 8 (l / 32) + j).  LDS is dynamic (b3_lds_bytes).  Tiles are aligned to ABSOLUTE row numbers: a window
+// that starts inside a tile computes the tile's leading rows too and stores nothing for them (row - first_row < 0).
+// QRAW: `qsplit` holds the fp32 queries themselves and the work-group splits them as they go into LDS (a launch of few
+// work-groups: cheaper than the split kernel's launch ahead of it).
 // BMIN (round 6, one K-split, windows above 16 384 rows): the epilogue also leaves, per query and per BLOCK of 32 rows (a
 // wave's 32 x 32 accumulator), the minimum of  |d|^2 - 2 q.d  over the block's rows of the window -- the coarse distance
 // without the query's norm, which does not change an order.  The KC smallest coarse distances of the window lie in blocks
 // whose minimum is <= the KC-th smallest block minimum (that one is the minimum of KC distinct rows), so the selection that
 // follows reads 32 x KC partial dots per query instead of the window's (select_blocks_body): at 64 x 125 000, 1 MB instead
 // of 32 MB, one launch of 9 us instead of the slices' 28 - 34.
+template <int NT>
+constexpr int b3_lds_bytes() {  // 2 buffers x [h | m] x 4 planes x PLANE slots of 16 B
+  return 2 * 2 * 4 * (64 + 64 * NT + 2) * 16;
+}
 template <int NT, bool QRAW, bool BMIN = false>
 __global__ __launch_bounds__(256) void dist_bf16x3_tiled_kernel(const u32x4* __restrict__ mirror,
                                                                 const float* __restrict__ qsplit /* split_queries_kernel, or raw */,
@@ -865,6 +686,8 @@ __global__ __launch_bounds__(256) void dist_bf16x3_tiled_kernel(const u32x4* __r
   constexpr int BQ = 64;
   constexpr int BN = 64 * NT;
   constexpr int ROWS = BQ + BN;
+  // 16-B slots per k / 8 plane, = 2 mod 8: the eight lanes of a ds_write_b128 group of the queries (two rows x four planes)
+  // fall on eight different slots of the 128-B bank row (PLANE = ROWS + 1: two-way, a third of all LDS cycles by the counters)
   constexpr int PLANE = ROWS + 2;
   constexpr int BK = 8 * KO;
   constexpr int NQ = BQ * KO / 256;       // 8-float chunks of the queries per thread and step
@@ -897,6 +720,8 @@ __global__ __launch_bounds__(256) void dist_bf16x3_tiled_kernel(const u32x4* __r
     qsrc[i] = qsplit + (size_t)(qq < nq ? qq : 0) * dim;
   }
   // slot i of the thread: tile i / 2, then 16-B slot (i % 2) * 256 + tid of the step's 8-KB run = [plane][h | m][row]
+  // (the loads are left raw -- no select on a loaded value before its stage is stored, or the wait for it lands right
+  // behind the load and the two stages in flight are none: what lies beyond kend is zeroed at the store)
   struct Pre {
     f32x4 q[NQ][2];
     u32x4 d[ND];
@@ -948,6 +773,8 @@ __global__ __launch_bounds__(256) void dist_bf16x3_tiled_kernel(const u32x4* __r
     }
   };
 
+  // acc: the chain of one group of 64 k (its first MFMA takes a literal zero as C: nothing to clear), added to tot at the
+  // group's end.  The loop below walks two steps of 32 k per turn: buffer 0 opens a group and buffer 1 ends it.
   f32x16 acc[NT], tot[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -1246,8 +1073,7 @@ template <int MODE>
 __device__ __forceinline__ float selq_select(const float* __restrict__ row, size_t strideP, int n_splits,
                                              const float* __restrict__ qr, int dim, const float* __restrict__ dn,
                                              size_t first_row, int n_range, int K, uint64_t* buf /* [SEL_LIST] */,
-                                             float* qred /* [16] */, uint64_t* tau_s, int* cnt,
-                                             unsigned long long* st = nullptr /* dev: 4 stamps */) {
+                                             float* qred /* [16] */, uint64_t* tau_s, int* cnt) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   // the loads of the keys' operands go out before the norm's reduction (one memory round trip, not two)
   // (split by split with every key slot's load issued before the first use: the first form walked the
@@ -1310,10 +1136,8 @@ __device__ __forceinline__ float selq_select(const float* __restrict__ row, size
     }
     mn = key[e] < mn ? key[e] : mn;
   }
-  if (st && tid == 0) st[0] = __builtin_amdgcn_s_memtime();
   // 2: the wave's minima, sorted over its lanes
   uint64_t x = wave_sort_u64<true>(mn, lane);
-  if (st && tid == 0) st[1] = __builtin_amdgcn_s_memtime();
   // 3: tournament
   if (tid == 0) *cnt = 0;
 #pragma unroll
@@ -1328,7 +1152,6 @@ __device__ __forceinline__ float selq_select(const float* __restrict__ row, size
   }
   if (w == 0 && lane == K - 1) *tau_s = x;
   __syncthreads();
-  if (st && tid == 0) st[2] = __builtin_amdgcn_s_memtime();
   const uint64_t tau = *tau_s;
   // 4: everything <= tau (one LDS atomic per wave and key slot)
 #pragma unroll
@@ -1344,7 +1167,6 @@ __device__ __forceinline__ float selq_select(const float* __restrict__ row, size
     }
   }
   __syncthreads();
-  if (st && tid == 0) st[3] = __builtin_amdgcn_s_memtime();
   const int c = *cnt < SEL_LIST ? *cnt : SEL_LIST;
   if (c <= 64) {  // 5: the usual case -- one wave, in registers
     uint64_t v = KEY_SENTINEL;
@@ -1757,8 +1579,7 @@ constexpr int SRR_LD = SRR_G + 4;    // floats per candidate row: 16 bytes of sh
 // groups while waves 4-15 form the group sums of chunk c + 1 (three rows per wave: random 16-KB reads from
 // HBM); a barrier per chunk hands the chunks over.  (Unpipelined: 6.0 + 5.9 us; the sums now hide behind the chains.)
 __device__ __forceinline__ void srr_exact_batch(const float* __restrict__ db, const float* qs, int dim,
-                                                const uint32_t* rows_s, int m, float* S, float* exact_s,
-                                                unsigned long long* stamp = nullptr /* dev: [1] = after the first chunk's sums */) {
+                                                const uint32_t* rows_s, int m, float* S, float* exact_s) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int G = dim >> 2;
   const int n_chunks = (G + 255) / 256;
@@ -1801,7 +1622,6 @@ __device__ __forceinline__ void srr_exact_batch(const float* __restrict__ db, co
   float acc = 0.f;
   if (summing) sums(0);
   __syncthreads();
-  if (stamp && tid == 0) stamp[0] = __builtin_amdgcn_s_memtime();
   for (int ch = 0; ch < n_chunks; ++ch) {
     if (summing) {
       if (ch + 1 < n_chunks) sums(ch + 1);
@@ -1868,11 +1688,9 @@ __global__ __launch_bounds__(SELQ_THREADS) void select_rerank_kernel(
     const float* __restrict__ db, const uint32_t* __restrict__ dn_max_bits, float eps_rel_d, float eps_rel_n,
     float* __restrict__ qn_out, uint64_t* __restrict__ out_keys /* [nq][k] */, int* __restrict__ flags,
     unsigned long long* __restrict__ n_incomplete, FinalOut fo, float* __restrict__ dist_scratch /* = P: row q of split 0 is this query's */,
-    unsigned long long* __restrict__ dev_trace /* dev only: [nq][8] phase stamps, or null */,
     const uint64_t* __restrict__ lists = nullptr, int n_list = 0,
     const float* __restrict__ bmin = nullptr /* LISTS: != null -- the lists are made HERE from the coarse kernel's block minima [NB][nq] */,
     int NB = 0, uint64_t* __restrict__ blist = nullptr /* [nq][SELB_LIST]: room for them */) {
-  const unsigned long long t_start = dev_trace ? __builtin_amdgcn_s_memtime() : 0ull;
   __shared__ uint64_t buf[SEL_LIST];
   __shared__ float qred[SELQ_THREADS / 64];
   __shared__ uint64_t tau_s;
@@ -1897,16 +1715,10 @@ __global__ __launch_bounds__(SELQ_THREADS) void select_rerank_kernel(
       lq = mine;
       nl = SELB_LIST;
     }
-    qnv = selq_select<2>(reinterpret_cast<const float*>(lq), 0, 1, qp, dim, dn, 0, nl, KC, buf,
-                         qred, &tau_s, &cnt, dev_trace ? dev_trace + q * 16 + 8 : nullptr);
+    qnv = selq_select<2>(reinterpret_cast<const float*>(lq), 0, 1, qp, dim, dn, 0, nl, KC, buf, qred, &tau_s, &cnt);
   } else
-    qnv = selq_select<1>(P + (size_t)q * ld, strideP, n_splits, qp, dim, dn, first_row, n_range, KC, buf,
-                         qred, &tau_s, &cnt, dev_trace ? dev_trace + q * 16 + 8 : nullptr);
+    qnv = selq_select<1>(P + (size_t)q * ld, strideP, n_splits, qp, dim, dn, first_row, n_range, KC, buf, qred, &tau_s, &cnt);
   if (tid == 0) qn_out[q] = qnv;
-  if (dev_trace && tid == 0) {
-    dev_trace[q * 16 + 0] = t_start;
-    dev_trace[q * 16 + 1] = __builtin_amdgcn_s_memtime();
-  }
   // the prefix of candidates that gets reference-order distances (every wave computes the same values)
   const uint64_t ck = (lane < KC) ? buf[lane] : KEY_SENTINEL;
   const bool valid = ck != KEY_SENTINEL;
@@ -1926,9 +1738,7 @@ __global__ __launch_bounds__(SELQ_THREADS) void select_rerank_kernel(
   float* qs = reinterpret_cast<float*>(buf);
   srr_stage_query(qp, dim, qs);
   __syncthreads();
-  if (dev_trace && tid == 0) dev_trace[q * 16 + 2] = __builtin_amdgcn_s_memtime();
-  srr_exact_batch(db, qs, dim, rows_s, m, S, exact_s, dev_trace ? dev_trace + q * 16 + 3 : nullptr);
-  if (dev_trace && tid == 0) dev_trace[q * 16 + 4] = __builtin_amdgcn_s_memtime();
+  srr_exact_batch(db, qs, dim, rows_s, m, S, exact_s);
   // F: rank the exact keys (distinct: distinct rows)
   if (w == 0) {
     const uint64_t ek = (lane < m) ? make_key(exact_s[lane], (uint32_t)ck) : KEY_SENTINEL;
@@ -1949,10 +1759,6 @@ __global__ __launch_bounds__(SELQ_THREADS) void select_rerank_kernel(
     if (lane == 0) {
       flags[q] = complete ? 0 : 1;
       if (!complete && n_incomplete) atomicAdd(n_incomplete, 1ull);
-      if (dev_trace) {
-        dev_trace[q * 16 + 5] = __builtin_amdgcn_s_memtime();
-        dev_trace[q * 16 + 6] = (unsigned long long)m;
-      }
     }
   }
   // (a window above 16 384 rows is not searched exactly by ONE work-group -- 16 GB through one CU at a million rows: the

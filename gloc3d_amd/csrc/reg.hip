@@ -180,8 +180,7 @@ int setup_split(gloc_reg* h, const BatchDims& bd, int cs) {
   sp.hx = hx;
   // (the chained launch hides a job's longest wave behind the other jobs' work, so fewer groups need splitting: one query
   // alone, registration of 20 jobs, threshold 45 / 60 / 75 / 90 / 120 thousand cycles: 2.92 / 2.89 / 2.79 / 2.78 / 3.03 ms)
-  static const bool chain_off = getenv("GLOC3D_NN_NO_CHAIN") != nullptr;  // developer switch (chain_passes)
-  const bool chains = h->nn_chain && !h->chain_broken && !h->prof.enabled && !h->trace_on && cs == 2 && bd.n_jobs < 48 && !chain_off;
+  const bool chains = h->nn_chain && !h->chain_broken && !h->prof.enabled && !h->trace_on && cs == 2 && bd.n_jobs < 48;
   sp.thresh = h->nn_split_thresh_set || !chains ? h->nn_split_thresh : 85000u;
   return GLOC_OK;
 }
@@ -191,11 +190,9 @@ int setup_split(gloc_reg* h, const BatchDims& bd, int cs) {
 int setup_heavy(gloc_reg* h, const BatchDims& bd, int cs, uint32_t G = 1) {
   for (uint32_t g = 0; g < gloc_reg::MAX_SUB; ++g) h->heavy_of[g] = NnHeavy{};
 #ifdef GLOC_NN_R5_COLD
-  static const bool off = true;
-#else
-  static const bool off = getenv("GLOC3D_NN_NO_HEAVY") != nullptr;  // developer switch
+  return GLOC_OK;  // (round 5's cold pass keeps no lists)
 #endif
-  if (h->nn_mode == 1 || cs != 2 || h->nn_heavy_thresh <= 0 || off || h->trace_on) return GLOC_OK;
+  if (h->nn_mode == 1 || cs != 2 || h->nn_heavy_thresh <= 0 || h->trace_on) return GLOC_OK;
   const size_t per = ((size_t)bd.n_jobs + G - 1) / G;
   const size_t cap = std::min<size_t>(per * 16, 16384), S = 64 * (size_t)cs;
   hipStream_t s = h->stream;
@@ -353,13 +350,11 @@ int launch_nn(gloc_reg* h, const BatchDims& bd, const WsView& v, bool warm, bool
 // (NnChain, reg_kernels.hpp; nn_chain_kernel, nn_compact.hpp).  0 passes: the batch does not qualify (the caller goes on
 // launch by launch).
 uint32_t chain_passes(const gloc_reg* h, const BatchDims& bd, const WsView& v, uint32_t remaining) {
-  static const bool off = getenv("GLOC3D_NN_NO_CHAIN") != nullptr;  // developer switch
-  static const bool force = getenv("GLOC3D_NN_CHAIN_FORCE") != nullptr;  // developer switch: any batch size, with or without the plan, under the per-kernel events
-  if (off || !h->nn_chain || h->chain_broken || h->nn_mode == 1 || h->nn_src_per_lane != 2 || h->trace_on || remaining < 2 || NN_WPB != 1) return 0;
-  if (!force && (!v.split.hx || h->prof.enabled)) return 0;
+  if (!h->nn_chain || h->chain_broken || h->nn_mode == 1 || h->nn_src_per_lane != 2 || h->trace_on || remaining < 2 || NN_WPB != 1) return 0;
+  if (!v.split.hx || h->prof.enabled) return 0;
   uint32_t jg, subs;
   launch_order(h, v.n_jobs, jg, subs);
-  if ((!force && v.n_jobs >= 48) || (jg & 7u) || jg % subs) return 0;  // (small batches; a group of slots holds whole jobs)
+  if (v.n_jobs >= 48 || (jg & 7u) || jg % subs) return 0;  // (small batches; a group of slots holds whole jobs)
   if ((bd.n_part & 31u) || (v.split.hx & 31u)) return 0;  // (a job's rows of the per-pass tables are whole cache lines)
   const uint32_t n_wg = ((bd.max_groups + v.split.hx + NN_WPB - 1) / NN_WPB + subs - 1) / subs;
   const uint32_t groups = (v.n_jobs * subs + jg - 1) / jg;
@@ -411,17 +406,14 @@ int launch_nn_chain(gloc_reg* h, const BatchDims& bd, const WsView& v, uint32_t 
   h->nn_launches += n_pass;
   h->chain_launches++;
   h->chain_in_batch = true;
-  {
-    ProfScope ps(h->prof, "nn", v.s);  // (only with GLOC3D_NN_CHAIN_FORCE: the events otherwise switch the chain off)
-    if (v.split.hx)
-      hipLaunchKernelGGL((nn_chain_kernel<2, true>), dim3(ch.pass_size * n_pass), dim3(64 * NN_WPB), 0, v.s, v.jobs, v.n_jobs, jg, n_wg, subs,
-                         v.states, v.corr, v.corr, v.d2, v.pairs, v.partials, bd.n_part, bd.ld, gate2, v.split, NnHeavy{},
-                         (unsigned long long*)nullptr, (uint32_t*)nullptr, ch);
-    else
-      hipLaunchKernelGGL((nn_chain_kernel<2, false>), dim3(ch.pass_size * n_pass), dim3(64 * NN_WPB), 0, v.s, v.jobs, v.n_jobs, jg, n_wg, subs,
-                         v.states, v.corr, v.corr, v.d2, v.pairs, v.partials, bd.n_part, bd.ld, gate2, v.split, NnHeavy{},
-                         (unsigned long long*)nullptr, (uint32_t*)nullptr, ch);
-  }
+  if (v.split.hx)
+    hipLaunchKernelGGL((nn_chain_kernel<2, true>), dim3(ch.pass_size * n_pass), dim3(64 * NN_WPB), 0, v.s, v.jobs, v.n_jobs, jg, n_wg, subs,
+                       v.states, v.corr, v.corr, v.d2, v.pairs, v.partials, bd.n_part, bd.ld, gate2, v.split, NnHeavy{},
+                       (unsigned long long*)nullptr, (uint32_t*)nullptr, ch);
+  else
+    hipLaunchKernelGGL((nn_chain_kernel<2, false>), dim3(ch.pass_size * n_pass), dim3(64 * NN_WPB), 0, v.s, v.jobs, v.n_jobs, jg, n_wg, subs,
+                       v.states, v.corr, v.corr, v.d2, v.pairs, v.partials, bd.n_part, bd.ld, gate2, v.split, NnHeavy{},
+                       (unsigned long long*)nullptr, (uint32_t*)nullptr, ch);
   GLOC_HIP(hipGetLastError());
   GLOC_HIP(hipMemcpyAsync(h->h_chain_err, ch.err, 4, hipMemcpyDeviceToHost, v.s));
   return GLOC_OK;
@@ -472,8 +464,7 @@ int enqueue_pipeline(gloc_reg* h, const BatchDims& bd, const gloc_reg_params* pr
     const float thr2 = prm->inlier_thresh * prm->inlier_thresh;
     // pairs per work-group of the scoring: 4096 -- or 1024 in a small batch (one query alone: 20 jobs x 31 chunks = 620
     // work-groups for 256 CUs, each walking 16 tiles behind two barriers: 75 us for the first 16 hypotheses)
-    static const unsigned chunk_env = getenv("GLOC3D_RANSAC_CHUNK") ? (unsigned)atoi(getenv("GLOC3D_RANSAC_CHUNK")) : 0u;  // developer override
-    const uint32_t chunk_len = chunk_env ? chunk_env : ((size_t)n_jobs * ((bd.max_src + SC_CHUNK - 1) / SC_CHUNK) >= 2048 ? (uint32_t)SC_CHUNK : 1024u);
+    const uint32_t chunk_len = (size_t)n_jobs * ((bd.max_src + SC_CHUNK - 1) / SC_CHUNK) >= 2048 ? (uint32_t)SC_CHUNK : 1024u;
     static_assert(1024 % SC_STAGE == 0 && SC_CHUNK % SC_STAGE == 0, "whole tiles");
     const unsigned cchunks = (bd.max_src + chunk_len - 1) / chunk_len;
     for (int ph = 0; ph < n_ph; ++ph) {
@@ -488,8 +479,7 @@ int enqueue_pipeline(gloc_reg* h, const BatchDims& bd, const gloc_reg_params* pr
       ProfScope ps(h->prof, "ransac_score", s);
       // hypotheses per work-group: 16 / 64 (its four waves share them and split every staged tile) or thread <-> hypothesis
       const uint32_t hpb = len <= 16 ? 16u : (len <= 64 ? 64u : 256u);
-      static const unsigned parts_env = getenv("GLOC3D_RANSAC_PARTS") ? (unsigned)atoi(getenv("GLOC3D_RANSAC_PARTS")) : 0u;  // developer override
-      const unsigned NP = parts_env ? parts_env : 8u;
+      const unsigned NP = 8;
       if (!adaptive && ph > 0 && len >= 512 && cchunks >= NP) {
         // every hypothesis scored, not every pair of every hypothesis: an eighth of the pairs at a time, the hypotheses
         // that can no longer beat the first phase's winner dropped in between (ransac_alive_kernel)
@@ -619,11 +609,9 @@ int enqueue_jobs(gloc_reg* h, const std::vector<JobHost>& jh, const gloc_reg_par
   // waves over 6 144 slots: 69 us at full occupancy, 105 - 120 measured, + 14 us of solve with the chip idle).  With G
   // streams one sub-batch's solve and ramp run under the others' searches.  Results are the same bits (a job's
   // arithmetic never sees the batch).  Not with the per-kernel events on (they bracket launches on ONE stream), nor the trace.
-  static const int g_env = getenv("GLOC3D_REG_SUBBATCHES") ? atoi(getenv("GLOC3D_REG_SUBBATCHES")) : -1;  // developer override
   uint32_t G = 1;
   if (!h->prof.enabled && !h->trace_on && h->nn_mode != 1) {
-    if (g_env >= 1) G = (uint32_t)g_env;
-    else if (h->sub_batches > 0) G = (uint32_t)h->sub_batches;
+    if (h->sub_batches > 0) G = (uint32_t)h->sub_batches;
     // (-1, the default, is OFF: measured for one query alone -- 20 jobs -- 3.20 ms on one stream, 3.28 with 2 sub-batches,
     // 3.9 with 4, 5.0 with 8, enqueued one after the other or from a host thread each: a search launch of even 5 jobs has
     // 4 845 + helper waves for 6 144 slots, so the streams' kernels mostly run one after the other, each with its own ramp)
@@ -735,12 +723,6 @@ int collect_jobs(gloc_reg* h, uint32_t n_jobs, const size_t* n_src_of, float max
     const gloc_reg_params prm = h->retry_prm;
     GLOC_TRY(enqueue_jobs(h, jh, &prm));
     GLOC_HIP(hipEventSynchronize(h->done_ev));
-  }
-  static const bool heavy_dbg = getenv("GLOC3D_NN_HEAVY_DEBUG") != nullptr;  // developer switch: the length of the last cold pass's list
-  if (heavy_dbg && h->heavy_of[0].cap) {
-    uint32_t cnt = 0;
-    (void)hipMemcpy(&cnt, h->heavy_of[0].count, 4, hipMemcpyDeviceToHost);
-    fprintf(stderr, "[gloc3d] cold pass of %u jobs: %u groups given up in the first sub-batch (list of %u)\n", n_jobs, cnt, h->heavy_of[0].cap);
   }
   for (uint32_t c = 0; c < n_jobs; ++c) {
     const CandState& st = h->h_states[c];

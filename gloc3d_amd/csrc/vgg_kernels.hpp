@@ -6,7 +6,7 @@
 //
 // Precision: every fp32 operand x is cut in two bf16 values, h = bf16(x), m = bf16(x - h)
 // (x - h is exact in fp32, both conversions round to nearest), and a product is taken as  ah bm + am bh + ah bh:
-// three v_mfma_f32_32x32x16_bf16, the form of dist_bf16x3_kernel (knn_kernels.hpp).  The dropped terms, am bm and the
+// three v_mfma_f32_32x32x16_bf16, the form of dist_bf16x3_tiled_kernel (knn_kernels.hpp).  The dropped terms, am bm and the
 // residuals below m, are at most 3.03 * 2^-16 |a| |w| per product and of either sign.  The weights are split once
 // when they are set (vgg_split_weights_kernel); the activations are split on their way into LDS.  The MFMA chain of one
 // 32-k step starts from zero and is added to an fp32 total by the VALU after the step: at most six MFMA accumulations
@@ -19,7 +19,7 @@
 // Zero padding is the operand load's: taps outside the image are stored to LDS as zeros; no padded copy exists.
 // LDS image [buffer][h | m][k / 8 plane][row]: one ds_read_b128 is a lane's K = 16 fragment half (row l % 32,
 // k = 8 (l / 32) + j), pixel rows first, then Cout rows; PLANE = ROWS + 2 keeps the ds_write_b128 groups on distinct
-// banks (as dist_bf16x3_kernel).
+// banks (as dist_bf16x3_tiled_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

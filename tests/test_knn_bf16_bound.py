@@ -1,4 +1,4 @@
-"""The algebra behind the split-bf16 coarse pass of the descriptor kNN (gloc3d_amd/csrc/knn_kernels.hpp, dist_bf16x3_kernel;
+"""The algebra behind the split-bf16 coarse pass of the descriptor kNN (gloc3d_amd/csrc/knn_kernels.hpp, dist_bf16x3_tiled_kernel;
 DESIGN.md section 2), restated in numpy: x = h + m + r with h = bf16(x), m = bf16(x - h), both conversions rounding to
 nearest even as v_cvt_pk_bf16_f32 does, and  q d ~ qh dh + qh dm + qm dh.  What the device's completeness proof
 relies on (knn.hip: 776 u of its bound) is checked here on vectors of every scale; the kernel itself is checked on the GPU

@@ -27,15 +27,3 @@ if os.environ.get("GLOC3D_KNN_PROF"):  # dev: per-stage device time (HIP events 
     ix.set_option(capi.KNN_OPT_PROFILE, 1); ix.profile_reset()
     for _ in range(10): ix.search_device(q.data_ptr(), a.q, a.k, idx.data_ptr(), d2.data_ptr())
     print("stage us:", {n: round(ix.profile(n)[0] / 10 * 1e3, 1) for n in ("norms", "dist_mfma", "dist_exact", "select", "select_rerank", "rerank", "finalize")})
-if os.environ.get("GLOC3D_KNN_TRACE"):  # dev: phase stamps of the fused select + re-rank kernel (s_memtime ticks)
-    import ctypes as C
-    L = capi.lib(); f = L.gloc_knn_debug_trace; f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    f(ix._h, a.q, None, 0)
-    ix.search_device(q.data_ptr(), a.q, a.k, idx.data_ptr(), d2.data_ptr()); ix.synchronize()
-    tr = np.zeros((a.q, 16), np.uint64); f(ix._h, 0, tr.ctypes.data_as(C.c_void_p), a.q * 16)
-    t = tr[:, :6].astype(np.int64); d = np.diff(t, axis=1)
-    s4 = tr[:, 8:12].astype(np.int64) - t[:, :1]
-    print("inside select (ticks from kernel start, mean): keys ready %d, minima sorted %d, tournament done %d, collected %d, end %d" % (*s4.mean(0), d[:, 0].mean()))
-    print("phase ticks (mean over queries): select %d, prefix+stage %d, R1 group sums %d, R2 chains %d, rank %d | m mean %.1f | first start -> last end %d"
-          % (*d.mean(0), tr[:, 6].mean(), t[:, 5].max() - t[:, 0].min()))

@@ -65,7 +65,6 @@ constexpr float NN_LB_SCALE = 0.999998f;
 #endif
 constexpr int NN_WPB = GLOC_NN_WPB;
 constexpr uint32_t NN_STAT_SLOTS = 4096;  // partial counters of the pairs-evaluated statistic
-constexpr uint32_t NN_TRACE_WORDS = 32;   // dev trace: words per wave
 
 // Wave-wide min / max without the LDS crossbar: four DPP steps inside every row of 16 lanes (quad
 // swaps, then the half-row and row mirrors: after each step the lanes already paired hold one value,
@@ -180,18 +179,17 @@ __device__ __forceinline__ float exchange_add(float x, float y) {
 // FRESH: the word is at an address nobody reads before it can have its final value's predecessor written through -- the
 // first look is an ordinary load (served by the XCD's L2 to the 1 200 other waves of the job; a copy from before the
 // value was complete only sends the wave on to the loads past the caches).
-// Returns 0: a wait ran out; 1: the ordinary look sufficed; 2: the first look past the caches; 3: after polling.
 template <bool FRESH>
-__device__ __forceinline__ int chain_wait(const uint32_t* p, uint32_t need, uint32_t* err) {
+__device__ __forceinline__ bool chain_wait(const uint32_t* p, uint32_t need, uint32_t* err) {
   const int lane = threadIdx.x & 63;
   uint32_t v = 0;
   if constexpr (FRESH) {
     asm volatile("global_load_dword %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-    if (__builtin_amdgcn_readfirstlane(v) >= need) return 1;
+    if (__builtin_amdgcn_readfirstlane(v) >= need) return true;
     v = 0;
   }
   if (lane == 0) v = ld_u32<true>(p);
-  if (__builtin_amdgcn_readfirstlane(v) >= need) return 2;
+  if (__builtin_amdgcn_readfirstlane(v) >= need) return true;
   const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
   for (;;) {
     __builtin_amdgcn_s_sleep(16);
@@ -200,23 +198,12 @@ __device__ __forceinline__ int chain_wait(const uint32_t* p, uint32_t need, uint
       v = ld_u32<true>(p);
       e = ld_u32<true>(err);
     }
-    if (__builtin_amdgcn_readfirstlane(v) >= need) return 3;
-    if (__builtin_amdgcn_readfirstlane(e) != 0u) return 0;
+    if (__builtin_amdgcn_readfirstlane(v) >= need) return true;
+    if (__builtin_amdgcn_readfirstlane(e) != 0u) return false;
     if (__builtin_amdgcn_s_memrealtime() - t0 > NN_CHAIN_WAIT_TICKS) {
       if (lane == 0) st_u32<true>(err, 1u);
-      return 0;
+      return false;
     }
-  }
-}
-
-// dev: a stamp of the 100 MHz clock in slot k of (pass, job) -- first / last writer as `mode` says
-__device__ __forceinline__ void chain_stamp(const NnChain& ch, uint32_t pass, uint32_t job, uint32_t n_jobs, int k, int mode /* 0 store, 1 min, 2 max */) {
-  if (ch.dbg && (threadIdx.x & 63) == 0) {
-    uint32_t* p = ch.dbg + ((size_t)pass * n_jobs + job) * 16 + k;
-    const uint32_t t = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    if (mode == 0) *p = t;
-    else if (mode == 1) atomicMin(p, t);
-    else atomicMax(p, t);
   }
 }
 
@@ -264,9 +251,7 @@ __device__ __forceinline__ void chain_reduce_solve(uint32_t job, uint32_t pass, 
     x += xor_lane<1>(x);
     if (lane == 0) st_f64<true>(sub + k, x);
   }
-  if (r == 0) chain_stamp(ch, pass, job, n_jobs, 5, 0);  // reducer 0 has stored its sub-sum
   if (chain_arrive(ch.sdone + (size_t)pass * n_jobs + job) != NN_CHAIN_RED - 1u) return;
-  chain_stamp(ch, pass, job, n_jobs, 6, 0);  // the last reducer is in
   // the 16 sub-sums in order, a lane per moment; the state's fp64 pose beside them (loads past the caches: all in flight together)
   {
     const double* all = ch.sub + (size_t)job * NN_CHAIN_RED * ACC_NV;
@@ -288,13 +273,11 @@ __device__ __forceinline__ void chain_reduce_solve(uint32_t job, uint32_t pass, 
     frozen = (uint32_t)__builtin_amdgcn_readlane((int)frozen, ACC_NV + 12);
     __builtin_amdgcn_s_waitcnt(0);  // (the LDS stores before lane 0 reads them: one wave, in order -- the counter makes it explicit)
     asm volatile("" ::: "memory");
-    chain_stamp(ch, pass, job, n_jobs, 7, 0);  // sums and pose loaded
     // (the next pass's pose goes to its own address too: solve_compose's T_also -- a job whose pose does not change any
     // more, frozen or short of correspondences, hands on the one it was given)
     float* t_next = pass + 1u < ch.n_pass ? ch.Tp + ((size_t)(pass + 1u) * n_jobs + job) * NN_CHAIN_T_STRIDE : nullptr;
     const float* t_now = pass ? ch.Tp + ((size_t)pass * n_jobs + job) * NN_CHAIN_T_STRIDE : states[job].Tf;
     if (lane == 0) solve_compose<0, true, true>(ws, states + job, ws + ACC_NV, frozen, ws + ACC_NV + 12, t_next, t_now);
-    chain_stamp(ch, pass, job, n_jobs, 8, 0);  // solved
   }
   if (pass + 1u < ch.n_pass) (void)chain_arrive(ch.ready + ((size_t)(pass + 1u) * n_jobs + job) * NN_CHAIN_PAD);
 }
@@ -375,7 +358,7 @@ struct NnPos {
   uint32_t role = 0, pass = 0, job = 0;  // chained launch only: 0 a search wave; 1 + r: reducer r of `job`; 1 + NN_CHAIN_RED: its planner
 };
 
-template <int CS, bool PAIRS, bool TRACE = false, bool SPLIT = false /* with the plan for heavy groups (NnSplit; sp.hx > 0) */,
+template <int CS, bool PAIRS, bool SPLIT = false /* with the plan for heavy groups (NnSplit; sp.hx > 0) */,
           bool WARM = false, bool HEAVY = false /* the second launch of a cold pass: the groups its waves gave up (NnHeavy) */,
           bool CHAIN = false /* a pass of the chained launch (NnChain): what other waves of the SAME launch wrote or will read goes past the caches */>
 __device__ __forceinline__ void nn_compact_body(
@@ -385,7 +368,6 @@ __device__ __forceinline__ void nn_compact_body(
     const uint32_t* prev_corr /* may alias corr; null: cold start */, uint32_t* corr, float* __restrict__ d2out,
     f32x4* __restrict__ pairs, double* __restrict__ partials /* [job][n_part][ACC_NV] */, uint32_t n_part,
     size_t ld, float gate2, NnSplit sp, NnHeavy hv, unsigned long long* __restrict__ stat_pairs /* [NN_STAT_SLOTS] pairs evaluated, or null */,
-    uint32_t* __restrict__ trace /* dev only: [wave][NN_TRACE_WORDS]: counts in words 0-7, cycles per region in 8-19 (tools/dev_nn_trace3.py) */,
     const NnChain ch = NnChain{}) {
   constexpr int S = 64 * CS;        // sources per wave
   constexpr int NSB = CH / SB;      // sub-blocks per chunk
@@ -411,9 +393,6 @@ __device__ __forceinline__ void nn_compact_body(
     uint8_t tie[S];                 // (CS = 2: 6.3 KB per wave, 78 VGPRs: six waves per SIMD)
     uint16_t list[S + 16];          // source slots that passed the chunk-level test, padded to a multiple of 16 with S
     uint16_t queue[QCAP];           // work items: (source slot << 3) | sub-block within the chunk
-#ifdef GLOC_NN_LDS_PAD
-    uint8_t pad_[GLOC_NN_LDS_PAD];  // dev: occupancy experiments
-#endif
   };
   static_assert(SB % 16 == 0 && NSB == 8, "items pack the sub-block into 3 bits");
   __shared__ WaveLds lds_all[NN_WPB];
@@ -529,13 +508,11 @@ __device__ __forceinline__ void nn_compact_body(
     if (own_wave && (plan_word & 0xFFu) != 0u) return;  // the helpers have this group, all its parts
     hid = plan_word >> 8;
   }
-  const unsigned long long t_start = TRACE ? __builtin_amdgcn_s_memtime() : 0ull;
-  const unsigned long long rt_start = TRACE ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  uint32_t n_processed = 0, n_rounds = 0, n_live_sb = 0, n_live_pairs = 0, n_steps = 0, n_cand = 0, round_hist = 0, n_ties = 0;
+  uint32_t n_processed = 0;  // (the cold pass's give-up rule and the work estimate: chunks processed, items evaluated)
   unsigned long long n_items = 0;
-  // dev trace: cycles per region (s_memtime; a wave's wall clock among the other waves of its SIMD)
-  auto now = [&]() { return TRACE ? __builtin_amdgcn_s_memtime() : 0ull; };
-  unsigned long long a_cand = 0, a_thin = 0, a_stage = 0, a_tests = 0, a_rounds = 0, a_refresh = 0, a_batch = 0;
+  // Evaluation rounds, counted and never read: the count in the round loop shapes how the compiler lays out the cold
+  // kernels (without it the 500-job cold launch measured 0.5 - 1 % slower and one query's cold pass 1 %; same results).
+  [[maybe_unused]] uint32_t n_rounds = 0;
 
   NN_MARK("load_xform_box");
   float px[CS], py[CS], pz[CS], best[CS];
@@ -575,7 +552,6 @@ __device__ __forceinline__ void nn_compact_body(
   }
   wave_box(wlo, whi);
 
-  const unsigned long long t_box = now();
   NN_MARK("upper_bounds");
   // ---- upper bounds -> LDS state -----------------------------------------------------------------
   // warm: the previous pass's correspondence (a sorted position: one coherent 16-byte gather);
@@ -725,13 +701,8 @@ __device__ __forceinline__ void nn_compact_body(
     return wave_minmax<true>(m);
   };
   float wmax_s = wave_max_best();  // the wave's bound, in those units
-  const unsigned long long t_pro = TRACE ? __builtin_amdgcn_s_memtime() : 0ull;
-  unsigned long long t_chunks = 0;
 
   NN_MARK("sweep");
-#if defined(GLOC_NN_RET) && GLOC_NN_RET == 1  // dev (timing only, wrong results): stop after the prologue
-  if (wmax_s > -2.f) return;
-#endif
   // ---- sweep: super-chunk boxes first (64 per ballot), then 64 chunk boxes per surviving batch ----
   auto box_box_lb = [&](const f32x4& blo, const f32x4& bhi) {  // (super-chunk boxes: corners; the result in units of (64 m)^2)
     const float ex = fmaxf(fmaxf(blo.x - whi[0], wlo[0] - bhi.x), 0.f);
@@ -781,27 +752,13 @@ __device__ __forceinline__ void nn_compact_body(
     // sub-block tests, the evaluation rounds, the refresh of the bounds.  A lambda since round 6: the cold pass calls it
     // for its SEED chunks before the sweep as well (below); the warm kernel has the one call site it always had.
     bool gave_up = false;  // (cold pass: the wave has handed its group to the second launch -- NnHeavy)
-    auto visit = [&](const uint32_t c, const bool last, const unsigned long long t_k0) {
+    auto visit = [&](const uint32_t c, const bool last) {
       // the chunk's box straight into scalar registers (round 3: six v_readlane from the lane that tested it before)
       const f32x4 lo = ix.cbox_lo[c], hi = ix.cbox_hi[c];
       bool need[CS];
       unsigned long long nm[CS];
-#ifdef GLOC_NN_DUP_CAND  // dev: the lane-level test of a candidate chunk twice
-      {
-        bool need2[CS];
-        unsigned long long nm2[CS];
-        f32x4 lo2 = lo;
-        asm volatile("" : "+s"(lo2.x));
-        unsigned long long sink_ = lane_test(lo2, hi, need2, nm2);
-        asm volatile("" : : "s"(sink_));
-      }
-#endif
       const unsigned long long nm_any = lane_test(lo, hi, need, nm);
-      if constexpr (TRACE) a_cand += now() - t_k0;
       if (nm_any == 0ull) return;
-#if defined(GLOC_NN_RET) && GLOC_NN_RET == 2  // dev (timing only): candidates are tested, none is processed
-      if (nm_any != 0x12345ull) return;
-#endif
       n_processed++;  NN_MARK("candidate_tested");
       if constexpr (!WARM && !HEAVY) {
         // a cold wave this deep into its sweep is one of the heavy ones (p99 of a cold wave: ~30 chunks): hand the group to
@@ -824,7 +781,6 @@ __device__ __forceinline__ void nn_compact_body(
         }
       }
 
-      const unsigned long long t_c0 = now();
       // stage the chunk (wave-private LDS; padding never wins) and fetch its 8 sub-block boxes
 #pragma unroll
       for (int u = 0; u < CH / 64; ++u) {
@@ -851,18 +807,16 @@ __device__ __forceinline__ void nn_compact_body(
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if constexpr (TRACE) a_stage += now() - t_c0;
   NN_MARK("staged_listed");
       // sub-block tests: a lane takes one listed source and TWO sub-blocks (packed fp32: both boxes per
       // instruction), against the source's CURRENT bound; the passing pairs become the work items
       const f32x2 bcx = {bA.x, bA.y}, bcy = {bA.z, bA.w}, bcz = {bB.x, bB.y};   // centres of the lane's two sub-blocks
       const f32x2 nhx = {bB.z, bB.w}, nhy = {bC.x, bC.y}, nhz = {bC.z, bC.w};   // -(half extent) / SB2_RANGE
-      uint32_t total = 0, sbmask = 0;
+      uint32_t total = 0;
       // evaluate the queued work items: all of them, or (between two test steps: FULL_ONLY) the full rounds only -- the
       // items of an incomplete round stay queued (moved to the front) and wait for company
       auto run_rounds = [&](auto full_tag) {
         constexpr bool FULL_ONLY = decltype(full_tag)::value;
-        const unsigned long long t_r0 = now();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -938,18 +892,9 @@ __device__ __forceinline__ void nn_compact_body(
             }
           }
         };
-#ifdef GLOC_NN_DUP_ROUNDS  // dev: every evaluation round twice (idempotent: the same keys again) -- what the rounds cost
-        for (uint32_t r = 0; r < total; r += 64) {
-          const uint32_t left = total - r;
-          if (left <= 16) round_body(r, std::integral_constant<int, 4>{});
-          else if (left <= 32) round_body(r, std::integral_constant<int, 2>{});
-          else round_body(r, std::integral_constant<int, 1>{});
-        }
-#endif
         for (uint32_t r = 0; r < total; r += 64) {
           n_rounds++;
           const uint32_t left = total - r;
-          if constexpr (TRACE) round_hist += 1u << (8 * (left >= 64 ? 3u : (left - 1) / 16));  // occupancy, in quarters
           if (left <= 16) round_body(r, std::integral_constant<int, 4>{});
           else if (left <= 32) round_body(r, std::integral_constant<int, 2>{});
           else round_body(r, std::integral_constant<int, 1>{});
@@ -967,19 +912,13 @@ __device__ __forceinline__ void nn_compact_body(
         } else {
           total = 0;
         }
-        if constexpr (TRACE) a_rounds += now() - t_r0;
       };
   NN_MARK("teststeps");
-      const unsigned long long t_s0 = now(), a_r_before = a_rounds;
       const uint32_t sb0 = (lane & 3) * 2;
       const uint16_t* list_lane = &L.list[lane >> 2];
       // one step of 16 listed sources (x 4 sub-block pairs) at a time: four steps unrolled together measured
       // 6 % slower -- a processed chunk lists 58 sources on average, many far fewer
       constexpr int TU = 1;
-#ifdef GLOC_NN_DUP_TESTS  // dev: the chunk's test steps twice (the second pass rewrites the same queue entries)
-      for (int rep_ = 0; rep_ < 2; ++rep_) {
-      if (rep_ == 1) total = 0;
-#endif
       for (uint32_t t0 = 0; t0 < k * (NSB / 2); t0 += 64 * TU) {
         // Between two steps every FULL round that is waiting is evaluated (round 4; until then only when the queue might
         // overflow): its lanes are as busy as they get, and the bounds it lowers save the chunk's later steps their items.
@@ -1032,23 +971,10 @@ __device__ __forceinline__ void nn_compact_body(
             L.queue[total + c0n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u))] =
                 (uint16_t)((si[u] << 3) | (sb0 + 1));
           total += c0n + (uint32_t)__popcll(m1);
-          if constexpr (TRACE) sbmask |= (nd0 ? (1u << sb0) : 0u) | (nd1 ? (2u << sb0) : 0u);
         }
       }
   NN_MARK("teststeps_end");
-#ifdef GLOC_NN_DUP_TESTS
-      }
-#endif
-      if constexpr (TRACE) {
-        uint32_t lm = 0;
-        for (int b = 0; b < 8; ++b) lm |= __builtin_amdgcn_ballot_w64((sbmask >> b) & 1u) ? (1u << b) : 0u;
-        n_live_sb += (uint32_t)__popc(lm);
-        n_live_pairs += (uint32_t)__popc((lm | (lm >> 1)) & 0x55u);
-        n_steps += (k + 15) / 16;
-      }
-      if constexpr (TRACE) a_tests += (now() - t_s0) - (a_rounds - a_r_before);
       run_rounds(std::false_type{});
-      const unsigned long long t_f0 = now();
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();  // all reads of the stage done, all key updates visible
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1095,11 +1021,6 @@ __device__ __forceinline__ void nn_compact_body(
       if (!WARM || wmax_s > 1.0e30f) {
         if (__builtin_amdgcn_ballot_w64(changed) != 0ull) wmax_s = wave_max_best();
       }
-      if constexpr (TRACE) {
-        const unsigned long long t_e = now();
-        a_refresh += t_e - t_f0;
-        t_chunks += t_e - t_c0;
-      }
     };
   // ---- cold pass only: the SEED chunks first (round 6) -------------------------------------------------------
   // A cold source's bound is its distance to the best of five curve neighbours: within 1.2 x the true distance for half of
@@ -1115,7 +1036,6 @@ __device__ __forceinline__ void nn_compact_body(
   uint32_t seed_c[NSEED];
 #pragma unroll
   for (int k = 0; k < NSEED; ++k) seed_c[k] = 0xFFFFFFFFu;
-#ifndef GLOC_NN_R5_COLD  // (-DGLOC_NN_R5_COLD: round 5's cold pass -- no seeds, no second launch -- for same-box A/Bs: tools/dev_ab.sh)
   if constexpr (!WARM) {
     if (parts == 1 && ix.nchunks) {
       bool pend[CS];
@@ -1139,18 +1059,12 @@ __device__ __forceinline__ void nn_compact_body(
           if (j == k) seed_c[j] = c;
 #pragma unroll
         for (int s = 0; s < CS; ++s) pend[s] = pend[s] && sc[s] != c;
-        if constexpr (TRACE) n_cand++;
-        visit(c, false, now());
+        visit(c, false);
         if (gave_up) return;
       }
     }
   }
-#endif
-#if defined(GLOC_NN_RET) && GLOC_NN_RET == 6  // dev (timing only): no sweep at all -- prologue + epilogue
-  for (uint32_t s0 = 0; s0 < (wmax_s > -2.f ? 0u : ix.nsup); s0 += 64) {
-#else
   for (uint32_t s0 = 0; s0 < ix.nsup; s0 += 64) {
-#endif
     float lbs = __builtin_inff();  // (not FLT_MAX: a wave whose bound is still FLT_MAX -- a non-finite source point -- must not pass lanes past the end)
     if (s0 + lane < ix.nsup) {
       const f32x4 ulo = ix.sup_lo[s0 + lane], uhi = ix.sup_hi[s0 + lane];
@@ -1167,7 +1081,6 @@ __device__ __forceinline__ void nn_compact_body(
       if (cl < ix.nchunks) { nlo = ix.box_lo[cl]; nhi = ix.box_hi[cl]; }
     }
     while (cur >= 0) {
-    const unsigned long long t_b0 = now();
     const uint32_t c0 = (s0 + cur) * 64;
     const bool live = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lbs), cur)) <= wmax_s;
     const uint32_t cl = c0 + lane;
@@ -1187,7 +1100,6 @@ __device__ __forceinline__ void nn_compact_body(
       mask &= pmask;
       w_cand += (uint32_t)__popcll(mask);
     }
-    if constexpr (TRACE) a_batch += now() - t_b0;
   NN_MARK("batch_tested");
     // A wave over a sparse stretch of the curve (the far field: 128 points in a box of 60 m x 130 m, each 0.2 m from
     // its neighbour) lists hundreds of candidates here and fails nearly all of them at the lane level: it is the wave
@@ -1195,7 +1107,6 @@ __device__ __forceinline__ void nn_compact_body(
     // to overlap it with) is most of its time.  A batch with many survivors is therefore thinned first, with each box
     // taken from the lane that holds it (v_readlane: no memory): what remains goes through the loop below.
     if (__popcll(mask) > GLOC_NN_THIN_MIN) {
-      const unsigned long long t_t0 = now();
       unsigned long long keep = 0ull;
       while (mask) {
         const int b = __ffsll((long long)mask) - 1;
@@ -1204,16 +1115,13 @@ __device__ __forceinline__ void nn_compact_body(
         const f32x4 lo = {rl(blo.x), rl(blo.y), rl(blo.z), 0.f}, hi = {rl(bhi.x), rl(bhi.y), rl(bhi.z), 0.f};
         bool need[CS];
         unsigned long long nm[CS];
-        if constexpr (TRACE) n_cand++;
         if (lane_test(lo, hi, need, nm) != 0ull) keep |= 1ull << b;
       }
       mask = keep;
-      if constexpr (TRACE) a_thin += now() - t_t0;
     }
     while (mask) {
       const int b = __ffsll((long long)mask) - 1;
       mask &= mask - 1;
-      const unsigned long long t_k0 = now();
       if (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(lbw), b)) > wmax_s) continue;
       const uint32_t c = __builtin_amdgcn_readfirstlane(c0 + b);
       if constexpr (!WARM) {  // (a seed chunk: visited before the sweep)
@@ -1222,8 +1130,7 @@ __device__ __forceinline__ void nn_compact_body(
         for (int k = 0; k < NSEED; ++k) seeded |= c == seed_c[k];
         if (seeded) continue;
       }
-      if constexpr (TRACE) n_cand++;
-      visit(c, mask == 0ull && cur < 0 && s0 + 64 >= ix.nsup, t_k0);
+      visit(c, mask == 0ull && cur < 0 && s0 + 64 >= ix.nsup);
       if constexpr (!WARM && !HEAVY) {
         if (gave_up) return;
       }
@@ -1239,11 +1146,7 @@ __device__ __forceinline__ void nn_compact_body(
     uint32_t* wp = sp.work + (size_t)job * n_part + gi;
     if (parts == 1) st_u32<CHAIN>(wp, wk); else atomicAdd(wp, wk);  // (the planner left a zero)
   }
-  const unsigned long long t_sweep = TRACE ? __builtin_amdgcn_s_memtime() : 0ull;
 
-#if defined(GLOC_NN_RET) && GLOC_NN_RET == 3  // dev (timing only): no index recovery, no outputs
-  if (wmax_s > -2.f) return;
-#endif
   // (the bounds as the sweep left them: the fused minima -- the keys' high words)
 #pragma unroll
   for (int s = 0; s < CS; ++s) best[s] = __uint_as_float((uint32_t)(L.key[s * 64 + lane] >> 32));
@@ -1292,7 +1195,6 @@ __device__ __forceinline__ void nn_compact_body(
       if (bpos[s] != 0xFFFFFFFFu) best[s] = bd;
     }
   }
-  const unsigned long long t_rec = now();
   NN_MARK("tie");
   // rare: a source whose minimum is contested -- two targets at the same distance, or fused distances within NN_NEAR
   // of each other (tie flag).  The wave looks for it together: lanes <-> chunk boxes, then lanes <-> the targets of every
@@ -1302,7 +1204,6 @@ __device__ __forceinline__ void nn_compact_body(
 #pragma unroll
   for (int s = 0; s < CS; ++s) {
     unsigned long long tm = __builtin_amdgcn_ballot_w64(valid[s] && ix.n && L.tie[s * 64 + lane] != 0);
-    if constexpr (TRACE) n_ties += (uint32_t)__popcll(tm);
     while (tm) {
       const int tl = __ffsll((long long)tm) - 1;
       tm &= tm - 1;
@@ -1386,7 +1287,6 @@ __device__ __forceinline__ void nn_compact_body(
     }
     if (lane == 0) st_u32<CHAIN>(tick, 0u);
   }
-  const unsigned long long t_tie = now();
   NN_MARK("outputs");
   // ---- outputs: corr / d2 (sorted slots), pairs, the wave's moments ------------------------------
   // Moments about the WAVE'S OWN centre, in fp32 (round 3; fp64 raw moments until then: 11 % of the launch).  The ICP
@@ -1434,7 +1334,6 @@ __device__ __forceinline__ void nn_compact_body(
       pairs[o * 2 + 1] = q;
     }
   }
-  const unsigned long long t_out = now();
   NN_MARK("reduce");
   if (!PAIRS && partials) {
     // Sum over the 64 lanes in the order of the xor butterfly (o = 32, 16, ..., 1), but as a
@@ -1480,58 +1379,24 @@ __device__ __forceinline__ void nn_compact_body(
     if (lane == 32) st_f32<CHAIN>(out + 20, y);
   }
   NN_MARK("end");
-  if (TRACE && trace && lane == 0) {
-    const size_t wid = (size_t)lin_block * NN_WPB + w;
-    uint32_t* tw = trace + NN_TRACE_WORDS * wid;
-    const unsigned long long t_end = now();
-    tw[0] = (uint32_t)(t_end - t_start);
-    tw[1] = round_hist;  // rounds with <= 16 / 32 / 48 / 64 items, a byte each
-    tw[2] = n_processed;
-    tw[3] = (n_rounds & 0xFFFFu) | (n_cand << 16);  // rounds | candidate chunks (passed the wave-level test)
-    tw[4] = (uint32_t)n_items;
-    tw[5] = ((uint32_t)(t_pro - t_start) & 0xFFFFFFu) | (n_ties << 24);  // prologue cycles | contested sources
-    tw[6] = job;
-    tw[7] = (n_live_sb << 20) | (n_live_pairs << 10) | n_steps;  // per wave: live sub-blocks, live pairs, test steps
-    // cycles per region
-    tw[8] = (uint32_t)(t_box - t_start);   // load + transform + wave box
-    tw[9] = (uint32_t)(t_pro - t_box);     // upper bounds -> LDS state
-    tw[10] = (uint32_t)a_batch;            // batches of 64 chunk boxes (wave level), incl. the wait for their loads
-    tw[11] = (uint32_t)a_thin;             // thinning of many-survivor batches
-    tw[12] = (uint32_t)a_cand;             // lane-level tests of candidate chunks
-    tw[13] = (uint32_t)a_stage;            // staging + listing
-    tw[14] = (uint32_t)a_tests;            // sub-block test steps
-    tw[15] = (uint32_t)a_rounds;           // evaluation rounds
-    tw[16] = (uint32_t)a_refresh;          // bound refresh
-    tw[17] = (uint32_t)(t_sweep - t_pro);  // the whole sweep
-    tw[18] = (uint32_t)(t_rec - t_sweep);  // index recovery
-    tw[19] = (uint32_t)(t_tie - t_rec);    // contested minima
-    tw[20] = (uint32_t)(t_out - t_tie);    // outputs + moments
-    tw[21] = (uint32_t)(t_end - t_out);    // reduction of the moments
-    tw[22] = gi | (part << 20) | (parts << 24);
-    tw[23] = (uint32_t)rt_start;  // the constant 100 MHz clock all XCDs share (the shader clock above is not synchronised)
-    tw[24] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    tw[25] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-    tw[26] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID: wave, simd, cu, sh, se
-    (void)t_chunks;
-  }
 }
 
 #define NN_COMPACT_PARAMS                                                                                              \
   const Job *__restrict__ jobs, uint32_t n_jobs, uint32_t job_group, uint32_t n_wg, uint32_t subs,                     \
       const CandState *__restrict__ states, const uint32_t *prev_corr, uint32_t *corr, float *__restrict__ d2out,      \
       f32x4 *__restrict__ pairs, double *__restrict__ partials, uint32_t n_part, size_t ld, float gate2, NnSplit sp,   \
-      NnHeavy hv, unsigned long long *__restrict__ stat_pairs, uint32_t *__restrict__ trace
-#define NN_COMPACT_ARGS jobs, n_jobs, job_group, n_wg, subs, states, prev_corr, corr, d2out, pairs, partials, n_part, ld, gate2, sp, hv, stat_pairs, trace
+      NnHeavy hv, unsigned long long *__restrict__ stat_pairs
+#define NN_COMPACT_ARGS jobs, n_jobs, job_group, n_wg, subs, states, prev_corr, corr, d2out, pairs, partials, n_part, ld, gate2, sp, hv, stat_pairs
 
-template <int CS, bool PAIRS, bool TRACE = false, bool SPLIT = false, bool WARM = false>
+template <int CS, bool PAIRS, bool SPLIT = false, bool WARM = false>
 __global__ __launch_bounds__(64 * NN_WPB) void nn_compact_kernel(NN_COMPACT_PARAMS) {
-  nn_compact_body<CS, PAIRS, TRACE, SPLIT, WARM>(NnPos{blockIdx.z, blockIdx.x, blockIdx.y}, NN_COMPACT_ARGS);
+  nn_compact_body<CS, PAIRS, SPLIT, WARM>(NnPos{blockIdx.z, blockIdx.x, blockIdx.y}, NN_COMPACT_ARGS);
 }
 
 // The second launch of a cold pass: the groups its waves gave up, NN_HEAVY_PARTS waves each (NnHeavy).
 template <int CS, bool PAIRS>
 __global__ __launch_bounds__(64) void nn_compact_heavy_kernel(NN_COMPACT_PARAMS) {
-  nn_compact_body<CS, PAIRS, false, true, false, true>(NnPos{0u, 0u, 0u}, NN_COMPACT_ARGS);
+  nn_compact_body<CS, PAIRS, true, false, true>(NnPos{0u, 0u, 0u}, NN_COMPACT_ARGS);
 }
 
 // The warm moments pass with the split plan in it -- what one query alone runs 20 times -- held to the register budget
@@ -1539,13 +1404,14 @@ __global__ __launch_bounds__(64) void nn_compact_heavy_kernel(NN_COMPACT_PARAMS)
 // kernel fits by itself.
 template <int CS>
 __global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 6))) void nn_compact_split_warm_kernel(NN_COMPACT_PARAMS) {
-  nn_compact_body<CS, false, false, true, true>(NnPos{blockIdx.z, blockIdx.x, blockIdx.y}, NN_COMPACT_ARGS);
+  nn_compact_body<CS, false, true, true>(NnPos{blockIdx.z, blockIdx.x, blockIdx.y}, NN_COMPACT_ARGS);
 }
 
 // All warm moments passes of a small batch in ONE launch (NnChain): a one-dimensional grid of n_pass x pass_size
 // single-wave work-groups; a pass is `groups` runs of [job_group * n_wg searches | the group's roles | padding to a
-// multiple of 8, so that a slot keeps its XCD from pass to pass].  Held to six waves per SIMD like the warm kernel it chains.
-template <int CS, bool SPLIT = true>
+// multiple of 8, so that a slot keeps its XCD from pass to pass].  Held to six waves per SIMD like the warm kernel it chains,
+// and like it always with the split plan (the host chains only batches that have one).
+template <int CS>
 __global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 6))) void nn_chain_kernel(NN_COMPACT_PARAMS, NnChain ch) {
   static_assert(NN_WPB == 1, "a work-group is a wave: the roles and the arrival counts are per wave");
   const uint32_t b = blockIdx.x;
@@ -1556,7 +1422,6 @@ __global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 
     const uint32_t si = r2 - n_search, jl = si / NN_CHAIN_ROLES, role = si - jl * NN_CHAIN_ROLES;
     const uint32_t job = grp * ch.jobs_per_grp + jl;
     if (jl >= ch.jobs_per_grp || job >= n_jobs) return;  // padding
-    if (role == 0) chain_stamp(ch, pass, job, n_jobs, 3, 0);  // reducer 0 starts to wait
     // The search waves only add to `done` and leave (they do not wait for the sum to come back: 2 us of a slot, 8 % of
     // a wave); ONE wave per job, its planner, polls the counter and raises `go` for the reducers, who poll that -- a line
     // the 1 225 additions do not go through.
@@ -1564,13 +1429,11 @@ __global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 
     if (role == NN_CHAIN_RED) {
       if (!chain_wait<false>(ch.done + cell, ch.expected, ch.err)) return;
       if ((threadIdx.x & 63) == 0) st_u32<true>(ch.go + cell, 1u);
-      chain_stamp(ch, pass, job, n_jobs, 2, 0);  // the job's pass is seen complete
     } else if (!chain_wait<false>(ch.go + cell, 1u, ch.err)) {
       return;
     }
-    if (role == 0) chain_stamp(ch, pass, job, n_jobs, 4, 0);  // ... and sees the pass done
-    nn_compact_body<CS, false, false, SPLIT, true, false, true>(NnPos{0u, 0u, 0u, 1u + role, pass, job}, jobs, n_jobs, job_group, n_wg, subs, states,
-                                                                corr, corr, d2out, pairs, partials, n_part, ld, gate2, sp, hv, stat_pairs, trace, ch);
+    nn_compact_body<CS, false, true, true, false, true>(NnPos{0u, 0u, 0u, 1u + role, pass, job}, jobs, n_jobs, job_group, n_wg, subs, states,
+                                                        corr, corr, d2out, pairs, partials, n_part, ld, gate2, sp, hv, stat_pairs, ch);
     return;
   }
   const uint32_t wgv = r2 / job_group, slot = r2 - wgv * job_group;
@@ -1580,22 +1443,15 @@ __global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 
   const uint32_t vjob = grp * job_group + vin;
   if (vjob >= n_jobs * subs) return;
   const uint32_t job = vjob / subs;
-  const bool first_wave = wgv == 0u && vjob % subs == 0u;  // (dev stamps: the first wave of the job's first share)
-  if (first_wave) chain_stamp(ch, pass, job, n_jobs, 0, 0);  // a first search wave of the job's pass here
   const size_t cell = ((size_t)pass * n_jobs + job) * NN_CHAIN_PAD;
   NnSplit spp = sp;  // the pass's own plan and helpers' table (pass 0: the batch's, written by the launch before)
   if (pass > 0u) {
-    const int how = chain_wait<true>(ch.ready + cell, 2u, ch.err);
-    if (!how) return;
-    if (ch.dbg && (threadIdx.x & 63) == 0) atomicAdd(ch.dbg + ((size_t)pass * n_jobs + job) * 16 + 8 + how, 1u);  // dev: slots 9, 10, 11
-    if constexpr (SPLIT) {
-      spp.plan = ch.planp + (size_t)(pass - 1u) * n_jobs * n_part;
-      spp.helper = ch.helperp + (size_t)(pass - 1u) * n_jobs * sp.hx;
-    }
+    if (!chain_wait<true>(ch.ready + cell, 2u, ch.err)) return;
+    spp.plan = ch.planp + (size_t)(pass - 1u) * n_jobs * n_part;
+    spp.helper = ch.helperp + (size_t)(pass - 1u) * n_jobs * sp.hx;
   }
-  if (first_wave) chain_stamp(ch, pass, job, n_jobs, 1, 0);  // ... and past the wait
-  nn_compact_body<CS, false, false, SPLIT, true, false, true>(NnPos{grp, slot, wgv, 0u, pass, job}, jobs, n_jobs, job_group, n_wg, subs, states, corr, corr,
-                                                              d2out, pairs, partials, n_part, ld, gate2, spp, hv, stat_pairs, trace, ch);
+  nn_compact_body<CS, false, true, true, false, true>(NnPos{grp, slot, wgv, 0u, pass, job}, jobs, n_jobs, job_group, n_wg, subs, states, corr, corr,
+                                                      d2out, pairs, partials, n_part, ld, gate2, spp, hv, stat_pairs, ch);
   // (this wave's stores acknowledged, then its count -- not waited for)
   __builtin_amdgcn_s_waitcnt(0);
   asm volatile("" ::: "memory");

@@ -9,7 +9,6 @@
 #include <vector>
 
 #include "common.hpp"
-#include <future>
 
 #include "ndt.hpp"
 #include "nn_compact.hpp"
@@ -53,9 +52,6 @@ struct gloc_reg {
   } pending;
   std::vector<float> last_final_step;  // per job of the last collected batch (gloc_reg_final_steps)
   int nn_mode = 0;        // 0 culled + compacted (default), 1 exhaustive
-  bool trace_on = false;  // dev only: per-wave trace of the culled kernel
-  DevBuf trace;
-  size_t trace_waves = 0;
   int nn_src_per_lane = 2;  // culled kernel: source points per lane (1, 2, 4)
   int nn_job_group = 24;    // culled kernel: jobs interleaved in the launch order (a multiple of 8: see nn_compact.hpp)
   bool nn_job_group_set = false;  // by the caller (else a small batch takes its own: launch_order)
@@ -70,23 +66,14 @@ struct gloc_reg {
   NnSplit split{};                 // views into them for the batch being enqueued (hx = 0: off)
   // the groups a cold pass's waves give up and a second launch searches with NN_HEAVY_PARTS waves each (NnHeavy)
   int nn_heavy_thresh = 32;        // processed chunks at which a cold wave gives up (0: off)
-  static constexpr uint32_t MAX_SUB = 8;
-  DevBuf heavy_buf;                // per sub-batch a region [count | list | ticket | skey | hkey]
-  size_t heavy_cap = 0;            // entries a region holds (its ticket / skey parts are self-resetting)
-  size_t heavy_regions = 0;        // regions the buffer holds
-  NnHeavy heavy_of[MAX_SUB]{};     // the views for the batch being enqueued, one per sub-batch (cap = 0: off)
-  // sub-batches of a small batch, each on its own stream (enqueue_jobs): -1 by batch size (4 for 8 .. 64 jobs), 0 / 1 off
-  int sub_batches = -1;
-  hipStream_t sub_stream[MAX_SUB - 1] = {};
-  hipEvent_t fork_ev = nullptr, join_ev[MAX_SUB - 1] = {};
+  DevBuf heavy_buf;                // [count | list | ticket | skey | hkey]
+  size_t heavy_cap = 0;            // entries the buffer holds (its ticket / skey parts are self-resetting)
+  NnHeavy heavy{};                 // the view for the batch being enqueued (cap = 0: off)
   std::atomic<uint64_t> nn_launches{0};
   // the warm passes of a small batch chained in one launch (NnChain): 1 on (default), 0 off; stopped for good on a handle
   // whose chain once ran out of time
   int nn_chain = 1;
   bool chain_broken = false;
-  bool chain_trace = false;       // dev (gloc_reg_debug_chain_trace): stamps per (pass, job)
-  DevBuf chain_dbg;
-  uint32_t chain_dbg_pass = 0, chain_dbg_jobs = 0;
   bool chain_stall = false;       // test aid (gloc_reg_debug_chain_stall): the solvers wait for one wave more than there is
   DevBuf chain_buf;               // [ready | done | sdone | err] then the reducers' sub-sums
   uint32_t* h_chain_err = nullptr; // pinned: the batch's err word, copied behind the states
@@ -133,12 +120,10 @@ struct BatchDims {
   size_t ld;
 };
 
-// A batch -- or, round 6, one of the sub-batches a small batch is cut into, each on its own stream -- as the launches see
-// it: its jobs' slices of the handle's workspaces (every per-job array offset by the sub-batch's first job; strides --
-// bd.ld, bd.n_part, the hypothesis count -- are the whole batch's).
+// A batch as the launches see it: the stream and the handle's workspaces.
 struct WsView {
   hipStream_t s;
-  uint32_t job0, n_jobs;
+  uint32_t n_jobs;
   Job* jobs;
   CandState* states;
   uint32_t* corr;
@@ -152,17 +137,20 @@ struct WsView {
   NnHeavy heavy;
 };
 
-// The split plan's buffers for a batch (NnSplit): everything starts as "no group is split"; the first pass of a batch
-// therefore runs one wave per group and leaves the estimates the first plan is made from.
-int setup_split(gloc_reg* h, const BatchDims& bd, int cs) {
+// Helper wave slots per job of the split plan (NnSplit) for a batch; 0: no plan.  One query alone (20 jobs) is the case
+// that needs it: its launch is as long as its longest wave.  A launch of hundreds of jobs only loses its tail to such waves
+// (5 % at 500 jobs, measured per XCD) and the kernel with the plan in it is 3 % slower: off by default there.
+uint32_t split_helpers(const gloc_reg* h, const BatchDims& bd) {
+  if (h->nn_mode == 1 || h->nn_split_helpers == 0 || h->nn_split_thresh == 0) return 0;
+  const uint32_t hx = h->nn_split_helpers > 0 ? (uint32_t)h->nn_split_helpers : (bd.n_jobs <= 64 ? 256u : (bd.n_jobs <= 256 ? 64u : 0u));
+  return std::min<uint32_t>((hx + NN_WPB - 1) / NN_WPB * NN_WPB, 1u << 12);
+}
+
+// The split plan's buffers for a batch (NnSplit) with `hx` helper slots per job: everything starts as "no group is split";
+// the first pass of a batch therefore runs one wave per group and leaves the estimates the first plan is made from.
+int setup_split(gloc_reg* h, const BatchDims& bd, int cs, uint32_t hx, bool chained) {
   h->split = NnSplit{};
-  if (h->nn_mode == 1 || h->nn_split_helpers == 0 || h->nn_split_thresh == 0) return GLOC_OK;
-  // one query alone (20 jobs) is the case that needs it: its launch is as long as its longest wave.  A launch of hundreds
-  // of jobs only loses its tail to such waves (5 % at 500 jobs, measured per XCD) and the kernel with the plan in it is
-  // 3 % slower: off by default there
-  uint32_t hx = h->nn_split_helpers > 0 ? (uint32_t)h->nn_split_helpers : (bd.n_jobs <= 64 ? 256u : (bd.n_jobs <= 256 ? 64u : 0u));
   if (hx == 0) return GLOC_OK;
-  hx = std::min<uint32_t>((hx + NN_WPB - 1) / NN_WPB * NN_WPB, 1u << 12);
   const size_t S = 64 * (size_t)cs, nj = bd.n_jobs, np = bd.n_part;
   const size_t zero_words = nj * np * 2 + nj * hx;
   const size_t ff_bytes = nj * hx * S * 8 + nj * hx * 4;
@@ -180,56 +168,33 @@ int setup_split(gloc_reg* h, const BatchDims& bd, int cs) {
   sp.hx = hx;
   // (the chained launch hides a job's longest wave behind the other jobs' work, so fewer groups need splitting: one query
   // alone, registration of 20 jobs, threshold 45 / 60 / 75 / 90 / 120 thousand cycles: 2.92 / 2.89 / 2.79 / 2.78 / 3.03 ms)
-  const bool chains = h->nn_chain && !h->chain_broken && !h->prof.enabled && !h->trace_on && cs == 2 && bd.n_jobs < 48;
-  sp.thresh = h->nn_split_thresh_set || !chains ? h->nn_split_thresh : 85000u;
+  sp.thresh = h->nn_split_thresh_set || !chained ? h->nn_split_thresh : 85000u;
   return GLOC_OK;
 }
 
-// The lists of a cold pass's heavy groups (NnHeavy), one per sub-batch: 16 entries per job, at most 16 384; only at two
-// sources per lane.
-int setup_heavy(gloc_reg* h, const BatchDims& bd, int cs, uint32_t G = 1) {
-  for (uint32_t g = 0; g < gloc_reg::MAX_SUB; ++g) h->heavy_of[g] = NnHeavy{};
-#ifdef GLOC_NN_R5_COLD
-  return GLOC_OK;  // (round 5's cold pass keeps no lists)
-#endif
-  if (h->nn_mode == 1 || cs != 2 || h->nn_heavy_thresh <= 0 || h->trace_on) return GLOC_OK;
-  const size_t per = ((size_t)bd.n_jobs + G - 1) / G;
-  const size_t cap = std::min<size_t>(per * 16, 16384), S = 64 * (size_t)cs;
+// The list of a cold pass's heavy groups (NnHeavy): 16 entries per job, at most 16 384; only at two sources per lane.
+int setup_heavy(gloc_reg* h, const BatchDims& bd, int cs) {
+  h->heavy = NnHeavy{};
+  if (h->nn_mode == 1 || cs != 2 || h->nn_heavy_thresh <= 0) return GLOC_OK;
+  const size_t cap = std::min<size_t>((size_t)bd.n_jobs * 16, 16384), S = 64 * (size_t)cs;
   hipStream_t s = h->stream;
-  auto region_bytes = [&](size_t c) { return ((256 + c * 8 + c * 4 + 255) & ~(size_t)255) + 2 * c * S * 8; };
-  if (cap > h->heavy_cap || G > h->heavy_regions) {
-    const size_t cap2 = std::min<size_t>(std::max<size_t>(cap, h->heavy_cap), 16384), R = std::max<size_t>(G, h->heavy_regions);
-    GLOC_TRY(h->heavy_buf.ensure(R * region_bytes(cap2) + 256, s));
-    for (size_t g = 0; g < R; ++g) {
-      char* b = h->heavy_buf.as<char>() + g * region_bytes(cap2);
-      const size_t keys_at = (256 + cap2 * 8 + cap2 * 4 + 255) & ~(size_t)255;
-      GLOC_HIP(hipMemsetAsync(b, 0, keys_at, s));                      // count, list, tickets
-      GLOC_HIP(hipMemsetAsync(b + keys_at, 0xFF, cap2 * S * 8, s));     // fold keys (hkey behind them: written before read)
-    }
-    h->heavy_cap = cap2;
-    h->heavy_regions = R;
+  // [count | list (cap x 2 words) | ticket (cap words) | skey | hkey], laid out for the largest list the buffer has held
+  auto keys_at = [](size_t c) { return (256 + c * 8 + c * 4 + 255) & ~(size_t)255; };
+  if (cap > h->heavy_cap) {
+    GLOC_TRY(h->heavy_buf.ensure(keys_at(cap) + 2 * cap * S * 8 + 256, s));
+    GLOC_HIP(hipMemsetAsync(h->heavy_buf.p, 0, keys_at(cap), s));                                   // count, list, tickets
+    GLOC_HIP(hipMemsetAsync(h->heavy_buf.as<char>() + keys_at(cap), 0xFF, cap * S * 8, s));  // fold keys (hkey behind them: written before read)
+    h->heavy_cap = cap;
   }
-  for (uint32_t g = 0; g < G; ++g) {
-    char* b = h->heavy_buf.as<char>() + g * region_bytes(h->heavy_cap);
-    const size_t head = 256 + h->heavy_cap * 8, keys_at = (head + h->heavy_cap * 4 + 255) & ~(size_t)255;
-    NnHeavy& hv = h->heavy_of[g];
-    hv.count = reinterpret_cast<uint32_t*>(b);
-    hv.list = reinterpret_cast<uint32_t*>(b + 256);
-    hv.ticket = reinterpret_cast<uint32_t*>(b + head);
-    hv.skey = reinterpret_cast<unsigned long long*>(b + keys_at);
-    hv.hkey = hv.skey + h->heavy_cap * S;
-    hv.cap = (uint32_t)cap;
-    hv.thresh = (uint32_t)h->nn_heavy_thresh;
-  }
-  return GLOC_OK;
-}
-
-int ensure_sub_streams(gloc_reg* h, uint32_t G) {
-  if (!h->fork_ev) GLOC_HIP(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
-  for (uint32_t g = 1; g < G; ++g) {
-    if (!h->sub_stream[g - 1]) GLOC_HIP(hipStreamCreateWithFlags(&h->sub_stream[g - 1], hipStreamNonBlocking));
-    if (!h->join_ev[g - 1]) GLOC_HIP(hipEventCreateWithFlags(&h->join_ev[g - 1], hipEventDisableTiming));
-  }
+  char* b = h->heavy_buf.as<char>();
+  NnHeavy& hv = h->heavy;
+  hv.count = reinterpret_cast<uint32_t*>(b);
+  hv.list = reinterpret_cast<uint32_t*>(b + 256);
+  hv.ticket = reinterpret_cast<uint32_t*>(b + 256 + h->heavy_cap * 8);
+  hv.skey = reinterpret_cast<unsigned long long*>(b + keys_at(h->heavy_cap));
+  hv.hkey = hv.skey + h->heavy_cap * S;
+  hv.cap = (uint32_t)cap;
+  hv.thresh = (uint32_t)h->nn_heavy_thresh;
   return GLOC_OK;
 }
 
@@ -247,6 +212,40 @@ void launch_order(const gloc_reg* h, uint32_t n_jobs, uint32_t& jg, uint32_t& su
   if (h->nn_sub_jobs > 0 || h->nn_job_group_set || n_jobs >= 48) return;
   jg = 8u;
   subs = n_jobs % 4u == 0u ? 2u : (n_jobs % 2u == 0u ? 4u : 8u);
+}
+
+// What every launch of the culled search takes (NN_COMPACT_PARAMS, nn_compact.hpp) besides its own grid, start and lists.
+struct NnArgs {
+  const WsView& v;
+  const BatchDims& bd;
+  uint32_t jg, n_wg, subs;  // the launch order (launch_order)
+  float gate2;
+  unsigned long long* stat_pairs;  // profiling only, else null
+};
+
+// One launch of an instance of the culled search; `chain`: the chained launch's NnChain.
+template <auto KERNEL, typename... Chain>
+void launch_compact(const NnArgs& a, dim3 grid, const uint32_t* prev_corr, bool pairs, NnHeavy hv, Chain... chain) {
+  hipLaunchKernelGGL(KERNEL, grid, dim3(64 * NN_WPB), 0, a.v.s, a.v.jobs, a.v.n_jobs, a.jg, a.n_wg, a.subs, a.v.states, prev_corr,
+                     a.v.corr, a.v.d2, a.v.pairs, pairs ? (double*)nullptr : a.v.partials, a.bd.n_part, a.bd.ld, a.gate2, a.v.split, hv,
+                     a.stat_pairs, chain...);
+}
+
+// The instance of a pass: sources per lane x pass kind x the split plan.  The warm moments pass with the plan -- what one
+// query alone runs pass after pass -- is a kernel of its own at two sources per lane (nn_compact_split_warm_kernel).
+template <int CS, bool PAIRS, bool WARM>
+void launch_pass(const NnArgs& a, dim3 grid, const uint32_t* prev_corr, NnHeavy hv) {
+  if (!a.v.split.hx) launch_compact<nn_compact_kernel<CS, PAIRS, false, WARM>>(a, grid, prev_corr, PAIRS, hv);
+  else if constexpr (CS == 2 && !PAIRS && WARM) launch_compact<nn_compact_split_warm_kernel<2>>(a, grid, prev_corr, PAIRS, hv);
+  else launch_compact<nn_compact_kernel<CS, PAIRS, true, WARM>>(a, grid, prev_corr, PAIRS, hv);
+}
+
+// (the pass that writes the pairs is a batch's first: a cold one)
+template <int CS>
+void launch_kind(const NnArgs& a, dim3 grid, const uint32_t* prev_corr, NnHeavy hv, bool want_pairs, bool warm) {
+  if (want_pairs) launch_pass<CS, true, false>(a, grid, prev_corr, hv);
+  else if (warm) launch_pass<CS, false, true>(a, grid, prev_corr, hv);
+  else launch_pass<CS, false, false>(a, grid, prev_corr, hv);
 }
 
 // S1 for every job of the batch.  warm: corr holds the previous pass's result.  want_pairs: write the (moved
@@ -287,80 +286,39 @@ int launch_nn(gloc_reg* h, const BatchDims& bd, const WsView& v, bool warm, bool
     GLOC_REQUIRE(n_wg <= 65535u && (n_slots + jg - 1) / jg <= 65535u, GLOC_ERR_INVALID,
                  "the culled search's grid: %u work-groups per job slot (scans above ~8 M points) or %u job groups exceed 65535", n_wg,
                  (n_slots + jg - 1) / jg);
-    if (h->trace_on) {
-      h->trace_waves = (size_t)grid * NN_WPB;
-      if (h->trace.ensure(h->trace_waves * 4 * NN_TRACE_WORDS, v.s)) return GLOC_ERR_NOMEM;
-      GLOC_HIP(hipMemsetAsync(h->trace.p, 0, h->trace_waves * 4 * NN_TRACE_WORDS, v.s));
-    }
-// instantiations: sources per lane x (pairs | moments) x (first pass: cold start | later: warm) x (with the split plan);
-// the per-wave trace only at two sources per lane
-#define LAUNCH_COMPACT(CS_, P_, W_)                                                                      \
-  do {                                                                                                  \
-    if (h->trace_on && (CS_) == 2) {                                                                    \
-      if (v.split.hx) LAUNCH_COMPACT_T(2, P_, true, true, W_);                                         \
-      else LAUNCH_COMPACT_T(2, P_, true, false, W_);                                                    \
-    } else if (v.split.hx) {                                                                           \
-      if (!(P_) && (W_) && (CS_) == 2) LAUNCH_COMPACT_K((nn_compact_split_warm_kernel<2>), P_);         \
-      else LAUNCH_COMPACT_T(CS_, P_, false, true, W_);                                                  \
-    } else {                                                                                            \
-      LAUNCH_COMPACT_T(CS_, P_, false, false, W_);                                                      \
-    }                                                                                                   \
-  } while (0)
-#define LAUNCH_COMPACT_T(CS_, P_, T_, S_, W_) LAUNCH_COMPACT_K((nn_compact_kernel<CS_, P_, T_, S_, W_>), P_)
-#define LAUNCH_COMPACT_K(K_, P_)                                                                         \
-  hipLaunchKernelGGL(K_, dim3(jg, n_wg, (n_slots + jg - 1) / jg), dim3(64 * NN_WPB), 0, v.s, v.jobs, \
-                     v.n_jobs, jg, n_wg, subs, v.states,                               \
-                     warm ? v.corr : (const uint32_t*)nullptr, v.corr,   \
-                     v.d2, v.pairs, (P_) ? (double*)nullptr : v.partials, bd.n_part, bd.ld, \
-                     gate2, v.split, hv,                                                                \
-                     h->prof.enabled ? h->counters.as<unsigned long long>() : (unsigned long long*)nullptr, \
-                     h->trace_on ? h->trace.as<uint32_t>() : (uint32_t*)nullptr)
-#define LAUNCH_COMPACT_CS(P_, W_)                                                                        \
-  do {                                                                                                  \
-    if (cs == 1) LAUNCH_COMPACT(1, P_, W_);                                                             \
-    else if (cs == 2) LAUNCH_COMPACT(2, P_, W_);                                                        \
-    else LAUNCH_COMPACT(4, P_, W_);                                                                     \
-  } while (0)
     if (grid) {
-      if (want_pairs) LAUNCH_COMPACT_CS(true, false);  // (the pass that writes the pairs is a batch's first)
-      else if (warm) LAUNCH_COMPACT_CS(false, true);
-      else LAUNCH_COMPACT_CS(false, false);
+      const NnArgs a{v, bd, jg, n_wg, subs, gate2, h->prof.enabled ? h->counters.as<unsigned long long>() : nullptr};
+      const dim3 g3(jg, n_wg, (n_slots + jg - 1) / jg);
+      const uint32_t* prev_corr = warm ? v.corr : nullptr;
+      if (cs == 1) launch_kind<1>(a, g3, prev_corr, hv, want_pairs, warm);
+      else if (cs == 2) launch_kind<2>(a, g3, prev_corr, hv, want_pairs, warm);
+      else launch_kind<4>(a, g3, prev_corr, hv, want_pairs, warm);
       if (hv.cap) {  // the groups the cold pass's waves gave up: NN_HEAVY_PARTS waves each (the list's length stays on the device)
-#define LAUNCH_HEAVY(P_)                                                                                              \
-  hipLaunchKernelGGL((nn_compact_heavy_kernel<2, P_>), dim3(hv.cap * NN_HEAVY_PARTS), dim3(64), 0, v.s, v.jobs, \
-                     v.n_jobs, jg, n_wg, subs, v.states, (const uint32_t*)nullptr, v.corr,       \
-                     v.d2, v.pairs, (P_) ? (double*)nullptr : v.partials, bd.n_part, bd.ld, \
-                     gate2, v.split, hv,                                                                               \
-                     h->prof.enabled ? h->counters.as<unsigned long long>() : (unsigned long long*)nullptr, (uint32_t*)nullptr)
-        if (want_pairs) LAUNCH_HEAVY(true);
-        else LAUNCH_HEAVY(false);
-#undef LAUNCH_HEAVY
+        const dim3 gh(hv.cap * NN_HEAVY_PARTS);
+        if (want_pairs) launch_compact<nn_compact_heavy_kernel<2, true>>(a, gh, nullptr, true, hv);
+        else launch_compact<nn_compact_heavy_kernel<2, false>>(a, gh, nullptr, false, hv);
       }
     }
-#undef LAUNCH_COMPACT_CS
-#undef LAUNCH_COMPACT
-#undef LAUNCH_COMPACT_T
-#undef LAUNCH_COMPACT_K
   }
   GLOC_HIP(hipGetLastError());
   return GLOC_OK;
 }
 
-// The remaining warm moments passes of a small batch -- search, reduce, solve, plan, `n_pass` times -- in ONE launch
-// (NnChain, reg_kernels.hpp; nn_chain_kernel, nn_compact.hpp).  0 passes: the batch does not qualify (the caller goes on
-// launch by launch).
-uint32_t chain_passes(const gloc_reg* h, const BatchDims& bd, const WsView& v, uint32_t remaining) {
-  if (!h->nn_chain || h->chain_broken || h->nn_mode == 1 || h->nn_src_per_lane != 2 || h->trace_on || remaining < 2 || NN_WPB != 1) return 0;
-  if (!v.split.hx || h->prof.enabled) return 0;
+// Will the warm passes of a batch -- `warm_passes` of them behind its first, cold, pass -- run as ONE launch (NnChain,
+// reg_kernels.hpp; nn_chain_kernel, nn_compact.hpp): search, reduce, solve, plan, pass after pass?  Decided once per
+// batch, before the split threshold (setup_split) and for every pass of it: a small batch at two sources per lane with the
+// split plan (`hx` helper slots per job) and at least two warm passes; else the batch goes on launch by launch.
+bool batch_chains(const gloc_reg* h, const BatchDims& bd, uint32_t hx, uint32_t warm_passes) {
+  if (!h->nn_chain || h->chain_broken || h->nn_mode == 1 || h->nn_src_per_lane != 2 || h->prof.enabled || NN_WPB != 1) return false;
+  if (hx == 0 || warm_passes < 2) return false;
   uint32_t jg, subs;
-  launch_order(h, v.n_jobs, jg, subs);
-  if (v.n_jobs >= 48 || (jg & 7u) || jg % subs) return 0;  // (small batches; a group of slots holds whole jobs)
-  if ((bd.n_part & 31u) || (v.split.hx & 31u)) return 0;  // (a job's rows of the per-pass tables are whole cache lines)
-  const uint32_t n_wg = ((bd.max_groups + v.split.hx + NN_WPB - 1) / NN_WPB + subs - 1) / subs;
-  const uint32_t groups = (v.n_jobs * subs + jg - 1) / jg;
+  launch_order(h, bd.n_jobs, jg, subs);
+  if (bd.n_jobs >= 48 || (jg & 7u) || jg % subs) return false;  // (small batches; a group of slots holds whole jobs)
+  if ((bd.n_part & 31u) || (hx & 31u)) return false;            // (a job's rows of the per-pass tables are whole cache lines)
+  const uint32_t n_wg = ((bd.max_groups + hx + NN_WPB - 1) / NN_WPB + subs - 1) / subs;
+  const uint32_t groups = (bd.n_jobs * subs + jg - 1) / jg;
   const uint64_t grp_size = ((uint64_t)jg * n_wg + (jg / subs) * NN_CHAIN_ROLES + 7) & ~7ull;
-  if (grp_size * groups * remaining >= (1ull << 31)) return 0;
-  return remaining;
+  return grp_size * groups * warm_passes < (1ull << 31);
 }
 
 int launch_nn_chain(gloc_reg* h, const BatchDims& bd, const WsView& v, uint32_t n_pass, float gate2) {
@@ -393,27 +351,11 @@ int launch_nn_chain(gloc_reg* h, const BatchDims& bd, const WsView& v, uint32_t 
   ch.planp = reinterpret_cast<uint32_t*>(base + head + t_bytes);
   ch.helperp = reinterpret_cast<uint32_t*>(base + head + t_bytes + plan_bytes);
   ch.sub = reinterpret_cast<double*>(base + head + t_bytes + plan_bytes + help_bytes);
-  if (h->chain_trace) {
-    const size_t nb = (size_t)n_pass * v.n_jobs * 16 * 4;
-    GLOC_TRY(h->chain_dbg.ensure(nb, v.s));
-    GLOC_HIP(hipMemsetAsync(h->chain_dbg.p, 0, nb, v.s));
-    for (uint32_t q = 0; q < n_pass * v.n_jobs; ++q)  // (slots 0 and 1 take a minimum)
-      GLOC_HIP(hipMemsetAsync(h->chain_dbg.as<uint32_t>() + (size_t)q * 16, 0xFF, 8, v.s));
-    ch.dbg = h->chain_dbg.as<uint32_t>();
-    h->chain_dbg_pass = n_pass;
-    h->chain_dbg_jobs = v.n_jobs;
-  }
   h->nn_launches += n_pass;
   h->chain_launches++;
   h->chain_in_batch = true;
-  if (v.split.hx)
-    hipLaunchKernelGGL((nn_chain_kernel<2, true>), dim3(ch.pass_size * n_pass), dim3(64 * NN_WPB), 0, v.s, v.jobs, v.n_jobs, jg, n_wg, subs,
-                       v.states, v.corr, v.corr, v.d2, v.pairs, v.partials, bd.n_part, bd.ld, gate2, v.split, NnHeavy{},
-                       (unsigned long long*)nullptr, (uint32_t*)nullptr, ch);
-  else
-    hipLaunchKernelGGL((nn_chain_kernel<2, false>), dim3(ch.pass_size * n_pass), dim3(64 * NN_WPB), 0, v.s, v.jobs, v.n_jobs, jg, n_wg, subs,
-                       v.states, v.corr, v.corr, v.d2, v.pairs, v.partials, bd.n_part, bd.ld, gate2, v.split, NnHeavy{},
-                       (unsigned long long*)nullptr, (uint32_t*)nullptr, ch);
+  const NnArgs a{v, bd, jg, n_wg, subs, gate2, nullptr};
+  launch_compact<nn_chain_kernel<2>>(a, dim3(ch.pass_size * n_pass), v.corr, false, NnHeavy{}, ch);
   GLOC_HIP(hipGetLastError());
   GLOC_HIP(hipMemcpyAsync(h->h_chain_err, ch.err, 4, hipMemcpyDeviceToHost, v.s));
   return GLOC_OK;
@@ -435,9 +377,9 @@ int ensure_pinned(gloc_reg* h, uint32_t n_jobs) {
   return GLOC_OK;
 }
 
-// The launches of a batch -- or of one sub-batch on its own stream: S1 -> S2 (RANSAC + refit) -> S3 (ICP) over the view's jobs.
+// The launches of a batch: S1 -> S2 (RANSAC + refit) -> S3 (ICP).  chained: its warm passes are one launch (batch_chains).
 int enqueue_pipeline(gloc_reg* h, const BatchDims& bd, const gloc_reg_params* prm, const WsView& v, bool can, bool any_tgt,
-                     uint32_t nblocks) {
+                     uint32_t nblocks, bool chained) {
   const uint32_t n_jobs = v.n_jobs;
   hipStream_t s = v.s;
   const bool culled = h->nn_mode != 1;
@@ -524,12 +466,9 @@ int enqueue_pipeline(gloc_reg* h, const BatchDims& bd, const gloc_reg_params* pr
     }
   }
   for (uint32_t it = 0; it < prm->icp_iters && can && any_tgt; ++it) {
-    if (have_corr && v.job0 == 0 && v.n_jobs == bd.n_jobs) {
-      const uint32_t n_chain = chain_passes(h, bd, v, prm->icp_iters - it);
-      if (n_chain) {  // a small batch: all the passes that are left in one launch
-        GLOC_TRY(launch_nn_chain(h, bd, v, n_chain, gate2));
-        break;
-      }
+    if (chained && have_corr) {  // a small batch: all the passes that are left in one launch
+      GLOC_TRY(launch_nn_chain(h, bd, v, prm->icp_iters - it, gate2));
+      break;
     }
     GLOC_TRY(launch_nn(h, bd, v, have_corr, false, gate2));
     have_corr = true;
@@ -592,8 +531,12 @@ int enqueue_jobs(gloc_reg* h, const std::vector<JobHost>& jh, const gloc_reg_par
   GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part * n_jobs, s));
   GLOC_HIP(hipMemcpyAsync(h->jobs.p, jd, sizeof(Job) * n_jobs, hipMemcpyHostToDevice, s));
   GLOC_HIP(hipMemcpyAsync(h->states.p, h->h_states, sizeof(CandState) * n_jobs, hipMemcpyHostToDevice, s));
-  GLOC_TRY(setup_split(h, bd, cs));
   const bool ransac = can && any_tgt && prm->ransac_iters > 0;
+  // the warm passes: the ICP passes behind the batch's first, cold, pass (RANSAC's pairs pass, else the first ICP pass)
+  const uint32_t warm_passes = !(can && any_tgt) ? 0u : (ransac ? prm->icp_iters : std::max<uint32_t>(prm->icp_iters, 1u) - 1u);
+  const uint32_t hx = split_helpers(h, bd);
+  const bool chained = batch_chains(h, bd, hx, warm_passes);
+  GLOC_TRY(setup_split(h, bd, cs, hx, chained));
   const size_t H = prm->ransac_iters;
   const bool adaptive = prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f;
   if (ransac) {
@@ -603,86 +546,28 @@ int enqueue_jobs(gloc_reg* h, const std::vector<JobHost>& jh, const gloc_reg_par
     GLOC_TRY(h->inliers.ensure(sizeof(uint32_t) * H * n_jobs, s));
     if (!adaptive) GLOC_TRY(h->alive.ensure(sizeof(uint32_t) * (H + 1) * n_jobs, s));
   }
-  // Sub-batches (round 6): a SMALL batch -- one query alone: 20 jobs -- is cut into G runs of jobs, each enqueued on its
-  // own stream.  The jobs of a batch never depend on each other, but one stream makes all of them wait at every launch
-  // boundary: 21 x (search launch + solve) with the chip ramping up and draining 42 times (a pass of 20 jobs is 19 380
-  // waves over 6 144 slots: 69 us at full occupancy, 105 - 120 measured, + 14 us of solve with the chip idle).  With G
-  // streams one sub-batch's solve and ramp run under the others' searches.  Results are the same bits (a job's
-  // arithmetic never sees the batch).  Not with the per-kernel events on (they bracket launches on ONE stream), nor the trace.
-  uint32_t G = 1;
-  if (!h->prof.enabled && !h->trace_on && h->nn_mode != 1) {
-    if (h->sub_batches > 0) G = (uint32_t)h->sub_batches;
-    // (-1, the default, is OFF: measured for one query alone -- 20 jobs -- 3.20 ms on one stream, 3.28 with 2 sub-batches,
-    // 3.9 with 4, 5.0 with 8, enqueued one after the other or from a host thread each: a search launch of even 5 jobs has
-    // 4 845 + helper waves for 6 144 slots, so the streams' kernels mostly run one after the other, each with its own ramp)
-  }
-  G = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(G, n_jobs), gloc_reg::MAX_SUB));
-  GLOC_TRY(setup_heavy(h, bd, cs, G));
-  std::vector<WsView> views(G);
-  for (uint32_t g = 0; g < G; ++g) {
-    const uint32_t j0 = (uint32_t)((uint64_t)n_jobs * g / G), j1 = (uint32_t)((uint64_t)n_jobs * (g + 1) / G);
-    WsView& v = views[g];
-    v = WsView{};
-    v.s = s;
-    v.job0 = j0;
-    v.n_jobs = j1 - j0;
-    v.jobs = h->jobs.as<Job>() + j0;
-    v.states = h->states.as<CandState>() + j0;
-    v.corr = h->corr.as<uint32_t>() + (size_t)j0 * bd.ld;
-    v.d2 = h->d2.as<float>() + (size_t)j0 * bd.ld;
-    v.partials = h->partials.as<double>() + (size_t)j0 * bd.n_part * ACC_NV;
-    if (ransac) {
-      v.pairs = h->pairs.as<f32x4>() + 2 * bd.ld * (size_t)j0;
-      v.Rt = h->Rt.as<float>() + 12 * H * j0;
-      v.valid = h->valid.as<uint32_t>() + H * j0;
-      v.inliers = h->inliers.as<uint32_t>() + H * j0;
-      if (!adaptive) {
-        v.a_idx = h->alive.as<uint32_t>() + H * j0;
-        v.a_cnt = h->alive.as<uint32_t>() + H * n_jobs + j0;
-      }
-    }
-    v.split = h->split;
-    if (h->split.hx) {  // [job][...] arrays: the sub-batch's jobs
-      const size_t S = 64 * (size_t)cs;
-      v.split.work += (size_t)j0 * bd.n_part;
-      v.split.plan += (size_t)j0 * bd.n_part;
-      v.split.ticket += (size_t)j0 * h->split.hx;
-      v.split.helper += (size_t)j0 * h->split.hx;
-      v.split.skey += (size_t)j0 * h->split.hx * S;
-    }
-    v.heavy = h->heavy_of[g];
-  }
-  if (G > 1) {
-    GLOC_TRY(ensure_sub_streams(h, G));
-    GLOC_HIP(hipEventRecord(h->fork_ev, s));  // uploads, memsets and everything earlier on the handle's stream
-    for (uint32_t g = 1; g < G; ++g) {
-      views[g].s = h->sub_stream[g - 1];
-      GLOC_HIP(hipStreamWaitEvent(views[g].s, h->fork_ev, 0));
+  GLOC_TRY(setup_heavy(h, bd, cs));
+  WsView v{};
+  v.s = s;
+  v.n_jobs = n_jobs;
+  v.jobs = h->jobs.as<Job>();
+  v.states = h->states.as<CandState>();
+  v.corr = h->corr.as<uint32_t>();
+  v.d2 = h->d2.as<float>();
+  v.partials = h->partials.as<double>();
+  if (ransac) {
+    v.pairs = h->pairs.as<f32x4>();
+    v.Rt = h->Rt.as<float>();
+    v.valid = h->valid.as<uint32_t>();
+    v.inliers = h->inliers.as<uint32_t>();
+    if (!adaptive) {
+      v.a_idx = h->alive.as<uint32_t>();
+      v.a_cnt = h->alive.as<uint32_t>() + H * n_jobs;
     }
   }
-  int rc = GLOC_OK;
-  if (G > 1) {
-    // one host thread per sub-batch: 4 x 60 launches enqueued one stream after the other leave the later streams empty
-    // while the first runs (measured: 3.2 -> 3.9 ms for one query alone); side by side the streams fill together
-    std::vector<std::future<int>> fut;
-    for (uint32_t g = 1; g < G; ++g)
-      fut.push_back(std::async(std::launch::async, [&, g]() {
-        if (hipSetDevice(h->device) != hipSuccess) return (int)GLOC_ERR_HIP;
-        return enqueue_pipeline(h, bd, prm, views[g], can, any_tgt, nblocks);
-      }));
-    rc = enqueue_pipeline(h, bd, prm, views[0], can, any_tgt, nblocks);
-    for (auto& f : fut) {
-      const int r = f.get();
-      if (rc == GLOC_OK) rc = r;
-    }
-  } else {
-    rc = enqueue_pipeline(h, bd, prm, views[0], can, any_tgt, nblocks);
-  }
-  for (uint32_t g = 1; g < G; ++g) {  // (also after a failure part-way: whatever was launched is joined)
-    (void)hipEventRecord(h->join_ev[g - 1], views[g].s);
-    (void)hipStreamWaitEvent(s, h->join_ev[g - 1], 0);
-  }
-  GLOC_TRY(rc);
+  v.split = h->split;
+  v.heavy = h->heavy;
+  GLOC_TRY(enqueue_pipeline(h, bd, prm, v, can, any_tgt, nblocks, chained));
   GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState) * n_jobs, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipEventRecord(h->done_ev, s));
   if (h->chain_in_batch) {  // (a small batch: a few KB)
@@ -721,7 +606,11 @@ int collect_jobs(gloc_reg* h, uint32_t n_jobs, const size_t* n_src_of, float max
     for (uint32_t c = 0; c < n_jobs; ++c)
       if (jh[c].init_T) jh[c].init_T = &h->retry_T[(size_t)16 * c];
     const gloc_reg_params prm = h->retry_prm;
-    GLOC_TRY(enqueue_jobs(h, jh, &prm));
+    if (const int rc = enqueue_jobs(h, jh, &prm)) {
+      // (what it queued before failing may still read the batch's scans, and done_ev is the first run's: as multi_begin)
+      (void)hipStreamSynchronize(h->stream);
+      return rc;
+    }
     GLOC_HIP(hipEventSynchronize(h->done_ev));
   }
   for (uint32_t c = 0; c < n_jobs; ++c) {
@@ -890,14 +779,9 @@ int gloc_reg_destroy(gloc_reg* h) {
   h->prof.destroy();
   gloc::ndt::ws_free(h->ndt);
   for (DevBuf* b : {&h->jobs, &h->states, &h->corr, &h->d2, &h->pairs, &h->Rt, &h->valid, &h->inliers,
-                    &h->partials, &h->export_idx, &h->export_d2, &h->counters, &h->trace, &h->split_zero, &h->split_ff, &h->alive, &h->heavy_buf})
+                    &h->partials, &h->export_idx, &h->export_d2, &h->counters, &h->split_zero, &h->split_ff, &h->alive, &h->heavy_buf})
     b->release();
   if (h->done_ev) (void)hipEventDestroy(h->done_ev);
-  if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
-  for (uint32_t g = 0; g + 1 < gloc_reg::MAX_SUB; ++g) {
-    if (h->join_ev[g]) (void)hipEventDestroy(h->join_ev[g]);
-    if (h->sub_stream[g]) (void)hipStreamDestroy(h->sub_stream[g]);
-  }
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
@@ -952,9 +836,8 @@ int gloc_reg_set_option(gloc_reg* h, int option, int64_t value) {
     return GLOC_OK;
   }
   if (option == GLOC_REG_OPT_SUB_BATCHES) {
-    GLOC_REQUIRE(value >= -1 && value <= (int64_t)gloc_reg::MAX_SUB, GLOC_ERR_INVALID, "must be in [-1, %u]", gloc_reg::MAX_SUB);
-    h->sub_batches = (int)value;
-    return GLOC_OK;
+    GLOC_REQUIRE(value >= -1 && value <= 8, GLOC_ERR_INVALID, "must be in [-1, 8]");
+    return GLOC_OK;  // (accepted for existing callers; a batch is always enqueued on the handle's stream)
   }
   if (option == GLOC_REG_OPT_NN_CHAIN) {
     GLOC_REQUIRE(value == 0 || value == 1, GLOC_ERR_INVALID, "must be 0 or 1");
@@ -1297,7 +1180,7 @@ int gloc_reg_nn(gloc_reg* h, const float* src_xyz, size_t n_src, const float* tg
   v.corr = h->corr.as<uint32_t>();
   v.d2 = h->d2.as<float>();
   v.partials = h->partials.as<double>();
-  v.heavy = h->heavy_of[0];
+  v.heavy = h->heavy;
   int rc = launch_nn(h, bd, v, false, false, 0.f);
   if (rc != GLOC_OK) return done(rc);
   hipLaunchKernelGGL(export_corr_kernel, dim3((unsigned)((n_src + 255) / 256), 1), dim3(256), 0, s,
@@ -1410,23 +1293,6 @@ int gloc_reg_debug_chain(gloc_reg* h, uint64_t* launches, uint64_t* timeouts) {
   return GLOC_OK;
 }
 
-// Developer aid (not part of include/gloc3d.h): stamps of the last chained launch, [pass][job][16] words of the 100 MHz clock
-// (tools/dev_chain_trace.py): 0 first search wave arrives, 1 first one past its wait, 2 last one leaves, 3 reducer 0 starts
-// to wait, 4 sees the pass done, 5 has stored its sub-sum, 6 last reducer in, 7 sums loaded, 8 solved.
-int gloc_reg_debug_chain_trace(gloc_reg* h, int enable, uint32_t* out, size_t cap_words, uint32_t* n_pass, uint32_t* n_jobs) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  h->chain_trace = enable != 0;
-  if (n_pass) *n_pass = h->chain_dbg_pass;
-  if (n_jobs) *n_jobs = h->chain_dbg_jobs;
-  if (out && h->chain_dbg.p) {
-    const size_t n = std::min(cap_words, (size_t)h->chain_dbg_pass * h->chain_dbg_jobs * 16);
-    GLOC_HIP(hipStreamSynchronize(h->stream));
-    GLOC_HIP(hipMemcpy(out, h->chain_dbg.p, n * 4, hipMemcpyDeviceToHost));
-  }
-  return GLOC_OK;
-}
-
 // Test aid (not part of include/gloc3d.h): the adaptive stop's iteration count as the DEVICE computes it, for `count`
 // (inliers, points) pairs -- compared with the oracle's loop in tests/test_reg_gpu.py.
 int gloc_reg_debug_needed_iters(gloc_reg* h, const uint32_t* inl, const uint32_t* n, uint32_t count, float conf, uint32_t max_iters,
@@ -1451,20 +1317,6 @@ int gloc_reg_debug_needed_iters(gloc_reg* h, const uint32_t* inl, const uint32_t
 int gloc_reg_debug_chain_stall(gloc_reg* h, int on) {
   GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
   h->chain_stall = on != 0;
-  return GLOC_OK;
-}
-
-// Developer aid (not part of include/gloc3d.h): per-wave trace of the LAST culled 1-NN launch.
-int gloc_reg_debug_trace(gloc_reg* h, int enable, uint32_t* out, size_t cap_waves, size_t* n_waves) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  h->trace_on = enable != 0;
-  if (n_waves) *n_waves = h->trace_waves;
-  if (out && h->trace.p) {
-    const size_t n = std::min(cap_waves, h->trace_waves);
-    GLOC_HIP(hipMemcpyAsync(out, h->trace.p, n * 4 * NN_TRACE_WORDS, hipMemcpyDeviceToHost, h->stream));
-    GLOC_HIP(hipStreamSynchronize(h->stream));
-  }
   return GLOC_OK;
 }
 

@@ -122,7 +122,6 @@ struct NnChain {
   uint32_t* helperp; // [pass - 1][job][hx]: NnSplit::helper of passes 1 ..
   double* sub;       // [job][NN_CHAIN_RED][ACC_NV]: the reducers' sub-sums of the moments (solve_kernel's sub[][])
   uint32_t* err;     // != 0: a wait ran out
-  uint32_t* dbg;     // dev (gloc_reg_debug_chain_trace): [pass][job][16] stamps of the 100 MHz clock, or null
   uint32_t n_pass;
   uint32_t expected;      // search waves per job and pass
   uint32_t jobs_per_grp;  // jobs of a group of slots (job_group / subs)
@@ -136,7 +135,7 @@ constexpr uint32_t NN_CHAIN_ROLES = NN_CHAIN_RED + 1;  // + the planner
 constexpr unsigned long long NN_CHAIN_WAIT_TICKS = 300000000ull;  // 3 s of the 100 MHz clock
 constexpr uint32_t NN_NO_HELPER = 0xFFFFFFFFu;
 constexpr uint32_t NN_MAX_PARTS = 8;
-// the estimate, from the trace's regression of wave cycles on its counts (tools/dev_nn_trace3.py)
+// the estimate, from a regression of traced wave cycles on the waves' counts (round 6)
 constexpr uint32_t NN_W_FIXED = 21000, NN_W_CAND = 300, NN_W_CHUNK = 2800, NN_W_ITEM = 37;
 
 // waves for an estimate: 0 = the group's own wave at its rank in the launch order; 2, 4, 8 = that many parts in helper slots

@@ -22,7 +22,7 @@ FLAGS = EXTRA + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-co
 # totals every 64 k, and from AGPRs that is a v_accvgpr_read per register and step (measured: 121 of the main loop's
 # ~330 vector instructions); without AGPRs the kernel also fits three work-groups per CU (161 registers, not 192)
 MFMA_VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
-PER_SOURCE = {"knn.hip": MFMA_VGPR_FORM, "vgg.hip": MFMA_VGPR_FORM}
+PER_SOURCE = {"knn.hip": MFMA_VGPR_FORM, "vgg.hip": MFMA_VGPR_FORM, "pillar.hip": MFMA_VGPR_FORM}
 _probe = {}
 
 
@@ -164,19 +164,20 @@ def build_test_variant(force=False, verbose=False):
 
 
 def build_cli(force=False, verbose=False):
-    """The drop-in command lines (registration/global_localization, global_registration)."""
+    """The drop-in command lines (registration/global_localization, global_registration, s2s_feature_extract)."""
     build(force=force, verbose=verbose)
     bindir = os.path.join(HERE, "bin")
     os.makedirs(bindir, exist_ok=True)
     outs = []
-    for name in ("global_localization", "global_registration"):
+    for name in ("global_localization", "global_registration", "s2s_feature_extract"):
         src = os.path.join(CSRC, "cli", name + ".cpp")
         if not os.path.exists(src):
             continue
         out = os.path.join(bindir, name)
         deps = [src, LIB] + [os.path.join(CSRC, "host", f) for f in os.listdir(os.path.join(CSRC, "host"))]
         if force or _stale(out, deps):
-            cmd = ["g++", "-O2", "-std=c++17", "-I" + os.path.join(HERE, "..", "include"),
+            cmd = ["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                   "-I" + os.path.join(HERE, "..", "include"),
                    "-I" + os.path.join(CSRC, "host"), src, "-o", out, "-L" + LIBDIR, "-lgloc3d",
                    "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib",
                    "-Wl,-rpath,/opt/rocm/lib"]

@@ -225,6 +225,13 @@ _PROTOS = [
     ("gloc_pillar_inputs_device", _i, [_vp, _vp, _vp, _sz, _sz, C.POINTER(PillarParams), _vp]),
     ("gloc_pillar_canvas", _i, [_vp, _vp, _vp, _sz, _sz, C.POINTER(PillarParams), _vp]),
     ("gloc_pillar_canvas_device", _i, [_vp, _vp, _vp, _sz, _sz, C.POINTER(PillarParams), _vp]),
+    ("gloc_pillar_backbone_layer_shape", _i, [_i, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_i), C.POINTER(_i)]),
+    ("gloc_pillar_set_backbone_layer", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_float]),
+    ("gloc_pillar_backbone_device", _i, [_vp, _vp, _sz, _u32, _u32, _vp]),
+    ("gloc_pillar_backbone_layer_device", _i, [_vp, _i, _vp, _sz, _u32, _u32, _vp]),
+    ("gloc_pillar_upsample_device", _i, [_vp, _vp, _sz, _u32, _u32, _u32, _u32, _vp]),
+    ("gloc_pillar_features", _i, [_vp, _vp, _vp, _sz, _sz, C.POINTER(PillarParams), _vp]),
+    ("gloc_pillar_features_device", _i, [_vp, _vp, _vp, _sz, _sz, C.POINTER(PillarParams), _vp]),
     ("gloc_pillar_set_profile", _i, [_vp, _i]),
     ("gloc_pillar_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
     ("gloc_pillar_profile_reset", _i, [_vp]),
@@ -1070,6 +1077,16 @@ def _scan_batch(scans):
     return pts, off
 
 
+PILLAR_BACKBONE_LAYERS = 13
+
+
+def pillar_backbone_layer_shape(layer):
+    """(Cin, Cout, stride, relu) of PointPillar backbone layer `layer` (0..12), from the library's own table."""
+    ci, co, st, r = C.c_uint32(), C.c_uint32(), C.c_int(), C.c_int()
+    check(lib().gloc_pillar_backbone_layer_shape(layer, C.byref(ci), C.byref(co), C.byref(st), C.byref(r)))
+    return ci.value, co.value, st.value, bool(r.value)
+
+
 class PillarEncoder:
     """PointPillar scan front end: points_to_voxels + the traced model's [P, 16] input (model/voxel.py:23-133,
     gen_libtorch_pointpillar.py:47-62) and the PointNet + scatter-mean canvas [64, gx * gy * gz]
@@ -1128,6 +1145,43 @@ class PillarEncoder:
         off = np.ascontiguousarray(offsets, np.uint64)
         check(lib().gloc_pillar_canvas_device(self._h, C.c_void_p(pts_ptr), _np_ptr(off), off.shape[0] - 1,
                                               stride_floats, C.byref(p), C.c_void_p(out_ptr)))
+
+    def set_backbone_layer(self, layer, w, bn_weight, bn_bias, bn_mean, bn_var, eps=1e-5):
+        """w [Cout, Cin, 3, 3] (torch's Conv2d weight); BatchNorm2d weight, bias, running mean, running var [Cout]."""
+        ci, co, _, _ = pillar_backbone_layer_shape(layer)
+        wa = np.ascontiguousarray(w, np.float32)
+        bn = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in (bn_weight, bn_bias, bn_mean, bn_var)]
+        assert wa.shape == (co, ci, 3, 3) and all(x.size == co for x in bn), (layer, wa.shape)
+        check(lib().gloc_pillar_set_backbone_layer(self._h, layer, _np_ptr(wa), *[_np_ptr(x) for x in bn], float(eps)))
+
+    def backbone_device(self, canvas_ptr, n, gx, gy, out_ptr):
+        """Device buffers on the handle's stream: canvas [n, 64, gx * gy] -> [n, 128, gy * gx]."""
+        check(lib().gloc_pillar_backbone_device(self._h, C.c_void_p(canvas_ptr), n, gx, gy, C.c_void_p(out_ptr)))
+
+    def backbone_layer_device(self, layer, in_ptr, n, H, W, out_ptr):
+        """One backbone layer with its BatchNorm (+ ReLU), NCHW [n, Cin, H, W] -> [n, Cout, Ho, Wo] (layers 9 and 10:
+        the input before the upsample)."""
+        check(lib().gloc_pillar_backbone_layer_device(self._h, layer, C.c_void_p(in_ptr), n, H, W, C.c_void_p(out_ptr)))
+
+    def upsample_device(self, in_ptr, n, ch, H, W, factor, out_ptr):
+        """The backbone's bilinear upsample (align_corners=True), NCHW [n, ch, H, W] -> [n, ch, factor H, factor W]."""
+        check(lib().gloc_pillar_upsample_device(self._h, C.c_void_p(in_ptr), n, ch, H, W, factor, C.c_void_p(out_ptr)))
+
+    def features(self, scans, params=None):
+        """A scan [n, 4+] or a list of them -> backbone features [B, 128, gy * gx] float32 (canvas + backbone)."""
+        p = params or default_pillar_params()
+        pts, off = _scan_batch(scans)
+        gx, gy, gz = p.grid()
+        out = np.empty((len(off) - 1, 128, gx * gy * gz), np.float32)
+        check(lib().gloc_pillar_features(self._h, _np_ptr(pts), _np_ptr(off), len(off) - 1, pts.shape[1], C.byref(p),
+                                         _np_ptr(out)))
+        return out
+
+    def features_device(self, pts_ptr, offsets, stride_floats, out_ptr, params=None):
+        p = params or default_pillar_params()
+        off = np.ascontiguousarray(offsets, np.uint64)
+        check(lib().gloc_pillar_features_device(self._h, C.c_void_p(pts_ptr), _np_ptr(off), off.shape[0] - 1,
+                                                stride_floats, C.byref(p), C.c_void_p(out_ptr)))
 
     def set_stream(self, stream_ptr):
         check(lib().gloc_pillar_set_stream(self._h, C.c_void_p(stream_ptr)))

@@ -1,7 +1,7 @@
 """PointPillar-NetVLAD scan descriptor (the reference's PointPillarVLAD, model/s2s_merged.py:113-255, as traced by
-s2s_libtorch/gen_libtorch_pointpillar.py): the HIP canvas (capi.PillarEncoder), this project's restatement of the
-PointPillarTest backbone in torch (plumbing: dense 2-D convolution at 140 x 80), and the HIP NetVLAD-FC head
-(capi.NetVladFC).  torch is imported here only, never by `import gloc3d_amd`.
+s2s_libtorch/gen_libtorch_pointpillar.py): the HIP canvas (capi.PillarEncoder), the PointPillarTest backbone -- this
+project's restatement in torch (PillarBackbone, the default) or the library's HIP one (backbone="hip") -- and the HIP
+NetVLAD-FC head (capi.NetVladFC).  torch is imported here only, never by `import gloc3d_amd`.
 """
 import numpy as np
 import torch
@@ -56,11 +56,32 @@ class PillarBackbone(nn.Module):
         return self.conv_out(x).transpose(3, 2)
 
 
+# (conv, BatchNorm) of the backbone's 13 layers in the order of gloc_pillar_backbone_layer_shape, as PillarBackbone
+# (and the reference's PointPillarTest) names them in a state_dict
+BACKBONE_KEYS = [("block1.layers.0", "block1.layers.1"), ("block1.layers.3", "block1.layers.4"),
+                 ("block2.layers.0", "block2.layers.1"), ("block2.layers.3", "block2.layers.4"),
+                 ("block2.layers.6", "block2.layers.7"),
+                 ("block3.layers.0", "block3.layers.1"), ("block3.layers.3", "block3.layers.4"),
+                 ("block3.layers.6", "block3.layers.7"),
+                 ("up1.0", "up1.1"), ("up2.1", "up2.2"), ("up3.1", "up3.2"),
+                 ("conv_out.0", "conv_out.1"), ("conv_out.3", "conv_out.4")]
+
+
+def backbone_layers(sd, prefix="encoder."):
+    """13 tuples (w, bn_weight, bn_bias, bn_mean, bn_var) from a state_dict of numpy arrays."""
+    return [(sd[prefix + c + ".weight"], sd[prefix + b + ".weight"], sd[prefix + b + ".bias"],
+             sd[prefix + b + ".running_mean"], sd[prefix + b + ".running_var"]) for c, b in BACKBONE_KEYS]
+
+
 class PillarVladDescriptor:
     """Scans -> 128-D descriptors of PointPillarVLAD (encoder = PointPillarTest in vlad_mode, pool = NetVLAD 64 x 128 ->
-    128).  `device` is a torch device index; scans may be numpy arrays (host) or a torch tensor on that device."""
+    128).  `device` is a torch device index; scans may be numpy arrays (host) or a torch tensor on that device.
+    backbone="torch" runs PillarBackbone (torch convolutions); "hip" runs the library's backbone, the canvas, backbone
+    and head on one stream with no torch convolution in the path (loaded from the same `encoder.*` keys)."""
 
-    def __init__(self, state_dict, params=None, device=0, pn_eps=1e-5):
+    def __init__(self, state_dict, params=None, device=0, pn_eps=1e-5, backbone="torch", bn_eps=1e-5):
+        if backbone not in ("torch", "hip"):
+            raise ValueError(f"backbone must be 'torch' or 'hip', not {backbone!r}")
         self.params = params or capi.default_pillar_params()
         gx, gy, gz = self.params.grid()
         if gz != 1:
@@ -72,11 +93,17 @@ class PillarVladDescriptor:
         pn = "encoder.pn.pointnet."
         self.encoder.set_pointnet(sd[pn + "0.weight"].reshape(64, 14), sd[pn + "1.weight"], sd[pn + "1.bias"],
                                   sd[pn + "1.running_mean"], sd[pn + "1.running_var"], pn_eps)
-        self.backbone = PillarBackbone(gx, gy)
-        enc = {k[len("encoder."):]: torch.from_numpy(np.asarray(v)) for k, v in sd.items()
-               if k.startswith("encoder.") and not k.startswith(("encoder.pn.", "encoder.conv_out_pose."))}
-        self.backbone.load_state_dict(enc)          # strict: every backbone parameter must be in the checkpoint
-        self.backbone = self.backbone.to(self.tdev).eval()
+        self.grid = (gx, gy)
+        if backbone == "hip":
+            self.backbone = None
+            for layer, args in enumerate(backbone_layers(sd)):
+                self.encoder.set_backbone_layer(layer, *args, eps=bn_eps)
+        else:
+            self.backbone = PillarBackbone(gx, gy)
+            enc = {k[len("encoder."):]: torch.from_numpy(np.asarray(v)) for k, v in sd.items()
+                   if k.startswith("encoder.") and not k.startswith(("encoder.pn.", "encoder.conv_out_pose."))}
+            self.backbone.load_state_dict(enc)          # strict: every backbone parameter must be in the checkpoint
+            self.backbone = self.backbone.to(self.tdev).eval()
         conv_w = sd["pool.conv.weight"].reshape(sd["pool.conv.weight"].shape[0], -1)
         self.pool = capi.NetVladFC(conv_w, sd["pool.centroids"], sd["pool.hidden1_weights"],
                                    conv_b=sd.get("pool.conv.bias"), normalize_input=True, device=device)
@@ -107,19 +134,33 @@ class PillarVladDescriptor:
         caller.wait_stream(self.stream)
         return out
 
-    def _canvas(self, scans):
+    def _points(self, scans):
         if torch.is_tensor(scans):
             pts = scans.to(self.tdev, torch.float32).contiguous()
             off = np.array([0, pts.shape[0]], np.uint64)
         else:
             host, off = capi._scan_batch(scans)
             pts = torch.from_numpy(host).to(self.tdev)
+        pts.record_stream(self.stream)
+        return pts, off, pts.shape[1] if pts.dim() == 2 else 4
+
+    def _canvas(self, scans):
+        pts, off, stride = self._points(scans)
         gx, gy, gz = self.params.grid()
         out = torch.empty((len(off) - 1, capi.PILLAR_FEATURES, gx * gy * gz), dtype=torch.float32, device=self.tdev)
-        self.encoder.canvas_device(pts.data_ptr(), off, pts.shape[1] if pts.dim() == 2 else 4, out.data_ptr(),
-                                   self.params)
-        pts.record_stream(self.stream)
+        self.encoder.canvas_device(pts.data_ptr(), off, stride, out.data_ptr(), self.params)
         return out
+
+    def _features(self, scans):
+        """[B, 128, gy * gx] on the device (on self.stream): the torch or the HIP backbone behind the canvas."""
+        if self.backbone is not None:
+            feat = self.backbone(self._canvas(scans)).contiguous()     # [B, 128, gy, gx]
+            return feat.view(feat.shape[0], feat.shape[1], -1)
+        pts, off, stride = self._points(scans)
+        gx, gy = self.grid
+        feat = torch.empty((len(off) - 1, 128, gx * gy), dtype=torch.float32, device=self.tdev)
+        self.encoder.features_device(pts.data_ptr(), off, stride, feat.data_ptr(), self.params)
+        return feat
 
     @torch.no_grad()
     def __call__(self, scans):
@@ -127,8 +168,8 @@ class PillarVladDescriptor:
         caller = torch.cuda.current_stream(self.tdev)
         self.stream.wait_stream(caller)
         with torch.cuda.stream(self.stream):
-            feat = self.backbone(self._canvas(scans)).contiguous()     # [B, 128, gy, gx]
+            feat = self._features(scans)                               # [B, 128, gy * gx]
             out = torch.empty((feat.shape[0], self.out_dim), dtype=torch.float32, device=self.tdev)
-            self.pool.forward_device(feat.data_ptr(), feat.shape[0], feat.shape[2] * feat.shape[3], out.data_ptr())
+            self.pool.forward_device(feat.data_ptr(), feat.shape[0], feat.shape[2], out.data_ptr())
             res = out.cpu().numpy()
         return res

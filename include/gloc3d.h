@@ -623,9 +623,49 @@ int gloc_pillar_canvas(gloc_pillar* h, const float* pts, const uint64_t* offsets
                        const gloc_pillar_params* p, float* out);
 int gloc_pillar_canvas_device(gloc_pillar* h, const float* d_pts, const uint64_t* offsets, size_t n_scans,
                               size_t stride_floats, const gloc_pillar_params* p, float* d_out);
+/* The 2-D backbone behind the canvas, PointPillarTest after the scatter-mean in vlad_mode (model/s2s_merged.py:
+ * 152-188,219-247): 13 convolutions 3x3, pad 1, no bias, each followed by BatchNorm2d in eval mode and (but the last)
+ * ReLU.  Layers: 0-1 block1 64 -> 64; 2-4 block2 64 -> 128 (stride 2), 128 -> 128 x 2; 5-7 block3 128 -> 256
+ * (stride 2), 256 -> 256 x 2; 8 up1 64 -> 64 on block1's output; 9 up2 128 -> 128 on block2's output upsampled x 2;
+ * 10 up3 256 -> 256 on block3's output upsampled x 4 (bilinear, align_corners=True); 11 conv_out.0 448 -> 256 on the
+ * concatenation of up1, up2, up3; 12 conv_out.3 256 -> 128 without ReLU.  The canvas [64][gx*gy] is viewed as
+ * [64][H = gx][W = gy]; the output is .transpose(3, 2) of the last layer's, [128][gy][gx]: gloc_vlad_forward_device's
+ * [n][128][hw] with hw = gy*gx.  Inside, each convolution is an implicit GEMM on the bf16 matrix cores with both
+ * operands split in two bf16 halves (three products, as gloc_vgg); BatchNorm is applied to the fp32 sums.  Contract:
+ * max|out - fp32 reference| <= 1e-4 max|reference| per layer and for the whole backbone.  Every
+ * output has a fixed summation order: a batch gives the same bits as single calls. */
+/* Cin, Cout, stride and ReLU of backbone layer `layer` (0..12); needs no handle and no device.  Any pointer may be NULL. */
+int gloc_pillar_backbone_layer_shape(int layer, uint32_t* cin, uint32_t* cout, int* stride, int* relu);
+/* w [Cout][Cin][3][3] (torch's Conv2d layout), BatchNorm2d weight, bias, running mean and variance [Cout], eps (1e-5,
+ * torch's default); host fp32, copied and re-laid on the device before this returns.  The backbone and feature calls
+ * need all 13 layers (GLOC_ERR_STATE without). */
+int gloc_pillar_set_backbone_layer(gloc_pillar* h, int layer, const float* w, const float* bn_weight,
+                                   const float* bn_bias, const float* bn_mean, const float* bn_var, float eps);
+/* Device buffers on the handle's stream: canvas [n][64][gx*gy] -> out [n][128][gy*gx].  gx and gy multiples of 4 in
+ * [4, 4096] (up2 and up3 must give block1's size back); GLOC_ERR_INVALID otherwise. */
+int gloc_pillar_backbone_device(gloc_pillar* h, const float* d_canvas, size_t n, uint32_t gx, uint32_t gy,
+                                float* d_out);
+/* One layer with its BatchNorm and ReLU on device buffers, NCHW fp32: d_in [n][Cin][H][W] -> d_out [n][Cout][Ho][Wo],
+ * Ho = (H - 1) / stride + 1 (likewise Wo).  Layers 9 and 10 take their input before the upsample: Ho = 2H, 4H.
+ * Any H, W in [1, 4096] (after the upsample).  For tests and per-layer timing. */
+int gloc_pillar_backbone_layer_device(gloc_pillar* h, int layer, const float* d_in, size_t n, uint32_t H, uint32_t W,
+                                      float* d_out);
+/* The backbone's bilinear upsample (nn.Upsample(scale_factor=factor, mode="bilinear", align_corners=True)) on its own,
+ * NCHW: d_in [n][C][H][W] -> d_out [n][C][factor*H][factor*W].  For tests. */
+int gloc_pillar_upsample_device(gloc_pillar* h, const float* d_in, size_t n, uint32_t C, uint32_t H, uint32_t W,
+                                uint32_t factor, float* d_out);
+/* Scans -> canvas -> backbone in one call: out [n_scans][128][gy*gx], ready for gloc_vlad_forward_device (dim 128).
+ * The grid must give gz = 1 and gx, gy as gloc_pillar_backbone_device needs (GLOC_ERR_INVALID otherwise); needs the
+ * PointNet and all 13 backbone layers (GLOC_ERR_STATE).  Host buffers, synchronous. */
+int gloc_pillar_features(gloc_pillar* h, const float* pts, const uint64_t* offsets, size_t n_scans, size_t stride_floats,
+                         const gloc_pillar_params* p, float* out);
+/* The same on device buffers, on the handle's stream, without synchronisation. */
+int gloc_pillar_features_device(gloc_pillar* h, const float* d_pts, const uint64_t* offsets, size_t n_scans,
+                                size_t stride_floats, const gloc_pillar_params* p, float* d_out);
 int gloc_pillar_set_profile(gloc_pillar* h, int enable);
 /* kernel families: "pillar_classify", "pillar_sort", "pillar_runs", "pillar_voxel", "pillar_gather",
- * "pillar_partial", "pillar_canvas" */
+ * "pillar_partial", "pillar_canvas"; the backbone's "pillar_conv0" .. "pillar_conv12" (one per layer),
+ * "pillar_upsample" (in front of layers 9 and 10), "pillar_layout" (the canvas or a layer's NCHW input to NHWC) */
 int gloc_pillar_profile(gloc_pillar* h, const char* kernel, double* total_ms, uint64_t* launches);
 int gloc_pillar_profile_reset(gloc_pillar* h);
 

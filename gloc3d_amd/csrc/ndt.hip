@@ -387,6 +387,22 @@ void gloc_ndt_default_params(gloc_ndt_params* p) {
   p->min_covar_eigvalue_mult = 0.01f; // pcl::VoxelGridCovariance's default [upstream]
 }
 
+// Developer / test aid (not part of include/gloc3d.h): the line search's scalar pieces of ndt_kernels.hpp, run on the
+// host (no device is touched).  I = [a_l, f_l, g_l, a_u, f_u, g_u] is updated in place where the piece does so.
+//   op 0: *out = trial_value(I, x[0] = a_t, x[1] = f_t, x[2] = g_t)
+//   op 1: *out = update_interval(I, x[0], x[1], x[2]) ? 1 : 0
+//   op 2: close_interval(I, x[0] = phi_0, x[1] = dphi_0, x[2] = mu)
+//   op 3: *out = clamp_step(x[0] = a, x[1] = step_min, x[2] = step_max)
+int gloc_ndt_debug_line_search(int op, double* I, const double* x, double* out) {
+  GLOC_REQUIRE(I && x && out && op >= 0 && op <= 3, GLOC_ERR_INVALID, "null argument or unknown op %d", op);
+  *out = 0.0;
+  if (op == 0) *out = trial_value(I, x[0], x[1], x[2]);
+  if (op == 1) *out = update_interval(I, x[0], x[1], x[2]) ? 1.0 : 0.0;
+  if (op == 2) close_interval(I, x[0], x[1], x[2]);
+  if (op == 3) *out = clamp_step(x[0], x[1], x[2]);
+  return GLOC_OK;
+}
+
 int gloc_scan_store_add_approx_voxel(gloc_scan_store* st, uint32_t base_id, float leaf, uint32_t* new_id) {
   GLOC_REQUIRE(st && new_id, GLOC_ERR_INVALID, "null argument");
   GLOC_HIP(hipSetDevice(st->device));

@@ -581,14 +581,16 @@ __global__ __launch_bounds__(DERIV_THREADS) void ndt_deriv_kernel(
 }
 
 // ---- the Newton / More-Thuente state machine (tests/ndt_ref.py::align) -----------------------------------------------
-__device__ inline double psi_f(double a, double f_a, double f_0, double g_0, double mu) { return f_a - f_0 - mu * g_0 * a; }
-__device__ inline double dpsi_f(double g_a, double g_0, double mu) { return g_a - mu * g_0; }
-__device__ inline double cubic_min(double a_l, double f_l, double g_l, double a_t, double f_t, double g_t) {
+// The line search's scalar pieces are plain fp64 arithmetic, built for the host too: gloc_ndt_debug_line_search (ndt.hip)
+// runs them there, and tests/test_ndt_sweep_cpu.py holds them to the restatement's bit for bit.
+__host__ __device__ inline double psi_f(double a, double f_a, double f_0, double g_0, double mu) { return f_a - f_0 - mu * g_0 * a; }
+__host__ __device__ inline double dpsi_f(double g_a, double g_0, double mu) { return g_a - mu * g_0; }
+__host__ __device__ inline double cubic_min(double a_l, double f_l, double g_l, double a_t, double f_t, double g_t) {
   const double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
   const double w = sqrt(z * z - g_t * g_l);
   return a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
 }
-__device__ inline double trial_value(const double* I, double a_t, double f_t, double g_t) {
+__host__ __device__ inline double trial_value(const double* I, double a_t, double f_t, double g_t) {
   const double a_l = I[0], f_l = I[1], g_l = I[2], a_u = I[3], f_u = I[4], g_u = I[5];
   if (f_t > f_l) {
     const double a_c = cubic_min(a_l, f_l, g_l, a_t, f_t, g_t);
@@ -610,7 +612,7 @@ __device__ inline double trial_value(const double* I, double a_t, double f_t, do
   }
   return cubic_min(a_u, f_u, g_u, a_t, f_t, g_t);
 }
-__device__ inline bool update_interval(double* I, double a_t, double f_t, double g_t) {
+__host__ __device__ inline bool update_interval(double* I, double a_t, double f_t, double g_t) {
   if (f_t > I[1]) {
     I[3] = a_t; I[4] = f_t; I[5] = g_t;
     return false;
@@ -626,9 +628,17 @@ __device__ inline bool update_interval(double* I, double a_t, double f_t, double
   }
   return true;
 }
-__device__ inline double clamp_step(double a, double lo, double hi) {  // std::max(std::min(a, hi), lo): NaN stays NaN
+__host__ __device__ inline double clamp_step(double a, double lo, double hi) {  // std::max(std::min(a, hi), lo): NaN stays NaN
   a = (hi < a) ? hi : a;
   return (a < lo) ? lo : a;
+}
+
+// the interval's values turn from psi to phi once a trial has psi <= 0 and dpsi >= 0 (open -> closed)
+__host__ __device__ inline void close_interval(double* I, double phi_0, double dphi_0, double mu) {
+  I[1] = I[1] + phi_0 - mu * dphi_0 * I[0];
+  I[2] = I[2] + mu * dphi_0;
+  I[4] = I[4] + phi_0 - mu * dphi_0 * I[3];
+  I[5] = I[5] + mu * dphi_0;
 }
 
 __device__ inline void request(State& S, Eval* ev, const double* at, int phase, bool hess) {
@@ -745,10 +755,7 @@ __device__ inline void after_trial(State& S, Eval* ev, Out* out, uint32_t* done_
   if (!first) {
     if (S.open_interval && (psi_t <= 0 && dpsi_t >= 0)) {
       S.open_interval = 0;
-      S.I[1] = S.I[1] + S.phi_0 - mu * S.dphi_0 * S.I[0];
-      S.I[2] = S.I[2] + mu * S.dphi_0;
-      S.I[4] = S.I[4] + S.phi_0 - mu * S.dphi_0 * S.I[3];
-      S.I[5] = S.I[5] + mu * S.dphi_0;
+      close_interval(S.I, S.phi_0, S.dphi_0, mu);
     }
     S.interval_converged = S.open_interval ? update_interval(S.I, S.a_t, psi_t, dpsi_t)
                                            : update_interval(S.I, S.a_t, phi_t, dphi_t);

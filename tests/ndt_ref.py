@@ -335,43 +335,76 @@ def _cubic(a_l, f_l, g_l, a_t, f_t, g_t):
     return a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w)
 
 
-def trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t):
-    """More & Thuente's trial value selection, cases 1-4, as PCL's trialValueSelectionMT."""
+def _note(events, name):
+    """Read-only instrumentation: record that a branch was taken (align's `events` list); no arithmetic."""
+    if events is not None:
+        events.append(name)
+
+
+def trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t, events=None):
+    """More & Thuente's trial value selection, cases 1-4, as PCL's trialValueSelectionMT.  After update_interval has moved
+    a_l to the last trial (its outcomes 2 and 3) the next call has a_t == a_l, f_t == f_l, g_t == g_l: that is case 3
+    with a_c = a_s = NaN (0 / 0), and std::min / std::max (Python's too, in this argument order) return the bound
+    a_t + 0.66 (a_u - a_t).  With finite values case 4 cannot be reached at all (tests/test_ndt_sweep_cpu.py says why)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return _trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t, events)
+
+
+def _trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t, events):
     if f_t > f_l:
+        _note(events, "trial_case_1")
         a_c = _cubic(a_l, f_l, g_l, a_t, f_t, g_t)
         a_q = a_l - 0.5 * (a_l - a_t) * g_l / (g_l - (f_l - f_t) / (a_l - a_t))
         return a_c if abs(a_c - a_l) < abs(a_q - a_l) else 0.5 * (a_q + a_c)
     if g_t * g_l < 0:
+        _note(events, "trial_case_2")
         a_c = _cubic(a_l, f_l, g_l, a_t, f_t, g_t)
         a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l
         return a_c if abs(a_c - a_t) >= abs(a_s - a_t) else a_s
     if abs(g_t) <= abs(g_l):
+        _note(events, "trial_case_3")
         a_c = _cubic(a_l, f_l, g_l, a_t, f_t, g_t)
         a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l
         a_n = a_c if abs(a_c - a_t) < abs(a_s - a_t) else a_s
         return min(a_t + 0.66 * (a_u - a_t), a_n) if a_t > a_l else max(a_t + 0.66 * (a_u - a_t), a_n)
+    _note(events, "trial_case_4")
     return _cubic(a_u, f_u, g_u, a_t, f_t, g_t)
 
 
-def update_interval(I, a_t, f_t, g_t):
+def update_interval(I, a_t, f_t, g_t, events=None):
     """PCL's updateIntervalMT on I = [a_l, f_l, g_l, a_u, f_u, g_u] (in place); True: the interval has converged."""
     if f_t > I[1]:
+        _note(events, "interval_case_1")
         I[3:6] = [a_t, f_t, g_t]
         return False
     if g_t * (I[0] - a_t) > 0:
+        _note(events, "interval_case_2")
         I[0:3] = [a_t, f_t, g_t]
         return False
     if g_t * (I[0] - a_t) < 0:
+        _note(events, "interval_case_3")
         I[3:6] = I[0:3]
         I[0:3] = [a_t, f_t, g_t]
         return False
+    _note(events, "interval_converged")
     return True
 
 
-def align(src, cells, init_T=None, params=None, trace=None):
+EVENTS = ("trial_case_1", "trial_case_2", "trial_case_3", "trial_case_4",
+          "interval_case_1", "interval_case_2", "interval_case_3", "interval_converged",
+          "interval_closed", "direction_reversed", "dphi0_zero", "trial_clamped_max", "trial_clamped_min",
+          "search_cap", "hessian_reevaluated", "end_trans_eps", "end_iteration_cap", "end_zero_step", "end_nan_step")
+
+
+def align(src, cells, init_T=None, params=None, trace=None, events=None):
     """PCL's computeTransformation: returns dict(T [4,4] fp64, p, prob, iters, converged, evals).  `src` is the FILTERED
     source.  converged: the loop stopped on the step criterion or a zero step (stricter than PCL's hasConverged(),
-    which is also true at the iteration cap)."""
+    which is also true at the iteration cap).
+    events: an optional list that receives, in order, the names (EVENTS) of the branches the run takes; "first_clamped_max"
+    / "first_clamped_min" (the first trial step min(|delta|, step_max) of a search, as opposed to a selected trial value)
+    are recorded too.  "trial_clamped_max" / "_min" say which bound a selected trial value was outside of (above
+    step_max / below step_min) before max(min(a, step_max), step_min); where step_min exceeds step_max the value that
+    was cut at step_max ends at step_min.  Recording changes no value."""
     prm = dict(DEFAULTS, **(params or {}))
     res, o = prm["resolution"], prm["outlier_ratio"]
     eps, step_max, max_iters = prm["trans_eps"], prm["step_size"], prm["max_iters"]
@@ -388,6 +421,7 @@ def align(src, cells, init_T=None, params=None, trace=None):
         dn = float(np.sqrt(delta @ delta))
         if dn == 0 or dn != dn:
             converged = dn == dn
+            _note(events, "end_zero_step" if converged else "end_nan_step")
             break
         d = delta / dn
         # computeStepLengthMT(p, d, dn, step_max, step_min)
@@ -395,10 +429,12 @@ def align(src, cells, init_T=None, params=None, trace=None):
         dphi_0 = -(g @ d)
         if dphi_0 >= 0:
             if dphi_0 == 0:
+                _note(events, "dphi0_zero")
                 a_t = 0.0
                 x_t = p.copy()
                 stepped = False
             else:
+                _note(events, "direction_reversed")
                 dphi_0 = -dphi_0
                 d = -d
         if dphi_0 != 0:
@@ -408,6 +444,8 @@ def align(src, cells, init_T=None, params=None, trace=None):
             interval_converged = False
             open_interval = True
             a_t = max(min(dn, step_max), step_min)
+            if events is not None and a_t != dn:
+                events.append("first_clamped_max" if dn > step_max else "first_clamped_min")
             x_t = p + d * a_t
             score, g, H = derivatives(src, cells, x_t, res, o, True)
             evals += 1
@@ -417,10 +455,14 @@ def align(src, cells, init_T=None, params=None, trace=None):
             while (not interval_converged and step_iters < 10
                    and not (psi_t <= 0 and dphi_t <= -nu * dphi_0)):
                 if open_interval:
-                    a_t = trial_value(*I, a_t, psi_t, dpsi_t)
+                    a_t = trial_value(*I, a_t, psi_t, dpsi_t, events=events)
                 else:
-                    a_t = trial_value(*I, a_t, phi_t, dphi_t)
-                a_t = max(min(a_t, step_max), step_min)
+                    a_t = trial_value(*I, a_t, phi_t, dphi_t, events=events)
+                if events is not None and (a_t > step_max or a_t < step_min):
+                    events.append("trial_clamped_max" if a_t > step_max else "trial_clamped_min")
+                # np.float64, so that the next selection's a_t == a_l (both clamped to one bound) divides as IEEE
+                # arithmetic does (PCL's C++, the device): NaN, which min / max then drop -- not Python's ZeroDivisionError
+                a_t = np.float64(max(min(a_t, step_max), step_min))
                 x_t = p + d * a_t
                 score, g, _ = derivatives(src, cells, x_t, res, o, False)
                 evals += 1
@@ -428,16 +470,21 @@ def align(src, cells, init_T=None, params=None, trace=None):
                 psi_t, dpsi_t = _psi(a_t, phi_t, phi_0, dphi_0, mu), _dpsi(dphi_t, dphi_0, mu)
                 if open_interval and (psi_t <= 0 and dpsi_t >= 0):
                     open_interval = False
+                    _note(events, "interval_closed")
                     I[1] = I[1] + phi_0 - mu * dphi_0 * I[0]
                     I[2] = I[2] + mu * dphi_0
                     I[4] = I[4] + phi_0 - mu * dphi_0 * I[3]
                     I[5] = I[5] + mu * dphi_0
                 if open_interval:
-                    interval_converged = update_interval(I, a_t, psi_t, dpsi_t)
+                    interval_converged = update_interval(I, a_t, psi_t, dpsi_t, events=events)
                 else:
-                    interval_converged = update_interval(I, a_t, phi_t, dphi_t)
+                    interval_converged = update_interval(I, a_t, phi_t, dphi_t, events=events)
                 step_iters += 1
+            if (events is not None and step_iters >= 10 and not interval_converged
+                    and not (psi_t <= 0 and dphi_t <= -nu * dphi_0)):
+                events.append("search_cap")
             if step_iters:
+                _note(events, "hessian_reevaluated")
                 _, _, H = derivatives(src, cells, x_t, res, o, True)
                 evals += 1
         if trace is not None:
@@ -446,6 +493,7 @@ def align(src, cells, init_T=None, params=None, trace=None):
         stop = iters > max_iters or (iters and abs(a_t) < eps)
         if stop:
             converged = bool(iters and abs(a_t) < eps)
+            _note(events, "end_trans_eps" if converged else "end_iteration_cap")
             iters += 1
             break
         iters += 1

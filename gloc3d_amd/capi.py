@@ -328,8 +328,54 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-class KnnIndex:
+class _Handle:
+    """A C handle of prefix gloc_<_C>_: close() destroys it once (GlocError if the library refuses: live views, attached
+    handles) and garbage collection tries the same.  The plumbing entry points every module forwards to one shared
+    implementation are wrapped once below; a class takes the ones its part of the C ABI has."""
+    _C = None
+
+    def _fn(self, name):
+        return getattr(lib(), f"gloc_{self._C}_{name}")
+
+    def close(self):
+        if self._h:
+            check(self._fn("destroy")(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _set_stream(self, stream_ptr):
+    check(self._fn("set_stream")(self._h, C.c_void_p(stream_ptr or 0)))
+
+
+def _synchronize(self):
+    check(self._fn("synchronize")(self._h))
+
+
+def _set_profile(self, on=True):
+    check(self._fn("set_profile")(self._h, 1 if on else 0))
+
+
+def _profile(self, kernel):
+    ms, n = C.c_double(), C.c_uint64()
+    check(self._fn("profile")(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
+    return ms.value, n.value
+
+
+def _profile_reset(self):
+    check(self._fn("profile_reset")(self._h))
+
+
+class KnnIndex(_Handle):
     """Resident descriptor database + exact L2 top-k (the reference's InvKeyTree / IndexFlatL2)."""
+
+    _C = "knn"
+    synchronize, profile, profile_reset = _synchronize, _profile, _profile_reset
 
     def __init__(self, dim, device=0):
         self._h = C.c_void_p()
@@ -338,10 +384,8 @@ class KnnIndex:
         check(lib().gloc_knn_create(device, self.dim, C.byref(self._h)))
 
     def close(self):
-        if self._h:
-            check(lib().gloc_knn_destroy(self._h))
-            self._h = C.c_void_p()
-            self._parent = None
+        _Handle.close(self)
+        self._parent = None
 
     def view(self):
         """A second search handle over this index's rows (gloc_knn_create_view): own stream and workspace, so that a search
@@ -353,12 +397,6 @@ class KnnIndex:
         v._parent = self          # (keeps the parent alive as long as the view)
         return v
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def __len__(self):
         n = C.c_size_t()
         check(lib().gloc_knn_size(self._h, C.byref(n)))
@@ -368,10 +406,7 @@ class KnnIndex:
         check(lib().gloc_knn_set_option(self._h, option, int(value)))
 
     def set_stream(self, hip_stream):
-        check(lib().gloc_knn_set_stream(self._h, C.c_void_p(hip_stream or 0)))
-
-    def synchronize(self):
-        check(lib().gloc_knn_synchronize(self._h))
+        _set_stream(self, hip_stream)
 
     def reserve(self, n):
         check(lib().gloc_knn_reserve(self._h, n))
@@ -426,18 +461,12 @@ class KnnIndex:
         check(lib().gloc_knn_get_stats(self._h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in KnnStats._fields_}
 
-    def profile(self, kernel):
-        ms, n = C.c_double(), C.c_uint64()
-        check(lib().gloc_knn_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
 
-    def profile_reset(self):
-        check(lib().gloc_knn_profile_reset(self._h))
-
-
-class Comm:
+class Comm(_Handle):
     """RCCL communicator of this process's GPU (gloc_comm_*).  `exchange(id_bytes or None) -> id_bytes`
     broadcasts rank 0's 128-byte id to every rank (e.g. over torch.distributed or a shared file)."""
+
+    _C = "comm"
 
     def __init__(self, device, rank, world, exchange):
         uid = (C.c_uint8 * 128)()
@@ -457,17 +486,6 @@ class Comm:
         self._h = C.c_void_p()
         self.rank, self.world = rank, world
         check(lib().gloc_comm_create(device, rank, world, uid, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().gloc_comm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def rank_world(self):
         """(rank, world) as the communicator itself reports them (gloc_comm_rank)."""
@@ -510,25 +528,15 @@ def default_ndt_params(**over):
     return p
 
 
-class ScanStore:
+class ScanStore(_Handle):
     """Resident scans + their search index, shared by any number of Registrars."""
+
+    _C = "scan_store"
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
         self.device = device
         check(lib().gloc_scan_store_create(device, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            check(lib().gloc_scan_store_destroy(self._h))
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().gloc_scan_store_destroy(self._h)
-        except Exception:
-            pass
 
     def add(self, pts):
         pts = np.ascontiguousarray(pts, np.float32)
@@ -643,9 +651,12 @@ class ScanStore:
         return out
 
 
-class Registrar:
+class Registrar(_Handle):
     """Batched candidate registration (RANSAC-SVD + ICP) over a resident scan store (its own, or a
     shared ScanStore passed in / attached later)."""
+
+    _C = "reg"
+    synchronize, profile, profile_reset = _synchronize, _profile, _profile_reset
 
     def __init__(self, device=0, store=None):
         self._h = C.c_void_p()
@@ -656,10 +667,8 @@ class Registrar:
             self.attach_store(store)
 
     def close(self):
-        if self._h:
-            lib().gloc_reg_destroy(self._h)
-            self._h = C.c_void_p()
-            self._store = None
+        _Handle.close(self)
+        self._store = None
 
     def attach_store(self, store):
         check(lib().gloc_reg_attach_store(self._h, store._h if store is not None else None))
@@ -705,20 +714,11 @@ class Registrar:
         return dict(T=T.reshape(Q, n, 4, 4), rmse=rmse.reshape(Q, n), inliers=inl.reshape(Q, n),
                     ok=ok.astype(bool).reshape(Q, n))
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_option(self, option, value):
         check(lib().gloc_reg_set_option(self._h, option, int(value)))
 
     def set_stream(self, hip_stream):
-        check(lib().gloc_reg_set_stream(self._h, C.c_void_p(hip_stream or 0)))
-
-    def synchronize(self):
-        check(lib().gloc_reg_synchronize(self._h))
+        _set_stream(self, hip_stream)
 
     def scan_upload(self, pts):
         pts = np.ascontiguousarray(pts, np.float32)
@@ -853,14 +853,6 @@ class Registrar:
         check(lib().gloc_reg_final_steps(self._h, _np_ptr(out), n_jobs))
         return out
 
-    def profile(self, kernel):
-        ms, n = C.c_double(), C.c_uint64()
-        check(lib().gloc_reg_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-    def profile_reset(self):
-        check(lib().gloc_reg_profile_reset(self._h))
-
     def nn_stats(self):
         c, n = C.c_uint64(), C.c_uint64()
         check(lib().gloc_reg_nn_stats(self._h, C.byref(c), C.byref(n)))
@@ -907,8 +899,11 @@ def reg_select_first_ok(ok):
     return lib().gloc_reg_select_first_ok(_np_ptr(a), a.shape[0])
 
 
-class NetVladFC:
+class NetVladFC(_Handle):
     """NetVLAD-FC pooling head (model/netvlad_fc.py NetVLAD.forward without gating)."""
+
+    _C = "vlad"
+    set_stream, set_profile, profile = _set_stream, _set_profile, _profile
 
     def __init__(self, conv_w, centroids, fc_w, conv_b=None, normalize_input=True, device=0):
         cw = np.ascontiguousarray(conv_w, np.float32)
@@ -922,17 +917,6 @@ class NetVladFC:
         check(lib().gloc_vlad_create(device, self.C, self.K, self.out_dim, _np_ptr(cw),
                                      None if cb is None else _np_ptr(cb), _np_ptr(ce), _np_ptr(fw),
                                      1 if normalize_input else 0, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().gloc_vlad_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_gating(self, gating_w=None, scale=None, shift=None):
         """GatingContext after the FC: y * sigmoid((y W) * scale + shift); None switches it off."""
@@ -956,17 +940,6 @@ class NetVladFC:
     def forward_device(self, feat_ptr, n, hw, out_ptr):
         check(lib().gloc_vlad_forward_device(self._h, C.c_void_p(feat_ptr), n, hw, C.c_void_p(out_ptr)))
 
-    def set_stream(self, stream_ptr):
-        check(lib().gloc_vlad_set_stream(self._h, C.c_void_p(stream_ptr)))
-
-    def set_profile(self, on=True):
-        check(lib().gloc_vlad_set_profile(self._h, 1 if on else 0))
-
-    def profile(self, kernel):
-        ms, n = C.c_double(), C.c_uint64()
-        check(lib().gloc_vlad_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
 
 def default_bev_params(**over):
     p = BevParams()
@@ -980,24 +953,16 @@ def default_bev_params(**over):
     return p
 
 
-class BevProjector:
+class BevProjector(_Handle):
     """BEV occupancy projection (RpyPCLoopDetector::get_projected_grid + crop_pad_occupancy,
     registration/loop_detector.cpp:83-106,122-151)."""
+
+    _C = "bev"
+    set_stream, synchronize, set_profile, profile = _set_stream, _synchronize, _set_profile, _profile
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
         check(lib().gloc_bev_create(device, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().gloc_bev_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _out_array(p, n_scans=None):
@@ -1033,20 +998,6 @@ class BevProjector:
         out = np.empty((info["height"], info["width"]), np.uint8)
         check(lib().gloc_bev_raw_image(self._h, scan, _np_ptr(out), out.size))
         return out
-
-    def set_stream(self, stream_ptr):
-        check(lib().gloc_bev_set_stream(self._h, C.c_void_p(stream_ptr)))
-
-    def synchronize(self):
-        check(lib().gloc_bev_synchronize(self._h))
-
-    def set_profile(self, on=True):
-        check(lib().gloc_bev_set_profile(self._h, 1 if on else 0))
-
-    def profile(self, kernel):
-        ms, n = C.c_double(), C.c_uint64()
-        check(lib().gloc_bev_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
 
 
 def default_pillar_params(**over):
@@ -1087,26 +1038,19 @@ def pillar_backbone_layer_shape(layer):
     return ci.value, co.value, st.value, bool(r.value)
 
 
-class PillarEncoder:
+class PillarEncoder(_Handle):
     """PointPillar scan front end: points_to_voxels + the traced model's [P, 16] input (model/voxel.py:23-133,
     gen_libtorch_pointpillar.py:47-62) and the PointNet + scatter-mean canvas [64, gx * gy * gz]
     (model/s2s_merged.py:113-127,204-218)."""
+
+    _C = "pillar"
+    set_stream, synchronize = _set_stream, _synchronize
+    set_profile, profile, profile_reset = _set_profile, _profile, _profile_reset
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
         self.device = device
         check(lib().gloc_pillar_create(device, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().gloc_pillar_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_pointnet(self, w, bn_weight, bn_bias, bn_mean, bn_var, eps=1e-5):
         """w [64, 14] (or the Conv1d's [64, 14, 1]); BatchNorm1d weight, bias, running mean, running var [64]."""
@@ -1183,24 +1127,6 @@ class PillarEncoder:
         check(lib().gloc_pillar_features_device(self._h, C.c_void_p(pts_ptr), _np_ptr(off), off.shape[0] - 1,
                                                 stride_floats, C.byref(p), C.c_void_p(out_ptr)))
 
-    def set_stream(self, stream_ptr):
-        check(lib().gloc_pillar_set_stream(self._h, C.c_void_p(stream_ptr)))
-
-    def synchronize(self):
-        check(lib().gloc_pillar_synchronize(self._h))
-
-    def set_profile(self, on=True):
-        check(lib().gloc_pillar_set_profile(self._h, 1 if on else 0))
-
-    def profile(self, kernel):
-        ms, n = C.c_double(), C.c_uint64()
-        check(lib().gloc_pillar_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-    def profile_reset(self):
-        check(lib().gloc_pillar_profile_reset(self._h))
-
-
 VGG_LAYERS = 13
 
 
@@ -1211,25 +1137,18 @@ def vgg_layer_shape(layer):
     return ci.value, co.value, bool(r.value), bool(p.value)
 
 
-class VggEncoder:
+class VggEncoder(_Handle):
     """VGG16 features[:-2], the i2i model's encoder (s2s_libtorch/gen_libtorch_i2i.py:36-60): [n, 3, H, W] ->
     [n, 512, H / 16, W / 16], fp32 NCHW in and out (split-bf16 matrix cores inside, include/gloc3d.h)."""
+
+    _C = "vgg"
+    set_stream, synchronize = _set_stream, _synchronize
+    set_profile, profile, profile_reset = _set_profile, _profile, _profile_reset
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
         self.device = device
         check(lib().gloc_vgg_create(device, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().gloc_vgg_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_layer(self, layer, w, b):
         """w [Cout, Cin, 3, 3] (torch's Conv2d weight), b [Cout]."""
@@ -1262,23 +1181,6 @@ class VggEncoder:
         """One layer with its epilogue on device buffers, NCHW [n, Cin, H, W] -> [n, Cout, Ho, Wo]."""
         check(lib().gloc_vgg_forward_layer(self._h, layer, C.c_void_p(in_ptr), n, H, W, C.c_void_p(out_ptr)))
 
-    def set_stream(self, stream_ptr):
-        check(lib().gloc_vgg_set_stream(self._h, C.c_void_p(stream_ptr)))
-
-    def synchronize(self):
-        check(lib().gloc_vgg_synchronize(self._h))
-
-    def set_profile(self, on=True):
-        check(lib().gloc_vgg_set_profile(self._h, 1 if on else 0))
-
-    def profile(self, kernel):
-        ms, n = C.c_double(), C.c_uint64()
-        check(lib().gloc_vgg_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-    def profile_reset(self):
-        check(lib().gloc_vgg_profile_reset(self._h))
-
 
 def default_coarse_params(**over):
     p = CoarseParams()
@@ -1288,25 +1190,16 @@ def default_coarse_params(**over):
     return p
 
 
-class CoarseMatcher:
+class CoarseMatcher(_Handle):
     """Coarse global (x, y, yaw) match on BEV occupancy grids (RpyPCLoopDetector::match on two
     OccupancyGrids, registration/loop_detector.cpp:186-288)."""
+
+    _C = "coarse"
 
     def __init__(self, device=0, params=None):
         self._h = C.c_void_p()
         check(lib().gloc_coarse_create(device, C.byref(self._h)))
         self.params = params or default_coarse_params()
-
-    def close(self):
-        if self._h:
-            lib().gloc_coarse_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def add_image(self, occupancy, ox, oy, resolution):
         img = np.ascontiguousarray(occupancy, np.uint8)
@@ -1378,24 +1271,16 @@ def ground_transform_from_plane(plane):
     return T.reshape(4, 4)
 
 
-class GroundEstimator:
+class GroundEstimator(_Handle):
     """Ground pre-alignment (GroundEstimator::EsitmateGroundAndTransform,
     registration/ground_estimator.cpp:196-228)."""
+
+    _C = "ground"
+    set_profile, profile = _set_profile, _profile
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
         check(lib().gloc_ground_create(device, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().gloc_ground_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_option(self, option, value):
         check(lib().gloc_ground_set_option(self._h, option, value))
@@ -1430,11 +1315,3 @@ class GroundEstimator:
         bins = np.empty(p.shape[0], np.uint8)
         check(lib().gloc_ground_normals(self._h, _np_ptr(p), p.shape[0], k, _np_ptr(nrm), _np_ptr(bins)))
         return nrm, bins
-
-    def set_profile(self, on=True):
-        check(lib().gloc_ground_set_profile(self._h, 1 if on else 0))
-
-    def profile(self, kernel):
-        ms, n = C.c_double(), C.c_uint64()
-        check(lib().gloc_ground_profile(self._h, kernel.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value

@@ -3,7 +3,6 @@
 // get_place_feature (registration/loop_detector.cpp:83-106,122-151).
 #include <algorithm>
 #include <cmath>
-#include <new>
 
 #include "common.hpp"
 #include "bev_kernels.hpp"
@@ -11,16 +10,14 @@
 using namespace gloc;
 using namespace gloc::bev;
 
-struct gloc_bev {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+struct gloc_bev : Handle {
   DevBuf zcol, multi, meta, offsets;   // per column [n_scans][S][S]: one z index (u32), span flag (u8)
-  DevBuf stage_in, stage_out, raw;     // host-pointer API staging
+  Staging stage;                       // host-pointer API staging
+  DevBuf raw;
   std::vector<ScanMeta> h_meta;        // last projection, host copy (filled when infos were requested)
   bool meta_on_host = false;
   size_t last_scans = 0;
   int last_R = 0, last_S = 0;
-  Profiler prof;
 };
 
 namespace {
@@ -146,48 +143,13 @@ int gloc_bev_default_params(gloc_bev_params* p) {
   return GLOC_OK;
 }
 
-int gloc_bev_create(int device, gloc_bev** out) {
-  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is NULL");
-  GLOC_TRY(select_device(device));
-  gloc_bev* h = new (std::nothrow) gloc_bev();
-  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "out of host memory");
-  h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
-    return GLOC_ERR_HIP;
-  }
-  h->stream = h->own_stream;
-  *out = h;
-  return GLOC_OK;
-}
+int gloc_bev_create(int device, gloc_bev** out) { return create_handle(device, out); }
 
-int gloc_bev_destroy(gloc_bev* h) {
-  if (!h) return GLOC_OK;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  h->prof.destroy();
-  for (DevBuf* b : {&h->zcol, &h->multi, &h->meta, &h->offsets, &h->stage_in, &h->stage_out, &h->raw}) b->release();
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
-  return GLOC_OK;
-}
+int gloc_bev_destroy(gloc_bev* h) { return destroy_handle(h); }
 
-int gloc_bev_set_stream(gloc_bev* h, void* hip_stream) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
-  return GLOC_OK;
-}
+int gloc_bev_set_stream(gloc_bev* h, void* hip_stream) { return handle_set_stream(h, hip_stream); }
 
-int gloc_bev_synchronize(gloc_bev* h) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  return GLOC_OK;
-}
+int gloc_bev_synchronize(gloc_bev* h) { return handle_synchronize(h); }
 
 int gloc_bev_project(gloc_bev* h, const float* xyz, size_t n, size_t stride_floats,
                      const gloc_bev_params* p, void* out_image, gloc_bev_info* info) {
@@ -197,16 +159,11 @@ int gloc_bev_project(gloc_bev* h, const float* xyz, size_t n, size_t stride_floa
   GLOC_TRY(check_params(p, &R));
   GLOC_REQUIRE(stride_floats >= 3 && stride_floats <= 64, GLOC_ERR_INVALID, "stride_floats must be in [3, 64]");
   GLOC_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const size_t in_bytes = sizeof(float) * n * stride_floats, out_bytes = image_bytes(p);
-  GLOC_TRY(h->stage_in.ensure(std::max<size_t>(in_bytes, 16), s));
-  GLOC_TRY(h->stage_out.ensure(out_bytes, s));
-  if (n) GLOC_HIP(hipMemcpyAsync(h->stage_in.p, xyz, in_bytes, hipMemcpyHostToDevice, s));
   const uint64_t offsets[2] = {0, (uint64_t)n};
   gloc_bev_info local;
-  GLOC_TRY(project_device(h, h->stage_in.as<float>(), offsets, 1, stride_floats, p, h->stage_out.p, &local));
-  GLOC_HIP(hipMemcpyAsync(out_image, h->stage_out.p, out_bytes, hipMemcpyDeviceToHost, s));
-  GLOC_HIP(hipStreamSynchronize(s));
+  GLOC_TRY(h->stage.call(h->stream, xyz, sizeof(float) * n * stride_floats, out_image, image_bytes(p), [&](void* d_in, void* d_out) {
+    return project_device(h, (const float*)d_in, offsets, 1, stride_floats, p, d_out, &local);
+  }));
   if (info) *info = local;
   return GLOC_OK;
 }
@@ -257,20 +214,10 @@ int gloc_bev_device_flags(gloc_bev* h, size_t scan, const uint8_t** d_flags, int
   return GLOC_OK;
 }
 
-int gloc_bev_set_profile(gloc_bev* h, int enable) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  h->prof.enabled = enable != 0;
-  return GLOC_OK;
-}
+int gloc_bev_set_profile(gloc_bev* h, int enable) { return handle_set_profile(h, enable); }
 
 int gloc_bev_profile(gloc_bev* h, const char* kernel, double* total_ms, uint64_t* launches) {
-  GLOC_REQUIRE(h && kernel, GLOC_ERR_INVALID, "NULL argument");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(h->prof.collect(h->stream));
-  auto it = h->prof.fam.find(kernel);
-  if (total_ms) *total_ms = it == h->prof.fam.end() ? 0.0 : it->second.total_ms;
-  if (launches) *launches = it == h->prof.fam.end() ? 0 : it->second.launches;
-  return GLOC_OK;
+  return handle_profile(h, kernel, total_ms, launches);
 }
 
 }  // extern "C"

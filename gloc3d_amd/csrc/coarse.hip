@@ -7,7 +7,6 @@
 #include <cmath>
 #include <map>
 #include <mutex>
-#include <new>
 #include <vector>
 
 #include "coarse_kernels.hpp"
@@ -17,9 +16,7 @@
 using namespace gloc;
 using namespace gloc::coarse;
 
-struct gloc_coarse {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+struct gloc_coarse : Handle {  // (no profiling entry points: the base's profiler stays idle)
   std::vector<void*> blocks;      // one allocation per grid (null: released)
   std::vector<GridDev> grids;     // host copies of the device views
   std::vector<uint32_t> counts;   // occupied cells per grid
@@ -37,6 +34,13 @@ struct gloc_coarse {
   bool grids_dirty = true;
   uint32_t trig_n = 0;
   gloc_bev* bev = nullptr;        // created on first add_scan
+  ~gloc_coarse() {
+    for (void* b : blocks)
+      if (b) (void)hipFree(b);
+    for (auto& kv : free_blocks)
+      for (void* b : kv.second) (void)hipFree(b);
+    if (bev) (void)gloc_bev_destroy(bev);
+  }
 };
 
 namespace {
@@ -220,40 +224,9 @@ int gloc_coarse_default_params(gloc_coarse_params* p) {
   return GLOC_OK;
 }
 
-int gloc_coarse_create(int device, gloc_coarse** out) {
-  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is null");
-  *out = nullptr;
-  GLOC_TRY(select_device(device));
-  gloc_coarse* h = new (std::nothrow) gloc_coarse;
-  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "host allocation failed");
-  h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
-    delete h;
-    return GLOC_ERR_HIP;
-  }
-  h->stream = h->own_stream;
-  *out = h;
-  return GLOC_OK;
-}
+int gloc_coarse_create(int device, gloc_coarse** out) { return create_handle(device, out); }
 
-int gloc_coarse_destroy(gloc_coarse* h) {
-  if (!h) return GLOC_OK;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  for (void* b : h->blocks)
-    if (b) (void)hipFree(b);
-  for (auto& kv : h->free_blocks)
-    for (void* b : kv.second) (void)hipFree(b);
-  for (DevBuf* b : {&h->scratch_bits, &h->scratch_cnt, &h->stage_img, &h->tiny_img, &h->d_grids, &h->d_pq, &h->d_pd, &h->d_trig,
-                    &h->d_yaw, &h->d_yawout, &h->d_cand, &h->d_verify, &h->d_out, &h->d_scale})
-    b->release();
-  if (h->bev) (void)gloc_bev_destroy(h->bev);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
-  return GLOC_OK;
-}
+int gloc_coarse_destroy(gloc_coarse* h) { return destroy_handle(h); }
 
 int gloc_coarse_add_image(gloc_coarse* h, const uint8_t* occupancy, uint32_t width, uint32_t height, float ox,
                           float oy, float resolution, const gloc_coarse_params* params, uint32_t* grid_id) {

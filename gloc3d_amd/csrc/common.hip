@@ -127,6 +127,59 @@ void Profiler::destroy() {
   fam.clear();
 }
 
+Handle::~Handle() {
+  prof.destroy();
+  if (own_stream) (void)hipStreamDestroy(own_stream);
+}
+
+int handle_open(Handle* h, int device) {
+  h->device = device;
+  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
+    return GLOC_ERR_HIP;
+  }
+  h->stream = h->own_stream;
+  return GLOC_OK;
+}
+
+int handle_set_stream(Handle* h, void* hip_stream) {
+  GLOC_TRY(handle_synchronize(h));
+  h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
+  return GLOC_OK;
+}
+
+int handle_synchronize(Handle* h) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
+  GLOC_HIP(hipSetDevice(h->device));
+  GLOC_HIP(hipStreamSynchronize(h->stream));
+  return GLOC_OK;
+}
+
+int handle_set_profile(Handle* h, int enable) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
+  h->prof.enabled = enable != 0;
+  return GLOC_OK;
+}
+
+int handle_profile(Handle* h, const char* kernel, double* total_ms, uint64_t* launches) {
+  GLOC_REQUIRE(h && kernel, GLOC_ERR_INVALID, "NULL argument");
+  GLOC_HIP(hipSetDevice(h->device));
+  GLOC_TRY(h->prof.collect(h->stream));
+  auto it = h->prof.fam.find(kernel);
+  if (total_ms) *total_ms = it == h->prof.fam.end() ? 0.0 : it->second.total_ms;
+  if (launches) *launches = it == h->prof.fam.end() ? 0 : it->second.launches;
+  return GLOC_OK;
+}
+
+int handle_profile_reset(Handle* h) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
+  GLOC_HIP(hipSetDevice(h->device));
+  GLOC_TRY(h->prof.collect(h->stream));
+  h->prof.reset();
+  return GLOC_OK;
+}
+
 }  // namespace gloc
 
 extern "C" {

@@ -8,7 +8,9 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gloc3d.h"
@@ -44,10 +46,24 @@ void set_err(const char* fmt, ...);
 
 int select_device(int device);  // validates ordinal + gfx950, hipSetDevice
 
-// Growable device buffer (never shrinks).  Keeps contents on growth if `keep`.
+// Growable device buffer (never shrinks).  Keeps contents on growth if `keep`.  Owns its memory: freed when the
+// buffer goes (with the owner's device current: see destroy_handle), or early by release().
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, cap = o.cap;
+      o.p = nullptr, o.cap = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   int ensure(size_t bytes, hipStream_t s, bool keep = false, size_t used = 0);
   void release();
   template <class T>
@@ -55,6 +71,9 @@ struct DevBuf {
     return reinterpret_cast<T*>(p);
   }
 };
+
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value,
+              "a DevBuf has one owner: two copies would free the same memory");
 
 // HIP-event profiler: brackets kernel launches of one family and sums elapsed time lazily.
 struct Profiler {
@@ -86,6 +105,73 @@ struct ProfScope {
   }
   ~ProfScope() {
     if (p.enabled) p.end(name, s);
+  }
+};
+
+// What every handle of the C ABI starts with: its device, the stream it enqueues on (its own unless the caller gave
+// one), the per-kernel profiler.  Each `struct gloc_xxx` derives from it and adds what is its own; members that own
+// device memory (DevBuf) free it themselves, and what is not of that kind (pinned memory, events, blocks of a cache,
+// inner handles) goes in the struct's own destructor.
+struct Handle {
+  int device = 0;
+  hipStream_t own_stream = nullptr, stream = nullptr;
+  Profiler prof;
+  Handle() = default;
+  Handle(const Handle&) = delete;
+  Handle& operator=(const Handle&) = delete;
+  ~Handle();  // the profiler's events and the owned stream (runs after the derived handle's members have gone)
+};
+
+int handle_open(Handle* h, int device);  // the owned stream, made current; the device is selected already
+int handle_set_stream(Handle* h, void* hip_stream);  // waits for the old stream; null: back to the owned one
+int handle_synchronize(Handle* h);
+int handle_set_profile(Handle* h, int enable);
+int handle_profile(Handle* h, const char* kernel, double* total_ms, uint64_t* launches);
+int handle_profile_reset(Handle* h);
+
+// gloc_xxx_create: device selection, allocation, the owned stream.  *out is null on every failure.
+template <class H>
+int create_handle(int device, H** out) {
+  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  GLOC_TRY(select_device(device));
+  H* h = new (std::nothrow) H();
+  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "out of host memory");
+  const int rc = handle_open(h, device);
+  if (rc != GLOC_OK) {
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return GLOC_OK;
+}
+
+// gloc_xxx_destroy, once the module's own refusals (live views, attached handles) are past: the handle's work is waited
+// for, then -- with its device current -- the struct's destructor lets go of what is not a DevBuf and the members free
+// their memory.  (The wait is here and not in ~Handle: a base's destructor runs after the derived members have gone.)
+template <class H>
+int destroy_handle(H* h) {
+  if (!h) return GLOC_OK;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);
+  delete h;
+  return GLOC_OK;
+}
+
+// The host-pointer form of a device entry point: `src` goes up into the first staging buffer (never null: an empty
+// input still gets 16 bytes), run(d_in, d_out) enqueues the device form on `s`, the second staging buffer comes down into
+// `dst`, and the stream is waited for.
+struct Staging {
+  DevBuf in, out;
+  template <class F>
+  int call(hipStream_t s, const void* src, size_t in_bytes, void* dst, size_t out_bytes, F&& run) {
+    GLOC_TRY(in.ensure(in_bytes > 16 ? in_bytes : 16, s));
+    GLOC_TRY(out.ensure(out_bytes, s));
+    if (in_bytes) GLOC_HIP(hipMemcpyAsync(in.p, src, in_bytes, hipMemcpyHostToDevice, s));
+    GLOC_TRY(run(in.p, out.p));
+    GLOC_HIP(hipMemcpyAsync(dst, out.p, out_bytes, hipMemcpyDeviceToHost, s));
+    GLOC_HIP(hipStreamSynchronize(s));
+    return GLOC_OK;
   }
 };
 

@@ -5,7 +5,6 @@
 // the sequential RANSAC rule, T_l2g from the plane) are a few dozen scalar operations.
 #include <algorithm>
 #include <cmath>
-#include <new>
 
 #include "common.hpp"
 #include "ground_kernels.hpp"
@@ -14,9 +13,7 @@
 using namespace gloc;
 using namespace gloc::ground;
 
-struct gloc_ground {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+struct gloc_ground : Handle {
   DevBuf stage_in, stage_out;            // host-pointer API staging
   DevBuf flag, sel, count, tile_cnt;     // stream compaction
   DevBuf sort_segs, sort_hist;           // the segmented radix sort's descriptor and scratch (seg_sort.hpp)
@@ -24,7 +21,6 @@ struct gloc_ground {
   DevBuf skeys, svals, skeys2, sperm, spts, cbox_lo, cbox_hi;  // culled 10-NN: Hilbert-sorted copy + chunk boxes
   int knn_exhaustive = 0;                // 1: the exhaustive form (kept for comparison)
   DevBuf gpts, planes, valid, inliers, T12;
-  Profiler prof;
 };
 
 namespace {
@@ -322,45 +318,11 @@ int gloc_ground_default_params(gloc_ground_params* p) {
   return GLOC_OK;
 }
 
-int gloc_ground_create(int device, gloc_ground** out) {
-  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is NULL");
-  GLOC_TRY(select_device(device));
-  gloc_ground* h = new (std::nothrow) gloc_ground();
-  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "out of host memory");
-  h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
-    return GLOC_ERR_HIP;
-  }
-  h->stream = h->own_stream;
-  *out = h;
-  return GLOC_OK;
-}
+int gloc_ground_create(int device, gloc_ground** out) { return create_handle(device, out); }
 
-int gloc_ground_destroy(gloc_ground* h) {
-  if (!h) return GLOC_OK;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  h->prof.destroy();
-  for (DevBuf* b : {&h->stage_in, &h->stage_out, &h->flag, &h->sel, &h->count, &h->tile_cnt, &h->sort_segs, &h->sort_hist, &h->near, &h->knn_idx,
-                    &h->knn_d2, &h->knn_pidx, &h->knn_pd2, &h->skeys, &h->svals, &h->skeys2, &h->sperm, &h->spts,
-                    &h->cbox_lo, &h->cbox_hi, &h->bins, &h->hist, &h->normals, &h->gpts, &h->planes, &h->valid, &h->inliers,
-                    &h->T12})
-    b->release();
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
-  return GLOC_OK;
-}
+int gloc_ground_destroy(gloc_ground* h) { return destroy_handle(h); }
 
-int gloc_ground_set_stream(gloc_ground* h, void* hip_stream) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
-  return GLOC_OK;
-}
+int gloc_ground_set_stream(gloc_ground* h, void* hip_stream) { return handle_set_stream(h, hip_stream); }
 
 int gloc_ground_estimate(gloc_ground* h, const float* xyz, size_t n, size_t stride_floats,
                          const gloc_ground_params* p, float* T16, gloc_ground_info* info, float* out_xyz) {
@@ -451,20 +413,10 @@ int gloc_ground_set_option(gloc_ground* h, int option, int64_t value) {
   return GLOC_ERR_INVALID;
 }
 
-int gloc_ground_set_profile(gloc_ground* h, int enable) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  h->prof.enabled = enable != 0;
-  return GLOC_OK;
-}
+int gloc_ground_set_profile(gloc_ground* h, int enable) { return handle_set_profile(h, enable); }
 
 int gloc_ground_profile(gloc_ground* h, const char* kernel, double* total_ms, uint64_t* launches) {
-  GLOC_REQUIRE(h && kernel, GLOC_ERR_INVALID, "NULL argument");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(h->prof.collect(h->stream));
-  auto it = h->prof.fam.find(kernel);
-  if (total_ms) *total_ms = it == h->prof.fam.end() ? 0.0 : it->second.total_ms;
-  if (launches) *launches = it == h->prof.fam.end() ? 0 : it->second.launches;
-  return GLOC_OK;
+  return handle_profile(h, kernel, total_ms, launches);
 }
 
 }  // extern "C"

@@ -5,7 +5,6 @@
 #include <atomic>
 #include <cfloat>
 #include <vector>
-#include <new>
 
 #include "comm.hpp"
 #include "common.hpp"
@@ -15,17 +14,21 @@
 using namespace gloc;
 using namespace gloc::knn;
 
-struct gloc_knn {
-  int device = 0;
-  size_t dim = 0;
+// The database: what a handle owns and its views (gloc_knn_create_view) read.
+struct KnnRows {
   size_t n = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
   DevBuf rows;      // n x dim fp32, row-major, dense
   DevBuf norms;     // n fp32 (coarse form only)
   DevBuf mirror;    // the rows again, split into two bf16 values and tiled by 64 rows (knn_kernels.hpp: mirror_rows_kernel) --
                     // what the split-bf16 coarse pass streams; dim % 8 == 0 only; kept current by every add
   DevBuf dn_max;    // 1 x uint32 (bits of the largest row norm)
+};
+
+struct gloc_knn : Handle {
+  size_t dim = 0;
+  KnnRows own;       // (stays empty in a view)
+  KnnRows* db = &own;  // the rows searched: a view's are its parent's, as they are now -- read through this pointer, never
+                       // grown or freed through it (GLOC_NOT_VIEW)
   DevBuf dist;      // exact: [nq][ld]; mfma: [splits][Qpad][ld]
   DevBuf keys;      // select output [nq][K]
   DevBuf n_incomplete;  // 1 x u64: queries the MFMA path sent to the exact fallback (device counter)
@@ -55,12 +58,14 @@ struct gloc_knn {
   int coarse_fp32_left = 0;             // searches still to run on the fp32 coarse pass
   int algo = GLOC_KNN_ALGO_AUTO;
   int candidates = 32;
-  Profiler prof;
   gloc_knn_stats stats{};
-  // gloc_knn_create_view: a view searches its parent's rows / norms with its own stream and workspace (rows, norms, dn_max
-  // below are then ALIASES of the parent's buffers, refreshed at every search and never grown or freed through the view)
-  gloc_knn* parent = nullptr;
+  gloc_knn* parent = nullptr;  // gloc_knn_create_view: a view searches db = &parent->own with its own stream and workspace
   int views = 0;  // live views of this handle
+  ~gloc_knn() {
+    if (h_flags) (void)hipHostFree(h_flags);
+    if (h_inc) (void)hipHostFree(h_inc);
+    if (inc_ev) (void)hipEventDestroy(inc_ev);
+  }
 };
 
 namespace {
@@ -68,34 +73,19 @@ namespace {
 #define GLOC_NOT_VIEW(h) \
   GLOC_REQUIRE(!(h)->parent, GLOC_ERR_STATE, "a view (gloc_knn_create_view) searches its parent's rows: add / reserve / clear / load on the parent")
 
-// A view's rows are its parent's as of now (the parent may have grown since the view's last search).
-void view_sync(gloc_knn* h) {
-  if (!h->parent) return;
-  h->rows.p = h->parent->rows.p;
-  h->rows.cap = h->parent->rows.cap;
-  h->norms.p = h->parent->norms.p;
-  h->norms.cap = h->parent->norms.cap;
-  h->mirror.p = h->parent->mirror.p;
-  h->mirror.cap = h->parent->mirror.cap;
-  h->dn_max.p = h->parent->dn_max.p;
-  h->dn_max.cap = h->parent->dn_max.cap;
-  h->n = h->parent->n;
-}
-
 int ensure_rows(gloc_knn* h, size_t n_rows) {
   GLOC_NOT_VIEW(h);
-  GLOC_TRY(h->rows.ensure(n_rows * h->dim * sizeof(float), h->stream, true,
-                          h->n * h->dim * sizeof(float)));
-  GLOC_TRY(h->norms.ensure(n_rows * sizeof(float), h->stream, true, h->n * sizeof(float)));
+  GLOC_TRY(h->db->rows.ensure(n_rows * h->dim * sizeof(float), h->stream, true, h->db->n * h->dim * sizeof(float)));
+  GLOC_TRY(h->db->norms.ensure(n_rows * sizeof(float), h->stream, true, h->db->n * sizeof(float)));
   if (h->dim % 8 == 0) {  // (whole tiles, and two more: the coarse kernel's last work-group may own a tile past the end)
     const size_t tile_bytes = mirror_tile_u32x4((int)h->dim) * 16;
     // (+ 8 KB: a step's four planes of the last tile when dim / 8 is no multiple of four -- dist_bf16x3_tiled_kernel)
-    GLOC_TRY(h->mirror.ensure(((n_rows + MIR_ROWS - 1) / MIR_ROWS + 2) * tile_bytes + 8192, h->stream, true,
-                              (h->n + MIR_ROWS - 1) / MIR_ROWS * tile_bytes));
+    GLOC_TRY(h->db->mirror.ensure(((n_rows + MIR_ROWS - 1) / MIR_ROWS + 2) * tile_bytes + 8192, h->stream, true,
+                                  (h->db->n + MIR_ROWS - 1) / MIR_ROWS * tile_bytes));
   }
-  if (!h->dn_max.p) {
-    GLOC_TRY(h->dn_max.ensure(sizeof(uint32_t), h->stream));
-    GLOC_HIP(hipMemsetAsync(h->dn_max.p, 0, sizeof(uint32_t), h->stream));
+  if (!h->db->dn_max.p) {
+    GLOC_TRY(h->db->dn_max.ensure(sizeof(uint32_t), h->stream));
+    GLOC_HIP(hipMemsetAsync(h->db->dn_max.p, 0, sizeof(uint32_t), h->stream));
   }
   return GLOC_OK;
 }
@@ -105,13 +95,13 @@ int update_norms(gloc_knn* h, size_t first, size_t count) {
   ProfScope ps(h->prof, "norms", h->stream);
   const unsigned blocks = (unsigned)((count + 3) / 4);
   hipLaunchKernelGGL(row_norms_kernel, dim3(blocks), dim3(256), 0, h->stream,
-                     h->rows.as<float>() + first * h->dim, count, (int)h->dim,
-                     h->norms.as<float>() + first, h->dn_max.as<uint32_t>());
+                     h->db->rows.as<float>() + first * h->dim, count, (int)h->dim,
+                     h->db->norms.as<float>() + first, h->db->dn_max.as<uint32_t>());
   GLOC_HIP(hipGetLastError());
   if (h->dim % 8 == 0) {  // the coarse pass's mirror of the same rows
     ProfScope pm(h->prof, "mirror", h->stream);
     hipLaunchKernelGGL(mirror_rows_kernel, dim3((unsigned)((count + 63) / 64), (unsigned)((h->dim / 8 + 3) / 4)), dim3(256), 0, h->stream,
-                       h->rows.as<float>(), first, count, (int)h->dim, h->mirror.as<u32x4>());
+                       h->db->rows.as<float>(), first, count, (int)h->dim, h->db->mirror.as<u32x4>());
     GLOC_HIP(hipGetLastError());
   }
   return GLOC_OK;
@@ -128,7 +118,7 @@ int launch_dist_exact(gloc_knn* h, const float* d_q, int nq, size_t first, int n
     // measured against the general kernel at 4541 x 4096: Q = 1 18.6 vs 33 us, Q = 2 equal, Q = 4 / 8 slower
     const int G = (int)h->dim >> 2, Gs = std::min(G, EXS_G);
     float* dist = h->dist.as<float>();
-    const float* db = h->rows.as<float>();
+    const float* db = h->db->rows.as<float>();
 #define LAUNCH_SMALL(QT_, RW_)                                                                             \
   hipLaunchKernelGGL((dist_exact_small_kernel<QT_, RW_>), dim3((unsigned)((n_range + RW_ - 1) / RW_), (unsigned)qgroups), \
                      dim3(64), sizeof(float) * (QT_ * RW_) * (Gs + 4), h->stream, db, d_q, dist, (int)h->dim, \
@@ -147,7 +137,7 @@ int launch_dist_exact(gloc_knn* h, const float* d_q, int nq, size_t first, int n
   // (the flagged pass over a large window: y = 1, every work-group walks the flags)
   dim3 grid(gx, (only_flagged && (long long)gx * qgroups > 4096) ? 1u : (unsigned)qgroups), block(256);
   float* dist = h->dist.as<float>();
-  const float* db = h->rows.as<float>();
+  const float* db = h->db->rows.as<float>();
 #define LAUNCH_EXACT(QT_)                                                                      \
   hipLaunchKernelGGL(dist_exact_kernel<QT_>, grid, block, 0, h->stream, db, d_q, dist,         \
                      (int)h->dim, first, n_range, nq, RW, ld, only_flagged)
@@ -186,7 +176,7 @@ int launch_slices(gloc_knn* h, const float* d_q, int nq, int K, size_t first, in
   // (the flagged pass: y = 1, every work-group walks the flags)
 #define SLICES_ARGS                                                                                                 \
   dim3(SELQ_THREADS), 0, h->stream, h->dist.as<float>(), ld, strideP, n_splits, h->qnorm.as<float>(), d_q, (int)h->dim, \
-      h->norms.as<float>(), first, n_range, sl.L, K, h->klists.as<uint64_t>(), only_flagged, nq
+      h->db->norms.as<float>(), first, n_range, sl.L, K, h->klists.as<uint64_t>(), only_flagged, nq
   if constexpr (MODE == 0) {  // (only the exact pass is ever launched for flagged queries)
     if (only_flagged)
       hipLaunchKernelGGL((select_slices_kernel<0, true>), dim3(sl.S, 1), SLICES_ARGS);
@@ -209,7 +199,7 @@ int run_select(gloc_knn* h, const float* d_q, int nq, int K, size_t first, int n
   ProfScope ps(h->prof, "select", h->stream);
   if (n_range <= SELQ_MAX_ROWS && K <= 64) {  // one launch, one work-group per query
     hipLaunchKernelGGL(select_query_kernel<MODE>, dim3(nq), dim3(SELQ_THREADS), 0, h->stream, h->dist.as<float>(), ld,
-                       strideP, n_splits, h->qnorm.as<float>(), d_q, (int)h->dim, h->norms.as<float>(), first, n_range,
+                       strideP, n_splits, h->qnorm.as<float>(), d_q, (int)h->dim, h->db->norms.as<float>(), first, n_range,
                        K, d_keys_out, only_flagged, fo);
     GLOC_HIP(hipGetLastError());
     if (finalized) *finalized = fo.idx != nullptr;
@@ -240,7 +230,7 @@ int run_select(gloc_knn* h, const float* d_q, int nq, int K, size_t first, int n
   uint64_t* cur = nlists == 1 ? d_keys_out : h->klists.as<uint64_t>();
   hipLaunchKernelGGL(select_chunk_kernel<MODE>, dim3(nlists, nq), dim3(256), 0, h->stream,
                      h->dist.as<float>(), ld, strideP, n_splits, h->qnorm.as<float>(), d_q, (int)h->dim,
-                     h->norms.as<float>(), first, n_range, K, E, cur, only_flagged);
+                     h->db->norms.as<float>(), first, n_range, K, E, cur, only_flagged);
   GLOC_HIP(hipGetLastError());
   bool flip = false;
   while (nlists > 1) {
@@ -339,11 +329,11 @@ void launch_mfma_inst(gloc_knn* h, const MfmaPlan& p, const float* d_q, int nq, 
   const int kps = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
   if (kps < 128)
     hipLaunchKernelGGL((dist_mfma_kernel<WQ, NT, 8>), grid, dim3(256), 0, h->stream,
-                       h->rows.as<float>(), d_q, h->dist.as<float>(), (int)h->dim, first, n_range,
+                       h->db->rows.as<float>(), d_q, h->dist.as<float>(), (int)h->dim, first, n_range,
                        nq, kps, ld, strideP);
   else
     hipLaunchKernelGGL((dist_mfma_kernel<WQ, NT, 16>), grid, dim3(256), 0, h->stream,
-                       h->rows.as<float>(), d_q, h->dist.as<float>(), (int)h->dim, first, n_range,
+                       h->db->rows.as<float>(), d_q, h->dist.as<float>(), (int)h->dim, first, n_range,
                        nq, kps, ld, strideP);
 }
 
@@ -365,12 +355,12 @@ int launch_bf16x3(gloc_knn* h, dim3 grid, const float* qsrc, size_t first, int n
   constexpr int lds_bytes = b3_lds_bytes<NT>();
   if (use_bmin) {
     GLOC_TRY((allow_lds<dist_bf16x3_tiled_kernel<NT, QRAW, true>>(h->device, lds_bytes)));
-    hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT, QRAW, true>), grid, dim3(256), lds_bytes, h->stream, h->mirror.as<u32x4>(),
-                       qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps, ld, strideP, h->norms.as<float>(),
+    hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT, QRAW, true>), grid, dim3(256), lds_bytes, h->stream, h->db->mirror.as<u32x4>(),
+                       qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps, ld, strideP, h->db->norms.as<float>(),
                        h->bmin.as<float>(), n_blocks);
   } else {
     GLOC_TRY((allow_lds<dist_bf16x3_tiled_kernel<NT, QRAW>>(h->device, lds_bytes)));
-    hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT, QRAW>), grid, dim3(256), lds_bytes, h->stream, h->mirror.as<u32x4>(),
+    hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT, QRAW>), grid, dim3(256), lds_bytes, h->stream, h->db->mirror.as<u32x4>(),
                        qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps, ld, strideP, (const float*)nullptr,
                        (float*)nullptr, 0);
   }
@@ -412,7 +402,7 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
     }
     ProfScope ps(h->prof, "dist_mfma", h->stream);
     // the rows from their tiled, pre-split mirror (round 6), which every add keeps when dim % 8 == 0
-    GLOC_REQUIRE(h->mirror.p, GLOC_ERR_STATE, "internal: the split-bf16 coarse pass without the rows' mirror");
+    GLOC_REQUIRE(h->db->mirror.p, GLOC_ERR_STATE, "internal: the split-bf16 coarse pass without the rows' mirror");
     const int kps3 = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
     const dim3 tgrid((unsigned)((first % MIR_ROWS + (size_t)n_range + p.BN - 1) / p.BN), grid.y, grid.z);
     // a large window in one K-split: the epilogue leaves block minima for the selection (select_blocks_body)
@@ -428,7 +418,7 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
     // (plan_mfma's one 32 x 32 plan: NT = 2, and steps of 32 k)
     dim3 grid((unsigned)((n_range + p.BN - 1) / p.BN), (unsigned)((nq + p.BQ - 1) / p.BQ), (unsigned)p.KS);
     const int kps32 = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
-    hipLaunchKernelGGL((dist_mfma32_kernel<2, 8>), grid, dim3(256), 0, h->stream, h->rows.as<float>(), d_q,
+    hipLaunchKernelGGL((dist_mfma32_kernel<2, 8>), grid, dim3(256), 0, h->stream, h->db->rows.as<float>(), d_q,
                        h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps32, ld, strideP);
     GLOC_HIP(hipGetLastError());
   } else {
@@ -469,7 +459,7 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
     ProfScope ps(h->prof, "select_rerank", h->stream);
 #define SRR_ARGS                                                                                                          \
   dim3(nq), dim3(SELQ_THREADS), 0, h->stream, h->dist.as<float>(), ld, strideP, p.KS, d_q, (int)h->dim,                  \
-      h->norms.as<float>(), first, n_range, KC, k, h->rows.as<float>(), h->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n, \
+      h->db->norms.as<float>(), first, n_range, KC, k, h->db->rows.as<float>(), h->db->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n, \
       h->qnorm.as<float>(), d_keys_out, h->flags.as<int>(), h->n_incomplete.as<unsigned long long>(), fo,                \
       h->dist.as<float>()
     if (large)
@@ -499,12 +489,12 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
     ProfScope ps(h->prof, "rerank", h->stream);
     GLOC_TRY(h->exact.ensure((size_t)nq * KC * sizeof(float), h->stream));
     hipLaunchKernelGGL(rerank_dist_kernel, dim3((KC + RR - 1) / RR, nq), dim3(64), 0, h->stream,
-                       h->rows.as<float>(), d_q, (int)h->dim, h->keys.as<uint64_t>(), KC, k,
-                       h->qnorm.as<float>(), h->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n,
+                       h->db->rows.as<float>(), d_q, (int)h->dim, h->keys.as<uint64_t>(), KC, k,
+                       h->qnorm.as<float>(), h->db->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n,
                        h->exact.as<float>());
     hipLaunchKernelGGL(rerank_final_kernel, dim3(nq), dim3(64), 0, h->stream,
                        h->keys.as<uint64_t>(), h->exact.as<float>(), KC, k, n_range,
-                       h->qnorm.as<float>(), h->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n,
+                       h->qnorm.as<float>(), h->db->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n,
                        d_keys_out, h->flags.as<int>(), h->n_incomplete.as<unsigned long long>());
     GLOC_HIP(hipGetLastError());
   }
@@ -534,7 +524,7 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
         if (h->redo_tickets.cap != before) GLOC_HIP(hipMemsetAsync(h->redo_tickets.p, 0, h->redo_tickets.cap, h->stream));
         GLOC_TRY(h->klists.ensure((size_t)nq * S * k * sizeof(uint64_t), h->stream));
         ProfScope ps(h->prof, "dist_exact", h->stream);
-        hipLaunchKernelGGL(flagged_redo_kernel, dim3((unsigned)S), dim3(SELQ_THREADS), 0, h->stream, h->rows.as<float>(), d_q,
+        hipLaunchKernelGGL(flagged_redo_kernel, dim3((unsigned)S), dim3(SELQ_THREADS), 0, h->stream, h->db->rows.as<float>(), d_q,
                            (int)h->dim, first, n_range, L, k, h->dist.as<float>(), ld, h->klists.as<uint64_t>(),
                            h->redo_tickets.as<unsigned int>(), h->flags.as<int>(), nq, d_keys_out, fo);
         GLOC_HIP(hipGetLastError());
@@ -582,8 +572,7 @@ int search_device_impl(gloc_knn* h, const float* d_q, size_t nq, size_t k, size_
   GLOC_REQUIRE(k >= 1 && k <= 256, GLOC_ERR_INVALID, "k = %zu outside [1,256]", k);
   GLOC_REQUIRE(nq >= 1 && nq <= (1u << 20), GLOC_ERR_INVALID, "nq = %zu outside [1,2^20]", nq);
   GLOC_HIP(hipSetDevice(h->device));
-  view_sync(h);
-  if (last_row > h->n) last_row = h->n;
+  if (last_row > h->db->n) last_row = h->db->n;
   if (first_row > last_row) first_row = last_row;
   const size_t range = last_row - first_row;
   GLOC_REQUIRE(range < (1ull << 31), GLOC_ERR_INVALID, "row window too large");
@@ -666,19 +655,8 @@ int gloc_knn_create(int device, size_t dim, gloc_knn** out) {
   GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is null");
   *out = nullptr;
   GLOC_REQUIRE(dim >= 1 && dim <= (1u << 20), GLOC_ERR_INVALID, "dim = %zu outside [1,2^20]", dim);
-  GLOC_TRY(select_device(device));
-  gloc_knn* h = new (std::nothrow) gloc_knn;
-  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "host allocation failed");
-  h->device = device;
-  h->dim = dim;
-  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
-    delete h;
-    return GLOC_ERR_HIP;
-  }
-  h->stream = h->own_stream;
-  *out = h;
+  GLOC_TRY(create_handle(device, out));
+  (*out)->dim = dim;
   return GLOC_OK;
 }
 
@@ -692,7 +670,7 @@ int gloc_knn_create_view(gloc_knn* parent, gloc_knn** out) {
   v->algo = parent->algo;
   v->candidates = parent->candidates;
   parent->views++;
-  view_sync(v);
+  v->db = &parent->own;
   *out = v;
   return GLOC_OK;
 }
@@ -700,58 +678,13 @@ int gloc_knn_create_view(gloc_knn* parent, gloc_knn** out) {
 int gloc_knn_destroy(gloc_knn* h) {
   if (!h) return GLOC_OK;
   GLOC_REQUIRE(h->views == 0, GLOC_ERR_STATE, "%d view(s) of this handle are still alive (gloc_knn_create_view): destroy them first", h->views);
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  h->prof.destroy();
-  if (h->parent) {  // the rows are the parent's
-    h->rows = DevBuf{};
-    h->norms = DevBuf{};
-    h->mirror = DevBuf{};
-    h->dn_max = DevBuf{};
-    h->parent->views--;
-  }
-  h->rows.release();
-  h->norms.release();
-  h->mirror.release();
-  h->dn_max.release();
-  h->dist.release();
-  h->keys.release();
-  h->n_incomplete.release();
-  h->shard_ws.release();
-  h->klists.release();
-  h->klists2.release();
-  h->exact.release();
-  h->keys2.release();
-  h->qnorm.release();
-  h->qsplit.release();
-  h->flags.release();
-  h->redo_tickets.release();
-  h->bmin.release();
-  h->stage_q.release();
-  h->stage_idx.release();
-  h->stage_d2.release();
-  if (h->h_flags) (void)hipHostFree(h->h_flags);
-  if (h->h_inc) (void)hipHostFree(h->h_inc);
-  if (h->inc_ev) (void)hipEventDestroy(h->inc_ev);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
-  return GLOC_OK;
+  if (h->parent) h->parent->views--;
+  return destroy_handle(h);
 }
 
-int gloc_knn_set_stream(gloc_knn* h, void* hip_stream) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
-  return GLOC_OK;
-}
+int gloc_knn_set_stream(gloc_knn* h, void* hip_stream) { return handle_set_stream(h, hip_stream); }
 
-int gloc_knn_synchronize(gloc_knn* h) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  return GLOC_OK;
-}
+int gloc_knn_synchronize(gloc_knn* h) { return handle_synchronize(h); }
 
 int gloc_knn_set_option(gloc_knn* h, int option, int64_t value) {
   GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
@@ -783,27 +716,27 @@ int gloc_knn_reserve(gloc_knn* h, size_t n_rows) {
 int gloc_knn_add(gloc_knn* h, const float* rows, size_t n) {
   GLOC_REQUIRE(h && (rows || n == 0), GLOC_ERR_INVALID, "null argument");
   if (n == 0) return GLOC_OK;
-  GLOC_REQUIRE(h->n + n < (1ull << 32) - 1, GLOC_ERR_INVALID, "database limited to 2^32-2 rows");
+  GLOC_REQUIRE(h->db->n + n < (1ull << 32) - 1, GLOC_ERR_INVALID, "database limited to 2^32-2 rows");
   GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(ensure_rows(h, h->n + n));
-  GLOC_HIP(hipMemcpyAsync(h->rows.as<float>() + h->n * h->dim, rows, n * h->dim * sizeof(float),
+  GLOC_TRY(ensure_rows(h, h->db->n + n));
+  GLOC_HIP(hipMemcpyAsync(h->db->rows.as<float>() + h->db->n * h->dim, rows, n * h->dim * sizeof(float),
                           hipMemcpyHostToDevice, h->stream));
-  GLOC_TRY(update_norms(h, h->n, n));
+  GLOC_TRY(update_norms(h, h->db->n, n));
   GLOC_HIP(hipStreamSynchronize(h->stream));  // the caller may free `rows` on return
-  h->n += n;
+  h->db->n += n;
   return GLOC_OK;
 }
 
 int gloc_knn_add_device(gloc_knn* h, const float* d_rows, size_t n) {
   GLOC_REQUIRE(h && (d_rows || n == 0), GLOC_ERR_INVALID, "null argument");
   if (n == 0) return GLOC_OK;
-  GLOC_REQUIRE(h->n + n < (1ull << 32) - 1, GLOC_ERR_INVALID, "database limited to 2^32-2 rows");
+  GLOC_REQUIRE(h->db->n + n < (1ull << 32) - 1, GLOC_ERR_INVALID, "database limited to 2^32-2 rows");
   GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(ensure_rows(h, h->n + n));
-  GLOC_HIP(hipMemcpyAsync(h->rows.as<float>() + h->n * h->dim, d_rows,
+  GLOC_TRY(ensure_rows(h, h->db->n + n));
+  GLOC_HIP(hipMemcpyAsync(h->db->rows.as<float>() + h->db->n * h->dim, d_rows,
                           n * h->dim * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  GLOC_TRY(update_norms(h, h->n, n));
-  h->n += n;
+  GLOC_TRY(update_norms(h, h->db->n, n));
+  h->db->n += n;
   return GLOC_OK;
 }
 
@@ -812,14 +745,14 @@ int gloc_knn_add_synthetic(gloc_knn* h, int kind, uint64_t seed, uint64_t first_
   GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
   GLOC_REQUIRE(kind == 0 || kind == 1, GLOC_ERR_INVALID, "kind must be 0 (iid) or 1 (trajectory)");
   if (n == 0) return GLOC_OK;
-  GLOC_REQUIRE(h->n + n < (1ull << 32) - 1, GLOC_ERR_INVALID, "database limited to 2^32-2 rows");
+  GLOC_REQUIRE(h->db->n + n < (1ull << 32) - 1, GLOC_ERR_INVALID, "database limited to 2^32-2 rows");
   GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(ensure_rows(h, h->n + n));
+  GLOC_TRY(ensure_rows(h, h->db->n + n));
   gloc::synth::launch_fill(h->stream, kind, seed, first_row, n, h->dim, row_stride ? row_stride : 1,
-                           h->rows.as<float>() + h->n * h->dim);
+                           h->db->rows.as<float>() + h->db->n * h->dim);
   GLOC_HIP(hipGetLastError());
-  GLOC_TRY(update_norms(h, h->n, n));
-  h->n += n;
+  GLOC_TRY(update_norms(h, h->db->n, n));
+  h->db->n += n;
   return GLOC_OK;
 }
 
@@ -841,14 +774,14 @@ int gloc_knn_clear(gloc_knn* h) {
   GLOC_NOT_VIEW(h);
   GLOC_HIP(hipSetDevice(h->device));
   GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->n = 0;
-  if (h->dn_max.p) GLOC_HIP(hipMemsetAsync(h->dn_max.p, 0, sizeof(uint32_t), h->stream));
+  h->db->n = 0;
+  if (h->db->dn_max.p) GLOC_HIP(hipMemsetAsync(h->db->dn_max.p, 0, sizeof(uint32_t), h->stream));
   return GLOC_OK;
 }
 
 int gloc_knn_size(const gloc_knn* h, size_t* n_rows) {
   GLOC_REQUIRE(h && n_rows, GLOC_ERR_INVALID, "null argument");
-  *n_rows = h->parent ? h->parent->n : h->n;
+  *n_rows = h->db->n;
   return GLOC_OK;
 }
 
@@ -860,7 +793,7 @@ int gloc_knn_dim(const gloc_knn* h, size_t* dim) {
 
 int gloc_knn_device_rows(const gloc_knn* h, const float** d_rows) {
   GLOC_REQUIRE(h && d_rows, GLOC_ERR_INVALID, "null argument");
-  *d_rows = h->rows.as<float>();
+  *d_rows = h->db->rows.as<float>();
   return GLOC_OK;
 }
 
@@ -869,14 +802,14 @@ int gloc_knn_save(gloc_knn* h, const char* path) {
   GLOC_HIP(hipSetDevice(h->device));
   FILE* f = fopen(path, "wb");
   GLOC_REQUIRE(f, GLOC_ERR_INVALID, "cannot open %s for writing", path);
-  const uint32_t hdr[2] = {(uint32_t)h->n, (uint32_t)h->dim};
+  const uint32_t hdr[2] = {(uint32_t)h->db->n, (uint32_t)h->dim};
   bool ok = fwrite("GLOCDESC", 1, 8, f) == 8 && fwrite(hdr, 4, 2, f) == 2;
   std::vector<float> buf;
   const size_t chunk = std::max<size_t>(1, (64u << 20) / (h->dim * sizeof(float)));  // 64 MiB pieces
-  for (size_t r = 0; ok && r < h->n; r += chunk) {
-    const size_t cnt = std::min(chunk, h->n - r);
+  for (size_t r = 0; ok && r < h->db->n; r += chunk) {
+    const size_t cnt = std::min(chunk, h->db->n - r);
     buf.resize(cnt * h->dim);
-    if (hipMemcpyAsync(buf.data(), h->rows.as<float>() + r * h->dim, buf.size() * sizeof(float),
+    if (hipMemcpyAsync(buf.data(), h->db->rows.as<float>() + r * h->dim, buf.size() * sizeof(float),
                        hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess)
       ok = false;
@@ -920,7 +853,7 @@ int gloc_knn_load(gloc_knn* h, const char* path) {
   (void)fseek(f, pos, SEEK_SET);
   std::vector<float> buf;
   const size_t chunk = std::max<size_t>(1, (64u << 20) / (h->dim * sizeof(float)));
-  const size_t n0 = h->n;  // on any failure below the index is rolled back to this many rows
+  const size_t n0 = h->db->n;  // on any failure below the index is rolled back to this many rows
   int rc = GLOC_OK;
   for (size_t r = 0; rc == GLOC_OK && r < hdr[0]; r += chunk) {
     const size_t cnt = std::min<size_t>(chunk, hdr[0] - r);
@@ -933,7 +866,7 @@ int gloc_knn_load(gloc_knn* h, const char* path) {
     }
   }
   fclose(f);
-  if (rc != GLOC_OK) h->n = n0;  // (the running maximum norm may stay larger: it only widens the re-rank window)
+  if (rc != GLOC_OK) h->db->n = n0;  // (the running maximum norm may stay larger: it only widens the re-rank window)
   return rc;
 }
 
@@ -1056,21 +989,9 @@ int gloc_knn_get_stats(const gloc_knn* h, gloc_knn_stats* out) {
 }
 
 int gloc_knn_profile(gloc_knn* h, const char* kernel, double* total_ms, uint64_t* launches) {
-  GLOC_REQUIRE(h && kernel, GLOC_ERR_INVALID, "null argument");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(h->prof.collect(h->stream));
-  auto it = h->prof.fam.find(kernel);
-  if (total_ms) *total_ms = it == h->prof.fam.end() ? 0.0 : it->second.total_ms;
-  if (launches) *launches = it == h->prof.fam.end() ? 0 : it->second.launches;
-  return GLOC_OK;
+  return handle_profile(h, kernel, total_ms, launches);
 }
 
-int gloc_knn_profile_reset(gloc_knn* h) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->prof.reset();
-  return GLOC_OK;
-}
+int gloc_knn_profile_reset(gloc_knn* h) { return handle_profile_reset(h); }
 
 }  // extern "C"

@@ -22,9 +22,6 @@ struct Ws {
   uint32_t* h_done = nullptr;  // pinned
   hipEvent_t ev = nullptr;
   ~Ws() {
-    for (DevBuf* b : {&k0, &k1, &v0, &v1, &hist, &segs, &flag, &pos, &bsum, &total, &filt, &tgt_desc, &first, &cells, &hkey,
-                      &hval, &toff, &tmask, &states, &evals, &outs, &partials, &cand_tgt, &init_T, &p6, &done, &exp})
-      b->release();
     if (h_done) (void)hipHostFree(h_done);
     if (ev) (void)hipEventDestroy(ev);
   }

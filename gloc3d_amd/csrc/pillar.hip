@@ -5,7 +5,6 @@
 // backbone behind it (PointPillarTest after the scatter-mean, s2s_merged.py:152-188,219-247; pillar_backbone_kernels.hpp).
 #include <algorithm>
 #include <cmath>
-#include <new>
 
 #include "common.hpp"
 #include "pillar_backbone_kernels.hpp"
@@ -39,11 +38,9 @@ constexpr uint32_t BB_MAX_SIDE = 4096;
 
 }  // namespace
 
-struct gloc_pillar {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+struct gloc_pillar : Handle {
   DevBuf keys[2], vals[2], flags, hist, segs, offsets, vrange, vcent, vcnt, inputs, part, pn;
-  DevBuf stage_in, stage_out;             // host-pointer API staging
+  Staging stage;                          // host-pointer API staging
   std::vector<segsort::Seg> h_segs;       // kept alive until the next call (the uploads are asynchronous)
   std::vector<uint64_t> h_offsets;
   bool have_pn = false;
@@ -52,7 +49,6 @@ struct gloc_pillar {
   bool bset[BB_LAYERS] = {};
   DevBuf braw, canvas, big, a64, f1, half[2], quarter[2], cat, lay_in, lay_up;
   bool bb_lds_attr[2] = {};  // dynamic-LDS limit raised for bb_conv_kernel<2, 1>, <2, 2>
-  Profiler prof;
 };
 
 namespace {
@@ -329,15 +325,8 @@ int host_call(gloc_pillar* h, const float* pts, const uint64_t* offsets, size_t 
   GLOC_REQUIRE(stride >= 4 && stride <= 64, GLOC_ERR_INVALID, "stride_floats must be in [4, 64]");
   GLOC_REQUIRE(offsets[n_scans] == 0 || pts, GLOC_ERR_INVALID, "points pointer is NULL");
   GLOC_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const size_t in_bytes = sizeof(float) * offsets[n_scans] * stride, out_bytes = sizeof(float) * out_floats;
-  GLOC_TRY(h->stage_in.ensure(std::max<size_t>(in_bytes, 16), s));
-  GLOC_TRY(h->stage_out.ensure(out_bytes, s));
-  if (in_bytes) GLOC_HIP(hipMemcpyAsync(h->stage_in.p, pts, in_bytes, hipMemcpyHostToDevice, s));
-  GLOC_TRY(dev(h, h->stage_in.as<float>(), offsets, n_scans, stride, p, h->stage_out.as<float>()));
-  GLOC_HIP(hipMemcpyAsync(out, h->stage_out.p, out_bytes, hipMemcpyDeviceToHost, s));
-  GLOC_HIP(hipStreamSynchronize(s));
-  return GLOC_OK;
+  return h->stage.call(h->stream, pts, sizeof(float) * offsets[n_scans] * stride, out, sizeof(float) * out_floats,
+                       [&](void* d_in, void* d_out) { return dev(h, (const float*)d_in, offsets, n_scans, stride, p, (float*)d_out); });
 }
 
 }  // namespace
@@ -356,55 +345,13 @@ int gloc_pillar_default_params(gloc_pillar_params* p) {
   return GLOC_OK;
 }
 
-int gloc_pillar_create(int device, gloc_pillar** out) {
-  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is NULL");
-  GLOC_TRY(select_device(device));
-  gloc_pillar* h = new (std::nothrow) gloc_pillar();
-  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "out of host memory");
-  h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
-    return GLOC_ERR_HIP;
-  }
-  h->stream = h->own_stream;
-  *out = h;
-  return GLOC_OK;
-}
+int gloc_pillar_create(int device, gloc_pillar** out) { return create_handle(device, out); }
 
-int gloc_pillar_destroy(gloc_pillar* h) {
-  if (!h) return GLOC_OK;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  h->prof.destroy();
-  for (DevBuf* b : {&h->keys[0], &h->keys[1], &h->vals[0], &h->vals[1], &h->flags, &h->hist, &h->segs, &h->offsets,
-                    &h->vrange, &h->vcent, &h->vcnt, &h->inputs, &h->part, &h->pn, &h->stage_in, &h->stage_out})
-    b->release();
-  for (int l = 0; l < BB_LAYERS; ++l)
-    for (DevBuf* b : {&h->bw[l], &h->bscale[l], &h->bshift[l]}) b->release();
-  for (DevBuf* b : {&h->braw, &h->canvas, &h->big, &h->a64, &h->f1, &h->half[0], &h->half[1], &h->quarter[0],
-                    &h->quarter[1], &h->cat, &h->lay_in, &h->lay_up})
-    b->release();
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
-  return GLOC_OK;
-}
+int gloc_pillar_destroy(gloc_pillar* h) { return destroy_handle(h); }
 
-int gloc_pillar_set_stream(gloc_pillar* h, void* hip_stream) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
-  return GLOC_OK;
-}
+int gloc_pillar_set_stream(gloc_pillar* h, void* hip_stream) { return handle_set_stream(h, hip_stream); }
 
-int gloc_pillar_synchronize(gloc_pillar* h) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  return GLOC_OK;
-}
+int gloc_pillar_synchronize(gloc_pillar* h) { return handle_synchronize(h); }
 
 int gloc_pillar_set_pointnet(gloc_pillar* h, const float* w, const float* bn_weight, const float* bn_bias,
                              const float* bn_mean, const float* bn_var, float eps) {
@@ -552,28 +499,12 @@ int gloc_pillar_features_device(gloc_pillar* h, const float* d_pts, const uint64
   return features_device(h, d_pts, offsets, n_scans, stride_floats, p, d_out);
 }
 
-int gloc_pillar_set_profile(gloc_pillar* h, int enable) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  h->prof.enabled = enable != 0;
-  return GLOC_OK;
-}
+int gloc_pillar_set_profile(gloc_pillar* h, int enable) { return handle_set_profile(h, enable); }
 
 int gloc_pillar_profile(gloc_pillar* h, const char* kernel, double* total_ms, uint64_t* launches) {
-  GLOC_REQUIRE(h && kernel, GLOC_ERR_INVALID, "NULL argument");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(h->prof.collect(h->stream));
-  auto it = h->prof.fam.find(kernel);
-  if (total_ms) *total_ms = it == h->prof.fam.end() ? 0.0 : it->second.total_ms;
-  if (launches) *launches = it == h->prof.fam.end() ? 0 : it->second.launches;
-  return GLOC_OK;
+  return handle_profile(h, kernel, total_ms, launches);
 }
 
-int gloc_pillar_profile_reset(gloc_pillar* h) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(h->prof.collect(h->stream));
-  h->prof.reset();
-  return GLOC_OK;
-}
+int gloc_pillar_profile_reset(gloc_pillar* h) { return handle_profile_reset(h); }
 
 }  // extern "C"

@@ -5,7 +5,6 @@
 // and over any number of queries in flight (one launch covers all their candidates).
 #include <algorithm>
 #include <cmath>
-#include <new>
 #include <vector>
 
 #include "common.hpp"
@@ -18,9 +17,7 @@
 using namespace gloc;
 using namespace gloc::reg;
 
-struct gloc_reg {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+struct gloc_reg : Handle {
   hipEvent_t done_ev = nullptr;  // a batch waits for ITS OWN results, not for the stream: handles that share a stream
                                  // (gloc_reg_set_stream) queue their batches back to back while the host reads results
   gloc_scan_store* store = nullptr;  // scans are looked up here (attached, or the handle's own)
@@ -86,8 +83,15 @@ struct gloc_reg {
   std::atomic<uint64_t> chain_launches{0}, chain_timeouts{0};
   size_t last_ld = 0;      // shape of the last batch (gloc_reg_debug_corr)
   uint32_t last_jobs = 0;
-  Profiler prof;
   gloc::ndt::Ws* ndt = nullptr;  // NDT workspace (ndt.hip), made on first use
+  ~gloc_reg() {  // (the handle's work has been waited for: destroy_handle)
+    if (pending.active && pending.store) store_pin(pending.store, pending.pinned.data(), pending.pinned.size(), -1);
+    if (store) store->attached--;
+    if (own_store) (void)gloc_scan_store_destroy(own_store);
+    gloc::ndt::ws_free(ndt);
+    if (done_ev) (void)hipEventDestroy(done_ev);
+    if (pin) (void)hipHostFree(pin);
+  }
 };
 
 namespace {
@@ -722,27 +726,15 @@ void gloc_reg_default_params(gloc_reg_params* p) {
 }
 
 int gloc_reg_create(int device, gloc_reg** out) {
-  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is null");
-  *out = nullptr;
-  GLOC_TRY(select_device(device));
-  gloc_reg* h = new (std::nothrow) gloc_reg;
-  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "host allocation failed");
-  h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
-    delete h;
-    return GLOC_ERR_HIP;
-  }
-  h->stream = h->own_stream;
-  e = hipEventCreateWithFlags(&h->done_ev, hipEventDisableTiming);
+  GLOC_TRY(create_handle(device, out));
+  gloc_reg* h = *out;
+  hipError_t e = hipEventCreateWithFlags(&h->done_ev, hipEventDisableTiming);
   if (e != hipSuccess) {
     set_err("hipEventCreate failed: %s", hipGetErrorString(e));
-    (void)hipStreamDestroy(h->own_stream);
+    *out = nullptr;
     delete h;
     return GLOC_ERR_HIP;
   }
-  *out = h;
   return GLOC_OK;
 }
 
@@ -766,42 +758,11 @@ int gloc_reg_scan_clear(gloc_reg* h) {
   return gloc_scan_store_clear(h->store);
 }
 
-int gloc_reg_destroy(gloc_reg* h) {
-  if (!h) return GLOC_OK;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  if (h->pending.active && h->pending.store) store_pin(h->pending.store, h->pending.pinned.data(), h->pending.pinned.size(), -1);
-  h->pending.pinned.clear();
-  h->pending.active = false;
-  if (h->store) h->store->attached--;
-  h->store = nullptr;
-  if (h->own_store) (void)gloc_scan_store_destroy(h->own_store);
-  h->prof.destroy();
-  gloc::ndt::ws_free(h->ndt);
-  for (DevBuf* b : {&h->jobs, &h->states, &h->corr, &h->d2, &h->pairs, &h->Rt, &h->valid, &h->inliers,
-                    &h->partials, &h->export_idx, &h->export_d2, &h->counters, &h->split_zero, &h->split_ff, &h->alive, &h->heavy_buf})
-    b->release();
-  if (h->done_ev) (void)hipEventDestroy(h->done_ev);
-  if (h->pin) (void)hipHostFree(h->pin);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
-  return GLOC_OK;
-}
+int gloc_reg_destroy(gloc_reg* h) { return destroy_handle(h); }
 
-int gloc_reg_set_stream(gloc_reg* h, void* hip_stream) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
-  return GLOC_OK;
-}
+int gloc_reg_set_stream(gloc_reg* h, void* hip_stream) { return handle_set_stream(h, hip_stream); }
 
-int gloc_reg_synchronize(gloc_reg* h) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  return GLOC_OK;
-}
+int gloc_reg_synchronize(gloc_reg* h) { return handle_synchronize(h); }
 
 int gloc_reg_set_option(gloc_reg* h, int option, int64_t value) {
   GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
@@ -1355,20 +1316,11 @@ int gloc_reg_ndt_cells(gloc_reg* h, uint32_t scan_id, const gloc_ndt_params* prm
 }
 
 int gloc_reg_profile(gloc_reg* h, const char* kernel, double* total_ms, uint64_t* launches) {
-  GLOC_REQUIRE(h && kernel, GLOC_ERR_INVALID, "null argument");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(h->prof.collect(h->stream));
-  auto it = h->prof.fam.find(kernel);
-  if (total_ms) *total_ms = it == h->prof.fam.end() ? 0.0 : it->second.total_ms;
-  if (launches) *launches = it == h->prof.fam.end() ? 0 : it->second.launches;
-  return GLOC_OK;
+  return handle_profile(h, kernel, total_ms, launches);
 }
 
 int gloc_reg_profile_reset(gloc_reg* h) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->prof.reset();
+  GLOC_TRY(handle_profile_reset(h));
   h->nn_launches = 0;
   if (h->counters.p) GLOC_HIP(hipMemsetAsync(h->counters.p, 0, 8 * NN_STAT_SLOTS, h->stream));
   return GLOC_OK;

@@ -948,36 +948,13 @@ int gloc::reg::store_insert_scan(gloc_scan_store* st, const DevScan& s, uint32_t
 
 extern "C" {
 
-int gloc_scan_store_create(int device, gloc_scan_store** out) {
-  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is null");
-  *out = nullptr;
-  GLOC_TRY(select_device(device));
-  gloc_scan_store* st = new (std::nothrow) gloc_scan_store;
-  GLOC_REQUIRE(st, GLOC_ERR_NOMEM, "host allocation failed");
-  st->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
-    delete st;
-    return GLOC_ERR_HIP;
-  }
-  *out = st;
-  return GLOC_OK;
-}
+int gloc_scan_store_create(int device, gloc_scan_store** out) { return create_handle(device, out); }
 
 int gloc_scan_store_destroy(gloc_scan_store* st) {
   if (!st) return GLOC_OK;
   GLOC_REQUIRE(st->attached.load() == 0, GLOC_ERR_STATE,
                "%d registration handle(s) still attached to this scan store", st->attached.load());
-  (void)hipSetDevice(st->device);
-  (void)hipStreamSynchronize(st->stream);
-  for (auto& s : st->scans)
-    if (s.block) (void)hipFree(s.block);
-  for (auto& kv : st->free_blocks) (void)hipFree(kv.second);
-  for (DevBuf* b : st->scratch()) b->release();
-  (void)hipStreamDestroy(st->stream);
-  delete st;
-  return GLOC_OK;
+  return destroy_handle(st);
 }
 
 int gloc_scan_store_add(gloc_scan_store* st, const float* pts, size_t n, size_t stride_floats, uint32_t* scan_id) {

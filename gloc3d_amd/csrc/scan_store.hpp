@@ -36,10 +36,8 @@ struct DevScan {
                     // it may not be re-sorted in place meanwhile (store_pin / store_unpin, under the store's mutex)
 };
 
-struct gloc_scan_store {
-  int device = 0;
+struct gloc_scan_store : gloc::Handle {  // (always on its own stream; the base's profiler stays idle)
   std::mutex mu;  // guards the tables, the store's stream and its scratch
-  hipStream_t stream = nullptr;
   std::vector<DevScan> scans;
   std::vector<uint32_t> free_ids;
   std::multimap<size_t, void*> free_blocks;  // released allocations by capacity, reused by later adds
@@ -49,11 +47,12 @@ struct gloc_scan_store {
   gloc::DevBuf sort_keys, sort_keys2, sort_vals, sort_perm, sort_hist, stage, part, builds, segs;
   gloc::DevBuf grp_k0, grp_k1, grp_v0, grp_v1, grp_segs;
   gloc::DevBuf kd_k0, kd_k1, kd_v0, kd_v1, kd_p0, kd_p1, kd_h0, kd_h1, kd_box, kd_desc;
-  std::vector<gloc::DevBuf*> scratch() {
-    return {&sort_keys, &sort_keys2, &sort_vals, &sort_perm, &sort_hist, &stage, &part, &builds, &segs, &grp_k0, &grp_k1,
-            &grp_v0, &grp_v1, &grp_segs, &kd_k0, &kd_k1, &kd_v0, &kd_v1, &kd_p0, &kd_p1, &kd_h0, &kd_h1, &kd_box, &kd_desc};
-  }
   std::atomic<int> attached{0};  // registration handles using this store
+  ~gloc_scan_store() {
+    for (auto& s : scans)
+      if (s.block) (void)hipFree(s.block);
+    for (auto& kv : free_blocks) (void)hipFree(kv.second);
+  }
 };
 
 namespace gloc {

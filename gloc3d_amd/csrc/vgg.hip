@@ -3,7 +3,6 @@
 // main.py:531-541), the head of the TorchScript module RpyPCLoopDetector::get_place_feature runs
 // (registration/loop_detector.cpp:137-172).  Kernels and precision: vgg_kernels.hpp.
 #include <algorithm>
-#include <new>
 
 #include "common.hpp"
 #include "vgg_kernels.hpp"
@@ -34,15 +33,12 @@ int kpad(int cin) { return (9 * cin + BK - 1) / BK * BK; }
 
 }  // namespace
 
-struct gloc_vgg {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+struct gloc_vgg : Handle {
   DevBuf w[NLAYERS], b[NLAYERS];  // split weights [Cout][Kp / 8][h | m], bias [Cout]
   bool set[NLAYERS] = {};
   DevBuf act[2], nhwc, raw;       // activations (NHWC), the per-layer call's channels-last input, raw weights
-  DevBuf stage_in, stage_out;     // host-pointer API staging
+  Staging stage;                  // host-pointer API staging
   bool lds_attr_set[3] = {};       // dynamic-LDS limit raised for <2,1,true>, <2,1,false>, <2,2,false>
-  Profiler prof;
 };
 
 namespace {
@@ -116,53 +112,13 @@ int forward_device(gloc_vgg* h, const float* d_images, size_t n, int H, int W, f
 
 extern "C" {
 
-int gloc_vgg_create(int device, gloc_vgg** out) {
-  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  GLOC_TRY(select_device(device));
-  gloc_vgg* h = new (std::nothrow) gloc_vgg();
-  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "out of host memory");
-  h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
-    return GLOC_ERR_HIP;
-  }
-  h->stream = h->own_stream;
-  *out = h;
-  return GLOC_OK;
-}
+int gloc_vgg_create(int device, gloc_vgg** out) { return create_handle(device, out); }
 
-int gloc_vgg_destroy(gloc_vgg* h) {
-  if (!h) return GLOC_OK;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  h->prof.destroy();
-  for (int l = 0; l < NLAYERS; ++l) {
-    h->w[l].release();
-    h->b[l].release();
-  }
-  for (DevBuf* b : {&h->act[0], &h->act[1], &h->nhwc, &h->raw, &h->stage_in, &h->stage_out}) b->release();
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
-  return GLOC_OK;
-}
+int gloc_vgg_destroy(gloc_vgg* h) { return destroy_handle(h); }
 
-int gloc_vgg_set_stream(gloc_vgg* h, void* hip_stream) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
-  return GLOC_OK;
-}
+int gloc_vgg_set_stream(gloc_vgg* h, void* hip_stream) { return handle_set_stream(h, hip_stream); }
 
-int gloc_vgg_synchronize(gloc_vgg* h) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  return GLOC_OK;
-}
+int gloc_vgg_synchronize(gloc_vgg* h) { return handle_synchronize(h); }
 
 int gloc_vgg_layer_shape(int layer, uint32_t* cin, uint32_t* cout, int* relu, int* pool) {
   GLOC_REQUIRE(layer >= 0 && layer < NLAYERS, GLOC_ERR_INVALID, "layer must be in [0, %d]", NLAYERS - 1);
@@ -214,13 +170,9 @@ int gloc_vgg_forward(gloc_vgg* h, const float* images, size_t n, uint32_t H, uin
   GLOC_TRY(check_layers(h, 0, NLAYERS - 1));
   GLOC_HIP(hipSetDevice(h->device));
   const size_t in_count = n * 3 * (size_t)H * W, out_count = n * 512 * (size_t)(H / 16) * (W / 16);
-  GLOC_TRY(h->stage_in.ensure(sizeof(float) * in_count, h->stream));
-  GLOC_TRY(h->stage_out.ensure(sizeof(float) * out_count, h->stream));
-  GLOC_HIP(hipMemcpyAsync(h->stage_in.p, images, sizeof(float) * in_count, hipMemcpyHostToDevice, h->stream));
-  GLOC_TRY(forward_device(h, h->stage_in.as<float>(), n, (int)H, (int)W, h->stage_out.as<float>()));
-  GLOC_HIP(hipMemcpyAsync(out, h->stage_out.p, sizeof(float) * out_count, hipMemcpyDeviceToHost, h->stream));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  return GLOC_OK;
+  return h->stage.call(h->stream, images, sizeof(float) * in_count, out, sizeof(float) * out_count, [&](void* d_in, void* d_out) {
+    return forward_device(h, (const float*)d_in, n, (int)H, (int)W, (float*)d_out);
+  });
 }
 
 int gloc_vgg_forward_layer(gloc_vgg* h, int layer, const float* d_in, size_t n, uint32_t H, uint32_t W, float* d_out) {
@@ -244,28 +196,12 @@ int gloc_vgg_forward_layer(gloc_vgg* h, int layer, const float* d_in, size_t n, 
   return conv(h, layer, in, d_out, n, (int)H, (int)W, true);
 }
 
-int gloc_vgg_set_profile(gloc_vgg* h, int enable) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  h->prof.enabled = enable != 0;
-  return GLOC_OK;
-}
+int gloc_vgg_set_profile(gloc_vgg* h, int enable) { return handle_set_profile(h, enable); }
 
 int gloc_vgg_profile(gloc_vgg* h, const char* kernel, double* total_ms, uint64_t* launches) {
-  GLOC_REQUIRE(h && kernel, GLOC_ERR_INVALID, "NULL argument");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(h->prof.collect(h->stream));
-  auto it = h->prof.fam.find(kernel);
-  if (total_ms) *total_ms = it == h->prof.fam.end() ? 0.0 : it->second.total_ms;
-  if (launches) *launches = it == h->prof.fam.end() ? 0 : it->second.launches;
-  return GLOC_OK;
+  return handle_profile(h, kernel, total_ms, launches);
 }
 
-int gloc_vgg_profile_reset(gloc_vgg* h) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "handle is NULL");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(h->prof.collect(h->stream));
-  h->prof.reset();
-  return GLOC_OK;
-}
+int gloc_vgg_profile_reset(gloc_vgg* h) { return handle_profile_reset(h); }
 
 }  // extern "C"

@@ -2,7 +2,6 @@
 // Replaces NetVLAD.forward (model/netvlad_fc.py:73-109), i.e. the tail of the TorchScript module the
 // reference runs in RpyPCLoopDetector::get_place_feature (registration/loop_detector.cpp:152-163).
 #include <algorithm>
-#include <new>
 
 #include "common.hpp"
 #include "vlad_kernels.hpp"
@@ -10,18 +9,15 @@
 using namespace gloc;
 using namespace gloc::vlad;
 
-struct gloc_vlad {
-  int device = 0;
+struct gloc_vlad : Handle {
   size_t C = 0, K = 0, Kp = 0, out_dim = 0;
   int normalize_input = 1;
   bool has_bias = false;
-  hipStream_t own_stream = nullptr, stream = nullptr;
   DevBuf conv_w, conv_b, centroids, fc_w;       // parameters, resident
   DevBuf gate_w, gate_scale, gate_shift, gate_tmp;  // optional GatingContext
   bool gating = false;
   DevBuf partV, partS, vlad, nrm2, fc_part;     // workspace
-  DevBuf stage_in, stage_out;                   // host-pointer API staging
-  Profiler prof;
+  Staging stage;                                // host-pointer API staging
 };
 
 namespace {
@@ -97,22 +93,14 @@ int gloc_vlad_create(int device, size_t dim, size_t clusters, size_t out_dim, co
   GLOC_REQUIRE(dim >= 1 && dim <= 560 && clusters >= 1 && clusters <= 64 && out_dim >= 1 &&
                    out_dim <= 65536,
                GLOC_ERR_INVALID, "need dim <= 560 (LDS tile), clusters <= 64, out_dim <= 65536");
-  GLOC_TRY(select_device(device));
-  gloc_vlad* h = new (std::nothrow) gloc_vlad;
-  GLOC_REQUIRE(h, GLOC_ERR_NOMEM, "host allocation failed");
-  h->device = device;
+  gloc_vlad* h = nullptr;
+  GLOC_TRY(create_handle(device, &h));
   h->C = dim;
   h->K = clusters;
   h->Kp = (clusters + 15) / 16 * 16;
   h->out_dim = out_dim;
   h->normalize_input = normalize_input;
   h->has_bias = conv_b != nullptr;
-  if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) {
-    set_err("hipStreamCreate failed");
-    delete h;
-    return GLOC_ERR_HIP;
-  }
-  h->stream = h->own_stream;
   int rc = upload(h, h->conv_w, conv_w, clusters * dim);
   if (rc == GLOC_OK && conv_b) rc = upload(h, h->conv_b, conv_b, clusters);
   if (rc == GLOC_OK) rc = upload(h, h->centroids, centroids, clusters * dim);
@@ -144,26 +132,9 @@ int gloc_vlad_set_gating(gloc_vlad* h, const float* gating_w, const float* scale
   return GLOC_OK;
 }
 
-int gloc_vlad_destroy(gloc_vlad* h) {
-  if (!h) return GLOC_OK;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
-  h->prof.destroy();
-  for (DevBuf* b : {&h->gate_w, &h->gate_scale, &h->gate_shift, &h->gate_tmp, &h->conv_w, &h->conv_b, &h->centroids, &h->fc_w, &h->partV, &h->partS, &h->vlad,
-                    &h->nrm2, &h->fc_part, &h->stage_in, &h->stage_out})
-    b->release();
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
-  return GLOC_OK;
-}
+int gloc_vlad_destroy(gloc_vlad* h) { return destroy_handle(h); }
 
-int gloc_vlad_set_stream(gloc_vlad* h, void* hip_stream) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
-  return GLOC_OK;
-}
+int gloc_vlad_set_stream(gloc_vlad* h, void* hip_stream) { return handle_set_stream(h, hip_stream); }
 
 int gloc_vlad_forward_device(gloc_vlad* h, const float* d_feat, size_t n, size_t hw, float* d_out) {
   GLOC_REQUIRE(h && d_feat && d_out, GLOC_ERR_INVALID, "null argument");
@@ -176,30 +147,14 @@ int gloc_vlad_forward(gloc_vlad* h, const float* feat, size_t n, size_t hw, floa
   GLOC_REQUIRE(h && feat && out, GLOC_ERR_INVALID, "null argument");
   GLOC_REQUIRE(n >= 1 && n <= (1u << 20) && hw >= 1 && hw <= (1u << 24), GLOC_ERR_INVALID, "bad sizes");
   GLOC_HIP(hipSetDevice(h->device));
-  const size_t in_count = n * h->C * hw;
-  GLOC_TRY(h->stage_in.ensure(sizeof(float) * in_count, h->stream));
-  GLOC_TRY(h->stage_out.ensure(sizeof(float) * n * h->out_dim, h->stream));
-  GLOC_HIP(hipMemcpyAsync(h->stage_in.p, feat, sizeof(float) * in_count, hipMemcpyHostToDevice, h->stream));
-  GLOC_TRY(forward_device(h, h->stage_in.as<float>(), n, hw, h->stage_out.as<float>()));
-  GLOC_HIP(hipMemcpyAsync(out, h->stage_out.p, sizeof(float) * n * h->out_dim, hipMemcpyDeviceToHost, h->stream));
-  GLOC_HIP(hipStreamSynchronize(h->stream));
-  return GLOC_OK;
+  return h->stage.call(h->stream, feat, sizeof(float) * n * h->C * hw, out, sizeof(float) * n * h->out_dim,
+                       [&](void* d_in, void* d_out) { return forward_device(h, (const float*)d_in, n, hw, (float*)d_out); });
 }
 
-int gloc_vlad_set_profile(gloc_vlad* h, int enable) {
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
-  h->prof.enabled = enable != 0;
-  return GLOC_OK;
-}
+int gloc_vlad_set_profile(gloc_vlad* h, int enable) { return handle_set_profile(h, enable); }
 
 int gloc_vlad_profile(gloc_vlad* h, const char* kernel, double* total_ms, uint64_t* launches) {
-  GLOC_REQUIRE(h && kernel, GLOC_ERR_INVALID, "null argument");
-  GLOC_HIP(hipSetDevice(h->device));
-  GLOC_TRY(h->prof.collect(h->stream));
-  auto it = h->prof.fam.find(kernel);
-  if (total_ms) *total_ms = it == h->prof.fam.end() ? 0.0 : it->second.total_ms;
-  if (launches) *launches = it == h->prof.fam.end() ? 0 : it->second.launches;
-  return GLOC_OK;
+  return handle_profile(h, kernel, total_ms, launches);
 }
 
 }  // extern "C"

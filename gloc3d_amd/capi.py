@@ -55,6 +55,11 @@ class NdtParams(C.Structure):
                 ("min_covar_eigvalue_mult", C.c_float)]
 
 
+class P2lParams(C.Structure):
+    _fields_ = [("max_iters", C.c_uint32), ("max_corr_dist", C.c_float), ("trans_eps", C.c_float), ("rot_eps", C.c_float),
+                ("normal_k", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class BevParams(C.Structure):
     _fields_ = [("resolution", C.c_float), ("max_range", C.c_float), ("out_width", C.c_uint32),
                 ("out_height", C.c_uint32), ("format", C.c_uint32), ("pad_bgr", C.c_uint8 * 3),
@@ -192,6 +197,12 @@ _PROTOS = [
     ("gloc_reg_profile_reset", _i, [_vp]),
     ("gloc_reg_nn_stats", _i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     ("gloc_ndt_default_params", None, [C.POINTER(NdtParams)]),
+    ("gloc_scan_store_build_normals", _i, [_vp, _u32, _u32]),
+    ("gloc_scan_store_normals", _i, [_vp, _u32, _vp, _sz]),
+    ("gloc_p2l_default_params", None, [C.POINTER(P2lParams)]),
+    ("gloc_reg_p2l_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(P2lParams), _vp, _vp, _vp, _vp]),
+    ("gloc_reg_p2l_system", _i, [_vp, _u32, _u32, _vp, C.POINTER(P2lParams), _vp, _vp, C.POINTER(C.c_double),
+                             C.POINTER(C.c_uint64)]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
@@ -528,6 +539,15 @@ def default_ndt_params(**over):
     return p
 
 
+def default_p2l_params(**over):
+    """gloc_p2l_params as gloc_p2l_default_params leaves them (30 passes, no rejection, no early stop, k = 10), then `over`."""
+    p = P2lParams()
+    lib().gloc_p2l_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
 class ScanStore(_Handle):
     """Resident scans + their search index, shared by any number of Registrars."""
 
@@ -648,6 +668,17 @@ class ScanStore(_Handle):
         n = self.points(scan_id)
         out = np.empty((n, 3), np.float32)
         check(lib().gloc_scan_store_download(self._h, int(scan_id), _np_ptr(out), n))
+        return out
+
+    def build_normals(self, scan_id, k=10):
+        """Per-point normals of a resident scan from its k nearest neighbours (gloc_scan_store_build_normals)."""
+        check(lib().gloc_scan_store_build_normals(self._h, int(scan_id), int(k)))
+
+    def normals(self, scan_id):
+        """The scan's normals [n, 3] float32 in original order; a zero row means "no normal"."""
+        n = self.points(scan_id)
+        out = np.empty((n, 3), np.float32)
+        check(lib().gloc_scan_store_normals(self._h, int(scan_id), _np_ptr(out), n))
         return out
 
 
@@ -786,6 +817,28 @@ class Registrar(_Handle):
         check(lib().gloc_reg_ndt_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
                                            C.byref(prm), _np_ptr(T), _np_ptr(prob), _np_ptr(iters), _np_ptr(conv)))
         return T, prob, iters, conv.astype(bool)
+
+    def p2l_batch(self, src_id, tgt_ids, init_T=None, params=None):
+        """Point-to-plane ICP of scan src_id against each of tgt_ids (gloc_reg_p2l_batch_ids): returns T [n, 4, 4] float32,
+        rmse [n] float32 (point-to-plane, at the final pose), iterations [n], status [n] (0 cap, 1 converged, 2 degenerate)."""
+        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
+        n = ids.shape[0]
+        prm = params or default_p2l_params()
+        it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
+        T = np.empty((n, 4, 4), np.float32)
+        rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        check(lib().gloc_reg_p2l_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
+                                           C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
+        return T, rmse, iters, status
+
+    def p2l_system(self, src_id, tgt_id, T=None, params=None):
+        """One evaluation of the point-to-plane normal equations at T: H [6, 6], g [6], sum r^2, pairs used."""
+        prm = params or default_p2l_params()
+        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
+        H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
+        check(lib().gloc_reg_p2l_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
+                                        _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
+        return H, g, s.value, c.value
 
     def ndt_derivatives(self, src_id, tgt_id, p6, params=None):
         """score, gradient [6], Hessian [6, 6] of the filtered source against the target's cells at p6."""

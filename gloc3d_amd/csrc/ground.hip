@@ -8,6 +8,7 @@
 
 #include "common.hpp"
 #include "ground_kernels.hpp"
+#include "ground_normals.hpp"
 #include "seg_sort.hpp"
 
 using namespace gloc;
@@ -303,6 +304,46 @@ int estimate_device(gloc_ground* h, const float* d_xyz, size_t n, size_t stride,
 }
 
 }  // namespace
+
+// ---- per-point normals of a whole resident scan (scan_store.hip: gloc_scan_store_build_normals) -----------------------
+// The kernels of G2 - G4 on a cloud that already has a spatially sorted copy: the exact k-NN is exact in whatever order
+// the points are cut into chunks, so the store's own sorted copy stands in for the Hilbert sort of knn_device and the
+// lists -- hence the normals -- are those of gloc_ground_normals on the same points, bit for bit.
+namespace gloc {
+namespace ground {
+
+__global__ __launch_bounds__(256) void unsort_f4_kernel(const f32x4* __restrict__ spts, uint32_t m, f32x4* __restrict__ pts) {
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= m) return;
+  const f32x4 p = spts[s];
+  const uint32_t o = __float_as_uint(p.w);
+  if (o < m) pts[o] = f32x4{p.x, p.y, p.z, 0.f};
+}
+
+int scan_normals(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, uint32_t k, float* out_normals) {
+  GLOC_REQUIRE(k >= 3 && k <= (uint32_t)KMAX, GLOC_ERR_INVALID, "k must be in [3, %d]", KMAX);
+  if (m == 0) return GLOC_OK;
+  const uint32_t nch = (m + KCH - 1) / KCH;
+  GLOC_TRY(w.pts.ensure(sizeof(f32x4) * m, s));
+  GLOC_TRY(w.knn_idx.ensure(sizeof(uint32_t) * (size_t)m * k, s));
+  GLOC_TRY(w.knn_d2.ensure(sizeof(float) * (size_t)m * k, s));
+  GLOC_TRY(w.cbox_lo.ensure(sizeof(f32x4) * nch, s));
+  GLOC_TRY(w.cbox_hi.ensure(sizeof(f32x4) * nch, s));
+  GLOC_TRY(w.bins.ensure(std::max<uint32_t>(m, 16), s));
+  GLOC_TRY(w.hist.ensure(sizeof(uint32_t) * 18, s));
+  GLOC_HIP(hipMemsetAsync(w.hist.p, 0, sizeof(uint32_t) * 18, s));
+  hipLaunchKernelGGL(unsort_f4_kernel, dim3((m + 255) / 256), dim3(256), 0, s, spts, m, w.pts.as<f32x4>());
+  hipLaunchKernelGGL(kchunk_boxes_kernel, dim3(nch), dim3(64), 0, s, spts, m, w.cbox_lo.as<f32x4>(), w.cbox_hi.as<f32x4>());
+  hipLaunchKernelGGL(knn_culled_kernel, dim3((nch + 3) / 4), dim3(256), 0, s, spts, m, w.cbox_lo.as<f32x4>(),
+                     w.cbox_hi.as<f32x4>(), nch, (int)k, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>());
+  hipLaunchKernelGGL(normals_kernel, dim3((m + 255) / 256), dim3(256), 0, s, w.pts.as<f32x4>(), m, w.knn_idx.as<uint32_t>(),
+                     (int)k, out_normals, w.bins.as<uint8_t>(), w.hist.as<uint32_t>());
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+}  // namespace ground
+}  // namespace gloc
 
 extern "C" {
 

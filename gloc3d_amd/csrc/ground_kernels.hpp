@@ -324,7 +324,9 @@ __global__ __launch_bounds__(256) void knn_culled_kernel(const f32x4* __restrict
   const f32x4 olo = box_lo[own], ohi = box_hi[own];
   for (uint32_t c0 = 0; c0 < nchunks; c0 += 64) {
     const uint32_t cl = c0 + lane;
-    float lbw = FLT_MAX;
+    // (infinity, not FLT_MAX: a wave with a lane whose list never fills -- a non-finite point -- has wmax = FLT_MAX, and
+    // its own chunk, evaluated above, must not pass the test and be inserted a second time)
+    float lbw = __builtin_inff();
     f32x4 blo = {0.f, 0.f, 0.f, 0.f}, bhi = {0.f, 0.f, 0.f, 0.f};
     if (cl < nchunks && cl != own) {
       blo = box_lo[cl]; bhi = box_hi[cl];

@@ -1,0 +1,20 @@
+// ground_normals.hpp -- the ground module's k-NN and normal kernels (ground_kernels.hpp, compiled in ground.hip) run over
+// a whole resident scan: what scan_store.hip calls to give a scan its per-point normals.
+#pragma once
+#include "common.hpp"
+#include "math3.hpp"
+
+namespace gloc {
+namespace ground {
+
+struct NormalsScratch {
+  DevBuf pts, knn_idx, knn_d2, cbox_lo, cbox_hi, bins, hist;
+};
+
+// Normals of the m points of `spts` (any spatially coherent order: x, y, z, bits(original index)) from their k nearest
+// neighbours within the cloud, as gloc_ground_normals computes them; out_normals [m][3] in ORIGINAL order (device).
+// Enqueued on s; k in [3, 16].
+int scan_normals(hipStream_t s, NormalsScratch& w, const reg::f32x4* spts, uint32_t m, uint32_t k, float* out_normals);
+
+}  // namespace ground
+}  // namespace gloc

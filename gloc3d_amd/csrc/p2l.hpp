@@ -1,0 +1,43 @@
+// p2l.hpp -- what reg.hip (which owns the registration handle and the 1-NN passes) calls of p2l.hip.
+#pragma once
+#include "common.hpp"
+#include "math3.hpp"
+
+namespace gloc {
+namespace p2l {
+
+struct Ws;  // a handle's point-to-plane workspace (created on first use)
+void ws_free(Ws* w);
+
+struct TargetView {  // a job's target as the search indexes it
+  const reg::f32x4* pts;
+  const float* nrm;
+  uint32_t n;
+};
+
+// The handle's view for one batch: its stream, profiler and workspace slot, and the batch reg.hip has set up for the
+// correspondence passes -- the source in search order, where job c's fp32 pose lives (what the search moves the source
+// by; written here after every update), where a pass leaves its matches, and the pass itself.
+struct Ctx {
+  hipStream_t stream;
+  Profiler* prof;
+  Ws** ws;
+  const reg::f32x4* src_pts;
+  uint32_t n_src, n_jobs;
+  float* pose_f32;     // device: 12 floats (R row-major 9, t 3) per job ...
+  size_t pose_stride;  // ... this many floats apart
+  const uint32_t* corr;  // device [job][ld]: sorted source slot -> position in the target's search order
+  const float* d2;
+  size_t ld;
+  int (*nn_pass)(void* self, bool warm);  // enqueues the exact 1-NN pass of every job at the current poses
+  void* self;
+};
+
+int check_params(const gloc_p2l_params* prm);
+// Refines every job from init_T ([n][16] or null: identity).  system36/g6/sum_r2/count non-null: ONE evaluation at init_T
+// of job 0 instead (gloc_reg_p2l_system).  Returns after the results have been copied out.
+int run(const Ctx& x, const TargetView* tgts, const float* init_T, const gloc_p2l_params* prm, float* out_T, float* out_rmse,
+        uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum_r2, uint64_t* out_count);
+
+}  // namespace p2l
+}  // namespace gloc

@@ -11,6 +11,7 @@
 
 #include "ndt.hpp"
 #include "nn_compact.hpp"
+#include "p2l.hpp"
 #include "reg_kernels.hpp"
 #include "scan_store.hpp"
 
@@ -84,11 +85,13 @@ struct gloc_reg : Handle {
   size_t last_ld = 0;      // shape of the last batch (gloc_reg_debug_corr)
   uint32_t last_jobs = 0;
   gloc::ndt::Ws* ndt = nullptr;  // NDT workspace (ndt.hip), made on first use
+  gloc::p2l::Ws* p2l = nullptr;  // point-to-plane workspace (p2l.hip), made on first use
   ~gloc_reg() {  // (the handle's work has been waited for: destroy_handle)
     if (pending.active && pending.store) store_pin(pending.store, pending.pinned.data(), pending.pinned.size(), -1);
     if (store) store->attached--;
     if (own_store) (void)gloc_scan_store_destroy(own_store);
     gloc::ndt::ws_free(ndt);
+    gloc::p2l::ws_free(p2l);
     if (done_ev) (void)hipEventDestroy(done_ev);
     if (pin) (void)hipHostFree(pin);
   }
@@ -708,6 +711,112 @@ struct TempScans {
   }
 };
 
+// Point-to-plane refinement of one source against n targets (p2l.hip): the batch is set up as enqueue_jobs sets one up --
+// job table, fp32 poses in the CandState array the search reads, corr / d2 -- without a split plan (it is solve_kernel
+// that makes one), and p2l::run drives the passes through launch_nn.  Synchronous: the scans are pinned for the call.
+struct P2lPass {
+  gloc_reg* h;
+  BatchDims bd;
+  WsView v;
+  static int run(void* self, bool warm) {
+    P2lPass* p = static_cast<P2lPass*>(self);
+    return launch_nn(p->h, p->bd, p->v, warm, false, 0.f);
+  }
+};
+
+int run_p2l(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_p2l_params* prm,
+            float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6,
+            double* out_sum_r2, uint64_t* out_count) {
+  GLOC_TRY(gloc::p2l::check_params(prm));
+  GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
+  GLOC_REQUIRE(h->store, GLOC_ERR_INVALID, "unknown scan id %u", src_id);
+  gloc_scan_store* st = h->store;
+  hipStream_t s = h->stream;
+  const int cs = h->nn_src_per_lane;
+  std::vector<uint32_t> ids(1 + n);
+  std::vector<int> css(1 + n, 0);
+  ids[0] = src_id;
+  css[0] = cs;
+  std::copy(tgt_ids, tgt_ids + n, ids.begin() + 1);
+  {  // targets without normals get them (an allocation beside the scan: nothing a batch in flight reads moves)
+    std::lock_guard<std::mutex> lk(st->mu);
+    for (size_t c = 0; c < n; ++c) {
+      GLOC_REQUIRE(tgt_ids[c] < st->scans.size() && st->scans[tgt_ids[c]].live, GLOC_ERR_INVALID, "unknown scan id %u", tgt_ids[c]);
+      DevScan& t = st->scans[tgt_ids[c]];
+      if (t.nrm_k == 0) GLOC_TRY(store_build_normals(st, t, prm->normal_k));
+    }
+  }
+  std::vector<DevScan> scans(1 + n);
+  GLOC_TRY(store_get_pinned(st, ids.data(), css.data(), ids.size(), scans.data()));
+  struct Unpin {
+    gloc_scan_store* st;
+    const std::vector<uint32_t>& ids;
+    hipStream_t s;
+    ~Unpin() {
+      (void)hipStreamSynchronize(s);
+      store_pin(st, ids.data(), ids.size(), -1);
+    }
+  } unpin{st, ids, s};
+  const DevScan& src = scans[0];
+  GLOC_REQUIRE(src.n >= 1 && src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
+  const uint32_t n_jobs = (uint32_t)n;
+  const uint32_t ng = (uint32_t)((src.n + 64 * cs - 1) / (64 * cs));
+  BatchDims bd{n_jobs, (uint32_t)src.n, ng, 0, 0};
+  const uint32_t nblocks = (bd.max_src + ACC_PER_BLOCK - 1) / ACC_PER_BLOCK;
+  bd.n_part = (std::max<uint32_t>(std::max(bd.max_groups, nblocks), 1) + 31u) & ~31u;
+  bd.ld = ((size_t)bd.max_src + 127) & ~(size_t)127;
+  h->last_ld = bd.ld;
+  h->last_jobs = n_jobs;
+  GLOC_TRY(ensure_pinned(h, n_jobs));
+  h->chain_in_batch = false;
+  std::vector<gloc::p2l::TargetView> tv(n);
+  for (uint32_t c = 0; c < n_jobs; ++c) {
+    const DevScan& t = scans[1 + c];
+    GLOC_REQUIRE(t.n == 0 || t.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", tgt_ids[c]);
+    h->h_jobs[c] = Job{src.idx.pts, src.order, src.idx.inv, t.xyz, t.idx, (uint32_t)src.n, ng, c, 0u};
+    init_state(h->h_states[c], init_T ? init_T + 16 * (size_t)c : nullptr);
+    tv[c] = gloc::p2l::TargetView{t.idx.pts, t.nrm, (uint32_t)t.n};
+  }
+  GLOC_TRY(h->jobs.ensure(sizeof(Job) * n_jobs, s));
+  if (!h->counters.p) {
+    GLOC_TRY(h->counters.ensure(8 * NN_STAT_SLOTS, s));
+    GLOC_HIP(hipMemsetAsync(h->counters.p, 0, 8 * NN_STAT_SLOTS, s));
+  }
+  GLOC_TRY(h->states.ensure(sizeof(CandState) * n_jobs, s));
+  GLOC_TRY(h->corr.ensure(sizeof(uint32_t) * bd.ld * n_jobs, s));
+  GLOC_TRY(h->d2.ensure(sizeof(float) * bd.ld * n_jobs, s));
+  GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part * n_jobs, s));
+  GLOC_HIP(hipMemcpyAsync(h->jobs.p, h->h_jobs, sizeof(Job) * n_jobs, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->states.p, h->h_states, sizeof(CandState) * n_jobs, hipMemcpyHostToDevice, s));
+  h->split = NnSplit{};
+  GLOC_TRY(setup_heavy(h, bd, cs));
+  P2lPass pass{h, bd, WsView{}};
+  pass.v.s = s;
+  pass.v.n_jobs = n_jobs;
+  pass.v.jobs = h->jobs.as<Job>();
+  pass.v.states = h->states.as<CandState>();
+  pass.v.corr = h->corr.as<uint32_t>();
+  pass.v.d2 = h->d2.as<float>();
+  pass.v.partials = h->partials.as<double>();
+  pass.v.heavy = h->heavy;
+  static_assert(sizeof(CandState) % sizeof(float) == 0, "the fp32 poses are a whole number of floats apart");
+  gloc::p2l::Ctx x{};
+  x.stream = s;
+  x.prof = &h->prof;
+  x.ws = &h->p2l;
+  x.src_pts = src.idx.pts;
+  x.n_src = (uint32_t)src.n;
+  x.n_jobs = n_jobs;
+  x.pose_f32 = reinterpret_cast<float*>(h->states.as<char>() + offsetof(CandState, Tf));
+  x.pose_stride = sizeof(CandState) / sizeof(float);
+  x.corr = pass.v.corr;
+  x.d2 = pass.v.d2;
+  x.ld = bd.ld;
+  x.nn_pass = &P2lPass::run;
+  x.self = &pass;
+  return gloc::p2l::run(x, tv.data(), init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum_r2, out_count);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1313,6 +1422,23 @@ int gloc_reg_ndt_cells(gloc_reg* h, uint32_t scan_id, const gloc_ndt_params* prm
   GLOC_HIP(hipSetDevice(h->device));
   const gloc::ndt::Ctx x{h->store, h->stream, &h->prof, &h->ndt};
   return gloc::ndt::cells(x, scan_id, prm, capacity, out_key3, out_count, out_mean3, out_icov9, n_cells);
+}
+
+int gloc_reg_p2l_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                           const gloc_p2l_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status) {
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids && prm, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_p2l(h, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+                 nullptr);
+}
+
+int gloc_reg_p2l_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_p2l_params* prm,
+                        double* out_H36, double* out_g6, double* out_sum_r2, uint64_t* out_count) {
+  GLOC_REQUIRE(h && prm && out_H36 && out_g6 && out_sum_r2 && out_count, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_p2l(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum_r2, out_count);
 }
 
 int gloc_reg_profile(gloc_reg* h, const char* kernel, double* total_ms, uint64_t* launches) {

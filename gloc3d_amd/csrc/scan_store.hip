@@ -597,7 +597,45 @@ void store_free_scan(gloc_scan_store* st, DevScan& s, bool cache_block) {
       (void)hipFree(s.block);
     }
   }
+  if (s.nrm) (void)hipFree(s.nrm);
   s = DevScan{};
+}
+
+// normals between original order and the order of the sorted points (pts[i].w = original index of sorted position i)
+__global__ __launch_bounds__(256) void normals_reorder_kernel(const f32x4* __restrict__ pts, uint32_t n, const float* __restrict__ in,
+                                                              float* __restrict__ out, bool to_sorted) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t o = __float_as_uint(pts[i].w);
+  if (o >= n) return;
+  const size_t src = 3 * (size_t)(to_sorted ? o : i), dst = 3 * (size_t)(to_sorted ? i : o);
+  out[dst + 0] = in[src + 0];
+  out[dst + 1] = in[src + 1];
+  out[dst + 2] = in[src + 2];
+}
+
+int store_build_normals(gloc_scan_store* st, DevScan& s, uint32_t k) {
+  GLOC_REQUIRE(k >= 3 && k <= 16, GLOC_ERR_INVALID, "k = %u outside [3, 16]", k);
+  if (s.nrm_k == k || s.n == 0) {
+    s.nrm_k = k;
+    return GLOC_OK;
+  }
+  GLOC_REQUIRE(!s.nrm || s.pins == 0, GLOC_ERR_STATE, "the scan's normals (k = %u) may be read by %d batch(es) in flight: not rebuilt with k = %u",
+               s.nrm_k, s.pins, k);
+  hipStream_t q = st->stream;
+  const uint32_t n = (uint32_t)s.n;
+  if (!s.nrm) {
+    GLOC_HIP(hipMalloc(reinterpret_cast<void**>(&s.nrm), 12 * s.n));
+    if (s.live) st->live_bytes += 12 * s.n;
+  }
+  s.nrm_k = 0;
+  GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
+  GLOC_TRY(gloc::ground::scan_normals(q, st->nrm_ws, s.idx.pts, n, k, st->nrm_tmp.as<float>()));
+  hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, s.idx.pts, n, st->nrm_tmp.as<float>(), s.nrm, true);
+  GLOC_HIP(hipGetLastError());
+  GLOC_HIP(hipStreamSynchronize(q));
+  s.nrm_k = k;
+  return GLOC_OK;
 }
 
 int store_build_order(gloc_scan_store* st, DevScan& s, int cs) {
@@ -833,6 +871,15 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
     unsigned long long* kk[2] = {st->kd_k0.as<unsigned long long>(), st->kd_k1.as<unsigned long long>()};
     uint32_t* vv[2] = {st->kd_v0.as<uint32_t>(), st->kd_v1.as<uint32_t>()};
     const dim3 gpt((max_n + 255) / 256, cnt), gblk(((max_n + SB - 1) / SB + 255) / 256, cnt);
+    // normals follow their points: out to original order before the points move, back in behind kd_finish_kernel
+    std::vector<DevBuf> nrm_keep(cnt);
+    for (uint32_t i = 0; i < cnt; ++i)
+      if (todo[i]->nrm) {
+        const uint32_t n = (uint32_t)todo[i]->n;
+        GLOC_TRY(nrm_keep[i].ensure(12 * (size_t)n, q));
+        hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, todo[i]->idx.pts, n, todo[i]->nrm,
+                           nrm_keep[i].as<float>(), false);
+      }
     hipLaunchKernelGGL(kd_load_kernel, gpt, dim3(256), 0, q, d_k, pp[0], hh[0]);
     int cur = 0;
     static_assert(SB == 16, "the node size arithmetic assumes 16-point leaves");
@@ -848,6 +895,12 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
     // write back and rebuild what depends on the order: inv, kpos, all boxes, the launch orders
     hipLaunchKernelGGL(kd_finish_kernel, dim3((max_np + 255) / 256, cnt), dim3(256), 0, q, d_k, pp[cur], hh[cur]);
     launch_boxes(q, st->builds.as<ScanBuild>(), cnt, max_nch, max_npairs, max_nsup);
+    for (uint32_t i = 0; i < cnt; ++i)
+      if (todo[i]->nrm) {
+        const uint32_t n = (uint32_t)todo[i]->n;
+        hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, todo[i]->idx.pts, n,
+                           nrm_keep[i].as<float>(), todo[i]->nrm, true);
+      }
     GLOC_HIP(hipGetLastError());
     // From here on the scans ARE in kd order (kd_finish_kernel rewrote their points, inverse permutations and kpos, the
     // boxes follow): the bookkeeping says so before anything else can fail, so that a failure below (the launch orders'
@@ -927,7 +980,7 @@ int store_insert(gloc_scan_store* st, const DevScan& s, uint32_t* id) {
     *id = (uint32_t)(st->scans.size() - 1);
   }
   st->live_count++;
-  st->live_bytes += s.block_bytes;
+  st->live_bytes += s.block_bytes + s.nrm_bytes();
   return GLOC_OK;
 }
 
@@ -1150,7 +1203,7 @@ int gloc_scan_store_release(gloc_scan_store* st, uint32_t scan_id) {
                "scan %u is read by %d registration batch(es) in flight (gloc_reg_batch_multi_begin without _end)", scan_id,
                st->scans[scan_id].pins);
   st->live_count--;
-  st->live_bytes -= st->scans[scan_id].block_bytes;
+  st->live_bytes -= st->scans[scan_id].block_bytes + st->scans[scan_id].nrm_bytes();
   store_free_scan(st, st->scans[scan_id], true);
   st->free_ids.push_back(scan_id);
   return GLOC_OK;
@@ -1161,8 +1214,10 @@ int gloc_scan_store_clear(gloc_scan_store* st) {
   GLOC_HIP(hipSetDevice(st->device));
   std::lock_guard<std::mutex> lk(st->mu);
   GLOC_HIP(hipStreamSynchronize(st->stream));
-  for (auto& s : st->scans)
+  for (auto& s : st->scans) {
     if (s.block) (void)hipFree(s.block);
+    if (s.nrm) (void)hipFree(s.nrm);
+  }
   for (auto& kv : st->free_blocks) (void)hipFree(kv.second);
   st->scans.clear();
   st->free_ids.clear();
@@ -1246,6 +1301,35 @@ int gloc_scan_store_download(gloc_scan_store* st, uint32_t scan_id, float* out_x
   if (s.n) {
     GLOC_HIP(hipMemcpyAsync(out_xyz, s.xyz, sizeof(float) * 3 * s.n, hipMemcpyDeviceToHost, st->stream));
     GLOC_HIP(hipStreamSynchronize(st->stream));
+  }
+  return GLOC_OK;
+}
+
+int gloc_scan_store_build_normals(gloc_scan_store* st, uint32_t scan_id, uint32_t k) {
+  GLOC_REQUIRE(k >= 3 && k <= 16, GLOC_ERR_INVALID, "k = %u outside [3, 16]", k);
+  GLOC_REQUIRE(st, GLOC_ERR_INVALID, "null store");
+  GLOC_HIP(hipSetDevice(st->device));
+  std::lock_guard<std::mutex> lk(st->mu);
+  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
+  return store_build_normals(st, st->scans[scan_id], k);
+}
+
+int gloc_scan_store_normals(gloc_scan_store* st, uint32_t scan_id, float* out_nxyz, size_t capacity_points) {
+  GLOC_REQUIRE(st && out_nxyz, GLOC_ERR_INVALID, "null argument");
+  GLOC_HIP(hipSetDevice(st->device));
+  std::lock_guard<std::mutex> lk(st->mu);
+  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
+  const DevScan& s = st->scans[scan_id];
+  GLOC_REQUIRE(s.nrm_k != 0, GLOC_ERR_STATE, "scan %u has no normals: call gloc_scan_store_build_normals first", scan_id);
+  GLOC_REQUIRE(capacity_points >= s.n, GLOC_ERR_INVALID, "buffer holds %zu points, the scan has %zu", capacity_points, s.n);
+  if (s.n) {
+    hipStream_t q = st->stream;
+    const uint32_t n = (uint32_t)s.n;
+    GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
+    hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, s.idx.pts, n, s.nrm, st->nrm_tmp.as<float>(), false);
+    GLOC_HIP(hipGetLastError());
+    GLOC_HIP(hipMemcpyAsync(out_nxyz, st->nrm_tmp.p, 12 * s.n, hipMemcpyDeviceToHost, q));
+    GLOC_HIP(hipStreamSynchronize(q));
   }
   return GLOC_OK;
 }

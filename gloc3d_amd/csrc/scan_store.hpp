@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "ground_normals.hpp"
 #include "scan_index.hpp"
 
 // A scan resident in HBM: original-order xyz plus its search index (Hilbert-sorted copy with the
@@ -30,6 +31,12 @@ struct DevScan {
   uint32_t* order_of(int cs) const {
     return order_base + (cs == 1 ? 0 : cs == 2 ? order_g1 : order_g1 + (order_g1 + 1) / 2);
   }
+  // Per-point normals (gloc_scan_store_build_normals), an OPTIONAL SECOND allocation of 12 B per point: packed xyz in the
+  // order of idx.pts -- the order the 1-NN search reports its matches in -- so that a correspondence reads its normal at
+  // the index it got.  Built once per (scan, k); re-ordered with the points by the kd re-sort; zero = no normal.
+  float* nrm = nullptr;
+  uint32_t nrm_k = 0;  // the k they were built with (0: none)
+  size_t nrm_bytes() const { return nrm ? 12 * n : 0; }
   bool live = false;
   bool kd = false;  // the index is in kd order (target index)
   int pins = 0;     // batches in flight (gloc_reg_batch_multi_begin .. _end) whose jobs hold a by-value view of THIS scan:
@@ -47,10 +54,14 @@ struct gloc_scan_store : gloc::Handle {  // (always on its own stream; the base'
   gloc::DevBuf sort_keys, sort_keys2, sort_vals, sort_perm, sort_hist, stage, part, builds, segs;
   gloc::DevBuf grp_k0, grp_k1, grp_v0, grp_v1, grp_segs;
   gloc::DevBuf kd_k0, kd_k1, kd_v0, kd_v1, kd_p0, kd_p1, kd_h0, kd_h1, kd_box, kd_desc;
+  gloc::ground::NormalsScratch nrm_ws;  // the normals' k-NN lists and staging (gloc_scan_store_build_normals)
+  gloc::DevBuf nrm_tmp;                 // normals in original order, between the normal kernel / a download and the sorted copy
   std::atomic<int> attached{0};  // registration handles using this store
   ~gloc_scan_store() {
-    for (auto& s : scans)
+    for (auto& s : scans) {
       if (s.block) (void)hipFree(s.block);
+      if (s.nrm) (void)hipFree(s.nrm);
+    }
     for (auto& kv : free_blocks) (void)hipFree(kv.second);
   }
 };
@@ -84,6 +95,10 @@ int store_get(gloc_scan_store* st, uint32_t id, int cs, DevScan* out);
 // pins nothing.  ids may repeat (pins are counted).  gloc_scan_store_build_target_index refuses a pinned scan that still
 // needs the re-sort, gloc_scan_store_release refuses any pinned scan.
 int store_get_pinned(gloc_scan_store* st, const uint32_t* ids, const int* cs, size_t count, DevScan* out);
+// Give a scan its normals from k neighbours (no-op when it has them with this k).  Caller holds store->mu; returns after
+// the work has completed.  Adds an allocation and moves nothing: safe on a pinned scan, except that normals a batch may
+// be reading are not rebuilt with another k (GLOC_ERR_STATE).
+int store_build_normals(gloc_scan_store* st, DevScan& s, uint32_t k);
 // The pins' release (delta = -1) once the batch's event has been waited for.  Ids no longer live are skipped.
 void store_pin(gloc_scan_store* st, const uint32_t* ids, size_t count, int delta);
 

@@ -323,6 +323,19 @@ int gloc_scan_store_points(gloc_scan_store* st, uint32_t scan_id, size_t* n_poin
 /* The scan's points, original order, packed xyz (tests). */
 int gloc_scan_store_download(gloc_scan_store* st, uint32_t scan_id, float* out_xyz,
                              size_t capacity_points);
+/* Per-point unit normals of a resident scan, for the point-to-plane refinement (gloc_reg_p2l_batch_ids).  Exactly
+ * gloc_ground_normals applied to the whole scan, with no range filter: the k nearest neighbours within the scan, self
+ * included, in ascending (d2, index) order; fp64 mean and covariance accumulated in that order; the eigenvector of the
+ * smallest eigenvalue (cyclic Jacobi, ties keep the lower column); flipped towards the origin; stored as fp32.  A point
+ * with fewer than 3 usable neighbours or non-finite coordinates gets the ZERO normal, which means "no normal".
+ * k in [3, 16]; 10 is the reference's (registration/ground_estimator.cpp:79).  An optional second allocation of the
+ * scan, 12 B per point, kept in the order the 1-NN search reports its matches in; built at most once per (scan, k)
+ * (the same k again is a no-op), freed by release / clear, counted by gloc_scan_store_bytes, carried along by
+ * gloc_scan_store_build_target_index.  Safe on a scan that batches in flight have pinned -- it adds data and moves
+ * nothing -- except that EXISTING normals of a pinned scan are not rebuilt with another k (GLOC_ERR_STATE). */
+int gloc_scan_store_build_normals(gloc_scan_store* st, uint32_t scan_id, uint32_t k /* 3..16 */);
+/* The scan's normals, original order, packed xyz, as gloc_scan_store_download (GLOC_ERR_STATE: none built). */
+int gloc_scan_store_normals(gloc_scan_store* st, uint32_t scan_id, float* out_nxyz, size_t capacity_points);
 
 /* Use `store` for every scan id of this handle (NULL: back to the handle's private store, which
  * gloc_reg_scan_upload creates on first use). */
@@ -456,6 +469,48 @@ int gloc_reg_ndt_cells(gloc_reg* h, uint32_t scan_id, const gloc_ndt_params* prm
  * cell is flushed first) of scan base_id at `leaf` -- the NDT source filter on its own, e.g. to thin a source before ICP.
  * Rows come out in (slot, first point) order. */
 int gloc_scan_store_add_approx_voxel(gloc_scan_store* st, uint32_t base_id, float leaf, uint32_t* new_id);
+
+/* ---- point-to-plane ICP refinement -------------------------------------------------------------------- *
+ * The linearised point-to-plane step (Chen & Medioni; pcl::IterativeClosestPointWithNormals, Open3D's
+ * TransformationEstimationPointToPlane) behind the exact 1-NN search of the ICP above, on the TARGET's normals
+ * (gloc_scan_store_build_normals).  Lidar scans are mostly ground and walls: point-to-point pairs resist sliding along
+ * those surfaces, point-to-plane pairs do not, so it needs fewer passes.  An alternative a caller chooses; the default
+ * pipeline is unchanged.  The executable contract is the float64 restatement tests/p2l_ref.py.
+ *
+ * One pass at pose T = (R, t), source -> target:
+ *   1. every source point s: p = R s + t in fp32 (the pose rounded to fp32, the ICP's operation order);
+ *   2. j = the exact 1-NN of p in the target (the ICP's search: same bits, same tie rule);
+ *   3. the pair is used iff d2 is finite, max_corr_dist <= 0 or d2 <= max_corr_dist^2, and the normal n_j is not zero;
+ *   4. in fp64, r = n_j . (p - q_j), J = [p x n_j ; n_j]:  H += J J^T, g += J r, sum r^2, the count;
+ *   5. fewer than 6 pairs, or a pivot of the fp64 Cholesky factorisation of H <= 1e-12 x the largest diagonal entry of H:
+ *      status 2, the pose stays, the job stops;
+ *   6. H xi = -g, xi = (w, v);  7. T <- (Rodrigues(w), v) . T, held in fp64;
+ *   8. both eps > 0 and |v| < trans_eps and |w| < rot_eps: status 1, the job stops (the updating pass is counted);
+ *   9. a job that has stopped is frozen: later passes of the batch leave its pose alone. */
+typedef struct gloc_p2l_params {
+  uint32_t max_iters;  /* 30, as the reference's ICP (registration/global_registration.cpp:242) */
+  float max_corr_dist; /* <= 0: no rejection, as gloc_reg_params */
+  float trans_eps;     /* stop when |v| < trans_eps AND |w| < rot_eps; both <= 0 (default): run max_iters passes */
+  float rot_eps;
+  uint32_t normal_k;   /* 10: targets without normals get them built with this k (existing normals are used as they are) */
+  uint32_t reserved_;
+} gloc_p2l_params;
+
+void gloc_p2l_default_params(gloc_p2l_params* p);
+
+/* Refine n candidates: the source scan against each target scan (ids of the handle's store) from init_T (n x 16
+ * row-major floats, source -> target; NULL = identity).  Outputs per candidate (any may be NULL except out_T): the pose,
+ * the RMS point-to-plane residual of ONE more evaluation at the final pose, the number of updates applied, and the
+ * status: 0 the iteration cap stopped it, 1 converged, 2 degenerate (the pose is the last one before the degenerate
+ * pass: the guess, if it was the first).  Every candidate's result is independent of the batch it is in, bit for bit.
+ * GLOC_ERR_INVALID: null arguments, an unknown id, an empty source, max_iters = 0, normal_k outside [3, 16];
+ * GLOC_ERR_STATE: a batch in flight on the handle. */
+int gloc_reg_p2l_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                           const gloc_p2l_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status);
+/* Steps 1 - 4 once at T16 (NULL = identity): H (6 x 6 row-major), g, sum r^2 and the number of pairs used (tests, and
+ * callers that drive the loop themselves). */
+int gloc_reg_p2l_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_p2l_params* prm,
+                        double* out_H36, double* out_g6, double* out_sum_r2, uint64_t* out_count);
 
 /* ============================ NetVLAD-FC pooling head ("next" row N2) ===================== *
  * Replaces NetVLAD.forward of the reference (model/netvlad_fc.py:73-109, built without gating at

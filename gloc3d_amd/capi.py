@@ -60,6 +60,11 @@ class P2lParams(C.Structure):
                 ("normal_k", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class GicpParams(C.Structure):
+    _fields_ = [("max_iters", C.c_uint32), ("max_corr_dist", C.c_float), ("trans_eps", C.c_float), ("rot_eps", C.c_float),
+                ("normal_k", C.c_uint32), ("plane_eps", C.c_float)]
+
+
 class BevParams(C.Structure):
     _fields_ = [("resolution", C.c_float), ("max_range", C.c_float), ("out_width", C.c_uint32),
                 ("out_height", C.c_uint32), ("format", C.c_uint32), ("pad_bgr", C.c_uint8 * 3),
@@ -203,6 +208,10 @@ _PROTOS = [
     ("gloc_reg_p2l_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(P2lParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_p2l_system", _i, [_vp, _u32, _u32, _vp, C.POINTER(P2lParams), _vp, _vp, C.POINTER(C.c_double),
                              C.POINTER(C.c_uint64)]),
+    ("gloc_gicp_default_params", None, [C.POINTER(GicpParams)]),
+    ("gloc_reg_gicp_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(GicpParams), _vp, _vp, _vp, _vp]),
+    ("gloc_reg_gicp_system", _i, [_vp, _u32, _u32, _vp, C.POINTER(GicpParams), _vp, _vp, C.POINTER(C.c_double),
+                              C.POINTER(C.c_uint64)]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
@@ -548,6 +557,16 @@ def default_p2l_params(**over):
     return p
 
 
+def default_gicp_params(**over):
+    """gloc_gicp_params as gloc_gicp_default_params leaves them (30 passes, no rejection, no early stop, k = 10,
+    plane_eps = 1e-3), then `over`."""
+    p = GicpParams()
+    lib().gloc_gicp_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
 class ScanStore(_Handle):
     """Resident scans + their search index, shared by any number of Registrars."""
 
@@ -838,6 +857,29 @@ class Registrar(_Handle):
         H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
         check(lib().gloc_reg_p2l_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
                                         _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
+        return H, g, s.value, c.value
+
+    def gicp_batch(self, src_id, tgt_ids, init_T=None, params=None):
+        """Generalized ICP of scan src_id against each of tgt_ids (gloc_reg_gicp_batch_ids): returns T [n, 4, 4] float32,
+        rmse [n] float32 (sqrt of the mean e^T M e at the final pose), iterations [n], status [n] (0 cap, 1 converged,
+        2 degenerate)."""
+        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
+        n = ids.shape[0]
+        prm = params or default_gicp_params()
+        it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
+        T = np.empty((n, 4, 4), np.float32)
+        rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        check(lib().gloc_reg_gicp_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
+                                            C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
+        return T, rmse, iters, status
+
+    def gicp_system(self, src_id, tgt_id, T=None, params=None):
+        """One evaluation of the generalized ICP normal equations at T: H [6, 6], g [6], sum e^T M e, pairs used."""
+        prm = params or default_gicp_params()
+        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
+        H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
+        check(lib().gloc_reg_gicp_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
+                                         _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
         return H, g, s.value, c.value
 
     def ndt_derivatives(self, src_id, tgt_id, p6, params=None):

@@ -1,0 +1,143 @@
+// gn6.hpp -- the host side the Gauss-Newton refinements share (p2l.hip, gicp.hip): the handle's workspace and the loop of
+// passes.  A pass is three enqueues: the registration's exact 1-NN search, the refinement's own accumulate kernel, the
+// solve kernel of gn6_kernels.hpp.
+//
+// Synchronisation between passes: none.  Whether a job has stopped is a flag on the device that the accumulate and solve
+// kernels of later passes read.  With both eps off a job can only stop early by being degenerate, so all max_iters passes
+// go in back to back; with eps set the host looks at the count of stopped jobs every LOOK_EVERY passes -- one 4-byte copy
+// and an event -- to cut the tail once every job has stopped.
+#pragma once
+#include <algorithm>
+#include <vector>
+
+#include "gn6_kernels.hpp"
+#include "p2l.hpp"
+
+namespace gloc {
+namespace p2l {
+
+struct Ws {  // (one per handle, whichever refinement runs: the calls are synchronous)
+  DevBuf tgts, states, partials, done, exp;
+  uint32_t* h_done = nullptr;  // pinned
+  hipEvent_t ev = nullptr;
+  ~Ws() {
+    if (h_done) (void)hipHostFree(h_done);
+    if (ev) (void)hipEventDestroy(ev);
+  }
+};
+
+}  // namespace p2l
+
+namespace gn6 {
+
+constexpr uint32_t LOOK_EVERY = 4;
+
+struct Loop {  // what the refinements' parameter blocks have in common
+  uint32_t max_iters;
+  float max_corr_dist, trans_eps, rot_eps;
+  const char *accum_name, *solve_name;  // in the handle's profile
+};
+
+// Refines every job from init_T ([n][16] or null: identity); any of the last four non-null: ONE evaluation at init_T of
+// job 0 instead.  `tgts`: the jobs' targets as the accumulate kernel takes them, copied to the device; accum(targets on
+// the device, states, gate^2, skip_stopped, partials, n_blk) enqueues that kernel.  Returns after the results have been
+// copied out.
+template <class Target, class Accum>
+int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, const float* init_T, Accum&& accum, float* out_T,
+        float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count) {
+  if (!*x.ws) {
+    *x.ws = new (std::nothrow) p2l::Ws;
+    GLOC_REQUIRE(*x.ws, GLOC_ERR_NOMEM, "host allocation failed");
+  }
+  p2l::Ws& w = **x.ws;
+  const hipStream_t q = x.stream;
+  const uint32_t n = x.n_jobs;
+  const bool system = out_H36 || out_g6 || out_sum || out_count;
+  const uint32_t n_blk = std::max<uint32_t>(1, (x.n_src + ACC_THREADS - 1) / ACC_THREADS);
+  std::vector<State> hs(n);
+  static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  for (uint32_t c = 0; c < n; ++c) {
+    State& s = hs[c];
+    memset(&s, 0, sizeof(s));
+    const float* T = init_T ? init_T + 16 * (size_t)c : I16;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) s.Td[3 * i + j] = (double)T[4 * i + j];
+      s.Td[9 + i] = (double)T[4 * i + 3];
+    }
+  }
+  GLOC_TRY(w.tgts.ensure(sizeof(Target) * n, q));
+  GLOC_TRY(w.states.ensure(sizeof(State) * n, q));
+  GLOC_TRY(w.partials.ensure(sizeof(double) * NSLOT * (size_t)n_blk * n, q));
+  GLOC_TRY(w.done.ensure(16, q));
+  GLOC_TRY(w.exp.ensure(sizeof(double) * NSUM * n, q));
+  if (!w.h_done) GLOC_HIP(hipHostMalloc(reinterpret_cast<void**>(&w.h_done), 16, hipHostMallocDefault));
+  if (!w.ev) GLOC_HIP(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+  GLOC_HIP(hipMemcpyAsync(w.tgts.p, tgts.data(), sizeof(Target) * n, hipMemcpyHostToDevice, q));
+  GLOC_HIP(hipMemcpyAsync(w.states.p, hs.data(), sizeof(State) * n, hipMemcpyHostToDevice, q));
+  GLOC_HIP(hipMemsetAsync(w.done.p, 0, 16, q));
+  GLOC_HIP(hipStreamSynchronize(q));  // (tgts and hs are host vectors)
+  const float gate2 = lp.max_corr_dist > 0.f ? lp.max_corr_dist * lp.max_corr_dist : 0.f;
+  bool warm = false;
+  // search, accumulate, solve at the current poses; mode 1: evaluation only
+  auto pass = [&](int mode, double* exp) -> int {
+    GLOC_TRY(x.nn_pass(x.self, warm));
+    warm = true;
+    {
+      ProfScope ps(*x.prof, lp.accum_name, q);
+      accum(w.tgts.template as<Target>(), w.states.template as<State>(), gate2, mode == 0, w.partials.template as<double>(), n_blk);
+    }
+    {
+      ProfScope ps(*x.prof, lp.solve_name, q);
+      hipLaunchKernelGGL(solve_kernel, dim3(n), dim3(64), 0, q, w.partials.template as<double>(), n_blk, w.states.template as<State>(),
+                         x.pose_f32, x.pose_stride, (double)lp.trans_eps, (double)lp.rot_eps, mode, w.done.template as<uint32_t>(), exp);
+    }
+    GLOC_HIP(hipGetLastError());
+    return GLOC_OK;
+  };
+  if (system) {
+    GLOC_TRY(pass(1, w.exp.template as<double>()));
+    double s[NSUM];
+    GLOC_HIP(hipMemcpyAsync(s, w.exp.p, sizeof(double) * NSUM, hipMemcpyDeviceToHost, q));
+    GLOC_HIP(hipStreamSynchronize(q));
+    if (out_H36) {
+      int e = 0;
+      for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b, ++e) out_H36[6 * a + b] = out_H36[6 * b + a] = s[e];
+    }
+    if (out_g6) std::copy(s + 21, s + 27, out_g6);
+    if (out_sum) *out_sum = s[27];
+    if (out_count) *out_count = (uint64_t)s[28];
+    return GLOC_OK;
+  }
+  const bool can_converge = lp.trans_eps > 0.f && lp.rot_eps > 0.f;
+  for (uint32_t it = 0; it < lp.max_iters; ++it) {
+    GLOC_TRY(pass(0, nullptr));
+    if (can_converge && (it + 1) % LOOK_EVERY == 0 && it + 1 < lp.max_iters) {
+      GLOC_HIP(hipMemcpyAsync(w.h_done, w.done.p, 4, hipMemcpyDeviceToHost, q));
+      GLOC_HIP(hipEventRecord(w.ev, q));
+      GLOC_HIP(hipEventSynchronize(w.ev));
+      if (*w.h_done >= n) break;
+    }
+  }
+  GLOC_TRY(pass(1, nullptr));  // the residual at the final pose
+  GLOC_HIP(hipMemcpyAsync(hs.data(), w.states.p, sizeof(State) * n, hipMemcpyDeviceToHost, q));
+  GLOC_HIP(hipStreamSynchronize(q));
+  for (uint32_t c = 0; c < n; ++c) {
+    const State& s = hs[c];
+    if (out_T) {
+      float* T = out_T + 16 * (size_t)c;
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) T[4 * i + j] = (float)s.Td[3 * i + j];
+        T[4 * i + 3] = (float)s.Td[9 + i];
+      }
+      T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
+    }
+    if (out_rmse) out_rmse[c] = (float)s.rmse;
+    if (out_iters) out_iters[c] = s.iters;
+    if (out_status) out_status[c] = s.status;
+  }
+  return GLOC_OK;
+}
+
+}  // namespace gn6
+}  // namespace gloc

@@ -6,7 +6,7 @@
 namespace gloc {
 namespace p2l {
 
-struct Ws;  // a handle's point-to-plane workspace (created on first use)
+struct Ws;  // a handle's workspace for point-to-plane and generalized ICP (gn6.hpp; created on first use)
 void ws_free(Ws* w);
 
 struct TargetView {  // a job's target as the search indexes it

@@ -11,6 +11,7 @@
 
 #include "ndt.hpp"
 #include "nn_compact.hpp"
+#include "gicp.hpp"
 #include "p2l.hpp"
 #include "reg_kernels.hpp"
 #include "scan_store.hpp"
@@ -85,7 +86,7 @@ struct gloc_reg : Handle {
   size_t last_ld = 0;      // shape of the last batch (gloc_reg_debug_corr)
   uint32_t last_jobs = 0;
   gloc::ndt::Ws* ndt = nullptr;  // NDT workspace (ndt.hip), made on first use
-  gloc::p2l::Ws* p2l = nullptr;  // point-to-plane workspace (p2l.hip), made on first use
+  gloc::p2l::Ws* p2l = nullptr;  // point-to-plane / generalized ICP workspace (gn6.hpp), made on first use
   ~gloc_reg() {  // (the handle's work has been waited for: destroy_handle)
     if (pending.active && pending.store) store_pin(pending.store, pending.pinned.data(), pending.pinned.size(), -1);
     if (store) store->attached--;
@@ -711,9 +712,12 @@ struct TempScans {
   }
 };
 
-// Point-to-plane refinement of one source against n targets (p2l.hip): the batch is set up as enqueue_jobs sets one up --
-// job table, fp32 poses in the CandState array the search reads, corr / d2 -- without a split plan (it is solve_kernel
-// that makes one), and p2l::run drives the passes through launch_nn.  Synchronous: the scans are pinned for the call.
+// Point-to-plane or generalized ICP refinement of one source against n targets (p2l.hip, gicp.hip): the batch is set up as
+// enqueue_jobs sets one up -- job table, fp32 poses in the CandState array the search reads, corr / d2 -- without a split
+// plan (it is solve_kernel that makes one), and `refine` (p2l::run or gicp::run behind their arguments) drives the passes
+// through launch_nn.  Synchronous: the scans are pinned for the call.  Targets without normals get them with normal_k, and
+// with src_normals so does the source; `refine` is handed the source's (null without src_normals): DevScan::nrm is in the
+// order of idx.pts whatever that order is (curve or kd: scan_store.hpp), the order of the slots corr is indexed by.
 struct P2lPass {
   gloc_reg* h;
   BatchDims bd;
@@ -724,10 +728,9 @@ struct P2lPass {
   }
 };
 
-int run_p2l(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_p2l_params* prm,
-            float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6,
-            double* out_sum_r2, uint64_t* out_count) {
-  GLOC_TRY(gloc::p2l::check_params(prm));
+template <class Refine>
+int run_refine(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, uint32_t normal_k,
+               bool src_normals, Refine&& refine) {
   GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
   GLOC_REQUIRE(h->store, GLOC_ERR_INVALID, "unknown scan id %u", src_id);
   gloc_scan_store* st = h->store;
@@ -743,7 +746,12 @@ int run_p2l(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, con
     for (size_t c = 0; c < n; ++c) {
       GLOC_REQUIRE(tgt_ids[c] < st->scans.size() && st->scans[tgt_ids[c]].live, GLOC_ERR_INVALID, "unknown scan id %u", tgt_ids[c]);
       DevScan& t = st->scans[tgt_ids[c]];
-      if (t.nrm_k == 0) GLOC_TRY(store_build_normals(st, t, prm->normal_k));
+      if (t.nrm_k == 0) GLOC_TRY(store_build_normals(st, t, normal_k));
+    }
+    if (src_normals) {
+      GLOC_REQUIRE(src_id < st->scans.size() && st->scans[src_id].live, GLOC_ERR_INVALID, "unknown scan id %u", src_id);
+      DevScan& sc = st->scans[src_id];
+      if (sc.nrm_k == 0) GLOC_TRY(store_build_normals(st, sc, normal_k));
     }
   }
   std::vector<DevScan> scans(1 + n);
@@ -759,6 +767,7 @@ int run_p2l(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, con
   } unpin{st, ids, s};
   const DevScan& src = scans[0];
   GLOC_REQUIRE(src.n >= 1 && src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
+  GLOC_REQUIRE(!src_normals || src.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", src_id);
   const uint32_t n_jobs = (uint32_t)n;
   const uint32_t ng = (uint32_t)((src.n + 64 * cs - 1) / (64 * cs));
   BatchDims bd{n_jobs, (uint32_t)src.n, ng, 0, 0};
@@ -814,7 +823,27 @@ int run_p2l(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, con
   x.ld = bd.ld;
   x.nn_pass = &P2lPass::run;
   x.self = &pass;
-  return gloc::p2l::run(x, tv.data(), init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum_r2, out_count);
+  return refine(x, src_normals ? src.nrm : nullptr, tv.data());
+}
+
+int run_p2l(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_p2l_params* prm,
+            float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6,
+            double* out_sum_r2, uint64_t* out_count) {
+  GLOC_TRY(gloc::p2l::check_params(prm));
+  return run_refine(h, src_id, tgt_ids, n, init_T, prm->normal_k, false,
+                    [&](const gloc::p2l::Ctx& x, const float*, const gloc::p2l::TargetView* tv) {
+                      return gloc::p2l::run(x, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum_r2, out_count);
+                    });
+}
+
+int run_gicp(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_gicp_params* prm,
+             float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum,
+             uint64_t* out_count) {
+  return run_refine(h, src_id, tgt_ids, n, init_T, prm->normal_k, true,
+                    [&](const gloc::p2l::Ctx& x, const float* src_nrm, const gloc::p2l::TargetView* tv) {
+                      return gloc::gicp::run(x, src_nrm, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum,
+                                             out_count);
+                    });
 }
 
 }  // namespace
@@ -1439,6 +1468,26 @@ int gloc_reg_p2l_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id,
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
   return run_p2l(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum_r2, out_count);
+}
+
+// (the parameters are looked at before the handle: a bad block is refused whatever it is handed with)
+int gloc_reg_gicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                            const gloc_gicp_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status) {
+  GLOC_TRY(gloc::gicp::check_params(prm));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_gicp(h, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+                  nullptr);
+}
+
+int gloc_reg_gicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_gicp_params* prm,
+                         double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count) {
+  GLOC_TRY(gloc::gicp::check_params(prm));
+  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_gicp(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum, out_count);
 }
 
 int gloc_reg_profile(gloc_reg* h, const char* kernel, double* total_ms, uint64_t* launches) {

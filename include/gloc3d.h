@@ -512,6 +512,59 @@ int gloc_reg_p2l_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tg
 int gloc_reg_p2l_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_p2l_params* prm,
                         double* out_H36, double* out_g6, double* out_sum_r2, uint64_t* out_count);
 
+/* ---- generalized (plane-to-plane) ICP refinement ------------------------------------------------------ *
+ * Generalized ICP (Segal, Haehnel & Thrun; pcl::GeneralizedIterativeClosestPoint, fast_gicp) behind the same exact 1-NN
+ * search, on BOTH scans' normals.  Every pair is weighted by a full 3 x 3 information matrix built from the two local
+ * surface models: it slides along ground and walls as point-to-plane does, down-weights pairs whose two surfaces
+ * disagree, and is point-to-point where a side has no normal.  The covariances are PCL's plane-to-plane regularisation --
+ * the eigenvalues of a neighbourhood's covariance replaced by (1, 1, plane_eps) -- which makes a point's covariance a
+ * function of its normal alone, C = I - (1 - plane_eps) n n^T, so the scans' normals (gloc_scan_store_build_normals) are
+ * all it stores.  An alternative a caller chooses; the default pipeline is unchanged.  The executable contract is the
+ * float64 restatement tests/gicp_ref.py.
+ *
+ * M is frozen at each pass's linearisation point: this is the Gauss-Newton step as fast_gicp takes it, NOT PCL's BFGS
+ * inner loop, and parity with PCL is unpinned.  PCL's neighbourhood size is 20; the store's k-NN stops at 16.
+ *
+ * One pass at pose T = (R, t), source -> target, with a = 1 - plane_eps:
+ *   1. every source point s: p = R s + t in fp32 (the pose rounded to fp32, the ICP's operation order);
+ *   2. j = the exact 1-NN of p in the target (the ICP's search: same bits, same tie rule);
+ *   3. the pair is used iff d2 is finite, p is finite, and max_corr_dist <= 0 or d2 <= max_corr_dist^2;
+ *   4. C_A = I - a n_s n_s^T from the source point's normal, C_B = I - a n_j n_j^T from the match's; a zero normal means
+ *      "no normal" and gives C = I: the pair stays and is isotropic on that side.  From here on in fp64;
+ *   5. m = R n_s (R the fp32 pose widened), S = C_B + R C_A R^T = 2I - a (n_j n_j^T + m m^T), M = S^-1 (S is symmetric
+ *      with eigenvalues >= 2 plane_eps);
+ *   6. e = p - q_j, and for T <- exp(xi) T, xi = (w, v), J = [-[p]x , I]:  H += J^T M J, g += J^T M e, sum e^T M e, the
+ *      count;
+ *   7. fewer than 6 pairs, or a pivot of the fp64 Cholesky factorisation of H <= 1e-12 x the largest diagonal entry of H:
+ *      status 2, the pose stays, the job stops;
+ *   8. H xi = -g;  T <- (Rodrigues(w), v) . T, held in fp64;
+ *   9. both eps > 0 and |v| < trans_eps and |w| < rot_eps: status 1, the job stops (the updating pass is counted);
+ *  10. a job that has stopped is frozen: later passes of the batch leave its pose alone. */
+typedef struct gloc_gicp_params {
+  uint32_t max_iters;  /* 30, as the reference's ICP (registration/global_registration.cpp:242) */
+  float max_corr_dist; /* <= 0: no rejection, as gloc_reg_params */
+  float trans_eps;     /* stop when |v| < trans_eps AND |w| < rot_eps; both <= 0 (default): run max_iters passes */
+  float rot_eps;
+  uint32_t normal_k;   /* 10: scans without normals, the source included, get them built with this k (existing normals
+                          are used as they are) */
+  float plane_eps;     /* 1e-3: pcl::GeneralizedIterativeClosestPoint's gicp_epsilon_ [upstream default]; must be in
+                          (0, 1]; 1 makes every pair point-to-point.  The normals are unit to fp32 rounding only: below
+                          about 1e-6 S is no longer safely positive definite */
+} gloc_gicp_params;    /* 24 bytes */
+
+void gloc_gicp_default_params(gloc_gicp_params* p);
+
+/* Refine n candidates as gloc_reg_p2l_batch_ids does: the same arguments and outputs, the rmse being
+ * sqrt(sum e^T M e / count) of ONE more evaluation at the final pose.  Every candidate's result is independent of the
+ * batch it is in, bit for bit.  Normals missing on the source or on a target are built first, under the rule of
+ * gloc_scan_store_build_normals.  GLOC_ERR_INVALID: null arguments, an unknown id, an empty source, max_iters = 0,
+ * normal_k outside [3, 16], plane_eps outside (0, 1]; GLOC_ERR_STATE: a batch in flight on the handle. */
+int gloc_reg_gicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                            const gloc_gicp_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status);
+/* Steps 1 - 6 once at T16 (NULL = identity): H (6 x 6 row-major), g, sum e^T M e and the number of pairs used. */
+int gloc_reg_gicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_gicp_params* prm,
+                         double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count);
+
 /* ============================ NetVLAD-FC pooling head ("next" row N2) ===================== *
  * Replaces NetVLAD.forward of the reference (model/netvlad_fc.py:73-109, built without gating at
  * main.py:594) -- the tail of the TorchScript module RpyPCLoopDetector::get_place_feature runs

@@ -9,6 +9,9 @@ One pass at pose T = (R, t), source -> target (include/gloc3d.h), a = 1 - plane_
   J = [-[p]x , I] for T <- exp(xi) T, xi = (w, v); H = sum J^T M J, g = sum J^T M e, sum e^T M e; fewer than 6 pairs or a
   Cholesky pivot <= 1e-12 max diag(H): degenerate (status 2); H xi = -g; T <- (Rodrigues(w), v) T.
 
+A zero normal on either side is KEPT (that side's covariance is I) and the pair counted; a non-finite source point is in
+no pair; an empty target gives no pairs.
+
 M is frozen at the linearisation point of each pass: Gauss-Newton as in fast_gicp, not PCL's BFGS inner loop.
 
 `exact=True` keeps p and R in float64.  `how` picks the inverse ("inv": numpy.linalg.inv, "adj": the symmetric adjugate)
@@ -17,7 +20,7 @@ further from) -- two evaluations of the same formulas whose difference is the re
 """
 import numpy as np
 
-from p2l_ref import cholesky_solve, move, p2p_align, pose_err, rodrigues  # noqa: F401  (re-exported: the tests' R.*)
+from p2l_ref import EVENTS, _sum, cholesky_solve, gauss_newton, move, p2p_align, pose_err, rodrigues  # noqa: F401  (re-exported: the tests' R.*)
 
 
 def rotation(T, exact=False):
@@ -29,6 +32,8 @@ def rotation(T, exact=False):
 def pairs(src, src_nrm, tgt, tgt_nrm, T, nn, max_corr_dist=0.0, exact=False):
     """(p, q, n_s, n_j) of the pairs one pass uses, float64 [m, 3] each.  A normals argument of None: no normals."""
     p = move(T, src, exact)
+    if len(tgt) == 0:
+        return np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3))
     idx, d2 = nn(p.astype(np.float32), np.asarray(tgt, np.float32))
     idx = idx.astype(np.int64)
     ok = np.isfinite(d2) & np.isfinite(p).all(1) & (idx < len(tgt))
@@ -75,14 +80,6 @@ def jacobian(p):
     return J
 
 
-def _sum(c, order):
-    if len(c) == 0:
-        return np.zeros(c.shape[1:])
-    if order == "reversed":
-        c = c[::-1]
-    return np.cumsum(c, axis=0)[-1]
-
-
 def system_of_pairs(p, q, ns, nt, R, plane_eps=1e-3, how="inv", order="forward"):
     """H [6, 6], g [6], sum e^T M e, pairs used -- of pairs already chosen."""
     M = information(ns, nt, R, plane_eps, how)
@@ -102,27 +99,9 @@ def system(src, src_nrm, tgt, tgt_nrm, T, nn, max_corr_dist=0.0, plane_eps=1e-3,
 
 
 def align(src, src_nrm, tgt, tgt_nrm, nn, init_T=None, max_iters=30, max_corr_dist=0.0, trans_eps=0.0, rot_eps=0.0,
-          plane_eps=1e-3, exact=False, how="inv", order="forward"):
-    """The whole refinement: dict(T float64 [4, 4], iters, status 0 cap / 1 converged / 2 degenerate, rmse, trace)."""
-    T = np.eye(4) if init_T is None else np.asarray(init_T, np.float64).copy()
-    if not exact:
-        T = np.asarray(init_T if init_T is not None else np.eye(4), np.float32).astype(np.float64)
+          plane_eps=1e-3, exact=False, how="inv", order="forward", events=None):
+    """The whole refinement: dict(T float64 [4, 4], iters, status 0 cap / 1 converged / 2 degenerate, rmse, trace, steps);
+    `events` as p2l_ref.align."""
     kw = dict(max_corr_dist=max_corr_dist, plane_eps=plane_eps, exact=exact, how=how, order=order)
-    iters, status, trace = 0, 0, [T.copy()]
-    for _ in range(int(max_iters)):
-        H, g, _, cnt = system(src, src_nrm, tgt, tgt_nrm, T, nn, **kw)
-        xi = cholesky_solve(H, g) if cnt >= 6 else None
-        if xi is None:
-            status = 2
-            break
-        Tk = np.eye(4)
-        Tk[:3, :3] = rodrigues(xi[:3])
-        Tk[:3, 3] = xi[3:]
-        T = Tk @ T
-        iters += 1
-        trace.append(T.copy())
-        if trans_eps > 0 and rot_eps > 0 and np.linalg.norm(xi[3:]) < trans_eps and np.linalg.norm(xi[:3]) < rot_eps:
-            status = 1
-            break
-    _, _, s, cnt = system(src, src_nrm, tgt, tgt_nrm, T, nn, **kw)
-    return dict(T=T, iters=iters, status=status, rmse=np.sqrt(s / cnt) if cnt else 0.0, trace=trace)
+    return gauss_newton(lambda T: system(src, src_nrm, tgt, tgt_nrm, T, nn, **kw), init_T, max_iters, trans_eps, rot_eps,
+                        exact, events)

@@ -8,10 +8,18 @@ One pass at pose T = (R, t), source -> target (include/gloc3d.h):
   r = n_j . (p - q_j), J = [p x n_j ; n_j] in fp64; H = sum J J^T, g = sum J r; fewer than 6 pairs or a Cholesky pivot
   <= 1e-12 max diag(H): degenerate (status 2); H xi = -g, xi = (w, v); T <- (Rodrigues(w), v) T.
 
+A non-finite source point is in no pair (its p is not finite), and neither is a pair whose target normal is zero -- which
+is what a non-finite or isolated target point has (oracle/ground_oracle.c: normal_of); an empty target gives no pairs.
+
 `exact=True` keeps p in float64 (no fp32 rounding anywhere but inside the search): the form the CPU tests use to state
-properties of the formulas to 1e-9.
+properties of the formulas to 1e-9.  `order` is the order the pairs are summed in ("forward", "reversed": one after the
+other, which no reduction tree is further from) -- two evaluations of the same formulas whose difference is the
+restatement's own noise floor.  `events`, a list, gets the branches of the loop a run takes (EVENTS).
 """
 import numpy as np
+
+# What align() records in `events`: how the run ended, and the two branches of an update that the end pose does not show.
+EVENTS = ("converged", "capped", "degenerate_at_0", "degenerate_later", "zero_angle", "angle_above_0.3")
 
 
 def move(T, src, exact=False):
@@ -31,6 +39,8 @@ def move(T, src, exact=False):
 def pairs(src, tgt, nrm, T, nn, max_corr_dist=0.0, exact=False):
     """(p, q, n) of the pairs one pass uses, float64 [m, 3] each."""
     p = move(T, src, exact)
+    if len(tgt) == 0:
+        return np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3))
     idx, d2 = nn(p.astype(np.float32), np.asarray(tgt, np.float32))
     idx = idx.astype(np.int64)
     ok = np.isfinite(d2) & np.isfinite(p).all(1) & (idx < len(tgt))
@@ -49,11 +59,23 @@ def jacobian(p, q, n):
     return r, np.concatenate([np.cross(p, n), n], axis=1)
 
 
-def system(src, tgt, nrm, T, nn, max_corr_dist=0.0, exact=False):
-    """H [6, 6], g [6], sum r^2, pairs used."""
-    p, q, n = pairs(src, tgt, nrm, T, nn, max_corr_dist, exact)
+def _sum(c, order):
+    if len(c) == 0:
+        return np.zeros(c.shape[1:])
+    if order == "reversed":
+        c = c[::-1]
+    return np.cumsum(c, axis=0)[-1]
+
+
+def system_of_pairs(p, q, n, order="forward"):
+    """H [6, 6], g [6], sum r^2, pairs used -- of pairs already chosen, summed one after the other in `order`."""
     r, J = jacobian(p, q, n)
-    return J.T @ J, J.T @ r, float(r @ r), len(r)
+    return _sum(J[:, :, None] * J[:, None, :], order), _sum(J * r[:, None], order), float(_sum(r * r, order)), len(r)
+
+
+def system(src, tgt, nrm, T, nn, max_corr_dist=0.0, exact=False, order="forward"):
+    """H [6, 6], g [6], sum r^2, pairs used."""
+    return system_of_pairs(*pairs(src, tgt, nrm, T, nn, max_corr_dist, exact), order=order)
 
 
 def cholesky_solve(H, g):
@@ -87,29 +109,46 @@ def rodrigues(w):
     return np.eye(3) + A * K + B * (K @ K)
 
 
-def align(src, tgt, nrm, nn, init_T=None, max_iters=30, max_corr_dist=0.0, trans_eps=0.0, rot_eps=0.0, exact=False):
-    """The whole refinement: dict(T float64 [4, 4], iters, status 0 cap / 1 converged / 2 degenerate, rmse, trace)."""
+def gauss_newton(system_at, init_T, max_iters, trans_eps, rot_eps, exact, events=None):
+    """The loop of passes both refinements share: system_at(T) -> H, g, squared residual, pairs.  A job converges only
+    with BOTH eps set; with one of them 0 it runs to the cap."""
     T = np.eye(4) if init_T is None else np.asarray(init_T, np.float64).copy()
     if not exact:
         T = np.asarray(init_T if init_T is not None else np.eye(4), np.float32).astype(np.float64)
-    iters, status, trace = 0, 0, [T.copy()]
+    ev = events if events is not None else []
+    iters, status, trace, steps = 0, 0, [T.copy()], []
     for _ in range(int(max_iters)):
-        H, g, _, cnt = system(src, tgt, nrm, T, nn, max_corr_dist, exact)
+        H, g, _, cnt = system_at(T)
         xi = cholesky_solve(H, g) if cnt >= 6 else None
         if xi is None:
             status = 2
             break
+        th, vn = float(np.sqrt(xi[:3] @ xi[:3])), float(np.linalg.norm(xi[3:]))
+        if th == 0.0 and "zero_angle" not in ev:
+            ev.append("zero_angle")
+        if th > 0.3 and "angle_above_0.3" not in ev:
+            ev.append("angle_above_0.3")
         Tk = np.eye(4)
         Tk[:3, :3] = rodrigues(xi[:3])
         Tk[:3, 3] = xi[3:]
         T = Tk @ T
         iters += 1
         trace.append(T.copy())
-        if trans_eps > 0 and rot_eps > 0 and np.linalg.norm(xi[3:]) < trans_eps and np.linalg.norm(xi[:3]) < rot_eps:
+        steps.append((vn, th))
+        if trans_eps > 0 and rot_eps > 0 and vn < trans_eps and th < rot_eps:
             status = 1
             break
-    _, _, sr2, cnt = system(src, tgt, nrm, T, nn, max_corr_dist, exact)
-    return dict(T=T, iters=iters, status=status, rmse=np.sqrt(sr2 / cnt) if cnt else 0.0, trace=trace)
+    ev.append(("capped", "converged", "degenerate_at_0" if iters == 0 else "degenerate_later")[status])
+    _, _, s, cnt = system_at(T)
+    return dict(T=T, iters=iters, status=status, rmse=np.sqrt(s / cnt) if cnt else 0.0, trace=trace, steps=steps)
+
+
+def align(src, tgt, nrm, nn, init_T=None, max_iters=30, max_corr_dist=0.0, trans_eps=0.0, rot_eps=0.0, exact=False,
+          order="forward", events=None):
+    """The whole refinement: dict(T float64 [4, 4], iters, status 0 cap / 1 converged / 2 degenerate, rmse, trace, steps
+    [(|v|, |w|) of every update])."""
+    return gauss_newton(lambda T: system(src, tgt, nrm, T, nn, max_corr_dist, exact, order), init_T, max_iters, trans_eps,
+                        rot_eps, exact, events)
 
 
 def p2p_align(src, tgt, nn, init_T=None, max_iters=30):

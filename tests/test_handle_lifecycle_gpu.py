@@ -95,6 +95,21 @@ def use_registrar_on_store(capi, clouds):
     return [r, st]
 
 
+def use_registrar_refinements(capi, clouds):
+    """Point-to-plane, then generalized ICP on one handle: the workspace they share (p2l::Ws: states, partials, the
+    pinned stop counter and its event) and the normals the calls build beside the scans."""
+    st = capi.ScanStore()
+    a, b = (st.add(c[:, :3]) for c in clouds)
+    r = capi.Registrar(store=st)
+    I = np.eye(4, dtype=np.float32)[None]
+    _, _, iters, status = r.p2l_batch(b, [a, a], init_T=np.concatenate([I, I]), params=capi.default_p2l_params(max_iters=5, trans_eps=1e-3, rot_eps=1e-4))
+    assert (status != 2).all() and (iters >= 1).all()
+    _, _, iters, status = r.gicp_batch(b, [a], init_T=I, params=capi.default_gicp_params(max_iters=3))
+    assert status[0] == 0 and iters[0] == 3
+    r.p2l_system(b, a)
+    return [r, st]
+
+
 def use_vlad(capi, clouds):
     rng = np.random.default_rng(2)
     K, Cc, D = 16, 64, 128
@@ -138,7 +153,7 @@ def use_ground(capi, clouds):
 
 
 USES = {"KnnIndex": use_knn, "ScanStore": use_scan_store, "Registrar": use_registrar,
-        "Registrar+ScanStore": use_registrar_on_store, "NetVladFC": use_vlad, "BevProjector": use_bev,
+        "Registrar+ScanStore": use_registrar_on_store, "Registrar p2l+gicp": use_registrar_refinements, "NetVladFC": use_vlad, "BevProjector": use_bev,
         "PillarEncoder": use_pillar, "CoarseMatcher": use_coarse, "GroundEstimator": use_ground}
 
 

@@ -65,6 +65,12 @@ class GicpParams(C.Structure):
                 ("normal_k", C.c_uint32), ("plane_eps", C.c_float)]
 
 
+class VgicpParams(C.Structure):
+    _fields_ = [("max_iters", C.c_uint32), ("max_corr_dist", C.c_float), ("trans_eps", C.c_float), ("rot_eps", C.c_float),
+                ("normal_k", C.c_uint32), ("plane_eps", C.c_float), ("resolution", C.c_float), ("neighbors", C.c_uint32),
+                ("min_points", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class BevParams(C.Structure):
     _fields_ = [("resolution", C.c_float), ("max_range", C.c_float), ("out_width", C.c_uint32),
                 ("out_height", C.c_uint32), ("format", C.c_uint32), ("pad_bgr", C.c_uint8 * 3),
@@ -212,6 +218,11 @@ _PROTOS = [
     ("gloc_reg_gicp_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(GicpParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_gicp_system", _i, [_vp, _u32, _u32, _vp, C.POINTER(GicpParams), _vp, _vp, C.POINTER(C.c_double),
                               C.POINTER(C.c_uint64)]),
+    ("gloc_vgicp_default_params", None, [C.POINTER(VgicpParams)]),
+    ("gloc_reg_vgicp_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(VgicpParams), _vp, _vp, _vp, _vp]),
+    ("gloc_reg_vgicp_system", _i, [_vp, _u32, _u32, _vp, C.POINTER(VgicpParams), _vp, _vp, C.POINTER(C.c_double),
+                               C.POINTER(C.c_uint64)]),
+    ("gloc_reg_vgicp_voxels", _i, [_vp, _u32, C.POINTER(VgicpParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
@@ -567,6 +578,16 @@ def default_gicp_params(**over):
     return p
 
 
+def default_vgicp_params(**over):
+    """gloc_vgicp_params as gloc_vgicp_default_params leaves them (generalized ICP's, 1 m voxels, 7 neighbours, voxels of
+    one point and more), then `over`."""
+    p = VgicpParams()
+    lib().gloc_vgicp_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
 class ScanStore(_Handle):
     """Resident scans + their search index, shared by any number of Registrars."""
 
@@ -881,6 +902,44 @@ class Registrar(_Handle):
         check(lib().gloc_reg_gicp_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
                                          _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
         return H, g, s.value, c.value
+
+    def vgicp_batch(self, src_id, tgt_ids, init_T=None, params=None):
+        """Voxelized generalized ICP of scan src_id against each of tgt_ids (gloc_reg_vgicp_batch_ids): returns
+        T [n, 4, 4] float32, rmse [n] float32 (sqrt of the weighted e^T M e per pair at the final pose), iterations [n],
+        status [n] (0 cap, 1 converged, 2 degenerate)."""
+        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
+        n = ids.shape[0]
+        prm = params or default_vgicp_params()
+        it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
+        T = np.empty((n, 4, 4), np.float32)
+        rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        check(lib().gloc_reg_vgicp_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
+                                             C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
+        return T, rmse, iters, status
+
+    def vgicp_system(self, src_id, tgt_id, T=None, params=None):
+        """One evaluation of the voxelized generalized ICP normal equations at T: H [6, 6], g [6], the weighted sum of
+        e^T M e, pairs used."""
+        prm = params or default_vgicp_params()
+        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
+        H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
+        check(lib().gloc_reg_vgicp_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
+                                          _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
+        return H, g, s.value, c.value
+
+    def vgicp_voxels(self, scan_id, params=None):
+        """The voxels of a scan, sorted by key: dict(key3 [m, 3] int32, count [m], mean [m, 3], nn6 [m, 6] = the mean of the
+        members' n n^T as xx xy xz yy yz zz)."""
+        prm = params or default_vgicp_params()
+        m = C.c_size_t()
+        check(lib().gloc_reg_vgicp_voxels(self._h, int(scan_id), C.byref(prm), 0, None, None, None, None, C.byref(m)))
+        k = m.value
+        key, cnt = np.empty((k, 3), np.int32), np.empty(k, np.uint32)
+        mean, nn6 = np.empty((k, 3), np.float64), np.empty((k, 6), np.float64)
+        if k:
+            check(lib().gloc_reg_vgicp_voxels(self._h, int(scan_id), C.byref(prm), k, _np_ptr(key), _np_ptr(cnt), _np_ptr(mean),
+                                              _np_ptr(nn6), C.byref(m)))
+        return dict(key3=key, count=cnt, mean=mean, nn6=nn6)
 
     def ndt_derivatives(self, src_id, tgt_id, p6, params=None):
         """score, gradient [6], Hessian [6, 6] of the filtered source against the target's cells at p6."""

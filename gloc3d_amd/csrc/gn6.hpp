@@ -1,6 +1,6 @@
-// gn6.hpp -- the host side the Gauss-Newton refinements share (p2l.hip, gicp.hip): the handle's workspace and the loop of
-// passes.  A pass is three enqueues: the registration's exact 1-NN search, the refinement's own accumulate kernel, the
-// solve kernel of gn6_kernels.hpp.
+// gn6.hpp -- the host side the Gauss-Newton refinements share (p2l.hip, gicp.hip, vgicp.hip): the handle's workspace and the
+// loop of passes.  A pass is three enqueues: the registration's exact 1-NN search (none for the voxelized refinement,
+// whose Ctx::nn_pass is null), the refinement's own accumulate kernel, the solve kernel of gn6_kernels.hpp.
 //
 // Synchronisation between passes: none.  Whether a job has stopped is a flag on the device that the accumulate and solve
 // kernels of later passes read.  With both eps off a job can only stop early by being degenerate, so all max_iters passes
@@ -80,7 +80,7 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
   bool warm = false;
   // search, accumulate, solve at the current poses; mode 1: evaluation only
   auto pass = [&](int mode, double* exp) -> int {
-    GLOC_TRY(x.nn_pass(x.self, warm));
+    if (x.nn_pass) GLOC_TRY(x.nn_pass(x.self, warm));  // (null: the accumulate kernel finds its own pairs -- vgicp.hip)
     warm = true;
     {
       ProfScope ps(*x.prof, lp.accum_name, q);

@@ -165,7 +165,7 @@ int build_cells(hipStream_t q, Ws& w, const std::vector<DevScan>& tg, const gloc
   GLOC_HIP(hipMemcpyAsync(w.tmask.p, out->tmask.data(), 4 * T, hipMemcpyHostToDevice, q));
   GLOC_HIP(hipMemcpyAsync(w.first.p, out->first.data(), 4 * (T + 1), hipMemcpyHostToDevice, q));
   if (max_cells)
-    hipLaunchKernelGGL(cell_hash_kernel, dim3(blocks(max_cells, 256), T), dim3(256), 0, q, w.first.as<uint32_t>(),
+    hipLaunchKernelGGL(cell_hash_kernel<Cell>, dim3(blocks(max_cells, 256), T), dim3(256), 0, q, w.first.as<uint32_t>(),
                        w.cells.as<Cell>(), w.toff.as<uint32_t>(), w.tmask.as<uint32_t>(),
                        reinterpret_cast<unsigned long long*>(w.hkey.p), w.hval.as<uint32_t>());
   GLOC_HIP(hipGetLastError());

@@ -1,5 +1,6 @@
 // ndt_kernels.hpp -- NDT scan registration on gfx950 (gloc_reg_ndt_*, gloc_scan_store_add_approx_voxel): the device
-// half of tests/ndt_ref.py, which states every step below in float64 numpy.  Included by ndt.hip only.
+// half of tests/ndt_ref.py, which states every step below in float64 numpy.  Included by ndt.hip, and by vgicp.hip for
+// the kernels that build the cells (keys, flags, scan, first, hash): the kernels are static, each file carries its copy.
 //
 //   approximate voxel filter   avf_keys_kernel -> segmented radix sort by hash slot (stable) -> avf_flags_kernel
 //                              (a run of equal cells inside a slot starts here) -> flag scan -> avf_emit_kernel (the
@@ -203,7 +204,7 @@ __device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* sh, uint32_t* t
   return incl - v;
 }
 
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_sum_kernel(const uint32_t* __restrict__ f, uint32_t n, uint32_t* __restrict__ bsum) {
+static __global__ __launch_bounds__(SCAN_BLOCK) void scan_sum_kernel(const uint32_t* __restrict__ f, uint32_t n, uint32_t* __restrict__ bsum) {
   __shared__ uint32_t sh[SCAN_BLOCK];
   const uint32_t i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
   uint32_t tot;
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_sum_kernel(const uint32_t* __
   if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_top_kernel(uint32_t* __restrict__ bsum, uint32_t nb, uint32_t* __restrict__ total) {
+static __global__ __launch_bounds__(SCAN_BLOCK) void scan_top_kernel(uint32_t* __restrict__ bsum, uint32_t nb, uint32_t* __restrict__ total) {
   __shared__ uint32_t sh[SCAN_BLOCK];
   uint32_t carry = 0;
   for (uint32_t b0 = 0; b0 < nb; b0 += SCAN_BLOCK) {
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_top_kernel(uint32_t* __restri
   if (threadIdx.x == 0) *total = carry;
 }
 
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const uint32_t* __restrict__ f, uint32_t n,
+static __global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const uint32_t* __restrict__ f, uint32_t n,
                                                                 const uint32_t* __restrict__ boff, uint32_t* __restrict__ pos) {
   __shared__ uint32_t sh[SCAN_BLOCK];
   const uint32_t i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
@@ -244,7 +245,7 @@ __device__ inline bool avf_cell(const float* __restrict__ xyz, uint32_t i, float
   return ok;
 }
 
-__global__ void avf_keys_kernel(const float* __restrict__ xyz, uint32_t n, float inv, uint32_t* __restrict__ key,
+static __global__ void avf_keys_kernel(const float* __restrict__ xyz, uint32_t n, float inv, uint32_t* __restrict__ key,
                                 uint32_t* __restrict__ val) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -256,7 +257,7 @@ __global__ void avf_keys_kernel(const float* __restrict__ xyz, uint32_t n, float
 }
 
 // single: no filter (leaf <= 0), every finite point is a run of its own, unsorted
-__global__ void avf_flags_kernel(const float* __restrict__ xyz, uint32_t n, float inv, const uint32_t* __restrict__ key,
+static __global__ void avf_flags_kernel(const float* __restrict__ xyz, uint32_t n, float inv, const uint32_t* __restrict__ key,
                                  const uint32_t* __restrict__ val, uint32_t* __restrict__ flag, int single) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
@@ -276,7 +277,7 @@ __global__ void avf_flags_kernel(const float* __restrict__ xyz, uint32_t n, floa
 }
 
 // one thread per run: its fp32 sum in point order (the sort is stable), divided by the fp32 count
-__global__ void avf_emit_kernel(const float* __restrict__ xyz, uint32_t n, const uint32_t* __restrict__ key,
+static __global__ void avf_emit_kernel(const float* __restrict__ xyz, uint32_t n, const uint32_t* __restrict__ key,
                                 const uint32_t* __restrict__ val, const uint32_t* __restrict__ flag,
                                 const uint32_t* __restrict__ pos, float* __restrict__ out, int single) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -304,7 +305,7 @@ __device__ inline unsigned long long pack_key(long long kx, long long ky, long l
          (unsigned long long)(kz + KEY_BIAS);
 }
 
-__global__ void cell_keys_kernel(const TgtDesc* __restrict__ tg, float inv, unsigned long long* __restrict__ key,
+static __global__ void cell_keys_kernel(const TgtDesc* __restrict__ tg, float inv, unsigned long long* __restrict__ key,
                                  uint32_t* __restrict__ val) {
   const TgtDesc d = tg[blockIdx.y];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -320,7 +321,7 @@ __global__ void cell_keys_kernel(const TgtDesc* __restrict__ tg, float inv, unsi
   val[d.begin + i] = i;
 }
 
-__global__ void cell_flags_kernel(const TgtDesc* __restrict__ tg, const unsigned long long* __restrict__ key,
+static __global__ void cell_flags_kernel(const TgtDesc* __restrict__ tg, const unsigned long long* __restrict__ key,
                                   uint32_t* __restrict__ flag) {
   const TgtDesc d = tg[blockIdx.y];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -330,7 +331,7 @@ __global__ void cell_flags_kernel(const TgtDesc* __restrict__ tg, const unsigned
 }
 
 // first cell of every target (the scanned flag at its segment's start) and the total behind the last
-__global__ void cell_first_kernel(const TgtDesc* __restrict__ tg, uint32_t n_tgt, const uint32_t* __restrict__ pos,
+static __global__ void cell_first_kernel(const TgtDesc* __restrict__ tg, uint32_t n_tgt, const uint32_t* __restrict__ pos,
                                   const uint32_t* __restrict__ total, uint32_t* __restrict__ first) {
   for (uint32_t t = threadIdx.x; t < n_tgt; t += blockDim.x)
     first[t] = tg[t].n ? pos[tg[t].begin] : 0u;  // (an empty target: fixed up on the host)
@@ -350,7 +351,7 @@ __device__ inline void inv_sym3(const double* C, double* I) {  // cofactors / de
   I[5] = (a * d - b * b) * r;
 }
 
-__global__ void cell_stats_kernel(const TgtDesc* __restrict__ tg, const unsigned long long* __restrict__ key,
+static __global__ void cell_stats_kernel(const TgtDesc* __restrict__ tg, const unsigned long long* __restrict__ key,
                                   const uint32_t* __restrict__ val, const uint32_t* __restrict__ flag,
                                   const uint32_t* __restrict__ pos, double res, uint32_t min_pts, double eig_mult,
                                   Cell* __restrict__ cells) {
@@ -433,8 +434,10 @@ __device__ __forceinline__ uint32_t hash_slot(unsigned long long k, uint32_t mas
   return (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 32) & mask;
 }
 
-// hash tables: target t owns slots [toff[t], toff[t] + tmask[t] + 1); valid cells only
-__global__ void cell_hash_kernel(const uint32_t* __restrict__ first, const Cell* __restrict__ cells,
+// hash tables: target t owns slots [toff[t], toff[t] + tmask[t] + 1); valid cells only.  CellT: anything with a key and
+// a valid flag (Cell here, the voxels of vgicp_kernels.hpp)
+template <class CellT>
+static __global__ void cell_hash_kernel(const uint32_t* __restrict__ first, const CellT* __restrict__ cells,
                                  const uint32_t* __restrict__ toff, const uint32_t* __restrict__ tmask,
                                  unsigned long long* __restrict__ hkey, uint32_t* __restrict__ hval) {
   const uint32_t t = blockIdx.y;
@@ -457,7 +460,7 @@ __global__ void cell_hash_kernel(const uint32_t* __restrict__ first, const Cell*
 // ---- derivatives -----------------------------------------------------------------------------------------------------
 // grid (work-groups over the filtered source, candidates): per work-group the fp64 sums [score, g 6, H upper 21] of its
 // CHUNK points, in a fixed order (lanes in order inside a wave by a butterfly, waves in order), no atomics
-__global__ __launch_bounds__(DERIV_THREADS) void ndt_deriv_kernel(
+static __global__ __launch_bounds__(DERIV_THREADS) void ndt_deriv_kernel(
     const float* __restrict__ src, uint32_t n_src, const Eval* __restrict__ evals, const int* __restrict__ cand_tgt,
     const Cell* __restrict__ cells, const unsigned long long* __restrict__ hkey, const uint32_t* __restrict__ hval,
     const uint32_t* __restrict__ toff, const uint32_t* __restrict__ tmask, Consts K, double* __restrict__ partials) {
@@ -777,7 +780,7 @@ __device__ inline void after_trial(State& S, Eval* ev, Out* out, uint32_t* done_
 
 // one wave per candidate: sum the work-groups' partials in block order, then step the state.  export_sums: only write
 // the sums (gloc_reg_ndt_derivatives)
-__global__ __launch_bounds__(64) void ndt_state_kernel(const double* __restrict__ partials, uint32_t n_blk, State* __restrict__ states,
+static __global__ __launch_bounds__(64) void ndt_state_kernel(const double* __restrict__ partials, uint32_t n_blk, State* __restrict__ states,
                                                        Eval* __restrict__ evals, Out* __restrict__ outs, uint32_t* __restrict__ done_count,
                                                        double* __restrict__ export_sums) {
   const uint32_t c = blockIdx.x;
@@ -828,7 +831,7 @@ __global__ __launch_bounds__(64) void ndt_state_kernel(const double* __restrict_
 
 // initial state of every candidate: p0 from its guess (Eigen's eulerAngles(0, 1, 2), fp64), an evaluation at p0 with the
 // Hessian.  init_T: [n][16] row-major floats or null (identity); p6: a fixed p for every candidate instead (derivatives)
-__global__ void ndt_init_kernel(uint32_t n, const float* __restrict__ init_T, const double* __restrict__ p6, const int* __restrict__ cand_tgt,
+static __global__ void ndt_init_kernel(uint32_t n, const float* __restrict__ init_T, const double* __restrict__ p6, const int* __restrict__ cand_tgt,
                                 double n_src, double step_max, double step_min, double eps, int max_iters,
                                 State* __restrict__ states, Eval* __restrict__ evals) {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;

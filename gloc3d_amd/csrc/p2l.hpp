@@ -29,7 +29,7 @@ struct Ctx {
   const uint32_t* corr;  // device [job][ld]: sorted source slot -> position in the target's search order
   const float* d2;
   size_t ld;
-  int (*nn_pass)(void* self, bool warm);  // enqueues the exact 1-NN pass of every job at the current poses
+  int (*nn_pass)(void* self, bool warm);  // enqueues the exact 1-NN pass of every job at the current poses (null: no search)
   void* self;
 };
 

@@ -15,6 +15,7 @@
 #include "p2l.hpp"
 #include "reg_kernels.hpp"
 #include "scan_store.hpp"
+#include "vgicp.hpp"
 
 using namespace gloc;
 using namespace gloc::reg;
@@ -87,12 +88,14 @@ struct gloc_reg : Handle {
   uint32_t last_jobs = 0;
   gloc::ndt::Ws* ndt = nullptr;  // NDT workspace (ndt.hip), made on first use
   gloc::p2l::Ws* p2l = nullptr;  // point-to-plane / generalized ICP workspace (gn6.hpp), made on first use
+  gloc::vgicp::Ws* vgicp = nullptr;  // voxelized generalized ICP's voxel maps (vgicp.hip), made on first use
   ~gloc_reg() {  // (the handle's work has been waited for: destroy_handle)
     if (pending.active && pending.store) store_pin(pending.store, pending.pinned.data(), pending.pinned.size(), -1);
     if (store) store->attached--;
     if (own_store) (void)gloc_scan_store_destroy(own_store);
     gloc::ndt::ws_free(ndt);
     gloc::p2l::ws_free(p2l);
+    gloc::vgicp::ws_free(vgicp);
     if (done_ev) (void)hipEventDestroy(done_ev);
     if (pin) (void)hipHostFree(pin);
   }
@@ -1488,6 +1491,40 @@ int gloc_reg_gicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
   return run_gicp(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum, out_count);
+}
+
+// Voxelized generalized ICP (vgicp.hip): no 1-NN search, so none of this file's batch set-up -- the call builds its
+// targets' voxel maps and runs the shared loop of passes on the handle's stream.
+int gloc_reg_vgicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                             const gloc_vgicp_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status) {
+  GLOC_TRY(gloc::vgicp::check_params(prm));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  const gloc::vgicp::Ctx x{h->store, h->stream, &h->prof, &h->vgicp, &h->p2l};
+  return gloc::vgicp::run(x, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
+                          nullptr, nullptr);
+}
+
+int gloc_reg_vgicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_vgicp_params* prm,
+                          double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count) {
+  GLOC_TRY(gloc::vgicp::check_params(prm));
+  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  const gloc::vgicp::Ctx x{h->store, h->stream, &h->prof, &h->vgicp, &h->p2l};
+  return gloc::vgicp::run(x, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
+                          out_count);
+}
+
+int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3,
+                          uint32_t* out_count, double* out_mean3, double* out_nn6, size_t* n_voxels) {
+  GLOC_TRY(gloc::vgicp::check_params(prm));
+  GLOC_REQUIRE(h && n_voxels, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  const gloc::vgicp::Ctx x{h->store, h->stream, &h->prof, &h->vgicp, &h->p2l};
+  return gloc::vgicp::voxels(x, scan_id, prm, capacity, out_key3, out_count, out_mean3, out_nn6, n_voxels);
 }
 
 int gloc_reg_profile(gloc_reg* h, const char* kernel, double* total_ms, uint64_t* launches) {

@@ -565,6 +565,62 @@ int gloc_reg_gicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* t
 int gloc_reg_gicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_gicp_params* prm,
                          double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count);
 
+/* ---- voxelized generalized ICP refinement -------------------------------------------------------------- *
+ * Voxelized GICP (Koide, Yokozuka, Oishi & Banno; fast_gicp's FastVGICP): generalized ICP's distribution-to-distribution
+ * cost without its nearest-neighbour search.  The target is cut into voxels of `resolution`, each with the mean of its
+ * points and the mean of their plane-to-plane covariances; a moved source point is paired with the voxel it falls into
+ * (and, by `neighbors`, the voxels around it) by one hash-table lookup each.  No 1-NN search runs, so a target needs no
+ * target index: this is the one refinement usable on a scan that was only uploaded.  The voxel maps are built per call
+ * on the device, as NDT's cells are.  With a = 1 - plane_eps and a zero normal meaning "no normal":
+ *   1. normals: the source's and every target's, as generalized ICP takes them;
+ *   2. voxels of a target: per point, in the order the scan was uploaded, k = floor(x * inv) per axis in fp32 with
+ *      inv = 1.0f / resolution (a non-finite point, or one with |k| >= 2^20 on an axis, is in no voxel); per voxel with
+ *      N >= min_points members: N, the mean mu (fp64 sums relative to the voxel's corner k * resolution, in upload order)
+ *      and Nbar = (1 / N) sum n n^T over its members (fp64; a member without a normal adds zero).  The voxel's covariance is
+ *      C_B = I - a Nbar, the mean of its members' generalized-ICP covariances (fast_gicp's rule); nothing is inverted here;
+ *   3. each pass moves every source point by the pose rounded to fp32, p = R s + t in fp32, and finds its voxel by the
+ *      rule of step 2;
+ *   4. for each offset of the neighbourhood the voxel at (voxel of p) + offset, if the target has one, makes a pair.
+ *      neighbors = 1: (0,0,0); 7: (0,0,0) (-1,0,0) (1,0,0) (0,-1,0) (0,1,0) (0,0,-1) (0,0,1); 27: the 3 x 3 x 3 block,
+ *      dz, dy, dx from -1 to 1 with dx fastest -- the order the pairs of a point are summed in;
+ *   5. a pair is used iff p is finite and max_corr_dist <= 0 or |p - mu|^2 <= max_corr_dist^2 (fp64);
+ *   6. in fp64: m = R n_s, S = 2I - a (Nbar + m m^T), M = S^-1 (the symmetric adjugate; S has eigenvalues >= 2 plane_eps),
+ *      e = p - mu, J = [-[p]x , I], and the pair's weight is w = N:  H += w J^T M J, g += w J^T M e, sum w e^T M e, the
+ *      count of pairs (unweighted);
+ *   7. - 10. steps 7 - 10 of generalized ICP: status 2 below 6 pairs or at a bad pivot, H xi = -g, T <- exp(xi) T in fp64,
+ *      the stop test with both eps, stopped jobs frozen. */
+typedef struct gloc_vgicp_params {
+  uint32_t max_iters;  /* 30 */
+  float max_corr_dist; /* <= 0: no rejection; else a pair's |p - mu| may not exceed it */
+  float trans_eps;     /* stop when |v| < trans_eps AND |w| < rot_eps; both <= 0 (default): run max_iters passes */
+  float rot_eps;
+  uint32_t normal_k;   /* 10: scans without normals, the source included, get them built with this k */
+  float plane_eps;     /* 1e-3, in (0, 1], as gloc_gicp_params */
+  float resolution;    /* 1.0 m: the voxels' edge (fast_gicp's default); must be > 0 */
+  uint32_t neighbors;  /* 7: voxels probed per source point; one of 1, 7, 27 */
+  uint32_t min_points; /* 1: voxels with fewer points are left out; must be >= 1 */
+  uint32_t reserved_;
+} gloc_vgicp_params;   /* 40 bytes */
+
+void gloc_vgicp_default_params(gloc_vgicp_params* p);
+
+/* Refine n candidates as gloc_reg_gicp_batch_ids does: the same arguments and outputs.  The rmse is
+ * sqrt(sum w e^T M e / count) of ONE more evaluation at the final pose: the residuals are weighted by the voxels' point
+ * counts, the count is of pairs, so it is the WEIGHTED residual per pair, not a distance.  Every candidate's result is
+ * independent of the batch it is in, bit for bit, and of whether a target carries a target index.  Normals missing on
+ * the source or on a target are built first, under the rule of gloc_scan_store_build_normals.  GLOC_ERR_INVALID: null
+ * arguments, an unknown id, an empty source, max_iters = 0, normal_k outside [3, 16], plane_eps outside (0, 1],
+ * resolution <= 0, neighbors not 1, 7 or 27, min_points = 0; GLOC_ERR_STATE: a batch in flight on the handle. */
+int gloc_reg_vgicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                             const gloc_vgicp_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status);
+/* Steps 1 - 6 once at T16 (NULL = identity): H (6 x 6 row-major), g, sum w e^T M e and the number of pairs used. */
+int gloc_reg_vgicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_vgicp_params* prm,
+                          double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count);
+/* The voxels of a scan (step 2), sorted by (kx, ky, kz): integer voxel index, point count, mean, Nbar as xx xy xz yy yz zz.
+ * n_voxels: how many there are (the arrays may be NULL to ask). */
+int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3,
+                          uint32_t* out_count, double* out_mean3, double* out_nn6, size_t* n_voxels);
+
 /* ============================ NetVLAD-FC pooling head ("next" row N2) ===================== *
  * Replaces NetVLAD.forward of the reference (model/netvlad_fc.py:73-109, built without gating at
  * main.py:594) -- the tail of the TorchScript module RpyPCLoopDetector::get_place_feature runs

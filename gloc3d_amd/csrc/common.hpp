@@ -158,6 +158,14 @@ int destroy_handle(H* h) {
   return GLOC_OK;
 }
 
+// A workspace that a handle makes on first use: *slot is filled if it is still null.
+template <class W>
+int ensure_ws(W** slot) {
+  if (!*slot) *slot = new (std::nothrow) W;
+  GLOC_REQUIRE(*slot, GLOC_ERR_NOMEM, "host allocation failed");
+  return GLOC_OK;
+}
+
 // The host-pointer form of a device entry point: `src` goes up into the first staging buffer (never null: an empty
 // input still gets 16 bytes), run(d_in, d_out) enqueues the device form on `s`, the second staging buffer comes down into
 // `dst`, and the stream is waited for.

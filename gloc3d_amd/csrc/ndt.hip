@@ -6,18 +6,18 @@
 
 #include "ndt.hpp"
 #include "ndt_kernels.hpp"
-#include "seg_sort.hpp"
+#include "voxel_map.hpp"
 
 using namespace gloc;
 using namespace gloc::ndt;
+using gloc::voxmap::blocks;
 
 namespace gloc {
 namespace ndt {
 
 struct Ws {
-  DevBuf k0, k1, v0, v1, hist, segs, flag, pos, bsum, total;  // sorts and flag scans (filter and cells)
-  DevBuf filt;                                                // the filtered source, packed xyz
-  DevBuf tgt_desc, first, cells, hkey, hval, toff, tmask;     // cells of the batch's targets and their hash tables
+  voxmap::Ws map;  // cells of the batch's targets and their hash tables; its sort and scan buffers serve the filter too
+  DevBuf filt;     // the filtered source, packed xyz
   DevBuf states, evals, outs, partials, cand_tgt, init_T, p6, done, exp;
   uint32_t* h_done = nullptr;  // pinned
   hipEvent_t ev = nullptr;
@@ -33,22 +33,9 @@ namespace {
 
 constexpr int CHUNK_ROUNDS = 8;  // rounds of (derivatives, state) enqueued between two looks at the done count
 
-uint32_t blocks(size_t n, uint32_t t) { return (uint32_t)((n + t - 1) / t); }
-
-// exclusive prefix of n 0/1 flags into pos; *total (device) = their sum
-int scan_flags(hipStream_t q, Ws& w, const uint32_t* flag, uint32_t n, uint32_t* pos, uint32_t* total) {
-  const uint32_t nb = std::max<uint32_t>(1, blocks(n, SCAN_BLOCK));
-  GLOC_TRY(w.bsum.ensure(sizeof(uint32_t) * nb, q));
-  hipLaunchKernelGGL(scan_sum_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, q, flag, n, w.bsum.as<uint32_t>());
-  hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_BLOCK), 0, q, w.bsum.as<uint32_t>(), nb, total);
-  hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, q, flag, n, w.bsum.as<uint32_t>(), pos);
-  GLOC_HIP(hipGetLastError());
-  return GLOC_OK;
-}
-
-// The approximate voxel filter of n points (device, packed xyz) into w.filt; returns the output count (synchronises).
+// The approximate voxel filter of n points (device, packed xyz) into filt; returns the output count (synchronises).
 // leaf <= 0: the finite points, in order.
-int approx_voxel(hipStream_t q, Ws& w, const float* xyz, uint32_t n, float leaf, uint32_t* m) {
+int approx_voxel(hipStream_t q, voxmap::Ws& w, DevBuf& filt, const float* xyz, uint32_t n, float leaf, uint32_t* m) {
   *m = 0;
   if (n == 0) return GLOC_OK;
   const bool keep_all = !(leaf > 0.f);
@@ -77,99 +64,25 @@ int approx_voxel(hipStream_t q, Ws& w, const float* xyz, uint32_t n, float leaf,
   }
   hipLaunchKernelGGL(avf_flags_kernel, dim3(blocks(n, 256)), dim3(256), 0, q, xyz, n, keep_all ? 1.0f : inv, k[cur], v[cur],
                      w.flag.as<uint32_t>(), keep_all ? 1 : 0);
-  GLOC_TRY(scan_flags(q, w, w.flag.as<uint32_t>(), n, w.pos.as<uint32_t>(), w.total.as<uint32_t>()));
+  GLOC_TRY(voxmap::scan_flags(q, w, w.flag.as<uint32_t>(), n, w.pos.as<uint32_t>(), w.total.as<uint32_t>()));
   uint32_t cnt = 0;
   GLOC_HIP(hipMemcpyAsync(&cnt, w.total.p, 4, hipMemcpyDeviceToHost, q));
   GLOC_HIP(hipStreamSynchronize(q));
-  GLOC_TRY(w.filt.ensure(12 * (size_t)std::max<uint32_t>(cnt, 1), q));
+  GLOC_TRY(filt.ensure(12 * (size_t)std::max<uint32_t>(cnt, 1), q));
   hipLaunchKernelGGL(avf_emit_kernel, dim3(blocks(n, 256)), dim3(256), 0, q, xyz, n, k[cur], v[cur], w.flag.as<uint32_t>(),
-                     w.pos.as<uint32_t>(), w.filt.as<float>(), keep_all ? 1 : 0);
+                     w.pos.as<uint32_t>(), filt.as<float>(), keep_all ? 1 : 0);
   GLOC_HIP(hipGetLastError());
   *m = cnt;
   return GLOC_OK;
 }
 
-struct TargetCells {
-  std::vector<uint32_t> first;   // [n_tgt + 1] cell ranges
-  std::vector<uint32_t> toff, tmask;
-};
-
-// Cells of every target and their hash tables (synchronises once, to size the tables).
-int build_cells(hipStream_t q, Ws& w, const std::vector<DevScan>& tg, const gloc_ndt_params* prm, TargetCells* out) {
-  const uint32_t T = (uint32_t)tg.size();
-  std::vector<TgtDesc> desc(T);
-  uint32_t N = 0, max_n = 0;
-  for (uint32_t t = 0; t < T; ++t) {
-    desc[t] = TgtDesc{tg[t].xyz, (uint32_t)tg[t].n, N};
-    N += (uint32_t)tg[t].n;
-    max_n = std::max(max_n, (uint32_t)tg[t].n);
-  }
-  const size_t NN = std::max<uint32_t>(N, 1);
-  GLOC_TRY(w.tgt_desc.ensure(sizeof(TgtDesc) * T, q));
-  GLOC_TRY(w.segs.ensure(sizeof(segsort::Seg) * T, q));
-  GLOC_TRY(w.k0.ensure(8 * NN, q));
-  GLOC_TRY(w.k1.ensure(8 * NN, q));
-  GLOC_TRY(w.v0.ensure(4 * NN, q));
-  GLOC_TRY(w.v1.ensure(4 * NN, q));
-  GLOC_TRY(w.flag.ensure(4 * NN, q));
-  GLOC_TRY(w.pos.ensure(4 * NN, q));
-  GLOC_TRY(w.total.ensure(16, q));
-  GLOC_TRY(w.first.ensure(4 * (T + 1), q));
-  GLOC_TRY(w.cells.ensure(sizeof(Cell) * NN, q));
-  GLOC_TRY(w.hist.ensure(segsort::scratch_bytes(T, std::max<uint32_t>(max_n, 1)), q));
-  std::vector<segsort::Seg> segs(T);
-  for (uint32_t t = 0; t < T; ++t) segs[t] = segsort::Seg{desc[t].begin, desc[t].n};
-  GLOC_HIP(hipMemcpyAsync(w.tgt_desc.p, desc.data(), sizeof(TgtDesc) * T, hipMemcpyHostToDevice, q));
-  GLOC_HIP(hipMemcpyAsync(w.segs.p, segs.data(), sizeof(segsort::Seg) * T, hipMemcpyHostToDevice, q));
-  const float inv = 1.0f / (float)prm->resolution;
-  const dim3 g(std::max<uint32_t>(1, blocks(max_n, 256)), T);
-  auto* K = reinterpret_cast<unsigned long long*>(w.k0.p);
-  auto* K1 = reinterpret_cast<unsigned long long*>(w.k1.p);
-  hipLaunchKernelGGL(cell_keys_kernel, g, dim3(256), 0, q, w.tgt_desc.as<TgtDesc>(), inv, K, w.v0.as<uint32_t>());
-  unsigned long long* kk[2] = {K, K1};
-  uint32_t* vv[2] = {w.v0.as<uint32_t>(), w.v1.as<uint32_t>()};
-  const int cur = max_n ? segsort::sort_pairs<unsigned long long, 8>(q, kk[0], kk[1], vv[0], vv[1], w.segs.as<segsort::Seg>(), T,
-                                                                       max_n, 0, 64, w.hist.as<uint32_t>())
-                        : 0;
-  hipLaunchKernelGGL(cell_flags_kernel, g, dim3(256), 0, q, w.tgt_desc.as<TgtDesc>(), kk[cur], w.flag.as<uint32_t>());
-  GLOC_TRY(scan_flags(q, w, w.flag.as<uint32_t>(), N, w.pos.as<uint32_t>(), w.total.as<uint32_t>()));
-  hipLaunchKernelGGL(cell_first_kernel, dim3(1), dim3(256), 0, q,
-                     w.tgt_desc.as<TgtDesc>(), T, w.pos.as<uint32_t>(), w.total.as<uint32_t>(), w.first.as<uint32_t>());
-  hipLaunchKernelGGL(cell_stats_kernel, g, dim3(256), 0, q, w.tgt_desc.as<TgtDesc>(), kk[cur], vv[cur], w.flag.as<uint32_t>(),
-                     w.pos.as<uint32_t>(), (double)prm->resolution, prm->min_points_per_cell, (double)prm->min_covar_eigvalue_mult,
-                     w.cells.as<Cell>());
-  GLOC_HIP(hipGetLastError());
-  out->first.assign(T + 1, 0);
-  GLOC_HIP(hipMemcpyAsync(out->first.data(), w.first.p, 4 * (T + 1), hipMemcpyDeviceToHost, q));
-  GLOC_HIP(hipStreamSynchronize(q));
-  for (uint32_t t = T; t-- > 0;)  // an empty target has no cells: its range starts where the next one does
-    if (desc[t].n == 0) out->first[t] = out->first[t + 1];
-  out->toff.assign(T, 0);
-  out->tmask.assign(T, 0);
-  size_t slots = 0, max_cells = 0;
-  for (uint32_t t = 0; t < T; ++t) {
-    const size_t nc = out->first[t + 1] - out->first[t];
-    max_cells = std::max(max_cells, nc);
-    size_t s = 16;
-    while (s < 2 * nc) s <<= 1;
-    out->toff[t] = (uint32_t)slots;
-    out->tmask[t] = (uint32_t)(s - 1);
-    slots += s;
-  }
-  GLOC_TRY(w.hkey.ensure(8 * slots, q));
-  GLOC_TRY(w.hval.ensure(4 * slots, q));
-  GLOC_TRY(w.toff.ensure(4 * T, q));
-  GLOC_TRY(w.tmask.ensure(4 * T, q));
-  GLOC_HIP(hipMemsetAsync(w.hkey.p, 0xFF, 8 * slots, q));
-  GLOC_HIP(hipMemcpyAsync(w.toff.p, out->toff.data(), 4 * T, hipMemcpyHostToDevice, q));
-  GLOC_HIP(hipMemcpyAsync(w.tmask.p, out->tmask.data(), 4 * T, hipMemcpyHostToDevice, q));
-  GLOC_HIP(hipMemcpyAsync(w.first.p, out->first.data(), 4 * (T + 1), hipMemcpyHostToDevice, q));
-  if (max_cells)
-    hipLaunchKernelGGL(cell_hash_kernel<Cell>, dim3(blocks(max_cells, 256), T), dim3(256), 0, q, w.first.as<uint32_t>(),
-                       w.cells.as<Cell>(), w.toff.as<uint32_t>(), w.tmask.as<uint32_t>(),
-                       reinterpret_cast<unsigned long long*>(w.hkey.p), w.hval.as<uint32_t>());
-  GLOC_HIP(hipGetLastError());
-  return GLOC_OK;
+// Cells of every target and their hash tables (voxmap::build with NDT's statistics kernel)
+int target_cells(hipStream_t q, voxmap::Ws& w, const std::vector<DevScan>& tg, const gloc_ndt_params* prm, voxmap::Maps* out) {
+  return voxmap::build<Cell>(q, w, tg, prm->resolution, [&](dim3 g, const TgtDesc* d, const unsigned long long* key, const uint32_t* val,
+                                                            const uint32_t* flag, const uint32_t* pos) {
+    hipLaunchKernelGGL(cell_stats_kernel, g, dim3(256), 0, q, d, key, val, flag, pos, (double)prm->resolution, prm->min_points_per_cell,
+                       (double)prm->min_covar_eigvalue_mult, w.cells.as<Cell>());
+  }, out);
 }
 
 Consts consts_of(const gloc_ndt_params* prm) {
@@ -180,19 +93,6 @@ Consts consts_of(const gloc_ndt_params* prm) {
   const double d2 = -2.0 * log((-log(c1 * exp(-0.5) + c2) - d3) / d1);
   return Consts{r, 1.0 / r, d1, d2};
 }
-
-// Pins the scans for the duration of a call (store_get_pinned / store_pin)
-struct Pins {
-  gloc_scan_store* st;
-  std::vector<uint32_t> ids;
-  hipStream_t q;
-  ~Pins() {
-    if (!ids.empty()) {
-      (void)hipStreamSynchronize(q);
-      reg::store_pin(st, ids.data(), ids.size(), -1);
-    }
-  }
-};
 
 int check_params(const gloc_ndt_params* p) {
   GLOC_REQUIRE(p, GLOC_ERR_INVALID, "params is null");
@@ -213,40 +113,30 @@ int run(const Ctx& x, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const 
   GLOC_TRY(check_params(prm));
   GLOC_REQUIRE(tgt_ids && n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096] or null target ids", n);
   GLOC_REQUIRE(x.store, GLOC_ERR_INVALID, "unknown scan id %u", src_id);
-  if (!*x.ws) {
-    *x.ws = new (std::nothrow) Ws;
-    GLOC_REQUIRE(*x.ws, GLOC_ERR_NOMEM, "host allocation failed");
-  }
+  GLOC_TRY(ensure_ws(x.ws));
   Ws& w = **x.ws;
   const hipStream_t q = x.stream;
   Profiler& prof = *x.prof;
-  // distinct targets, in order of first appearance
-  std::vector<uint32_t> uniq;
-  std::vector<int> cand_tgt(n);
-  for (size_t c = 0; c < n; ++c) {
-    auto it = std::find(uniq.begin(), uniq.end(), tgt_ids[c]);
-    cand_tgt[c] = (int)(it - uniq.begin());
-    if (it == uniq.end()) uniq.push_back(tgt_ids[c]);
-  }
+  std::vector<uint32_t> uniq, cand_tgt;  // one set of cells per distinct target (the kernels read cand_tgt as int: < 4096)
+  reg::distinct_in_order(tgt_ids, n, &uniq, &cand_tgt);
   std::vector<uint32_t> ids(1 + uniq.size());
   ids[0] = src_id;
   std::copy(uniq.begin(), uniq.end(), ids.begin() + 1);
-  std::vector<int> cs(ids.size(), 0);
-  std::vector<DevScan> scans(ids.size());
-  GLOC_TRY(reg::store_get_pinned(x.store, ids.data(), cs.data(), ids.size(), scans.data()));
-  Pins pins{x.store, ids, q};
+  reg::ScopedPins pins(x.store, q);
+  GLOC_TRY(pins.pin(ids.data(), nullptr, ids.size()));
+  const std::vector<DevScan>& scans = pins.scans;
   GLOC_REQUIRE(scans[0].n < (1ull << 31), GLOC_ERR_INVALID, "source scan too large");
   uint32_t m = 0;
   {
     ProfScope ps(prof, "ndt_filter", q);
-    GLOC_TRY(approx_voxel(q, w, scans[0].xyz, (uint32_t)scans[0].n, prm->source_leaf, &m));
+    GLOC_TRY(approx_voxel(q, w.map, w.filt, scans[0].xyz, (uint32_t)scans[0].n, prm->source_leaf, &m));
   }
   GLOC_REQUIRE(m > 0, GLOC_ERR_INVALID, "the filtered source scan is empty");
-  TargetCells tc;
+  voxmap::Maps tc;
   {
     ProfScope ps(prof, "ndt_cells", q);
     std::vector<DevScan> tg(scans.begin() + 1, scans.end());
-    GLOC_TRY(build_cells(q, w, tg, prm, &tc));
+    GLOC_TRY(target_cells(q, w.map, tg, prm, &tc));
   }
   const uint32_t n_blk = blocks(m, CHUNK);
   GLOC_TRY(w.states.ensure(sizeof(State) * n, q));
@@ -277,9 +167,9 @@ int run(const Ctx& x, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const 
     {
       ProfScope ps(prof, "ndt_deriv", q);
       hipLaunchKernelGGL(ndt_deriv_kernel, dim3(n_blk, (uint32_t)n), dim3(DERIV_THREADS), 0, q, w.filt.as<float>(), m,
-                         w.evals.as<Eval>(), w.cand_tgt.as<int>(), w.cells.as<Cell>(),
-                         reinterpret_cast<unsigned long long*>(w.hkey.p), w.hval.as<uint32_t>(), w.toff.as<uint32_t>(),
-                         w.tmask.as<uint32_t>(), K, w.partials.as<double>());
+                         w.evals.as<Eval>(), w.cand_tgt.as<int>(), w.map.cells.as<Cell>(),
+                         reinterpret_cast<unsigned long long*>(w.map.hkey.p), w.map.hval.as<uint32_t>(), w.map.toff.as<uint32_t>(),
+                         w.map.tmask.as<uint32_t>(), K, w.partials.as<double>());
     }
     {
       ProfScope ps(prof, "ndt_state", q);
@@ -325,45 +215,23 @@ int cells(const Ctx& x, uint32_t scan_id, const gloc_ndt_params* prm, size_t cap
   GLOC_TRY(check_params(prm));
   GLOC_REQUIRE(n_cells, GLOC_ERR_INVALID, "n_cells is null");
   GLOC_REQUIRE(x.store, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  if (!*x.ws) {
-    *x.ws = new (std::nothrow) Ws;
-    GLOC_REQUIRE(*x.ws, GLOC_ERR_NOMEM, "host allocation failed");
-  }
+  GLOC_TRY(ensure_ws(x.ws));
   Ws& w = **x.ws;
   const hipStream_t q = x.stream;
-  const int cs0 = 0;
-  std::vector<DevScan> tg(1);
-  GLOC_TRY(reg::store_get_pinned(x.store, &scan_id, &cs0, 1, tg.data()));
-  Pins pins{x.store, {scan_id}, q};
-  TargetCells tc;
+  reg::ScopedPins pins(x.store, q);
+  GLOC_TRY(pins.pin(&scan_id, nullptr, 1));
+  voxmap::Maps tc;
   {
     ProfScope ps(*x.prof, "ndt_cells", q);
-    GLOC_TRY(build_cells(q, w, tg, prm, &tc));
+    GLOC_TRY(target_cells(q, w.map, pins.scans, prm, &tc));
   }
-  const uint32_t nc = tc.first[1] - tc.first[0];
-  std::vector<Cell> all(nc);
-  if (nc) GLOC_HIP(hipMemcpyAsync(all.data(), w.cells.as<Cell>() + tc.first[0], sizeof(Cell) * nc, hipMemcpyDeviceToHost, q));
-  GLOC_HIP(hipStreamSynchronize(q));
-  size_t v = 0;
-  for (const Cell& c : all) {
-    if (!c.valid) continue;
-    if (v < capacity) {
-      if (out_key3)
-        for (int a = 0; a < 3; ++a) out_key3[3 * v + a] = (int32_t)((long long)((c.key >> (42 - 21 * a)) & 0x1FFFFF) - KEY_BIAS);
-      if (out_count) out_count[v] = c.count;
-      if (out_mean3)
-        for (int a = 0; a < 3; ++a) out_mean3[3 * v + a] = c.mean[a];
-      if (out_icov9) {
-        const double* I = c.icov;
-        const double full[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
-        std::copy(full, full + 9, out_icov9 + 9 * v);
-      }
-    }
-    ++v;
-  }
-  *n_cells = v;
-  GLOC_REQUIRE(v <= capacity || (!out_key3 && !out_count && !out_mean3 && !out_icov9), GLOC_ERR_INVALID,
-               "buffers hold %zu cells, the scan has %zu valid cells", capacity, v);
+  GLOC_TRY(voxmap::export_valid<Cell>(q, w.map, tc, capacity, out_key3, out_count, out_mean3, [&](const Cell& c, size_t row) {
+    const double* I = c.icov;
+    const double full[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
+    if (out_icov9) std::copy(full, full + 9, out_icov9 + 9 * row);
+  }, n_cells));
+  GLOC_REQUIRE(*n_cells <= capacity || (!out_key3 && !out_count && !out_mean3 && !out_icov9), GLOC_ERR_INVALID,
+               "buffers hold %zu cells, the scan has %zu valid cells", capacity, *n_cells);
   return GLOC_OK;
 }
 
@@ -409,7 +277,7 @@ int gloc_scan_store_add_approx_voxel(gloc_scan_store* st, uint32_t base_id, floa
   GLOC_REQUIRE(base.n < (1ull << 31), GLOC_ERR_INVALID, "scan too large");
   Ws w;
   uint32_t m = 0;
-  GLOC_TRY(approx_voxel(st->stream, w, base.xyz, (uint32_t)base.n, leaf, &m));
+  GLOC_TRY(approx_voxel(st->stream, w.map, w.filt, base.xyz, (uint32_t)base.n, leaf, &m));
   DevScan s;
   GLOC_TRY(reg::store_make_scan(st, w.filt.as<float>(), m, 3, true, &s));
   return reg::store_insert_scan(st, s, new_id);

@@ -1,13 +1,13 @@
 // ndt_kernels.hpp -- NDT scan registration on gfx950 (gloc_reg_ndt_*, gloc_scan_store_add_approx_voxel): the device
-// half of tests/ndt_ref.py, which states every step below in float64 numpy.  Included by ndt.hip, and by vgicp.hip for
-// the kernels that build the cells (keys, flags, scan, first, hash): the kernels are static, each file carries its copy.
+// half of tests/ndt_ref.py, which states every step below in float64 numpy.  Included by ndt.hip alone.  The kernels that
+// key, sort, scan and hash the cells are voxel_map_kernels.hpp's, shared with the voxelized generalized ICP; what a cell
+// holds (Cell, cell_stats_kernel) is here.
 //
 //   approximate voxel filter   avf_keys_kernel -> segmented radix sort by hash slot (stable) -> avf_flags_kernel
 //                              (a run of equal cells inside a slot starts here) -> flag scan -> avf_emit_kernel (the
 //                              run's fp32 sum in point order / count)
-//   cells of the targets       cell_keys_kernel -> segmented radix sort by packed cell key -> cell_flags_kernel ->
-//                              flag scan -> cell_stats_kernel (fp64 sums relative to the cell corner, Jacobi eigen,
-//                              inflation, inverse) -> cell_hash_kernel (open addressing, valid cells only)
+//   cells of the targets       the voxel map of voxel_map_kernels.hpp with cell_stats_kernel as its statistics kernel
+//                              (fp64 sums relative to the cell corner, Jacobi eigen, inflation, inverse)
 //   Newton / More-Thuente      rounds of (ndt_deriv_kernel: score + gradient [+ Hessian] partials per work-group,
 //                              ndt_state_kernel: one wave per candidate sums them in block order and steps its state)
 #pragma once
@@ -15,19 +15,23 @@
 #include <stdint.h>
 
 #include "math3.hpp"
+#include "voxel_map_kernels.hpp"
 
 namespace gloc {
 namespace ndt {
 
+using voxmap::KEY_BIAS;
+using voxmap::KEY_NONE;
+using voxmap::TgtDesc;
+using voxmap::hash_slot;
+using voxmap::pack_key;
+
 constexpr int HIST = 512;                     // ApproximateVoxelGrid's slots
 constexpr uint32_t AVF_INVALID = HIST;        // slot key of a point the filter skips (sorts last)
-constexpr int64_t KEY_BIAS = 1 << 20;         // packed cell key: 21 bits per axis
-constexpr unsigned long long KEY_NONE = ~0ull;
 constexpr int NACC = 28;                      // score, gradient 6, Hessian upper triangle 21
 constexpr int DERIV_THREADS = 256;
 constexpr int PTS_PER_THREAD = 2;
 constexpr int CHUNK = DERIV_THREADS * PTS_PER_THREAD;  // filtered source points per work-group
-constexpr int SCAN_BLOCK = 1024;
 
 enum Phase : int { PH_INIT = 0, PH_FIRST = 1, PH_MORE = 2, PH_HESS = 3, PH_DONE = 4 };
 
@@ -53,11 +57,6 @@ struct Out {
   double prob;
   uint32_t iters;
   int converged;
-};
-
-struct TgtDesc {  // a target scan of the batch: its points and its slice of the concatenated key / value arrays
-  const float* xyz;
-  uint32_t n, begin;
 };
 
 struct Cell {
@@ -187,53 +186,6 @@ __device__ inline void jacobi_eig6(double* A, double* V) {
   }
 }
 
-// ---- flag scan (exclusive prefix of 0 / 1 flags): block sums, one work-group over the block sums, block scan --------
-__device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* sh, uint32_t* total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < SCAN_BLOCK; o <<= 1) {
-    const uint32_t a = t >= o ? sh[t - o] : 0u;
-    __syncthreads();
-    sh[t] += a;
-    __syncthreads();
-  }
-  const uint32_t incl = sh[t];
-  if (total) *total = sh[SCAN_BLOCK - 1];
-  __syncthreads();
-  return incl - v;
-}
-
-static __global__ __launch_bounds__(SCAN_BLOCK) void scan_sum_kernel(const uint32_t* __restrict__ f, uint32_t n, uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t sh[SCAN_BLOCK];
-  const uint32_t i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-  uint32_t tot;
-  block_excl_scan(i < n ? f[i] : 0u, sh, &tot);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-static __global__ __launch_bounds__(SCAN_BLOCK) void scan_top_kernel(uint32_t* __restrict__ bsum, uint32_t nb, uint32_t* __restrict__ total) {
-  __shared__ uint32_t sh[SCAN_BLOCK];
-  uint32_t carry = 0;
-  for (uint32_t b0 = 0; b0 < nb; b0 += SCAN_BLOCK) {
-    const uint32_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nb ? bsum[i] : 0u;
-    uint32_t tot;
-    const uint32_t ex = block_excl_scan(v, sh, &tot);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
-static __global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const uint32_t* __restrict__ f, uint32_t n,
-                                                                const uint32_t* __restrict__ boff, uint32_t* __restrict__ pos) {
-  __shared__ uint32_t sh[SCAN_BLOCK];
-  const uint32_t i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-  const uint32_t ex = block_excl_scan(i < n ? f[i] : 0u, sh, nullptr);
-  if (i < n) pos[i] = boff[blockIdx.x] + ex;
-}
-
 // ---- approximate voxel filter ----------------------------------------------------------------------------------------
 __device__ inline bool avf_cell(const float* __restrict__ xyz, uint32_t i, float inv, int* k) {
   bool ok = true;
@@ -299,45 +251,7 @@ static __global__ void avf_emit_kernel(const float* __restrict__ xyz, uint32_t n
   out[3 * o + 2] = sz / fc;
 }
 
-// ---- target cells ----------------------------------------------------------------------------------------------------
-__device__ inline unsigned long long pack_key(long long kx, long long ky, long long kz) {
-  return ((unsigned long long)(kx + KEY_BIAS) << 42) | ((unsigned long long)(ky + KEY_BIAS) << 21) |
-         (unsigned long long)(kz + KEY_BIAS);
-}
-
-static __global__ void cell_keys_kernel(const TgtDesc* __restrict__ tg, float inv, unsigned long long* __restrict__ key,
-                                 uint32_t* __restrict__ val) {
-  const TgtDesc d = tg[blockIdx.y];
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= d.n) return;
-  long long k[3];
-  bool ok = true;
-  for (int a = 0; a < 3; ++a) {
-    const float f = floorf(d.xyz[3 * i + a] * inv);
-    ok = ok && fabsf(f) < (float)KEY_BIAS;
-    k[a] = ok ? (long long)f : 0;
-  }
-  key[d.begin + i] = ok ? pack_key(k[0], k[1], k[2]) : KEY_NONE;
-  val[d.begin + i] = i;
-}
-
-static __global__ void cell_flags_kernel(const TgtDesc* __restrict__ tg, const unsigned long long* __restrict__ key,
-                                  uint32_t* __restrict__ flag) {
-  const TgtDesc d = tg[blockIdx.y];
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= d.n) return;
-  const unsigned long long k = key[d.begin + i];
-  flag[d.begin + i] = (k != KEY_NONE && (i == 0 || key[d.begin + i - 1] != k)) ? 1u : 0u;
-}
-
-// first cell of every target (the scanned flag at its segment's start) and the total behind the last
-static __global__ void cell_first_kernel(const TgtDesc* __restrict__ tg, uint32_t n_tgt, const uint32_t* __restrict__ pos,
-                                  const uint32_t* __restrict__ total, uint32_t* __restrict__ first) {
-  for (uint32_t t = threadIdx.x; t < n_tgt; t += blockDim.x)
-    first[t] = tg[t].n ? pos[tg[t].begin] : 0u;  // (an empty target: fixed up on the host)
-  if (threadIdx.x == 0) first[n_tgt] = *total;
-}
-
+// ---- target cells (one thread per cell: the first of a run of equal keys) -------------------------------------------
 __device__ inline void inv_sym3(const double* C, double* I) {  // cofactors / determinant (Eigen's 3x3 inverse)
   const double a = C[0], b = C[1], c = C[2], d = C[4], e = C[5], f = C[8];
   const double A = d * f - e * e, B = c * e - b * f, Cc = b * e - c * d;
@@ -428,33 +342,6 @@ static __global__ void cell_stats_kernel(const TgtDesc* __restrict__ tg, const u
     }
   }
   cells[pos[d.begin + i]] = out;
-}
-
-__device__ __forceinline__ uint32_t hash_slot(unsigned long long k, uint32_t mask) {
-  return (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 32) & mask;
-}
-
-// hash tables: target t owns slots [toff[t], toff[t] + tmask[t] + 1); valid cells only.  CellT: anything with a key and
-// a valid flag (Cell here, the voxels of vgicp_kernels.hpp)
-template <class CellT>
-static __global__ void cell_hash_kernel(const uint32_t* __restrict__ first, const CellT* __restrict__ cells,
-                                 const uint32_t* __restrict__ toff, const uint32_t* __restrict__ tmask,
-                                 unsigned long long* __restrict__ hkey, uint32_t* __restrict__ hval) {
-  const uint32_t t = blockIdx.y;
-  const uint32_t c = first[t] + blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= first[t + 1] || !cells[c].valid) return;
-  const unsigned long long k = cells[c].key;
-  const uint32_t mask = tmask[t];
-  unsigned long long* hk = hkey + toff[t];
-  uint32_t s = hash_slot(k, mask);
-  while (true) {
-    const unsigned long long prev = atomicCAS(&hk[s], KEY_NONE, k);
-    if (prev == KEY_NONE) {
-      hval[toff[t] + s] = c;
-      return;
-    }
-    s = (s + 1) & mask;
-  }
 }
 
 // ---- derivatives -----------------------------------------------------------------------------------------------------

@@ -744,30 +744,11 @@ int run_refine(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, 
   ids[0] = src_id;
   css[0] = cs;
   std::copy(tgt_ids, tgt_ids + n, ids.begin() + 1);
-  {  // targets without normals get them (an allocation beside the scan: nothing a batch in flight reads moves)
-    std::lock_guard<std::mutex> lk(st->mu);
-    for (size_t c = 0; c < n; ++c) {
-      GLOC_REQUIRE(tgt_ids[c] < st->scans.size() && st->scans[tgt_ids[c]].live, GLOC_ERR_INVALID, "unknown scan id %u", tgt_ids[c]);
-      DevScan& t = st->scans[tgt_ids[c]];
-      if (t.nrm_k == 0) GLOC_TRY(store_build_normals(st, t, normal_k));
-    }
-    if (src_normals) {
-      GLOC_REQUIRE(src_id < st->scans.size() && st->scans[src_id].live, GLOC_ERR_INVALID, "unknown scan id %u", src_id);
-      DevScan& sc = st->scans[src_id];
-      if (sc.nrm_k == 0) GLOC_TRY(store_build_normals(st, sc, normal_k));
-    }
-  }
-  std::vector<DevScan> scans(1 + n);
-  GLOC_TRY(store_get_pinned(st, ids.data(), css.data(), ids.size(), scans.data()));
-  struct Unpin {
-    gloc_scan_store* st;
-    const std::vector<uint32_t>& ids;
-    hipStream_t s;
-    ~Unpin() {
-      (void)hipStreamSynchronize(s);
-      store_pin(st, ids.data(), ids.size(), -1);
-    }
-  } unpin{st, ids, s};
+  GLOC_TRY(store_ensure_normals(st, tgt_ids, n, normal_k));  // (an unknown source id without src_normals: refused by pin())
+  if (src_normals) GLOC_TRY(store_ensure_normals(st, &src_id, 1, normal_k));
+  ScopedPins pins(st, s);
+  GLOC_TRY(pins.pin(ids.data(), css.data(), ids.size()));
+  const std::vector<DevScan>& scans = pins.scans;
   const DevScan& src = scans[0];
   GLOC_REQUIRE(src.n >= 1 && src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
   GLOC_REQUIRE(!src_normals || src.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", src_id);

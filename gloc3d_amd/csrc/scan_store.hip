@@ -962,6 +962,16 @@ void store_pin(gloc_scan_store* st, const uint32_t* ids, size_t count, int delta
     if (ids[i] < st->scans.size() && st->scans[ids[i]].live) st->scans[ids[i]].pins += delta;
 }
 
+int store_ensure_normals(gloc_scan_store* st, const uint32_t* ids, size_t n, uint32_t k) {
+  std::lock_guard<std::mutex> lk(st->mu);
+  for (size_t c = 0; c < n; ++c) {
+    GLOC_REQUIRE(ids[c] < st->scans.size() && st->scans[ids[c]].live, GLOC_ERR_INVALID, "unknown scan id %u", ids[c]);
+    DevScan& s = st->scans[ids[c]];
+    if (s.nrm_k == 0) GLOC_TRY(store_build_normals(st, s, k));
+  }
+  return GLOC_OK;
+}
+
 }  // namespace reg
 }  // namespace gloc
 

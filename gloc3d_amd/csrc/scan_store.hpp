@@ -1,6 +1,7 @@
 // scan_store.hpp -- host-side view of the resident scan store (gloc_scan_store of include/gloc3d.h),
 // shared by scan_store.hip (which owns it) and reg.hip (whose registration handles read it).
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -101,6 +102,45 @@ int store_get_pinned(gloc_scan_store* st, const uint32_t* ids, const int* cs, si
 int store_build_normals(gloc_scan_store* st, DevScan& s, uint32_t k);
 // The pins' release (delta = -1) once the batch's event has been waited for.  Ids no longer live are skipped.
 void store_pin(gloc_scan_store* st, const uint32_t* ids, size_t count, int delta);
+// Scans without normals get them from k neighbours (takes store->mu; an allocation beside the scan: nothing a batch in
+// flight reads moves).  GLOC_ERR_INVALID for an unknown id.
+int store_ensure_normals(gloc_scan_store* st, const uint32_t* ids, size_t n, uint32_t k);
+
+// The scans of a synchronous call, pinned for as long as the holder lives: pin() is store_get_pinned (cs null: no launch
+// orders, the scans are only read) and `scans` its views; the destructor waits for the stream and lets the pins go.  A
+// pin() that failed has pinned nothing, and then nothing is let go.
+struct ScopedPins {
+  gloc_scan_store* st;
+  hipStream_t q;
+  std::vector<uint32_t> ids;
+  std::vector<DevScan> scans;
+  ScopedPins(gloc_scan_store* st_, hipStream_t q_) : st(st_), q(q_) {}
+  ScopedPins(const ScopedPins&) = delete;
+  ScopedPins& operator=(const ScopedPins&) = delete;
+  int pin(const uint32_t* ids_, const int* cs, size_t n) {
+    const std::vector<int> none(cs ? 0 : n, 0);
+    scans.resize(n);
+    GLOC_TRY(store_get_pinned(st, ids_, cs ? cs : none.data(), n, scans.data()));
+    ids.assign(ids_, ids_ + n);
+    return GLOC_OK;
+  }
+  ~ScopedPins() {
+    if (ids.empty()) return;
+    (void)hipStreamSynchronize(q);
+    store_pin(st, ids.data(), ids.size(), -1);
+  }
+};
+
+// The distinct ids of a list in order of first appearance, and for every entry its index among them.
+inline void distinct_in_order(const uint32_t* ids, size_t n, std::vector<uint32_t>* uniq, std::vector<uint32_t>* index_of) {
+  uniq->clear();
+  index_of->resize(n);
+  for (size_t c = 0; c < n; ++c) {
+    auto it = std::find(uniq->begin(), uniq->end(), ids[c]);
+    (*index_of)[c] = (uint32_t)(it - uniq->begin());
+    if (it == uniq->end()) uniq->push_back(ids[c]);
+  }
+}
 
 }  // namespace reg
 }  // namespace gloc

@@ -1,8 +1,8 @@
 // vgicp_kernels.hpp -- the device half of the voxelized generalized ICP refinement (gfx950; Koide et al., fast_gicp's
 // FastVGICP).  tests/vgicp_ref.py is the contract.
 //
-//   voxel map of the targets   the key, flag, scan, first and hash kernels of ndt_kernels.hpp as NDT runs them, with
-//                              voxel_stats_kernel here between them: one thread per voxel, fp64 sums relative to the voxel's
+//   voxel map of the targets   the voxel map of voxel_map_kernels.hpp (keys, sort, flags, scan, first, hash) with
+//                              voxel_stats_kernel here as its statistics kernel: one thread per voxel, fp64 sums relative to the voxel's
 //                              corner of its points and of its normals' outer products, in the scan's ORIGINAL order
 //   vgicp_accum_kernel         one lane per source point (sorted slot): p = R s + t in fp32 as the other refinements move it,
 //                              the voxel p falls into by the fp32 rule of cell_keys_kernel, and per offset of the
@@ -29,7 +29,7 @@
 
 #include "gn6_kernels.hpp"
 #include "math3.hpp"  // f32x4, xform, cross3
-#include "ndt_kernels.hpp"
+#include "voxel_map_kernels.hpp"
 
 namespace gloc {
 namespace vgicp {
@@ -39,8 +39,8 @@ using gn6::ACC_THREADS;
 using gn6::NSLOT;
 using gn6::NSUM;
 using gn6::State;
-using ndt::KEY_BIAS;
-using ndt::KEY_NONE;
+using voxmap::KEY_BIAS;
+using voxmap::KEY_NONE;
 
 struct Voxel {  // 88 B; the accumulate kernel reads the 80 behind the key
   unsigned long long key;
@@ -49,7 +49,7 @@ struct Voxel {  // 88 B; the accumulate kernel reads the 80 behind the key
   double nn[6];  // (1 / N) sum n n^T: xx xy xz yy yz zz
 };
 
-struct TgtAux {  // beside ndt::TgtDesc: where a target's normals are
+struct TgtAux {  // beside voxmap::TgtDesc: where a target's normals are
   const uint32_t* inv;  // original index -> position in the normals' order
   const float* nrm;     // packed, zero = none
 };
@@ -62,11 +62,11 @@ struct Target {  // of a job: its target's hash table and voxels
 };
 
 // one thread per voxel (the first of a run of equal keys), as ndt::cell_stats_kernel
-static __global__ void voxel_stats_kernel(const ndt::TgtDesc* __restrict__ tg, const TgtAux* __restrict__ aux,
+static __global__ void voxel_stats_kernel(const voxmap::TgtDesc* __restrict__ tg, const TgtAux* __restrict__ aux,
                                           const unsigned long long* __restrict__ key, const uint32_t* __restrict__ val,
                                           const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos, double res,
                                           uint32_t min_pts, Voxel* __restrict__ vox) {
-  const ndt::TgtDesc d = tg[blockIdx.y];
+  const voxmap::TgtDesc d = tg[blockIdx.y];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= d.n || !flag[d.begin + i]) return;
   const TgtAux a = aux[blockIdx.y];
@@ -155,8 +155,8 @@ static __global__ __launch_bounds__(ACC_THREADS) void vgicp_accum_kernel(const f
         offset_of(neighbors, o, d);
         const long long kx = home[0] + d[0], ky = home[1] + d[1], kz = home[2] + d[2];
         if (!(kx > -KEY_BIAS && kx < KEY_BIAS && ky > -KEY_BIAS && ky < KEY_BIAS && kz > -KEY_BIAS && kz < KEY_BIAS)) continue;
-        const unsigned long long key = ndt::pack_key(kx, ky, kz);
-        uint32_t slot = ndt::hash_slot(key, T.mask);
+        const unsigned long long key = voxmap::pack_key(kx, ky, kz);
+        uint32_t slot = voxmap::hash_slot(key, T.mask);
         uint32_t ci = 0xFFFFFFFFu;
         while (true) {  // (the table is at most half full: an empty slot ends every probe)
           const unsigned long long hk = T.hkey[slot];

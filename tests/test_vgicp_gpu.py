@@ -336,3 +336,45 @@ def test_handle_lifecycle_and_a_workspace_shared_with_generalized_icp(capi):
         assert d.store.bytes()[0] < live
     finally:
         d.close()
+
+
+def test_ndt_and_vgicp_interleaved_on_one_handle_equal_fresh_handles(capi):
+    """NDT and the voxelized refinement build their maps with one builder, each in a workspace of its own: called in turn on
+    ONE handle -- maps of one scan, batches over [A, empty, A, 70 points] (a repeated id, an empty target, a table of the
+    minimum size), then maps of another scan -- every call equals the same call made alone on a fresh handle, bit for bit.
+    NDT at 0.5 m and the voxelized refinement at 1.0 m: the two maps of a scan differ."""
+    from gloc3d_amd import synth
+    world = synth.make_world(1001)
+    a = np.ascontiguousarray(synth.lidar_scan(world, None, seed=1001, n_az=32)[:, :3])
+    s = np.ascontiguousarray(synth.lidar_scan(world, synth.se3(2.0, (0.3, -0.2, 0.05)), seed=1002, n_az=32)[:, :3])
+    c = np.ascontiguousarray(a[::len(a) // 70][:70])
+    assert 1900 < len(a) < 2100 and 1900 < len(s) < 2100 and len(c) == 70
+    store = capi.ScanStore()
+    src, A, B, C = (store.add(x) for x in (s, a, np.zeros((0, 3), np.float32), c))
+    tgts = [A, B, A, C]
+    ndt, vg = capi.default_ndt_params(resolution=0.5), capi.default_vgicp_params(resolution=1.0, neighbors=7, max_iters=3)
+    steps = [("ndt_cells A", lambda r: r.ndt_cells(A, ndt)), ("vgicp_voxels A", lambda r: r.vgicp_voxels(A, vg)),
+             ("ndt_batch", lambda r: r.ndt_batch(src, tgts, params=ndt)), ("vgicp_batch", lambda r: r.vgicp_batch(src, tgts, params=vg)),
+             ("ndt_cells C", lambda r: r.ndt_cells(C, ndt)), ("vgicp_voxels C", lambda r: r.vgicp_voxels(C, vg)),
+             ("ndt_batch again", lambda r: r.ndt_batch(src, tgts, params=ndt))]
+
+    def arrays(out):
+        return [out[k] for k in sorted(out)] if isinstance(out, dict) else list(out)
+
+    one = capi.Registrar(store=store)
+    try:
+        for name, call in steps:
+            fresh = capi.Registrar(store=store)
+            try:
+                want = arrays(call(fresh))
+            finally:
+                fresh.close()
+            got = arrays(call(one))
+            assert len(got) == len(want) and all(np.array_equal(g, w) for g, w in zip(got, want)), name
+            if name == "ndt_cells A":
+                assert len(got[0]) > 0                                          # (there are cells to compare)
+            if name == "vgicp_voxels A":
+                assert len(got[0]) > 100
+    finally:
+        one.close()
+        store.close()

@@ -71,6 +71,16 @@ class VgicpParams(C.Structure):
                 ("min_points", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class FpfhParams(C.Structure):
+    _fields_ = [("normal_k", C.c_uint32), ("feature_k", C.c_uint32), ("mutual", C.c_uint32), ("ransac_iters", C.c_uint32),
+                ("inlier_thresh", C.c_float), ("min_inlier_ratio", C.c_float), ("ransac_confidence", C.c_float),
+                ("reserved_", C.c_uint32), ("seed", C.c_uint64)]
+
+
+FPFH_DIM = 33          # floats per feature row
+FPFH_MATCH_TILE = 128  # target rows per tile of the matcher (csrc/fpfh.hpp MATCH_TILE_ROWS)
+
+
 class BevParams(C.Structure):
     _fields_ = [("resolution", C.c_float), ("max_range", C.c_float), ("out_width", C.c_uint32),
                 ("out_height", C.c_uint32), ("format", C.c_uint32), ("pad_bgr", C.c_uint8 * 3),
@@ -223,6 +233,12 @@ _PROTOS = [
     ("gloc_reg_vgicp_system", _i, [_vp, _u32, _u32, _vp, C.POINTER(VgicpParams), _vp, _vp, C.POINTER(C.c_double),
                                C.POINTER(C.c_uint64)]),
     ("gloc_reg_vgicp_voxels", _i, [_vp, _u32, C.POINTER(VgicpParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
+    ("gloc_fpfh_default_params", None, [C.POINTER(FpfhParams)]),
+    ("gloc_scan_store_build_fpfh", _i, [_vp, _u32, _u32, _u32]),
+    ("gloc_scan_store_fpfh", _i, [_vp, _u32, _vp, _sz]),
+    ("gloc_scan_store_spfh", _i, [_vp, _u32, _u32, _vp, _vp, _sz]),
+    ("gloc_reg_fpfh_match", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _vp, _vp]),
+    ("gloc_reg_fpfh_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FpfhParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
@@ -588,6 +604,16 @@ def default_vgicp_params(**over):
     return p
 
 
+def default_fpfh_params(**over):
+    """gloc_fpfh_params as gloc_fpfh_default_params leaves them (normal_k = 10, feature_k = 16, mutual matches, 3000
+    hypotheses at most, 0.6 m inliers, confidence 0.99, seed 1234), then `over`."""
+    p = FpfhParams()
+    lib().gloc_fpfh_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
 class ScanStore(_Handle):
     """Resident scans + their search index, shared by any number of Registrars."""
 
@@ -720,6 +746,25 @@ class ScanStore(_Handle):
         out = np.empty((n, 3), np.float32)
         check(lib().gloc_scan_store_normals(self._h, int(scan_id), _np_ptr(out), n))
         return out
+
+
+    def build_fpfh(self, scan_id, normal_k=10, feature_k=16):
+        """FPFH features of a resident scan (gloc_scan_store_build_fpfh); builds the normals too if the scan has none."""
+        check(lib().gloc_scan_store_build_fpfh(self._h, int(scan_id), int(normal_k), int(feature_k)))
+
+    def fpfh(self, scan_id):
+        """The scan's features [n, 33] float32 in original order; a zero row means "no feature"."""
+        n = self.points(scan_id)
+        out = np.empty((n, FPFH_DIM), np.float32)
+        check(lib().gloc_scan_store_fpfh(self._h, int(scan_id), _np_ptr(out), n))
+        return out
+
+    def spfh(self, scan_id, feature_k=16):
+        """Diagnostic: the SPFH counts [n, 33] uint16 and the pairs counted [n] uint32 (0: no SPFH) from the scan's normals."""
+        n = self.points(scan_id)
+        counts, used = np.empty((n, FPFH_DIM), np.uint16), np.empty(n, np.uint32)
+        check(lib().gloc_scan_store_spfh(self._h, int(scan_id), int(feature_k), _np_ptr(counts), _np_ptr(used), n))
+        return counts, used
 
 
 class Registrar(_Handle):
@@ -902,6 +947,31 @@ class Registrar(_Handle):
         check(lib().gloc_reg_gicp_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
                                          _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
         return H, g, s.value, c.value
+
+    def fpfh_match(self, src_feat, tgt_feat, mutual=True):
+        """Nearest feature of every source row among the target rows (gloc_reg_fpfh_match): idx [n_src] uint32
+        (0xFFFFFFFF: none kept), d2 [n_src] float32 (+inf there)."""
+        a = np.ascontiguousarray(src_feat, np.float32).reshape(-1, FPFH_DIM)
+        b = np.ascontiguousarray(tgt_feat, np.float32).reshape(-1, FPFH_DIM)
+        idx, d2 = np.empty(a.shape[0], np.uint32), np.empty(a.shape[0], np.float32)
+        check(lib().gloc_reg_fpfh_match(self._h, _np_ptr(a) if a.size else None, a.shape[0], _np_ptr(b) if b.size else None,
+                                        b.shape[0], 1 if mutual else 0, _np_ptr(idx) if idx.size else _np_ptr(np.empty(1, np.uint32)),
+                                        _np_ptr(d2) if d2.size else None))
+        return idx, d2
+
+    def fpfh_batch(self, src_id, tgt_ids, stream_ids=None, params=None):
+        """Feature-based global registration of scan src_id against each of tgt_ids (gloc_reg_fpfh_batch_ids), no initial
+        guess: returns dict(T [n, 4, 4] float32 source -> target, inliers [n], n_pairs [n], ok [n] bool).  T is a start for
+        p2l_batch / gicp_batch / batch_ids(init_T=...), not a refined pose."""
+        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
+        n = ids.shape[0]
+        prm = params or default_fpfh_params()
+        sid = None if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32).reshape(n)
+        T = np.empty((n, 4, 4), np.float32)
+        inl, npairs, ok = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        check(lib().gloc_reg_fpfh_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if sid is None else _np_ptr(sid), C.byref(prm),
+                                            _np_ptr(T), _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
+        return dict(T=T, inliers=inl, n_pairs=npairs, ok=ok.astype(bool))
 
     def vgicp_batch(self, src_id, tgt_ids, init_T=None, params=None):
         """Voxelized generalized ICP of scan src_id against each of tgt_ids (gloc_reg_vgicp_batch_ids): returns

@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256) void unsort_f4_kernel(const f32x4* __restrict_
   if (o < m) pts[o] = f32x4{p.x, p.y, p.z, 0.f};
 }
 
-int scan_normals(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, uint32_t k, float* out_normals) {
+int scan_knn(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, uint32_t k) {
   GLOC_REQUIRE(k >= 3 && k <= (uint32_t)KMAX, GLOC_ERR_INVALID, "k must be in [3, %d]", KMAX);
   if (m == 0) return GLOC_OK;
   const uint32_t nch = (m + KCH - 1) / KCH;
@@ -329,13 +329,20 @@ int scan_normals(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m
   GLOC_TRY(w.knn_d2.ensure(sizeof(float) * (size_t)m * k, s));
   GLOC_TRY(w.cbox_lo.ensure(sizeof(f32x4) * nch, s));
   GLOC_TRY(w.cbox_hi.ensure(sizeof(f32x4) * nch, s));
-  GLOC_TRY(w.bins.ensure(std::max<uint32_t>(m, 16), s));
-  GLOC_TRY(w.hist.ensure(sizeof(uint32_t) * 18, s));
-  GLOC_HIP(hipMemsetAsync(w.hist.p, 0, sizeof(uint32_t) * 18, s));
   hipLaunchKernelGGL(unsort_f4_kernel, dim3((m + 255) / 256), dim3(256), 0, s, spts, m, w.pts.as<f32x4>());
   hipLaunchKernelGGL(kchunk_boxes_kernel, dim3(nch), dim3(64), 0, s, spts, m, w.cbox_lo.as<f32x4>(), w.cbox_hi.as<f32x4>());
   hipLaunchKernelGGL(knn_culled_kernel, dim3((nch + 3) / 4), dim3(256), 0, s, spts, m, w.cbox_lo.as<f32x4>(),
                      w.cbox_hi.as<f32x4>(), nch, (int)k, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>());
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int scan_normals(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, uint32_t k, float* out_normals) {
+  GLOC_TRY(scan_knn(s, w, spts, m, k));
+  if (m == 0) return GLOC_OK;
+  GLOC_TRY(w.bins.ensure(std::max<uint32_t>(m, 16), s));
+  GLOC_TRY(w.hist.ensure(sizeof(uint32_t) * 18, s));
+  GLOC_HIP(hipMemsetAsync(w.hist.p, 0, sizeof(uint32_t) * 18, s));
   hipLaunchKernelGGL(normals_kernel, dim3((m + 255) / 256), dim3(256), 0, s, w.pts.as<f32x4>(), m, w.knn_idx.as<uint32_t>(),
                      (int)k, out_normals, w.bins.as<uint8_t>(), w.hist.as<uint32_t>());
   GLOC_HIP(hipGetLastError());

@@ -11,6 +11,12 @@ struct NormalsScratch {
   DevBuf pts, knn_idx, knn_d2, cbox_lo, cbox_hi, bins, hist;
 };
 
+// The exact k-NN lists of the m points of `spts` (any spatially coherent order: x, y, z, bits(original index)) within the
+// cloud, self included, ascending (d2, index): w.knn_idx / w.knn_d2 [m][k] by ORIGINAL index, entries a list cannot fill
+// 0xFFFFFFFF / FLT_MAX, and w.pts the points in original order.  What scan_normals and the FPFH features (fpfh.hip) both
+// start from.  Enqueued on s; k in [3, 16].
+int scan_knn(hipStream_t s, NormalsScratch& w, const reg::f32x4* spts, uint32_t m, uint32_t k);
+
 // Normals of the m points of `spts` (any spatially coherent order: x, y, z, bits(original index)) from their k nearest
 // neighbours within the cloud, as gloc_ground_normals computes them; out_normals [m][3] in ORIGINAL order (device).
 // Enqueued on s; k in [3, 16].

@@ -9,6 +9,7 @@
 
 #include "common.hpp"
 
+#include "fpfh.hpp"
 #include "ndt.hpp"
 #include "nn_compact.hpp"
 #include "gicp.hpp"
@@ -89,6 +90,7 @@ struct gloc_reg : Handle {
   gloc::ndt::Ws* ndt = nullptr;  // NDT workspace (ndt.hip), made on first use
   gloc::p2l::Ws* p2l = nullptr;  // point-to-plane / generalized ICP workspace (gn6.hpp), made on first use
   gloc::vgicp::Ws* vgicp = nullptr;  // voxelized generalized ICP's voxel maps (vgicp.hip), made on first use
+  gloc::fpfh::Ws* fpfh = nullptr;    // the feature matcher's keys and tables (fpfh.hip), made on first use
   ~gloc_reg() {  // (the handle's work has been waited for: destroy_handle)
     if (pending.active && pending.store) store_pin(pending.store, pending.pinned.data(), pending.pinned.size(), -1);
     if (store) store->attached--;
@@ -96,6 +98,7 @@ struct gloc_reg : Handle {
     gloc::ndt::ws_free(ndt);
     gloc::p2l::ws_free(p2l);
     gloc::vgicp::ws_free(vgicp);
+    gloc::fpfh::ws_free(fpfh);
     if (done_ev) (void)hipEventDestroy(done_ev);
     if (pin) (void)hipHostFree(pin);
   }
@@ -388,6 +391,96 @@ int ensure_pinned(gloc_reg* h, uint32_t n_jobs) {
   return GLOC_OK;
 }
 
+// The RANSAC stage on the pairs in v.pairs (jobs[c].n_src of them per job, sampled through jobs[c].src_inv when it is set):
+// hypotheses, scores, the sequential rule with its adaptive stop, the refit on the winner's inliers.  What
+// gloc_reg_batch_* runs behind its pairs pass and gloc_reg_fpfh_batch_ids behind its descriptor matches.
+struct RansacRule {
+  uint32_t iters;
+  float inlier_thresh, min_inlier_ratio, confidence;
+  uint64_t seed;
+};
+
+int enqueue_ransac(gloc_reg* h, const BatchDims& bd, const RansacRule& r, const WsView& v, uint32_t nblocks) {
+  const uint32_t n_jobs = v.n_jobs;
+  hipStream_t s = v.s;
+  const uint32_t H = r.iters;
+  // Phases of hypotheses, each generated, scored and scanned before the next: with the adaptive stop (the
+  // reference's call: confidence 0.99) and ~85 % inliers the iteration count drops to 5 - 8 at the first good
+  // hypothesis, so [0, 16) settles nearly every job, [16, 64) most of the rest; a job that is done is skipped by the
+  // later phases (its blocks exit at once).  The rule is sequential in h (ransac_scan_kernel), so the split does not
+  // change the result.  (Round 2 scored 64 first: 2.1 ms per step of 500 jobs, 0.6 with 16.)
+  const bool adaptive = r.confidence > 0.f && r.confidence < 1.f;
+  uint32_t bounds[4] = {0u, 0u, 0u, 0u};
+  int n_ph = 0;
+  for (uint32_t b : {adaptive ? 16u : 256u, adaptive ? 64u : H, H})
+    if (b <= H && b > bounds[n_ph]) bounds[++n_ph] = b;
+  if (bounds[n_ph] < H) bounds[++n_ph] = H;
+  GLOC_HIP(hipMemsetAsync(v.valid, 0, sizeof(uint32_t) * (size_t)H * n_jobs, s));  // never-generated = invalid
+  GLOC_HIP(hipMemsetAsync(v.inliers, 0, sizeof(uint32_t) * (size_t)H * n_jobs, s));
+  const float thr2 = r.inlier_thresh * r.inlier_thresh;
+  // pairs per work-group of the scoring: 4096 -- or 1024 in a small batch (one query alone: 20 jobs x 31 chunks = 620
+  // work-groups for 256 CUs, each walking 16 tiles behind two barriers: 75 us for the first 16 hypotheses)
+  const uint32_t chunk_len = (size_t)n_jobs * ((bd.max_src + SC_CHUNK - 1) / SC_CHUNK) >= 2048 ? (uint32_t)SC_CHUNK : 1024u;
+  static_assert(1024 % SC_STAGE == 0 && SC_CHUNK % SC_STAGE == 0, "whole tiles");
+  const unsigned cchunks = (bd.max_src + chunk_len - 1) / chunk_len;
+  for (int ph = 0; ph < n_ph; ++ph) {
+    const uint32_t h0 = bounds[ph], h1 = bounds[ph + 1], len = h1 - h0;
+    const CandState* st = ph ? v.states : (const CandState*)nullptr;
+    {
+      ProfScope ps(h->prof, "ransac_hyp", s);
+      hipLaunchKernelGGL(ransac_hyp_kernel, dim3((len + 127) / 128, n_jobs), dim3(128), 0, s, v.pairs, bd.ld,
+                         v.jobs, r.seed, H, h0, h1, st, v.Rt, v.valid);
+      GLOC_HIP(hipGetLastError());
+    }
+    ProfScope ps(h->prof, "ransac_score", s);
+    // hypotheses per work-group: 16 / 64 (its four waves share them and split every staged tile) or thread <-> hypothesis
+    const uint32_t hpb = len <= 16 ? 16u : (len <= 64 ? 64u : 256u);
+    const unsigned NP = 8;
+    if (!adaptive && ph > 0 && len >= 512 && cchunks >= NP) {
+      // every hypothesis scored, not every pair of every hypothesis: an eighth of the pairs at a time, the hypotheses
+      // that can no longer beat the first phase's winner dropped in between (ransac_alive_kernel)
+      uint32_t* a_idx = v.a_idx;
+      uint32_t* a_cnt = v.a_cnt;
+      for (unsigned q = 0; q < NP; ++q) {
+        const unsigned c0 = q * cchunks / NP, c1 = (q + 1) * cchunks / NP;
+        hipLaunchKernelGGL(ransac_alive_kernel, dim3(n_jobs), dim3(1024), 0, s, v.inliers, v.valid,
+                           H, h0, h1, v.jobs, v.states, (uint32_t)(c0 * chunk_len), a_idx, a_cnt);
+        hipLaunchKernelGGL(ransac_score_kernel, dim3((len + 255) / 256, c1 - c0, n_jobs), dim3(256), 0, s,
+                           v.pairs, bd.ld, v.jobs, H, h0, 256u, v.Rt,
+                           v.valid, thr2, st, v.inliers, a_idx, a_cnt, (uint32_t)c0, chunk_len);
+      }
+    } else {
+      hipLaunchKernelGGL(ransac_score_kernel, dim3((len + hpb - 1) / hpb, cchunks, n_jobs), dim3(256), 0, s,
+                         v.pairs, bd.ld, v.jobs, H, h0, hpb, v.Rt,
+                         v.valid, thr2, st, v.inliers, (const uint32_t*)nullptr,
+                         (const uint32_t*)nullptr, 0u, chunk_len);
+    }
+    if (ph + 1 < n_ph)
+      hipLaunchKernelGGL(ransac_scan_kernel<false>, dim3(n_jobs), dim3(64), 0, s, v.inliers,
+                         v.valid, v.Rt, H, h0, h1, v.jobs, r.confidence,
+                         r.min_inlier_ratio, v.states);
+    else
+      hipLaunchKernelGGL(ransac_scan_kernel<true>, dim3(n_jobs), dim3(64), 0, s, v.inliers,
+                         v.valid, v.Rt, H, h0, h1, v.jobs, r.confidence,
+                         r.min_inlier_ratio, v.states);
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "accum", s);  // refit on the best hypothesis' inliers
+    hipLaunchKernelGGL(accum_kernel<1>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, s, v.jobs,
+                       v.states, v.corr, v.d2,
+                       v.pairs, bd.ld, thr2, v.partials, bd.n_part);
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "solve", s);
+    hipLaunchKernelGGL(solve_kernel<1>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(SOLVE_THREADS), 0, s, v.partials,
+                       bd.n_part, false, v.jobs, v.states, v.split, n_jobs);
+    GLOC_HIP(hipGetLastError());
+  }
+  return GLOC_OK;
+}
+
 // The launches of a batch: S1 -> S2 (RANSAC + refit) -> S3 (ICP).  chained: its warm passes are one launch (batch_chains).
 int enqueue_pipeline(gloc_reg* h, const BatchDims& bd, const gloc_reg_params* prm, const WsView& v, bool can, bool any_tgt,
                      uint32_t nblocks, bool chained) {
@@ -398,83 +491,10 @@ int enqueue_pipeline(gloc_reg* h, const BatchDims& bd, const gloc_reg_params* pr
   bool have_corr = false;  // corr holds a previous pass's result: warm start for the next one
 
   if (can && any_tgt && prm->ransac_iters > 0) {
-    const uint32_t H = prm->ransac_iters;
     GLOC_TRY(launch_nn(h, bd, v, false, true, 0.f));
     have_corr = true;
-    // Phases of hypotheses, each generated, scored and scanned before the next: with the adaptive stop (the
-    // reference's call: confidence 0.99) and ~85 % inliers the iteration count drops to 5 - 8 at the first good
-    // hypothesis, so [0, 16) settles nearly every job, [16, 64) most of the rest; a job that is done is skipped by the
-    // later phases (its blocks exit at once).  The rule is sequential in h (ransac_scan_kernel), so the split does not
-    // change the result.  (Round 2 scored 64 first: 2.1 ms per step of 500 jobs, 0.6 with 16.)
-    const bool adaptive = prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f;
-    uint32_t bounds[4] = {0u, 0u, 0u, 0u};
-    int n_ph = 0;
-    for (uint32_t b : {adaptive ? 16u : 256u, adaptive ? 64u : H, H})
-      if (b <= H && b > bounds[n_ph]) bounds[++n_ph] = b;
-    if (bounds[n_ph] < H) bounds[++n_ph] = H;
-    GLOC_HIP(hipMemsetAsync(v.valid, 0, sizeof(uint32_t) * (size_t)H * n_jobs, s));  // never-generated = invalid
-    GLOC_HIP(hipMemsetAsync(v.inliers, 0, sizeof(uint32_t) * (size_t)H * n_jobs, s));
-    const float thr2 = prm->inlier_thresh * prm->inlier_thresh;
-    // pairs per work-group of the scoring: 4096 -- or 1024 in a small batch (one query alone: 20 jobs x 31 chunks = 620
-    // work-groups for 256 CUs, each walking 16 tiles behind two barriers: 75 us for the first 16 hypotheses)
-    const uint32_t chunk_len = (size_t)n_jobs * ((bd.max_src + SC_CHUNK - 1) / SC_CHUNK) >= 2048 ? (uint32_t)SC_CHUNK : 1024u;
-    static_assert(1024 % SC_STAGE == 0 && SC_CHUNK % SC_STAGE == 0, "whole tiles");
-    const unsigned cchunks = (bd.max_src + chunk_len - 1) / chunk_len;
-    for (int ph = 0; ph < n_ph; ++ph) {
-      const uint32_t h0 = bounds[ph], h1 = bounds[ph + 1], len = h1 - h0;
-      const CandState* st = ph ? v.states : (const CandState*)nullptr;
-      {
-        ProfScope ps(h->prof, "ransac_hyp", s);
-        hipLaunchKernelGGL(ransac_hyp_kernel, dim3((len + 127) / 128, n_jobs), dim3(128), 0, s, v.pairs, bd.ld,
-                           v.jobs, prm->seed, H, h0, h1, st, v.Rt, v.valid);
-        GLOC_HIP(hipGetLastError());
-      }
-      ProfScope ps(h->prof, "ransac_score", s);
-      // hypotheses per work-group: 16 / 64 (its four waves share them and split every staged tile) or thread <-> hypothesis
-      const uint32_t hpb = len <= 16 ? 16u : (len <= 64 ? 64u : 256u);
-      const unsigned NP = 8;
-      if (!adaptive && ph > 0 && len >= 512 && cchunks >= NP) {
-        // every hypothesis scored, not every pair of every hypothesis: an eighth of the pairs at a time, the hypotheses
-        // that can no longer beat the first phase's winner dropped in between (ransac_alive_kernel)
-        uint32_t* a_idx = v.a_idx;
-        uint32_t* a_cnt = v.a_cnt;
-        for (unsigned q = 0; q < NP; ++q) {
-          const unsigned c0 = q * cchunks / NP, c1 = (q + 1) * cchunks / NP;
-          hipLaunchKernelGGL(ransac_alive_kernel, dim3(n_jobs), dim3(1024), 0, s, v.inliers, v.valid,
-                             H, h0, h1, v.jobs, v.states, (uint32_t)(c0 * chunk_len), a_idx, a_cnt);
-          hipLaunchKernelGGL(ransac_score_kernel, dim3((len + 255) / 256, c1 - c0, n_jobs), dim3(256), 0, s,
-                             v.pairs, bd.ld, v.jobs, H, h0, 256u, v.Rt,
-                             v.valid, thr2, st, v.inliers, a_idx, a_cnt, (uint32_t)c0, chunk_len);
-        }
-      } else {
-        hipLaunchKernelGGL(ransac_score_kernel, dim3((len + hpb - 1) / hpb, cchunks, n_jobs), dim3(256), 0, s,
-                           v.pairs, bd.ld, v.jobs, H, h0, hpb, v.Rt,
-                           v.valid, thr2, st, v.inliers, (const uint32_t*)nullptr,
-                           (const uint32_t*)nullptr, 0u, chunk_len);
-      }
-      if (ph + 1 < n_ph)
-        hipLaunchKernelGGL(ransac_scan_kernel<false>, dim3(n_jobs), dim3(64), 0, s, v.inliers,
-                           v.valid, v.Rt, H, h0, h1, v.jobs, prm->ransac_confidence,
-                           prm->min_inlier_ratio, v.states);
-      else
-        hipLaunchKernelGGL(ransac_scan_kernel<true>, dim3(n_jobs), dim3(64), 0, s, v.inliers,
-                           v.valid, v.Rt, H, h0, h1, v.jobs, prm->ransac_confidence,
-                           prm->min_inlier_ratio, v.states);
-      GLOC_HIP(hipGetLastError());
-    }
-    {
-      ProfScope ps(h->prof, "accum", s);  // refit on the best hypothesis' inliers
-      hipLaunchKernelGGL(accum_kernel<1>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, s, v.jobs,
-                         v.states, v.corr, v.d2,
-                         v.pairs, bd.ld, thr2, v.partials, bd.n_part);
-      GLOC_HIP(hipGetLastError());
-    }
-    {
-      ProfScope ps(h->prof, "solve", s);
-      hipLaunchKernelGGL(solve_kernel<1>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(SOLVE_THREADS), 0, s, v.partials,
-                         bd.n_part, false, v.jobs, v.states, v.split, n_jobs);
-      GLOC_HIP(hipGetLastError());
-    }
+    GLOC_TRY(enqueue_ransac(h, bd, RansacRule{prm->ransac_iters, prm->inlier_thresh, prm->min_inlier_ratio, prm->ransac_confidence, prm->seed},
+                            v, nblocks));
   }
   for (uint32_t it = 0; it < prm->icp_iters && can && any_tgt; ++it) {
     if (chained && have_corr) {  // a small batch: all the passes that are left in one launch
@@ -828,6 +848,138 @@ int run_gicp(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, co
                       return gloc::gicp::run(x, src_nrm, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum,
                                              out_count);
                     });
+}
+
+// FPFH feature-based global registration (fpfh.hip): the descriptor matches of the source against every target, forward and
+// -- mutual -- backward in ONE launch, compacted per job into the pairs layout, and enqueue_ransac on them from the
+// identity.  The Job of such a batch carries what the RANSAC kernels read: the pair count as n_src (written on the device
+// by the compaction), no src_inv (the sampled ids ARE positions of the list), the stream id.  Synchronous; scans pinned.
+__global__ void set_pair_counts_kernel(Job* __restrict__ jobs, const uint32_t* __restrict__ counts, uint32_t n_jobs) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < n_jobs) jobs[c].n_src = counts[c];
+}
+
+int run_fpfh(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const uint32_t* stream_ids, const gloc_fpfh_params* prm,
+             float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+  GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
+  GLOC_REQUIRE(h->store, GLOC_ERR_INVALID, "unknown scan id %u", src_id);
+  gloc_scan_store* st = h->store;
+  hipStream_t s = h->stream;
+  std::vector<uint32_t> ids(1 + n);
+  ids[0] = src_id;
+  std::copy(tgt_ids, tgt_ids + n, ids.begin() + 1);
+  GLOC_TRY(store_ensure_fpfh(st, ids.data(), ids.size(), prm->normal_k, prm->feature_k));
+  ScopedPins pins(st, s);
+  GLOC_TRY(pins.pin(ids.data(), nullptr, ids.size()));
+  const std::vector<DevScan>& scans = pins.scans;
+  const DevScan& src = scans[0];
+  GLOC_REQUIRE(src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is too large");
+  for (const DevScan& sc : scans)
+    GLOC_REQUIRE(sc.n == 0 || (sc.fpfh && sc.has_fpfh(prm->normal_k, prm->feature_k)), GLOC_ERR_STATE, "a scan lost its features during the call");
+  const uint32_t n_jobs = (uint32_t)n;
+  const bool mutual = prm->mutual != 0;
+  static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  for (uint32_t c = 0; c < n_jobs; ++c) {
+    memcpy(out_T + 16 * (size_t)c, I16, sizeof(I16));
+    if (out_inliers) out_inliers[c] = 0;
+    if (out_n_pairs) out_n_pairs[c] = 0;
+    if (out_ok) out_ok[c] = 0;
+  }
+  if (src.n < 3) return GLOC_OK;  // fewer than three pairs whatever matches
+  GLOC_TRY(ensure_ws(&h->fpfh));
+  gloc::fpfh::Ws& w = *h->fpfh;
+  BatchDims bd{n_jobs, (uint32_t)src.n, 0, 0, 0};
+  const uint32_t nblocks = (bd.max_src + ACC_PER_BLOCK - 1) / ACC_PER_BLOCK;
+  bd.n_part = (std::max<uint32_t>(nblocks, 1) + 31u) & ~31u;
+  bd.ld = ((size_t)bd.max_src + 127) & ~(size_t)127;
+  // keys: [job][src.n] forward, then each job's backward row of its target's length
+  std::vector<size_t> back_off(n_jobs, 0);
+  size_t n_keys = (size_t)n_jobs * src.n;
+  for (uint32_t c = 0; c < n_jobs && mutual; ++c) {
+    back_off[c] = n_keys;
+    n_keys += scans[1 + c].n;
+  }
+  GLOC_TRY(w.keys.ensure(sizeof(unsigned long long) * n_keys, s));
+  GLOC_HIP(hipMemsetAsync(w.keys.p, 0xFF, sizeof(unsigned long long) * n_keys, s));
+  unsigned long long* keys = w.keys.as<unsigned long long>();
+  std::vector<gloc::fpfh::MatchTask> tasks;
+  std::vector<gloc::fpfh::PairJob> pj(n_jobs);
+  for (uint32_t c = 0; c < n_jobs; ++c) {
+    const DevScan& t = scans[1 + c];
+    unsigned long long* fwd = keys + (size_t)c * src.n;
+    unsigned long long* bwd = mutual ? keys + back_off[c] : nullptr;
+    if (t.n) {
+      tasks.push_back(gloc::fpfh::MatchTask{src.fpfh, src.idx.pts, t.fpfh, t.idx.pts, fwd, (uint32_t)src.n, (uint32_t)t.n});
+      if (mutual) tasks.push_back(gloc::fpfh::MatchTask{t.fpfh, t.idx.pts, src.fpfh, src.idx.pts, bwd, (uint32_t)t.n, (uint32_t)src.n});
+    }
+    pj[c] = gloc::fpfh::PairJob{fwd, bwd, src.xyz, t.xyz, (uint32_t)src.n, (uint32_t)t.n};
+  }
+  GLOC_TRY(ensure_pinned(h, n_jobs));
+  h->chain_in_batch = false;
+  for (uint32_t c = 0; c < n_jobs; ++c) {
+    h->h_jobs[c] = Job{nullptr, nullptr, nullptr, nullptr, ScanIndexDev{}, 0u, 0u, stream_ids ? stream_ids[c] : c, 0u};
+    init_state(h->h_states[c], nullptr, prm->ransac_iters);
+  }
+  const size_t H = prm->ransac_iters;
+  const bool adaptive = prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f;
+  GLOC_TRY(h->jobs.ensure(sizeof(Job) * n_jobs, s));
+  GLOC_TRY(h->states.ensure(sizeof(CandState) * n_jobs, s));
+  GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part * n_jobs, s));
+  GLOC_TRY(h->pairs.ensure(sizeof(f32x4) * 2 * bd.ld * n_jobs, s));
+  GLOC_TRY(h->Rt.ensure(sizeof(float) * 12 * H * n_jobs, s));
+  GLOC_TRY(h->valid.ensure(sizeof(uint32_t) * H * n_jobs, s));
+  GLOC_TRY(h->inliers.ensure(sizeof(uint32_t) * H * n_jobs, s));
+  if (!adaptive) GLOC_TRY(h->alive.ensure(sizeof(uint32_t) * (H + 1) * n_jobs, s));
+  GLOC_TRY(w.counts.ensure(sizeof(uint32_t) * n_jobs, s));
+  GLOC_HIP(hipMemcpyAsync(h->jobs.p, h->h_jobs, sizeof(Job) * n_jobs, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->states.p, h->h_states, sizeof(CandState) * n_jobs, hipMemcpyHostToDevice, s));
+  {
+    ProfScope ps(h->prof, "fpfh_match", s);
+    GLOC_TRY(gloc::fpfh::match(s, w, tasks));
+  }
+  {
+    ProfScope ps(h->prof, "fpfh_pairs", s);
+    GLOC_TRY(gloc::fpfh::pairs(s, w, pj, bd.ld, h->pairs.as<f32x4>(), w.counts.as<uint32_t>()));
+  }
+  hipLaunchKernelGGL(set_pair_counts_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, s, h->jobs.as<Job>(), w.counts.as<uint32_t>(), n_jobs);
+  GLOC_HIP(hipGetLastError());
+  h->split = NnSplit{};
+  WsView v{};
+  v.s = s;
+  v.n_jobs = n_jobs;
+  v.jobs = h->jobs.as<Job>();
+  v.states = h->states.as<CandState>();
+  v.partials = h->partials.as<double>();
+  v.pairs = h->pairs.as<f32x4>();
+  v.Rt = h->Rt.as<float>();
+  v.valid = h->valid.as<uint32_t>();
+  v.inliers = h->inliers.as<uint32_t>();
+  if (!adaptive) {
+    v.a_idx = h->alive.as<uint32_t>();
+    v.a_cnt = h->alive.as<uint32_t>() + H * n_jobs;
+  }
+  GLOC_TRY(enqueue_ransac(h, bd, RansacRule{prm->ransac_iters, prm->inlier_thresh, prm->min_inlier_ratio, prm->ransac_confidence, prm->seed}, v,
+                          nblocks));
+  std::vector<uint32_t> counts(n_jobs);
+  GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState) * n_jobs, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipMemcpyAsync(counts.data(), w.counts.p, sizeof(uint32_t) * n_jobs, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipStreamSynchronize(s));
+  for (uint32_t c = 0; c < n_jobs; ++c) {
+    const CandState& cs = h->h_states[c];
+    float* T = out_T + 16 * (size_t)c;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) T[4 * i + j] = cs.Tf[3 * i + j];
+      T[4 * i + 3] = cs.Tf[9 + i];
+    }
+    const uint32_t M = counts[c];
+    const bool found = cs.best_h != 0xFFFFFFFFu && M >= 3;
+    if (out_n_pairs) out_n_pairs[c] = M;
+    if (out_inliers) out_inliers[c] = found ? cs.best_inl : 0u;
+    // ok by the stage's own statement of the threshold: max(3, ceil(min_inlier_ratio M)), the product in fp64
+    const double need = std::max(3.0, std::ceil((double)prm->min_inlier_ratio * (double)M));
+    if (out_ok) out_ok[c] = found && (double)cs.best_inl >= need;
+  }
+  return GLOC_OK;
 }
 
 }  // namespace
@@ -1506,6 +1658,60 @@ int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params
   GLOC_HIP(hipSetDevice(h->device));
   const gloc::vgicp::Ctx x{h->store, h->stream, &h->prof, &h->vgicp, &h->p2l};
   return gloc::vgicp::voxels(x, scan_id, prm, capacity, out_key3, out_count, out_mean3, out_nn6, n_voxels);
+}
+
+// (the parameters are looked at before the handle, as generalized ICP's are)
+int gloc_reg_fpfh_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
+                            const gloc_fpfh_params* prm, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+  GLOC_TRY(gloc::fpfh::check_params(prm));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_fpfh(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, out_T, out_inliers, out_n_pairs, out_ok);
+}
+
+int gloc_reg_fpfh_match(gloc_reg* h, const float* src_feat, size_t n_src, const float* tgt_feat, size_t n_tgt, uint32_t mutual,
+                        uint32_t* out_idx, float* out_d2) {
+  GLOC_REQUIRE(h && out_idx && (src_feat || n_src == 0) && (tgt_feat || n_tgt == 0), GLOC_ERR_INVALID, "null argument");
+  GLOC_REQUIRE(n_src < (1ull << 31) && n_tgt < (1ull << 31), GLOC_ERR_INVALID, "too many rows");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  for (size_t i = 0; i < n_src; ++i) {
+    out_idx[i] = 0xFFFFFFFFu;
+    if (out_d2) out_d2[i] = INFINITY;
+  }
+  if (n_src == 0 || n_tgt == 0) return GLOC_OK;
+  GLOC_TRY(ensure_ws(&h->fpfh));
+  gloc::fpfh::Ws& w = *h->fpfh;
+  hipStream_t s = h->stream;
+  const size_t row = sizeof(float) * gloc::fpfh::FEAT_DIM, n_keys = n_src + (mutual ? n_tgt : 0);
+  GLOC_TRY(w.feat_a.ensure(row * n_src, s));
+  GLOC_TRY(w.feat_b.ensure(row * n_tgt, s));
+  GLOC_TRY(w.keys.ensure(sizeof(unsigned long long) * n_keys, s));
+  GLOC_HIP(hipMemcpyAsync(w.feat_a.p, src_feat, row * n_src, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(w.feat_b.p, tgt_feat, row * n_tgt, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemsetAsync(w.keys.p, 0xFF, sizeof(unsigned long long) * n_keys, s));
+  unsigned long long* keys = w.keys.as<unsigned long long>();
+  std::vector<gloc::fpfh::MatchTask> tasks;
+  tasks.push_back(gloc::fpfh::MatchTask{w.feat_a.as<float>(), nullptr, w.feat_b.as<float>(), nullptr, keys, (uint32_t)n_src, (uint32_t)n_tgt});
+  if (mutual)
+    tasks.push_back(gloc::fpfh::MatchTask{w.feat_b.as<float>(), nullptr, w.feat_a.as<float>(), nullptr, keys + n_src, (uint32_t)n_tgt, (uint32_t)n_src});
+  {
+    ProfScope ps(h->prof, "fpfh_match", s);
+    GLOC_TRY(gloc::fpfh::match(s, w, tasks));
+  }
+  std::vector<unsigned long long> hk(n_keys);
+  GLOC_HIP(hipMemcpyAsync(hk.data(), w.keys.p, sizeof(unsigned long long) * n_keys, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipStreamSynchronize(s));
+  for (size_t i = 0; i < n_src; ++i) {
+    if (hk[i] == ~0ull) continue;
+    const uint32_t j = (uint32_t)(hk[i] & 0xFFFFFFFFull), bits = (uint32_t)(hk[i] >> 32);
+    if (j >= n_tgt) continue;
+    if (mutual && (hk[n_src + j] == ~0ull || (uint32_t)(hk[n_src + j] & 0xFFFFFFFFull) != (uint32_t)i)) continue;
+    out_idx[i] = j;
+    if (out_d2) memcpy(&out_d2[i], &bits, 4);
+  }
+  return GLOC_OK;
 }
 
 int gloc_reg_profile(gloc_reg* h, const char* kernel, double* total_ms, uint64_t* launches) {

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <new>
 
+#include "fpfh.hpp"
 #include "scan_store.hpp"
 #include "seg_sort.hpp"
 #include <cmath>
@@ -598,6 +599,7 @@ void store_free_scan(gloc_scan_store* st, DevScan& s, bool cache_block) {
     }
   }
   if (s.nrm) (void)hipFree(s.nrm);
+  if (s.fpfh) (void)hipFree(s.fpfh);
   s = DevScan{};
 }
 
@@ -629,12 +631,54 @@ int store_build_normals(gloc_scan_store* st, DevScan& s, uint32_t k) {
     if (s.live) st->live_bytes += 12 * s.n;
   }
   s.nrm_k = 0;
+  s.fpfh_nk = s.fpfh_fk = 0;  // (features of the old normals: rebuilt on the next request)
   GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
   GLOC_TRY(gloc::ground::scan_normals(q, st->nrm_ws, s.idx.pts, n, k, st->nrm_tmp.as<float>()));
   hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, s.idx.pts, n, st->nrm_tmp.as<float>(), s.nrm, true);
   GLOC_HIP(hipGetLastError());
   GLOC_HIP(hipStreamSynchronize(q));
   s.nrm_k = k;
+  return GLOC_OK;
+}
+
+// SPFH of a scan with normals into st->spfh_tmp (original order); the lists stay in st->nrm_ws for build_fpfh.
+static int store_spfh(gloc_scan_store* st, const DevScan& s, uint32_t feature_k) {
+  hipStream_t q = st->stream;
+  const uint32_t n = (uint32_t)s.n;
+  GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
+  GLOC_TRY(st->spfh_tmp.ensure((size_t)gloc::fpfh::SPFH_BYTES * s.n, q));
+  hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, s.idx.pts, n, s.nrm, st->nrm_tmp.as<float>(), false);
+  GLOC_HIP(hipGetLastError());
+  return gloc::fpfh::build_spfh(q, st->nrm_ws, s.idx.pts, st->nrm_tmp.as<float>(), n, feature_k, st->spfh_tmp.as<uint8_t>());
+}
+
+int store_build_fpfh(gloc_scan_store* st, DevScan& s, uint32_t normal_k, uint32_t feature_k) {
+  GLOC_REQUIRE(normal_k >= 3 && normal_k <= 16, GLOC_ERR_INVALID, "normal_k = %u outside [3, 16]", normal_k);
+  GLOC_REQUIRE(feature_k >= 4 && feature_k <= 16, GLOC_ERR_INVALID, "feature_k = %u outside [4, 16]", feature_k);
+  if (s.n == 0) {
+    s.nrm_k = s.fpfh_nk = normal_k;
+    s.fpfh_fk = feature_k;
+    return GLOC_OK;
+  }
+  if (s.has_fpfh(normal_k, feature_k)) return GLOC_OK;
+  GLOC_REQUIRE(!s.fpfh || s.pins == 0, GLOC_ERR_STATE,
+               "the scan's features (normal_k = %u, feature_k = %u) may be read by %d batch(es) in flight: not rebuilt with %u, %u", s.fpfh_nk,
+               s.fpfh_fk, s.pins, normal_k, feature_k);
+  GLOC_TRY(store_build_normals(st, s, normal_k));
+  hipStream_t q = st->stream;
+  const uint32_t n = (uint32_t)s.n;
+  if (!s.fpfh) {
+    GLOC_HIP(hipMalloc(reinterpret_cast<void**>(&s.fpfh), 132 * s.n));
+    if (s.live) st->live_bytes += 132 * s.n;
+  }
+  s.fpfh_nk = s.fpfh_fk = 0;
+  GLOC_TRY(st->fpfh_tmp.ensure(132 * s.n, q));
+  GLOC_TRY(store_spfh(st, s, feature_k));
+  GLOC_TRY(gloc::fpfh::build_fpfh(q, st->nrm_ws, st->spfh_tmp.as<uint8_t>(), n, feature_k, st->fpfh_tmp.as<float>()));
+  GLOC_TRY(gloc::fpfh::reorder_rows(q, s.idx.pts, n, st->fpfh_tmp.as<float>(), s.fpfh, gloc::fpfh::FEAT_DIM, true));
+  GLOC_HIP(hipStreamSynchronize(q));
+  s.fpfh_nk = normal_k;
+  s.fpfh_fk = feature_k;
   return GLOC_OK;
 }
 
@@ -880,6 +924,13 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
         hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, todo[i]->idx.pts, n, todo[i]->nrm,
                            nrm_keep[i].as<float>(), false);
       }
+    std::vector<DevBuf> fpfh_keep(cnt);  // (and so do the features)
+    for (uint32_t i = 0; i < cnt; ++i)
+      if (todo[i]->fpfh) {
+        const uint32_t n = (uint32_t)todo[i]->n;
+        GLOC_TRY(fpfh_keep[i].ensure(132 * (size_t)n, q));
+        GLOC_TRY(gloc::fpfh::reorder_rows(q, todo[i]->idx.pts, n, todo[i]->fpfh, fpfh_keep[i].as<float>(), gloc::fpfh::FEAT_DIM, false));
+      }
     hipLaunchKernelGGL(kd_load_kernel, gpt, dim3(256), 0, q, d_k, pp[0], hh[0]);
     int cur = 0;
     static_assert(SB == 16, "the node size arithmetic assumes 16-point leaves");
@@ -901,6 +952,10 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
         hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, todo[i]->idx.pts, n,
                            nrm_keep[i].as<float>(), todo[i]->nrm, true);
       }
+    for (uint32_t i = 0; i < cnt; ++i)
+      if (todo[i]->fpfh)
+        GLOC_TRY(gloc::fpfh::reorder_rows(q, todo[i]->idx.pts, (uint32_t)todo[i]->n, fpfh_keep[i].as<float>(), todo[i]->fpfh,
+                                          gloc::fpfh::FEAT_DIM, true));
     GLOC_HIP(hipGetLastError());
     // From here on the scans ARE in kd order (kd_finish_kernel rewrote their points, inverse permutations and kpos, the
     // boxes follow): the bookkeeping says so before anything else can fail, so that a failure below (the launch orders'
@@ -972,6 +1027,15 @@ int store_ensure_normals(gloc_scan_store* st, const uint32_t* ids, size_t n, uin
   return GLOC_OK;
 }
 
+int store_ensure_fpfh(gloc_scan_store* st, const uint32_t* ids, size_t n, uint32_t normal_k, uint32_t feature_k) {
+  std::lock_guard<std::mutex> lk(st->mu);
+  for (size_t c = 0; c < n; ++c) {
+    GLOC_REQUIRE(ids[c] < st->scans.size() && st->scans[ids[c]].live, GLOC_ERR_INVALID, "unknown scan id %u", ids[c]);
+    GLOC_TRY(store_build_fpfh(st, st->scans[ids[c]], normal_k, feature_k));
+  }
+  return GLOC_OK;
+}
+
 }  // namespace reg
 }  // namespace gloc
 
@@ -990,7 +1054,7 @@ int store_insert(gloc_scan_store* st, const DevScan& s, uint32_t* id) {
     *id = (uint32_t)(st->scans.size() - 1);
   }
   st->live_count++;
-  st->live_bytes += s.block_bytes + s.nrm_bytes();
+  st->live_bytes += s.block_bytes + s.nrm_bytes() + s.fpfh_bytes();
   return GLOC_OK;
 }
 
@@ -1213,7 +1277,7 @@ int gloc_scan_store_release(gloc_scan_store* st, uint32_t scan_id) {
                "scan %u is read by %d registration batch(es) in flight (gloc_reg_batch_multi_begin without _end)", scan_id,
                st->scans[scan_id].pins);
   st->live_count--;
-  st->live_bytes -= st->scans[scan_id].block_bytes + st->scans[scan_id].nrm_bytes();
+  st->live_bytes -= st->scans[scan_id].block_bytes + st->scans[scan_id].nrm_bytes() + st->scans[scan_id].fpfh_bytes();
   store_free_scan(st, st->scans[scan_id], true);
   st->free_ids.push_back(scan_id);
   return GLOC_OK;
@@ -1227,6 +1291,7 @@ int gloc_scan_store_clear(gloc_scan_store* st) {
   for (auto& s : st->scans) {
     if (s.block) (void)hipFree(s.block);
     if (s.nrm) (void)hipFree(s.nrm);
+    if (s.fpfh) (void)hipFree(s.fpfh);
   }
   for (auto& kv : st->free_blocks) (void)hipFree(kv.second);
   st->scans.clear();
@@ -1340,6 +1405,57 @@ int gloc_scan_store_normals(gloc_scan_store* st, uint32_t scan_id, float* out_nx
     GLOC_HIP(hipGetLastError());
     GLOC_HIP(hipMemcpyAsync(out_nxyz, st->nrm_tmp.p, 12 * s.n, hipMemcpyDeviceToHost, q));
     GLOC_HIP(hipStreamSynchronize(q));
+  }
+  return GLOC_OK;
+}
+
+int gloc_scan_store_build_fpfh(gloc_scan_store* st, uint32_t scan_id, uint32_t normal_k, uint32_t feature_k) {
+  GLOC_REQUIRE(normal_k >= 3 && normal_k <= 16, GLOC_ERR_INVALID, "normal_k = %u outside [3, 16]", normal_k);
+  GLOC_REQUIRE(feature_k >= 4 && feature_k <= 16, GLOC_ERR_INVALID, "feature_k = %u outside [4, 16]", feature_k);
+  GLOC_REQUIRE(st, GLOC_ERR_INVALID, "null store");
+  GLOC_HIP(hipSetDevice(st->device));
+  std::lock_guard<std::mutex> lk(st->mu);
+  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
+  return store_build_fpfh(st, st->scans[scan_id], normal_k, feature_k);
+}
+
+int gloc_scan_store_fpfh(gloc_scan_store* st, uint32_t scan_id, float* out_feat, size_t capacity_points) {
+  GLOC_REQUIRE(st && out_feat, GLOC_ERR_INVALID, "null argument");
+  GLOC_HIP(hipSetDevice(st->device));
+  std::lock_guard<std::mutex> lk(st->mu);
+  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
+  const DevScan& s = st->scans[scan_id];
+  GLOC_REQUIRE(s.fpfh_fk != 0, GLOC_ERR_STATE, "scan %u has no features: call gloc_scan_store_build_fpfh first", scan_id);
+  GLOC_REQUIRE(capacity_points >= s.n, GLOC_ERR_INVALID, "buffer holds %zu points, the scan has %zu", capacity_points, s.n);
+  if (s.n) {
+    hipStream_t q = st->stream;
+    GLOC_TRY(st->fpfh_tmp.ensure(132 * s.n, q));
+    GLOC_TRY(gloc::fpfh::reorder_rows(q, s.idx.pts, (uint32_t)s.n, s.fpfh, st->fpfh_tmp.as<float>(), gloc::fpfh::FEAT_DIM, false));
+    GLOC_HIP(hipMemcpyAsync(out_feat, st->fpfh_tmp.p, 132 * s.n, hipMemcpyDeviceToHost, q));
+    GLOC_HIP(hipStreamSynchronize(q));
+  }
+  return GLOC_OK;
+}
+
+int gloc_scan_store_spfh(gloc_scan_store* st, uint32_t scan_id, uint32_t feature_k, uint16_t* out_counts, uint32_t* out_used,
+                         size_t capacity_points) {
+  GLOC_REQUIRE(feature_k >= 4 && feature_k <= 16, GLOC_ERR_INVALID, "feature_k = %u outside [4, 16]", feature_k);
+  GLOC_REQUIRE(st && out_counts && out_used, GLOC_ERR_INVALID, "null argument");
+  GLOC_HIP(hipSetDevice(st->device));
+  std::lock_guard<std::mutex> lk(st->mu);
+  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
+  const DevScan& s = st->scans[scan_id];
+  GLOC_REQUIRE(s.nrm_k != 0, GLOC_ERR_STATE, "scan %u has no normals: call gloc_scan_store_build_normals first", scan_id);
+  GLOC_REQUIRE(capacity_points >= s.n, GLOC_ERR_INVALID, "buffer holds %zu points, the scan has %zu", capacity_points, s.n);
+  if (s.n) {
+    GLOC_TRY(store_spfh(st, s, feature_k));
+    std::vector<uint8_t> raw((size_t)gloc::fpfh::SPFH_BYTES * s.n);
+    GLOC_HIP(hipMemcpyAsync(raw.data(), st->spfh_tmp.p, raw.size(), hipMemcpyDeviceToHost, st->stream));
+    GLOC_HIP(hipStreamSynchronize(st->stream));
+    for (size_t i = 0; i < s.n; ++i) {
+      for (uint32_t b = 0; b < gloc::fpfh::FEAT_DIM; ++b) out_counts[i * gloc::fpfh::FEAT_DIM + b] = raw[i * gloc::fpfh::SPFH_BYTES + b];
+      out_used[i] = raw[i * gloc::fpfh::SPFH_BYTES + gloc::fpfh::FEAT_DIM];
+    }
   }
   return GLOC_OK;
 }

@@ -38,6 +38,13 @@ struct DevScan {
   float* nrm = nullptr;
   uint32_t nrm_k = 0;  // the k they were built with (0: none)
   size_t nrm_bytes() const { return nrm ? 12 * n : 0; }
+  // FPFH features (gloc_scan_store_build_fpfh), an OPTIONAL THIRD allocation of 132 B per point: rows of 33 floats in the
+  // order of idx.pts, as the normals are, and re-ordered with them.  Built once per (scan, normal_k, feature_k); valid for
+  // the normals they were built from only (fpfh_nk = that nrm_k); the zero row = no feature.
+  float* fpfh = nullptr;
+  uint32_t fpfh_nk = 0, fpfh_fk = 0;  // the k's they were built with (0: none)
+  size_t fpfh_bytes() const { return fpfh ? 132 * n : 0; }
+  bool has_fpfh(uint32_t nk, uint32_t fk) const { return fpfh_fk == fk && fpfh_nk == nk && nrm_k == nk; }
   bool live = false;
   bool kd = false;  // the index is in kd order (target index)
   int pins = 0;     // batches in flight (gloc_reg_batch_multi_begin .. _end) whose jobs hold a by-value view of THIS scan:
@@ -57,11 +64,13 @@ struct gloc_scan_store : gloc::Handle {  // (always on its own stream; the base'
   gloc::DevBuf kd_k0, kd_k1, kd_v0, kd_v1, kd_p0, kd_p1, kd_h0, kd_h1, kd_box, kd_desc;
   gloc::ground::NormalsScratch nrm_ws;  // the normals' k-NN lists and staging (gloc_scan_store_build_normals)
   gloc::DevBuf nrm_tmp;                 // normals in original order, between the normal kernel / a download and the sorted copy
+  gloc::DevBuf fpfh_tmp, spfh_tmp;      // features in original order (as nrm_tmp) and the SPFH counts they are summed from
   std::atomic<int> attached{0};  // registration handles using this store
   ~gloc_scan_store() {
     for (auto& s : scans) {
       if (s.block) (void)hipFree(s.block);
       if (s.nrm) (void)hipFree(s.nrm);
+      if (s.fpfh) (void)hipFree(s.fpfh);
     }
     for (auto& kv : free_blocks) (void)hipFree(kv.second);
   }
@@ -100,6 +109,12 @@ int store_get_pinned(gloc_scan_store* st, const uint32_t* ids, const int* cs, si
 // the work has completed.  Adds an allocation and moves nothing: safe on a pinned scan, except that normals a batch may
 // be reading are not rebuilt with another k (GLOC_ERR_STATE).
 int store_build_normals(gloc_scan_store* st, DevScan& s, uint32_t k);
+// Give a scan its FPFH features from feature_k neighbours and normals of normal_k (built or rebuilt first when the scan's
+// differ: store_build_normals and its rule); no-op when it has them with these k's.  Caller holds store->mu; returns after
+// the work has completed.  Features a batch may be reading are not rebuilt (GLOC_ERR_STATE).
+int store_build_fpfh(gloc_scan_store* st, DevScan& s, uint32_t normal_k, uint32_t feature_k);
+// ... for a list of ids (takes store->mu).  GLOC_ERR_INVALID for an unknown id.
+int store_ensure_fpfh(gloc_scan_store* st, const uint32_t* ids, size_t n, uint32_t normal_k, uint32_t feature_k);
 // The pins' release (delta = -1) once the batch's event has been waited for.  Ids no longer live are skipped.
 void store_pin(gloc_scan_store* st, const uint32_t* ids, size_t count, int delta);
 // Scans without normals get them from k neighbours (takes store->mu; an allocation beside the scan: nothing a batch in

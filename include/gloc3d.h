@@ -621,6 +621,77 @@ int gloc_reg_vgicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_i
 int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3,
                           uint32_t* out_count, double* out_mean3, double* out_nn6, size_t* n_voxels);
 
+/* ---- FPFH feature-based global registration ------------------------------------------------------------- *
+ * The 3-D answer to "where is this scan, from nothing": local shape descriptors (Fast Point Feature Histograms: Rusu,
+ * Blodow & Beetz; pcl::FPFHEstimation in its k-nearest form), descriptor matching, and the RANSAC stage of
+ * gloc_reg_batch_* run on the descriptor matches instead of nearest-neighbour pairs under a guess (the idea of
+ * pcl::SampleConsensusPrerejective).  It needs no initial pose and no level sensor; its pose is a START for one of the
+ * refinements above (out_T as their init_T), not a result.  A stage a caller chooses; the default pipeline is unchanged.
+ * The executable contract is the float64 restatement tests/fpfh_ref.py; parity with PCL is unpinned.
+ *
+ * F1  SPFH.  A point's list is its feature_k nearest neighbours within the scan, self included, ascending (d2, index) --
+ *     the lists the normals are built from, d2 = ((dx dx + dy dy) + dz dz) in fp32.  Entry j != i is usable iff d2 > 0, both
+ *     points are finite and both normals non-zero.  In fp64 from the fp32 inputs: dp = p_j - p_i, f4 = |dp|,
+ *     a1 = n_i.dp / f4, a2 = n_j.dp / f4; if acos(min(|a1|, 1)) > acos(min(|a2|, 1)) the roles swap (n1 = n_j, n2 = n_i,
+ *     dp = -dp, f3 = -a2), else n1 = n_i, n2 = n_j, f3 = a1; v = dp x n1, the pair is skipped if |v| = 0, v normalised;
+ *     w = n1 x v; f2 = v.n2; f1 = atan2(w.n2, n1.n2).  Bins, each clamped to [0, 10]: floor(11 (f1 + pi) / (2 pi)),
+ *     floor(11 (f2 + 1) / 2), floor(11 (f3 + 1) / 2).  The SPFH is the three count vectors and `used`, the pairs counted;
+ *     its real form is counts x 100 / used.  A point with a zero normal or used = 0 has none.
+ * F2  FPFH.  Over the usable entries j that have an SPFH, in list order: acc += SPFH_j x (1 / d2) in fp64; each of the
+ *     three sub-histograms rescaled to sum to 100; 33 fp32 values.  The all-zero row means "no feature".
+ * F3  Matching.  For every source row with a feature the target row with a feature at the smallest squared distance,
+ *     defined in fp32, un-fused: acc = 0; for c in 0..32: t = a[c] - b[c]; acc = acc + t * t.  Ties: the smaller target
+ *     index.  mutual: the same search target -> source; (i, j) is kept iff j's match is i.
+ * F4  RANSAC.  The kept pairs in ascending source index are the correspondence list, M long; the RANSAC stage of
+ *     gloc_reg_batch_* runs on it unchanged from the identity (3-point samples over [0, M) keyed by (seed, stream id, h),
+ *     fp64 Kabsch, near-collinear samples skipped, inliers over the M pairs at inlier_thresh, most inliers then smallest
+ *     h, the adaptive stop at ransac_confidence, the refit on the winner's inliers).  ok iff a valid hypothesis has at
+ *     least max(3, ceil(min_inlier_ratio M)) inliers.  M < 3: the identity, ok = 0, 0 inliers. */
+typedef struct gloc_fpfh_params {
+  uint32_t normal_k;        /* 3..16, default 10 (registration/ground_estimator.cpp:79) */
+  uint32_t feature_k;       /* 4..16, default 16: the list length, self included */
+  uint32_t mutual;          /* default 1 */
+  uint32_t ransac_iters;    /* default 3000 (registration/loop_detector.cpp:257); a cap, as in gloc_reg_params; >= 1 */
+  float inlier_thresh;      /* 0.6 m */
+  float min_inlier_ratio;   /* default 0: any valid hypothesis with >= 3 inliers is ok; plausibility belongs to the
+                               refinement behind it */
+  float ransac_confidence;  /* 0.99; outside (0, 1): every hypothesis is scored */
+  uint32_t reserved_;
+  uint64_t seed;            /* 1234 */
+} gloc_fpfh_params;         /* 40 bytes */
+
+void gloc_fpfh_default_params(gloc_fpfh_params* p);
+
+/* Give a resident scan its FPFH features (F1, F2): 132 bytes per point in an allocation beside the scan, counted by
+ * gloc_scan_store_bytes, freed with the scan, built at most once per (scan, normal_k, feature_k) -- a repeated call is a
+ * no-op.  Normals the scan lacks are built first with normal_k; normals it has are used as they are when their k is
+ * normal_k and rebuilt otherwise, under the rule of gloc_scan_store_build_normals (GLOC_ERR_STATE while a batch in flight
+ * may read them; the same holds for rebuilding features with other k).  GLOC_ERR_INVALID: normal_k outside [3, 16],
+ * feature_k outside [4, 16], a null store, an unknown id. */
+int gloc_scan_store_build_fpfh(gloc_scan_store* st, uint32_t scan_id, uint32_t normal_k, uint32_t feature_k);
+/* The features [n][33] in the order the scan was uploaded in.  GLOC_ERR_STATE: the scan has none. */
+int gloc_scan_store_fpfh(gloc_scan_store* st, uint32_t scan_id, float* out_feat, size_t capacity_points);
+/* Diagnostic, computed on demand from the scan's normals (GLOC_ERR_STATE without) and not kept: the SPFH counts
+ * [n][33] and the pairs counted [n] (0: no SPFH), in upload order. */
+int gloc_scan_store_spfh(gloc_scan_store* st, uint32_t scan_id, uint32_t feature_k, uint16_t* out_counts, uint32_t* out_used,
+                         size_t capacity_points);
+
+/* F3 on host buffers (a building block): src_feat [n_src][33], tgt_feat [n_tgt][33]; out_idx [n_src] the kept match of
+ * every source row, UINT32_MAX for a row without a feature, without a target, or (mutual != 0) not its match's match;
+ * out_d2 [n_src] the match's distance, +infinity where out_idx is UINT32_MAX (may be NULL). */
+int gloc_reg_fpfh_match(gloc_reg* h, const float* src_feat, size_t n_src, const float* tgt_feat, size_t n_tgt, uint32_t mutual,
+                        uint32_t* out_idx, float* out_d2);
+
+/* Locate scan src_scan_id in each of the n targets (F3, F4): out_T [n][16] source -> target, out_inliers, out_n_pairs (M),
+ * out_ok (each may be NULL but out_T).  stream_ids: the RANSAC stream of each job (NULL: 0 .. n - 1).  Features missing on
+ * a scan are built first as gloc_scan_store_build_fpfh builds them.  One launch sequence covers all n jobs; job c equals
+ * the single call with stream_ids[c], bit for bit, and the result does not depend on whether a scan carries a target
+ * index.  The parameter block is checked before the handle.  GLOC_ERR_INVALID: null arguments, an unknown id, n outside
+ * [1, 4096], normal_k outside [3, 16], feature_k outside [4, 16], ransac_iters = 0, inlier_thresh <= 0; GLOC_ERR_STATE: a
+ * batch in flight on the handle. */
+int gloc_reg_fpfh_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
+                            const gloc_fpfh_params* prm, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok);
+
 /* ============================ NetVLAD-FC pooling head ("next" row N2) ===================== *
  * Replaces NetVLAD.forward of the reference (model/netvlad_fc.py:73-109, built without gating at
  * main.py:594) -- the tail of the TorchScript module RpyPCLoopDetector::get_place_feature runs

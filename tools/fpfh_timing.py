@@ -1,0 +1,163 @@
+"""FPFH feature-based global registration on bench.py's kind of scans (tools/gicp_timing.py's road scans: 2 queries x 20
+candidates of ~121 k points, 10 same-world places and 10 of another world per query), voxel-filtered at the leaf the test
+table commits (tests/fpfh_cases.py LEAF): feature build per scan, the matcher per job with mutual on and off, the RANSAC
+stage, a 20-candidate batch end to end -- and how many of the 40 jobs are located within 1 m / 5 degrees of ground truth,
+beside the RANSAC stage of gloc_reg_batch_ids on the same filtered scans from the identity guess.
+
+    python tools/fpfh_timing.py [--queries 2] [--reps 5] [--leaf 0.5] [--out FILE]
+
+Medians of --reps runs on one box; host time of synchronous calls unless a line says "profiler".
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+OK_T, OK_R = 1.0, 5.0
+PEAK_FP32_VECTOR = 157.3e12   # MI355X, fp32 vector, an fma counted as two operations
+
+
+def pose_error(T, truth):
+    D = np.linalg.inv(np.asarray(truth, np.float64)) @ np.asarray(T, np.float64)
+    c = np.clip((np.trace(D[:3, :3]) - 1.0) / 2.0, -1.0, 1.0)
+    return float(np.linalg.norm(D[:3, 3])), float(np.degrees(np.arccos(c)))
+
+
+def med(f, reps):
+    f()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        f()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(t)), float(min(t))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--queries", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--leaf", type=float, default=0.5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from gloc3d_amd import capi, synth
+    traj, xy = synth.loop_trajectory(400, 328.0)
+    wa, wb = synth.make_road_world(1001, xy), synth.make_road_world(2002, xy)
+    store = capi.ScanStore()
+    reg = capi.Registrar(store=store)
+    lines = []
+    say = lambda s: (print(s, flush=True), lines.append(s))  # noqa: E731
+    rng = np.random.default_rng(11)
+    wobble = lambda: synth.se3(rng.uniform(-2, 2), (rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3), rng.uniform(-0.03, 0.03)))  # noqa: E731
+    seed = 1
+    rows = []
+    for qi in range(a.queries):
+        at = 60 + 90 * qi
+        q_pose = traj[at] @ synth.se3(rng.uniform(-3, 3), (rng.uniform(-0.4, 0.4), rng.uniform(-0.5, 0.5), 0.02))
+        same = [traj[at + d] @ wobble() for d in (-5, -4, -3, -2, -1, 1, 2, 3, 4, 5)]
+        diff = [traj[at + d] @ wobble() for d in (-5, -4, -3, -2, -1, 1, 2, 3, 4, 5)]
+        raw = store.add_raycast(wa, [q_pose] + same, np.arange(seed, seed + 11, dtype=np.uint64))
+        raw += store.add_raycast(wb, diff, np.arange(seed + 11, seed + 21, dtype=np.uint64))
+        seed += 21
+        ids = [store.add_approx_voxel(i, a.leaf) for i in raw]
+        for t in ids[1:]:
+            store.build_target_index(t)
+        truth = np.stack([np.linalg.inv(T) @ q_pose for T in same])
+        rows.append(dict(raw=raw, q=ids[0], db=ids[1:], truth=truth))
+    n_q, n_db = store.points(rows[0]["q"]), [store.points(t) for t in rows[0]["db"]]
+    say(f"scans: {store.points(rows[0]['raw'][0])} points raw, voxel-filtered at {a.leaf} m: {n_q} (query), {min(n_db)} .. {max(n_db)} (places); "
+        f"{a.queries} queries x 20 candidates (10 same-world, 10 different-world); default gloc_fpfh_params; medians of {a.reps}, one box")
+
+    # ---- feature build per scan (normals + lists + SPFH + FPFH) ---------------------------------------------------
+    r = rows[0]
+    t_full, t_feat = [], []
+    for i in r["raw"][:6]:
+        s = store.add_approx_voxel(i, a.leaf)
+        t0 = time.perf_counter()
+        store.build_fpfh(s, 10, 16)
+        t_full.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        store.build_fpfh(s, 10, 12)      # the normals stay: lists + SPFH + FPFH alone
+        t_feat.append((time.perf_counter() - t0) * 1e3)
+        store.release(s)
+    say(f"feature build per filtered scan (host time, synchronous): normals + features median {np.median(t_full[1:]):.3f} ms, "
+        f"features alone (normals present) {np.median(t_feat[1:]):.3f} ms")
+    t_raw = []
+    for i in r["raw"][:3]:
+        s = store.add_variant(i)
+        t0 = time.perf_counter()
+        store.build_fpfh(s, 10, 16)
+        t_raw.append((time.perf_counter() - t0) * 1e3)
+        store.release(s)
+    say(f"feature build on an unfiltered scan ({store.points(r['raw'][0])} points), normals + features: median {np.median(t_raw[1:]):.3f} ms")
+    for row in rows:
+        for t in [row["q"]] + row["db"]:
+            store.build_fpfh(t, 10, 16)
+
+    # ---- matcher, RANSAC (profiler on), end to end (profiler off) ------------------------------------------------------
+    reg.set_option(capi.REG_OPT_PROFILE, 1)
+    for mutual in (1, 0):
+        prm = capi.default_fpfh_params(mutual=mutual)
+        reg.fpfh_batch(r["q"], r["db"], params=prm)
+        reg.profile_reset()
+        for _ in range(a.reps):
+            reg.fpfh_batch(r["q"], r["db"], params=prm)
+        say(f"20 candidates, mutual = {mutual}, profiler on, per batch:")
+        for k in ("fpfh_match", "fpfh_pairs", "ransac_hyp", "ransac_score", "accum", "solve"):
+            tot, cnt = reg.profile(k)
+            if cnt:
+                say(f"  {k:12s} {tot / a.reps:8.3f} ms  {cnt / a.reps:5.1f} launches")
+        tot, _ = reg.profile("fpfh_match")
+        pairs = sum(n_q * n for n in n_db) * (2 if mutual else 1)
+        ops = pairs * 99.0                                        # 33 x (subtract, multiply, add), un-fused
+        ms = tot / a.reps
+        say(f"  matcher: {ms / 20:.4f} ms per job; {pairs / 1e6:.1f} M row pairs, {ops / (ms * 1e-3) / 1e12:.2f} Tflop/s un-fused = "
+            f"{100.0 * ops / (ms * 1e-3) / PEAK_FP32_VECTOR:.1f} % of the fp32 vector peak ({PEAK_FP32_VECTOR / 1e12:.1f} Tflop/s, fma = 2)")
+    reg.set_option(capi.REG_OPT_PROFILE, 0)
+    for mutual in (1, 0):
+        prm = capi.default_fpfh_params(mutual=mutual)
+        m20, lo20 = med(lambda: reg.fpfh_batch(r["q"], r["db"], params=prm), a.reps)
+        m1, lo1 = med(lambda: reg.fpfh_batch(r["q"], r["db"][:1], params=prm), a.reps)
+        say(f"end to end (features present), mutual = {mutual}: 20 candidates median {m20:.2f} ms (min {lo20:.2f}), 1 candidate {m1:.2f} ms (min {lo1:.2f})")
+
+    # ---- located within 1 m / 5 degrees: this stage against the nearest-neighbour RANSAC stage from the identity -------------
+    def located(T, ok, truth):
+        n = 0
+        for c in range(10):
+            e = pose_error(T[c], truth[c])
+            n += bool(ok[c]) and e[0] <= OK_T and e[1] <= OK_R
+        return n
+
+    tot_f = tot_b = acc_f = acc_b = 0
+    errs = []
+    for row in rows:
+        g = reg.fpfh_batch(row["q"], row["db"])
+        b = reg.batch_ids(row["q"], row["db"], params=capi.default_reg_params(icp_iters=0))
+        tot_f += located(g["T"], g["ok"], row["truth"])
+        tot_b += located(b["T"], b["ok"], row["truth"])
+        acc_f += int(np.sum(g["ok"][10:]))
+        acc_b += int(np.sum(b["ok"][10:]))
+        errs += [pose_error(g["T"][c], row["truth"][c]) for c in range(10)]
+        say(f"  query: pairs {g['n_pairs'].tolist()} inliers {g['inliers'].tolist()}")
+    n_same = 10 * a.queries
+    say(f"located within {OK_T} m / {OK_R} deg, same-world jobs: fpfh {tot_f} of {n_same}; nearest-neighbour RANSAC stage from the identity {tot_b} of {n_same}")
+    say(f"different-world jobs reported ok: fpfh {acc_f} of {n_same} (min_inlier_ratio 0: plausibility is left to the refinement); "
+        f"nearest-neighbour stage {acc_b} of {n_same} (min_inlier_ratio 0.3)")
+    say("fpfh pose error, same-world jobs, median (max): %.3f (%.3f) m, %.3f (%.3f) deg"
+        % (np.median([e[0] for e in errs]), max(e[0] for e in errs), np.median([e[1] for e in errs]), max(e[1] for e in errs)))
+    mb, lob = med(lambda: reg.batch_ids(rows[0]["q"], rows[0]["db"], params=capi.default_reg_params(icp_iters=0)), a.reps)
+    say(f"baseline, the RANSAC stage of gloc_reg_batch_ids on the same filtered scans from the identity, 20 candidates: median {mb:.2f} ms (min {lob:.2f})")
+    reg.close()
+    store.close()
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

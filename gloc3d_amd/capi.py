@@ -19,6 +19,7 @@ KNN_OPT_ALGO, KNN_OPT_CANDIDATES, KNN_OPT_PROFILE = 1, 2, 3
 REG_OPT_PROFILE, REG_OPT_NN_MODE, REG_OPT_NN_SRC_PER_LANE, REG_OPT_NN_JOB_GROUP, REG_OPT_TEMP_TARGET_INDEX = 1, 2, 3, 4, 5
 REG_OPT_NN_SPLIT_HELPERS, REG_OPT_NN_SPLIT_THRESH, REG_OPT_NN_SUB_JOBS, REG_OPT_NN_HEAVY_THRESH, REG_OPT_SUB_BATCHES = 6, 7, 8, 9, 10
 REG_OPT_NN_CHAIN = 11
+REG_OPT_PAIRGRAPH_BUDGET = 12
 REG_NN_CULLED, REG_NN_EXHAUSTIVE = 0, 1
 NO_SCAN = 0xFFFFFFFF
 SIZE_MAX = C.c_size_t(-1).value
@@ -75,6 +76,12 @@ class FpfhParams(C.Structure):
     _fields_ = [("normal_k", C.c_uint32), ("feature_k", C.c_uint32), ("mutual", C.c_uint32), ("ransac_iters", C.c_uint32),
                 ("inlier_thresh", C.c_float), ("min_inlier_ratio", C.c_float), ("ransac_confidence", C.c_float),
                 ("reserved_", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class FpfhGraphParams(C.Structure):
+    _fields_ = [("normal_k", C.c_uint32), ("feature_k", C.c_uint32), ("mutual", C.c_uint32), ("n_seeds", C.c_uint32),
+                ("compat_thresh", C.c_float), ("inlier_thresh", C.c_float), ("min_inlier_ratio", C.c_float),
+                ("theta_num", C.c_uint32), ("theta_den", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
 FPFH_DIM = 33          # floats per feature row
@@ -239,6 +246,9 @@ _PROTOS = [
     ("gloc_scan_store_spfh", _i, [_vp, _u32, _u32, _vp, _vp, _sz]),
     ("gloc_reg_fpfh_match", _i, [_vp, _vp, _sz, _vp, _sz, _u32, _vp, _vp]),
     ("gloc_reg_fpfh_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FpfhParams), _vp, _vp, _vp, _vp]),
+    ("gloc_fpfh_graph_default_params", None, [C.POINTER(FpfhGraphParams)]),
+    ("gloc_reg_fpfh_graph_batch_ids", _i, [_vp, _u32, _vp, _sz, C.POINTER(FpfhGraphParams), _vp, _vp, _vp, _vp]),
+    ("gloc_reg_pair_graph", _i, [_vp, _vp, _vp, _sz, C.POINTER(FpfhGraphParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
@@ -614,6 +624,16 @@ def default_fpfh_params(**over):
     return p
 
 
+def default_fpfh_graph_params(**over):
+    """gloc_fpfh_graph_params as gloc_fpfh_graph_default_params leaves them (normal_k = 10, feature_k = 16, mutual matches,
+    64 seeds, 0.6 m compatibility and inlier thresholds, theta = 1 / 2), then `over`."""
+    p = FpfhGraphParams()
+    lib().gloc_fpfh_graph_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
 class ScanStore(_Handle):
     """Resident scans + their search index, shared by any number of Registrars."""
 
@@ -972,6 +992,38 @@ class Registrar(_Handle):
         check(lib().gloc_reg_fpfh_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if sid is None else _np_ptr(sid), C.byref(prm),
                                             _np_ptr(T), _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
         return dict(T=T, inliers=inl, n_pairs=npairs, ok=ok.astype(bool))
+
+    def fpfh_graph_batch(self, src_id, tgt_ids, params=None):
+        """Feature-based global registration through the correspondence graph (gloc_reg_fpfh_graph_batch_ids): the matches of
+        fpfh_batch, the pose from their second-order compatibility instead of RANSAC.  Returns dict(T [n, 4, 4] float32
+        source -> target, inliers [n], n_pairs [n], ok [n] bool); T is a start for a refinement, as fpfh_batch's."""
+        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
+        n = ids.shape[0]
+        prm = params or default_fpfh_graph_params()
+        T = np.empty((n, 4, 4), np.float32)
+        inl, npairs, ok = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        check(lib().gloc_reg_fpfh_graph_batch_ids(self._h, int(src_id), _np_ptr(ids), n, C.byref(prm), _np_ptr(T), _np_ptr(inl),
+                                                  _np_ptr(npairs), _np_ptr(ok)))
+        return dict(T=T, inliers=inl, n_pairs=npairs, ok=ok.astype(bool))
+
+    def pair_graph(self, P, Q, params=None):
+        """The correspondence graph of a pair list P, Q [m, 3] (gloc_reg_pair_graph): dict(degree [m] uint32, score [m] uint64,
+        seeds, set_sizes, seed_inliers [n_seeds] uint32, T [4, 4] float32, inliers, winner_rank (0xFFFFFFFF: none), ok)."""
+        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        Q = np.ascontiguousarray(Q, np.float32).reshape(-1, 3)
+        m = P.shape[0]
+        assert Q.shape[0] == m
+        prm = params or default_fpfh_graph_params()
+        S = int(prm.n_seeds)
+        deg, score = np.empty(max(m, 1), np.uint32), np.empty(max(m, 1), np.uint64)
+        seeds, sizes, sinl = np.empty(S, np.uint32), np.empty(S, np.uint32), np.empty(S, np.uint32)
+        T = np.empty((4, 4), np.float32)
+        inl, rank, ok = C.c_uint32(), C.c_uint32(), C.c_int()
+        check(lib().gloc_reg_pair_graph(self._h, _np_ptr(P) if m else None, _np_ptr(Q) if m else None, m, C.byref(prm), _np_ptr(deg),
+                                        _np_ptr(score), _np_ptr(seeds), _np_ptr(sizes), _np_ptr(sinl), _np_ptr(T), C.byref(inl),
+                                        C.byref(rank), C.byref(ok)))
+        return dict(degree=deg[:m], score=score[:m], seeds=seeds, set_sizes=sizes, seed_inliers=sinl, T=T, inliers=inl.value,
+                    winner_rank=rank.value, ok=bool(ok.value))
 
     def vgicp_batch(self, src_id, tgt_ids, init_T=None, params=None):
         """Voxelized generalized ICP of scan src_id against each of tgt_ids (gloc_reg_vgicp_batch_ids): returns

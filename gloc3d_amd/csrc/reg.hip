@@ -14,6 +14,7 @@
 #include "nn_compact.hpp"
 #include "gicp.hpp"
 #include "p2l.hpp"
+#include "pairgraph.hpp"
 #include "reg_kernels.hpp"
 #include "scan_store.hpp"
 #include "vgicp.hpp"
@@ -91,6 +92,8 @@ struct gloc_reg : Handle {
   gloc::p2l::Ws* p2l = nullptr;  // point-to-plane / generalized ICP workspace (gn6.hpp), made on first use
   gloc::vgicp::Ws* vgicp = nullptr;  // voxelized generalized ICP's voxel maps (vgicp.hip), made on first use
   gloc::fpfh::Ws* fpfh = nullptr;    // the feature matcher's keys and tables (fpfh.hip), made on first use
+  gloc::pairgraph::Ws* pgraph = nullptr;  // the correspondence graph's bit matrices and seed rows (pairgraph.hip), made on first use
+  size_t pgraph_budget = 0;          // bytes of them in flight at a time (GLOC_REG_OPT_PAIRGRAPH_BUDGET; 0: pairgraph::BUDGET_BYTES)
   ~gloc_reg() {  // (the handle's work has been waited for: destroy_handle)
     if (pending.active && pending.store) store_pin(pending.store, pending.pinned.data(), pending.pinned.size(), -1);
     if (store) store->attached--;
@@ -99,6 +102,7 @@ struct gloc_reg : Handle {
     gloc::p2l::ws_free(p2l);
     gloc::vgicp::ws_free(vgicp);
     gloc::fpfh::ws_free(fpfh);
+    gloc::pairgraph::ws_free(pgraph);
     if (done_ev) (void)hipEventDestroy(done_ev);
     if (pin) (void)hipHostFree(pin);
   }
@@ -859,8 +863,19 @@ __global__ void set_pair_counts_kernel(Job* __restrict__ jobs, const uint32_t* _
   if (c < n_jobs) jobs[c].n_src = counts[c];
 }
 
-int run_fpfh(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const uint32_t* stream_ids, const gloc_fpfh_params* prm,
-             float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+// What the two stages that turn the match list into a pose differ in, as the shared part below sees it: the features'
+// and the matcher's parameters, the hypotheses per job, and whether all of them are scored (the alive lists).
+struct FpfhFront {
+  uint32_t normal_k, feature_k, mutual, n_hyp;
+  bool adaptive;
+  float min_inlier_ratio;
+};
+
+// stage(bd, v, nblocks, m_max): the launches from the pairs in v.pairs (M of job c in jobs[c].n_src; none above m_max) to
+// the pose in the states -- enqueue_ransac (F4) or enqueue_graph (G1 - G4).
+template <class Stage>
+int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const uint32_t* stream_ids, const FpfhFront* prm,
+                   float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok, Stage&& stage) {
   GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
   GLOC_REQUIRE(h->store, GLOC_ERR_INVALID, "unknown scan id %u", src_id);
   gloc_scan_store* st = h->store;
@@ -918,10 +933,10 @@ int run_fpfh(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, co
   h->chain_in_batch = false;
   for (uint32_t c = 0; c < n_jobs; ++c) {
     h->h_jobs[c] = Job{nullptr, nullptr, nullptr, nullptr, ScanIndexDev{}, 0u, 0u, stream_ids ? stream_ids[c] : c, 0u};
-    init_state(h->h_states[c], nullptr, prm->ransac_iters);
+    init_state(h->h_states[c], nullptr, prm->n_hyp);
   }
-  const size_t H = prm->ransac_iters;
-  const bool adaptive = prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f;
+  const size_t H = prm->n_hyp;
+  const bool adaptive = prm->adaptive;
   GLOC_TRY(h->jobs.ensure(sizeof(Job) * n_jobs, s));
   GLOC_TRY(h->states.ensure(sizeof(CandState) * n_jobs, s));
   GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part * n_jobs, s));
@@ -943,6 +958,11 @@ int run_fpfh(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, co
   }
   hipLaunchKernelGGL(set_pair_counts_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, s, h->jobs.as<Job>(), w.counts.as<uint32_t>(), n_jobs);
   GLOC_HIP(hipGetLastError());
+  // (the compaction has been waited for: the counts come down here, where the graph stage sizes its workspace by them)
+  std::vector<uint32_t> counts(n_jobs);
+  GLOC_HIP(hipMemcpyAsync(counts.data(), w.counts.p, sizeof(uint32_t) * n_jobs, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipStreamSynchronize(s));
+  const uint32_t m_max = *std::max_element(counts.begin(), counts.end());
   h->split = NnSplit{};
   WsView v{};
   v.s = s;
@@ -958,11 +978,8 @@ int run_fpfh(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, co
     v.a_idx = h->alive.as<uint32_t>();
     v.a_cnt = h->alive.as<uint32_t>() + H * n_jobs;
   }
-  GLOC_TRY(enqueue_ransac(h, bd, RansacRule{prm->ransac_iters, prm->inlier_thresh, prm->min_inlier_ratio, prm->ransac_confidence, prm->seed}, v,
-                          nblocks));
-  std::vector<uint32_t> counts(n_jobs);
+  GLOC_TRY(stage(bd, v, nblocks, m_max));
   GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState) * n_jobs, hipMemcpyDeviceToHost, s));
-  GLOC_HIP(hipMemcpyAsync(counts.data(), w.counts.p, sizeof(uint32_t) * n_jobs, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipStreamSynchronize(s));
   for (uint32_t c = 0; c < n_jobs; ++c) {
     const CandState& cs = h->h_states[c];
@@ -979,6 +996,167 @@ int run_fpfh(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, co
     const double need = std::max(3.0, std::ceil((double)prm->min_inlier_ratio * (double)M));
     if (out_ok) out_ok[c] = found && (double)cs.best_inl >= need;
   }
+  return GLOC_OK;
+}
+
+int run_fpfh(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const uint32_t* stream_ids, const gloc_fpfh_params* prm,
+             float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+  const FpfhFront f{prm->normal_k, prm->feature_k, prm->mutual, prm->ransac_iters, prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f,
+                    prm->min_inlier_ratio};
+  return run_fpfh_pairs(h, src_id, tgt_ids, n, stream_ids, &f, out_T, out_inliers, out_n_pairs, out_ok,
+                        [&](const BatchDims& bd, const WsView& v, uint32_t nblocks, uint32_t) {
+                          return enqueue_ransac(h, bd, RansacRule{prm->ransac_iters, prm->inlier_thresh, prm->min_inlier_ratio,
+                                                                  prm->ransac_confidence, prm->seed}, v, nblocks);
+                        });
+}
+
+// The fit of a consensus set from its raw moments (pairgraph.hip): one thread per (job, seed); centroids and covariance as
+// solve_compose forms them for the refit, kabsch_from_cov, the hypothesis rounded to fp32 as ransac_hyp_kernel leaves its own.
+__global__ void graph_solve_kernel(const double* __restrict__ moments, const uint32_t* __restrict__ valid, float* __restrict__ Rt, uint32_t count) {
+  const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= count || !valid[o]) return;
+  const double* v = moments + (size_t)o * gloc::pairgraph::MOMENTS;
+  const double cnt = v[0], inv = 1.0 / cnt;
+  double pbar[3], qbar[3], M[9], Rd[9], td[3];
+  for (int a = 0; a < 3; ++a) {
+    pbar[a] = v[1 + a] * inv;
+    qbar[a] = v[4 + a] * inv;
+  }
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) M[3 * a + b] = v[7 + 3 * a + b] - cnt * (pbar[a] * qbar[b]);
+  kabsch_from_cov(M, pbar, qbar, Rd, td);
+  float* out = Rt + (size_t)o * 12;
+  for (int i = 0; i < 9; ++i) out[i] = (float)Rd[i];
+  for (int i = 0; i < 3; ++i) out[9 + i] = (float)td[i];
+}
+
+// Correspondence-graph global registration (pairgraph.hip): G1 - G3 make n_seeds hypotheses per job in the RANSAC stage's
+// Rt / valid layout; G4 is that stage's own kernels, unchanged: ransac_score_kernel counts the inliers of all of them,
+// ransac_scan_kernel's sequential rule without the adaptive stop IS "the most inliers, then the smaller rank", and
+// accum_kernel<1> / solve_kernel<1> refit on the winner's inliers.  The states start as init_state(.., n_seeds) leaves them.
+int enqueue_graph(gloc_reg* h, const BatchDims& bd, const gloc_fpfh_graph_params* prm, const WsView& v, const uint32_t* counts, uint32_t nblocks,
+                  uint32_t m_max) {
+  const uint32_t n_jobs = v.n_jobs, S = prm->n_seeds;
+  hipStream_t s = v.s;
+  GLOC_TRY(ensure_ws(&h->pgraph));
+  GLOC_TRY(gloc::pairgraph::consensus_sets(s, h->prof, *h->pgraph, gloc::pairgraph::Batch{v.pairs, bd.ld, counts, n_jobs, m_max}, *prm,
+                                           h->pgraph_budget, v.valid));
+  if (m_max) {
+    ProfScope ps(h->prof, "pg_fit", s);
+    hipLaunchKernelGGL(graph_solve_kernel, dim3((S * n_jobs + 63) / 64), dim3(64), 0, s, h->pgraph->moments.as<double>(), v.valid, v.Rt, S * n_jobs);
+    GLOC_HIP(hipGetLastError());
+  }
+  GLOC_HIP(hipMemsetAsync(v.inliers, 0, sizeof(uint32_t) * (size_t)S * n_jobs, s));
+  const float thr2 = prm->inlier_thresh * prm->inlier_thresh;
+  {
+    ProfScope ps(h->prof, "ransac_score", s);
+    const uint32_t chunk_len = (size_t)n_jobs * ((bd.max_src + SC_CHUNK - 1) / SC_CHUNK) >= 2048 ? (uint32_t)SC_CHUNK : 1024u;
+    const unsigned cchunks = (std::max<uint32_t>(m_max, 1u) + chunk_len - 1) / chunk_len;
+    const uint32_t hpb = S <= 16 ? 16u : (S <= 64 ? 64u : 256u);
+    hipLaunchKernelGGL(ransac_score_kernel, dim3((S + hpb - 1) / hpb, cchunks, n_jobs), dim3(256), 0, s, v.pairs, bd.ld, v.jobs, S, 0u, hpb, v.Rt,
+                       v.valid, thr2, (const CandState*)nullptr, v.inliers, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, chunk_len);
+    hipLaunchKernelGGL(ransac_scan_kernel<true>, dim3(n_jobs), dim3(64), 0, s, v.inliers, v.valid, v.Rt, S, 0u, S, v.jobs, 0.f,
+                       prm->min_inlier_ratio, v.states);
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "accum", s);
+    hipLaunchKernelGGL(accum_kernel<1>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, s, v.jobs, v.states, v.corr, v.d2, v.pairs, bd.ld, thr2,
+                       v.partials, bd.n_part);
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "solve", s);
+    hipLaunchKernelGGL(solve_kernel<1>, dim3(n_jobs), dim3(SOLVE_THREADS), 0, s, v.partials, bd.n_part, false, v.jobs, v.states, NnSplit{}, n_jobs);
+    GLOC_HIP(hipGetLastError());
+  }
+  return GLOC_OK;
+}
+
+int run_fpfh_graph(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const gloc_fpfh_graph_params* prm, float* out_T,
+                   uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+  const FpfhFront f{prm->normal_k, prm->feature_k, prm->mutual, prm->n_seeds, true, prm->min_inlier_ratio};
+  return run_fpfh_pairs(h, src_id, tgt_ids, n, nullptr, &f, out_T, out_inliers, out_n_pairs, out_ok,
+                        [&](const BatchDims& bd, const WsView& v, uint32_t nblocks, uint32_t m_max) {
+                          return enqueue_graph(h, bd, prm, v, h->fpfh->counts.as<uint32_t>(), nblocks, m_max);
+                        });
+}
+
+// gloc_reg_pair_graph: one job on a host list, every diagnostic brought down.
+int run_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const gloc_fpfh_graph_params* prm, uint32_t* out_degree,
+                   uint64_t* out_score, uint32_t* out_seeds, uint32_t* out_set_sizes, uint32_t* out_seed_inliers, float* out_T,
+                   uint32_t* out_inliers, uint32_t* out_winner_rank, int* out_ok) {
+  const uint32_t S = prm->n_seeds, M = (uint32_t)m;
+  static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  if (out_T) memcpy(out_T, I16, sizeof(I16));
+  if (out_inliers) *out_inliers = 0;
+  if (out_winner_rank) *out_winner_rank = 0xFFFFFFFFu;
+  if (out_ok) *out_ok = 0;
+  for (uint32_t r = 0; r < S; ++r) {
+    if (out_seeds) out_seeds[r] = 0xFFFFFFFFu;
+    if (out_set_sizes) out_set_sizes[r] = 0;
+    if (out_seed_inliers) out_seed_inliers[r] = 0;
+  }
+  if (M == 0) return GLOC_OK;
+  hipStream_t s = h->stream;
+  BatchDims bd{1u, M, 0, 0, 0};
+  const uint32_t nblocks = (M + ACC_PER_BLOCK - 1) / ACC_PER_BLOCK;
+  bd.n_part = (std::max<uint32_t>(nblocks, 1) + 31u) & ~31u;
+  bd.ld = ((size_t)M + 127) & ~(size_t)127;
+  std::vector<float> hp(bd.ld * 8, 0.f);
+  for (size_t i = 0; i < m; ++i)
+    for (int a = 0; a < 3; ++a) {
+      hp[i * 8 + a] = P[3 * i + a];
+      hp[i * 8 + 4 + a] = Q[3 * i + a];
+    }
+  GLOC_TRY(ensure_pinned(h, 1));
+  h->chain_in_batch = false;
+  h->h_jobs[0] = Job{nullptr, nullptr, nullptr, nullptr, ScanIndexDev{}, M, 0u, 0u, 0u};
+  init_state(h->h_states[0], nullptr, S);
+  GLOC_TRY(h->jobs.ensure(sizeof(Job), s));
+  GLOC_TRY(h->states.ensure(sizeof(CandState), s));
+  GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part, s));
+  GLOC_TRY(h->pairs.ensure(sizeof(f32x4) * 2 * bd.ld, s));
+  GLOC_TRY(h->Rt.ensure(sizeof(float) * 12 * (size_t)S, s));
+  GLOC_TRY(h->valid.ensure(sizeof(uint32_t) * (size_t)S, s));
+  GLOC_TRY(h->inliers.ensure(sizeof(uint32_t) * (size_t)S, s));
+  GLOC_HIP(hipMemcpyAsync(h->jobs.p, h->h_jobs, sizeof(Job), hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->states.p, h->h_states, sizeof(CandState), hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->pairs.p, hp.data(), sizeof(float) * 8 * bd.ld, hipMemcpyHostToDevice, s));
+  h->split = NnSplit{};
+  WsView v{};
+  v.s = s;
+  v.n_jobs = 1;
+  v.jobs = h->jobs.as<Job>();
+  v.states = h->states.as<CandState>();
+  v.partials = h->partials.as<double>();
+  v.pairs = h->pairs.as<f32x4>();
+  v.Rt = h->Rt.as<float>();
+  v.valid = h->valid.as<uint32_t>();
+  v.inliers = h->inliers.as<uint32_t>();
+  GLOC_TRY(ensure_ws(&h->pgraph));
+  GLOC_TRY(h->pgraph->counts.ensure(sizeof(uint32_t), s));
+  GLOC_HIP(hipMemcpyAsync(h->pgraph->counts.p, &h->h_jobs[0].n_src, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  GLOC_TRY(enqueue_graph(h, bd, prm, v, h->pgraph->counts.as<uint32_t>(), nblocks, M));
+  const gloc::pairgraph::Ws& w = *h->pgraph;
+  GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState), hipMemcpyDeviceToHost, s));
+  if (out_degree) GLOC_HIP(hipMemcpyAsync(out_degree, w.degree.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, s));
+  if (out_score) GLOC_HIP(hipMemcpyAsync(out_score, w.score.p, sizeof(uint64_t) * m, hipMemcpyDeviceToHost, s));
+  if (out_seeds) GLOC_HIP(hipMemcpyAsync(out_seeds, w.seeds.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, s));
+  if (out_set_sizes) GLOC_HIP(hipMemcpyAsync(out_set_sizes, w.set_sizes.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, s));
+  if (out_seed_inliers) GLOC_HIP(hipMemcpyAsync(out_seed_inliers, h->inliers.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipStreamSynchronize(s));  // (hp, too, is done with)
+  const CandState& cs = h->h_states[0];
+  const bool found = cs.best_h != 0xFFFFFFFFu && M >= 3;
+  if (out_T)
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) out_T[4 * i + j] = cs.Tf[3 * i + j];
+      out_T[4 * i + 3] = cs.Tf[9 + i];
+    }
+  if (out_inliers) *out_inliers = found ? cs.best_inl : 0u;
+  if (out_winner_rank) *out_winner_rank = found ? cs.best_h : 0xFFFFFFFFu;
+  const double need = std::max(3.0, std::ceil((double)prm->min_inlier_ratio * (double)M));
+  if (out_ok) *out_ok = found && (double)cs.best_inl >= need;
   return GLOC_OK;
 }
 
@@ -1094,6 +1272,11 @@ int gloc_reg_set_option(gloc_reg* h, int option, int64_t value) {
   if (option == GLOC_REG_OPT_NN_SRC_PER_LANE) {
     GLOC_REQUIRE(value == 1 || value == 2 || value == 4, GLOC_ERR_INVALID, "must be 1, 2 or 4");
     h->nn_src_per_lane = (int)value;
+    return GLOC_OK;
+  }
+  if (option == GLOC_REG_OPT_PAIRGRAPH_BUDGET) {
+    GLOC_REQUIRE(value >= 0 && (uint64_t)value <= gloc::pairgraph::BUDGET_BYTES, GLOC_ERR_INVALID, "must be in [0, 2^30]");
+    h->pgraph_budget = (size_t)value;
     return GLOC_OK;
   }
   set_err("unknown option %d", option);
@@ -1668,6 +1851,28 @@ int gloc_reg_fpfh_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* t
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
   return run_fpfh(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, out_T, out_inliers, out_n_pairs, out_ok);
+}
+
+int gloc_reg_fpfh_graph_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n,
+                                  const gloc_fpfh_graph_params* prm, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs,
+                                  int* out_ok) {
+  GLOC_TRY(gloc::pairgraph::check_params(prm));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_fpfh_graph(h, src_scan_id, tgt_scan_ids, n, prm, out_T, out_inliers, out_n_pairs, out_ok);
+}
+
+int gloc_reg_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const gloc_fpfh_graph_params* prm,
+                        uint32_t* out_degree, uint64_t* out_score, uint32_t* out_seeds, uint32_t* out_set_sizes,
+                        uint32_t* out_seed_inliers, float* out_T, uint32_t* out_inliers, uint32_t* out_winner_rank, int* out_ok) {
+  GLOC_TRY(gloc::pairgraph::check_params(prm));
+  GLOC_REQUIRE(h && ((P && Q) || m == 0), GLOC_ERR_INVALID, "null argument");
+  GLOC_REQUIRE(m < (1ull << 31), GLOC_ERR_INVALID, "too many pairs");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_pair_graph(h, P, Q, m, prm, out_degree, out_score, out_seeds, out_set_sizes, out_seed_inliers, out_T, out_inliers,
+                        out_winner_rank, out_ok);
 }
 
 int gloc_reg_fpfh_match(gloc_reg* h, const float* src_feat, size_t n_src, const float* tgt_feat, size_t n_tgt, uint32_t mutual,

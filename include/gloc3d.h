@@ -266,7 +266,7 @@ enum {
                                        runs of jobs on internal streams of their own, which measured SLOWER for one query
                                        alone (20 jobs: 3.2 ms on one stream, 3.9 with 4); a batch is always enqueued on
                                        the handle's stream */
-  GLOC_REG_OPT_NN_CHAIN = 11         /* 1 (default): the warm ICP passes of a SMALL batch (fewer than 48 jobs: one query's
+  GLOC_REG_OPT_NN_CHAIN = 11,        /* 1 (default): the warm ICP passes of a SMALL batch (fewer than 48 jobs: one query's
                                        20 candidates) run as ONE launch -- every pass's searches, reductions, solves and
                                        plans laid end to end, a wave of pass p + 1 waiting on the device for its own
                                        job's solve of pass p -- instead of 2 launches per pass with the chip draining
@@ -274,6 +274,9 @@ enum {
                                        bounded (3 s): a batch whose chain runs out is run again launch by launch before
                                        the call returns (said once on stderr) and the handle stops chaining until this
                                        option is set again */
+  GLOC_REG_OPT_PAIRGRAPH_BUDGET = 12 /* internal (tests): bytes of graph workspace in flight at a time in
+                                       gloc_reg_fpfh_graph_batch_ids, which walks its batch in groups of jobs that fit;
+                                       0 (default): 1 GiB.  Identical results */
 };
 enum {
   GLOC_REG_NN_CULLED = 0,    /* default: Hilbert-sorted scans, box hierarchy, skip what cannot win */
@@ -691,6 +694,58 @@ int gloc_reg_fpfh_match(gloc_reg* h, const float* src_feat, size_t n_src, const 
  * batch in flight on the handle. */
 int gloc_reg_fpfh_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
                             const gloc_fpfh_params* prm, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok);
+
+/* ---- Correspondence-graph global registration on the FPFH matches ------------------------------------------ *
+ * A second way from F3's match list to a pose, beside F4 and not instead of it.  Two correct matches (p_i -> q_i),
+ * (p_j -> q_j) keep the distance between their points, two wrong ones almost never do: a compatibility graph over the
+ * matches, in its second-order form (the idea of SC2-PCR, Chen et al. 2022; TEASER uses the same invariant), picks the
+ * consistent set out without sampling.  n_seeds hypotheses instead of thousands, no random numbers, and integer
+ * arithmetic up to the Kabsch fits.  The executable contract is tests/pairgraph_ref.py.
+ *
+ * The list is F4's: the kept pairs in ascending source index, M long; P_i the source point, Q_i the target point, fp32.
+ * G1  Compatibility.  For i != j, in fp64 from the fp32 inputs: a = sqrt((dx dx + dy dy) + dz dz) over P_i - P_j, b
+ *     likewise over Q; C_ij = 1 iff |a - b| < compat_thresh (the fp32 parameter widened to fp64).  C_ii = 0.  A pair with
+ *     a non-finite coordinate is compatible with nothing.  C is symmetric by construction.  degree_i = sum_j C_ij.
+ * G2  Second-order scores.  S_ij = C_ij |{k : C_ik and C_jk}|, an integer; score_i = sum_j S_ij, unsigned 64-bit.
+ * G3  Seeds and consensus sets.  The seeds are the n_seeds pairs of largest score, ties to the smaller list position (rank
+ *     r >= M: none).  A seed s with max_j S_sj = 0 gives no hypothesis (its set size is reported 0).  Else its set is
+ *     {s} u {j : theta_den S_sj >= theta_num max_j S_sj and S_sj > 0} in ascending position; fewer than 3 members: no
+ *     hypothesis.  The hypothesis is the fp64 Kabsch fit of the set -- raw moments, centroids, covariance and 3 x 3 SVD as
+ *     the RANSAC refit forms them -- rounded to fp32.
+ * G4  Choice and refit.  The inliers of a hypothesis are counted over all M pairs as F4 counts them (fp32, un-fused,
+ *     < inlier_thresh^2).  The winner has the most inliers (at least one), then the smaller seed rank.  The refit on the
+ *     winner's inliers and ok (at least max(3, ceil(min_inlier_ratio M)) inliers, the product in fp64) are F4's.  M < 3 or
+ *     no hypothesis: the identity, ok = 0, 0 inliers. */
+typedef struct gloc_fpfh_graph_params {
+  uint32_t normal_k, feature_k, mutual; /* as gloc_fpfh_params: 10, 16, 1 */
+  uint32_t n_seeds;                     /* default 64, 1..1024 */
+  float compat_thresh;                  /* default 0.6 m, > 0 */
+  float inlier_thresh;                  /* default 0.6 m, > 0 */
+  float min_inlier_ratio;               /* default 0 */
+  uint32_t theta_num, theta_den;        /* default 1, 2; 0 < num <= den */
+  uint32_t reserved_;
+} gloc_fpfh_graph_params;               /* 40 bytes */
+
+void gloc_fpfh_graph_default_params(gloc_fpfh_graph_params* p);
+
+/* Locate scan src_scan_id in each of the n targets (F3, then G1 - G4), shaped like gloc_reg_fpfh_batch_ids without
+ * stream ids (nothing is random): out_T [n][16] source -> target, out_inliers, out_n_pairs (M), out_ok (each may be NULL
+ * but out_T).  Job c equals its single call bit for bit; the result does not depend on whether a scan carries a target
+ * index, nor on how the batch is cut to fit the graph workspace (1 GiB of bit matrices and seed rows in flight at a
+ * time: n M_max ceil(M_max / 64) 8 bytes and 8 n_seeds M_max per job).  The parameter block is checked before the handle.
+ * GLOC_ERR_INVALID: null arguments, an unknown id, n outside [1, 4096], a parameter outside its range; GLOC_ERR_NOMEM: one
+ * list alone beyond the workspace (M ~ 90 000); GLOC_ERR_STATE: a batch in flight on the handle. */
+int gloc_reg_fpfh_graph_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n,
+                                  const gloc_fpfh_graph_params* prm, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs,
+                                  int* out_ok);
+
+/* G1 - G4 on a host pair list (a building block and diagnostic): P, Q [m][3].  Any output may be NULL: out_degree [m],
+ * out_score [m], out_seeds [n_seeds] (list positions, UINT32_MAX past rank m), out_set_sizes [n_seeds] (0: no set),
+ * out_seed_inliers [n_seeds] (0: no hypothesis), out_T [16], out_inliers, out_winner_rank (UINT32_MAX: none), out_ok.
+ * normal_k, feature_k and mutual are checked and not used. */
+int gloc_reg_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const gloc_fpfh_graph_params* prm,
+                        uint32_t* out_degree, uint64_t* out_score, uint32_t* out_seeds, uint32_t* out_set_sizes,
+                        uint32_t* out_seed_inliers, float* out_T, uint32_t* out_inliers, uint32_t* out_winner_rank, int* out_ok);
 
 /* ============================ NetVLAD-FC pooling head ("next" row N2) ===================== *
  * Replaces NetVLAD.forward of the reference (model/netvlad_fc.py:73-109, built without gating at

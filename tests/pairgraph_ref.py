@@ -16,8 +16,14 @@ DEFAULTS = dict(normal_k=10, feature_k=16, mutual=1, n_seeds=64, compat_thresh=0
                 theta_num=1, theta_den=2)
 
 
-def _lengths(X):
-    d = X[:, None, :] - X[None, :, :]
+ROW_BLOCK = 256          # G1 and G2 are evaluated this many rows at a time: the peak stays at a few [ROW_BLOCK, M] arrays
+KEEP_MATRICES = 1025     # graph() hands C and S back for lists up to this long (tests/pairgraph_cases.py caches what it hands back)
+
+
+def _lengths(X, rows=slice(None)):
+    """The lengths |X_i - X_j| of rows i against every j: each entry is a function of its two points alone, so the row
+    blocks below are the whole matrix bit for bit."""
+    d = X[rows, None, :] - X[None, :, :]
     return np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
 
 
@@ -26,20 +32,38 @@ def compat(P, Q, compat_thresh=0.6):
     P, Q = np.asarray(P, np.float32).reshape(-1, 3), np.asarray(Q, np.float32).reshape(-1, 3)
     M = len(P)
     fin = np.isfinite(P).all(1) & np.isfinite(Q).all(1)
-    both = fin[:, None] & fin[None, :] & ~np.eye(M, dtype=bool)
     thr = float(np.float32(compat_thresh))
+    P64, Q64 = P.astype(np.float64), Q.astype(np.float64)
+    C, edge = np.zeros((M, M), bool), 0
     with np.errstate(all="ignore"):
-        diff = np.abs(_lengths(P.astype(np.float64)) - _lengths(Q.astype(np.float64)))
-        C = (diff < thr) & both
-        edge = int(((np.abs(diff - thr) < EDGE_EPS) & both).sum())
+        for r0 in range(0, M, ROW_BLOCK):
+            rows = slice(r0, min(r0 + ROW_BLOCK, M))
+            both = fin[rows, None] & fin[None, :]
+            both[np.arange(rows.stop - r0), np.arange(r0, rows.stop)] = False
+            diff = np.abs(_lengths(P64, rows) - _lengths(Q64, rows))
+            C[rows] = (diff < thr) & both
+            edge += int(((np.abs(diff - thr) < EDGE_EPS) & both).sum())
     return C, edge
 
 
-def second_order(C):
-    """G2: S [M, M] int64 = C_ij |{k: C_ik and C_jk}|, score [M] uint64."""
-    c = C.astype(np.float64)                     # (counts below 2^53: exact, and the product runs in BLAS)
-    S = np.where(C, np.rint(c @ c), 0).astype(np.int64)
-    return S, S.sum(1).astype(np.uint64)
+def second_rows(C, rows, c=None):
+    """G2: rows `rows` (a slice or an index array) of S = C_ij |{k: C_ik and C_jk}|, int64 [len, M]."""
+    c = C.astype(np.float64) if c is None else c      # (counts below 2^53: exact, and the product runs in BLAS)
+    return np.where(C[rows], np.rint(c[rows] @ c), 0).astype(np.int64)
+
+
+def second_order(C, keep=True):
+    """G2: S [M, M] int64 (None unless keep), score [M] uint64 = the row sums of S, a block of rows at a time."""
+    M = len(C)
+    c = C.astype(np.float64)
+    S, score = (np.zeros((M, M), np.int64) if keep else None), np.zeros(M, np.uint64)
+    for r0 in range(0, M, ROW_BLOCK):
+        rows = slice(r0, min(r0 + ROW_BLOCK, M))
+        blk = second_rows(C, rows, c)
+        score[rows] = blk.sum(1).astype(np.uint64)
+        if keep:
+            S[rows] = blk
+    return S, score
 
 
 def kabsch(p, q, oracle):
@@ -64,11 +88,13 @@ def inlier_mask(P, Q, R, t, thr):
 def graph(P, Q, oracle, n_seeds=64, compat_thresh=0.6, inlier_thresh=0.6, min_inlier_ratio=0.0, theta_num=1, theta_den=2, **_):
     """G1 - G4 on the pair list (P[m], Q[m]): dict(degree [M] uint32, score [M] uint64, seeds [n_seeds] uint32 (NONE beyond
     M), set_sizes [n_seeds], seed_inliers [n_seeds], sets (list of index arrays, None: no hypothesis), T [4, 4] float64,
-    inliers, winner_rank (NONE: none), ok, n_pairs, edge, density, C, S, winner_mask)."""
+    inliers, winner_rank (NONE: none), ok, n_pairs, edge, density, C, S (both None for a list longer than KEEP_MATRICES: 8 + 1
+    bytes per entry are not worth keeping; compat() and second_order() make them on request), winner_mask)."""
     P, Q = np.ascontiguousarray(P, np.float32).reshape(-1, 3), np.ascontiguousarray(Q, np.float32).reshape(-1, 3)
     M = len(P)
     C, edge = compat(P, Q, compat_thresh)
-    S, score = second_order(C)
+    keep = M <= KEEP_MATRICES
+    S, score = second_order(C, keep)
     order = np.lexsort((np.arange(M), -score.astype(np.int64)))[:n_seeds]       # score descending, position ascending
     seeds = np.full(n_seeds, NONE, np.uint32)
     seeds[:len(order)] = order
@@ -76,9 +102,10 @@ def graph(P, Q, oracle, n_seeds=64, compat_thresh=0.6, inlier_thresh=0.6, min_in
     sets, hyps = [None] * n_seeds, [None] * n_seeds
     corr = np.arange(M, dtype=np.uint32)
     thr = np.float32(inlier_thresh)
+    seed_rows = S[order] if keep else second_rows(C, order)                     # the seeds' rows of S are all G3 reads
     with np.errstate(all="ignore"):
         for r, s in enumerate(order):
-            row = S[s]
+            row = seed_rows[r]
             mx = int(row.max(initial=0))
             if mx == 0:
                 continue
@@ -93,9 +120,10 @@ def graph(P, Q, oracle, n_seeds=64, compat_thresh=0.6, inlier_thresh=0.6, min_in
             R32, t32 = Rd.astype(np.float32), td.astype(np.float32)
             hyps[r] = (R32, t32)
             seed_inl[r] = oracle.lib().oracle_count_inliers(P, Q, corr, M, R32, t32, thr)
-    out = dict(degree=C.sum(1).astype(np.uint32), score=score, seeds=seeds, set_sizes=set_sizes, seed_inliers=seed_inl, sets=sets,
+    degree = C.sum(1).astype(np.uint32)
+    out = dict(degree=degree, score=score, seeds=seeds, set_sizes=set_sizes, seed_inliers=seed_inl, sets=sets,
                T=np.eye(4), inliers=0, winner_rank=NONE, ok=False, n_pairs=M, edge=edge,
-               density=float(C.sum()) / max(M * (M - 1), 1), C=C, S=S, winner_mask=np.zeros(M, bool))
+               density=float(degree.sum(dtype=np.int64)) / max(M * (M - 1), 1), C=C if keep else None, S=S, winner_mask=np.zeros(M, bool))
     if M < 3 or not seed_inl.any():
         return out
     w = int(np.argmax(seed_inl))                                                # the most inliers, then the smaller rank

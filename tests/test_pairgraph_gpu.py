@@ -6,7 +6,16 @@ restatement tests/pairgraph_ref.py on the case table tests/pairgraph_cases.py.
   Poses     within 1e-4 m / 1e-4 rad of the restatement (the project's parity rule for poses that come out of an fp64
             Kabsch whose moments are reduced in another order and that come back in float32).
   Batch     the eight same-world known-answer pairs are located from resident scans; a batch of ten is its ten single
-            calls bit for bit; a forced small workspace budget, and a target index on either scan, change no bit."""
+            calls bit for bit; a forced small workspace budget, and a target index on either scan, change no bit.
+  Widths    pg_score_kernel cuts a wave into 64 / lanes_per_row teams, lanes_per_row the power of two >= min(words, 64),
+            and streams rows of more than 64 words 64 at a time.  K.CASES reach 1, 2, 4, 8 and 32 lanes; K.WIDE adds
+            16 lanes (M = 513, 600: 9, 10 words; 1000, 1024: 16), 64 lanes (2049: 33 words; 4096: 64) and the streaming
+            branch (4097, 4161: 65, 66 words), sparse (planted, density 0.14) and dense (all64: one word walked by 64
+            teams; all2049; all4100 streaming); with them up to 5 chunks of ransac_score_kernel and 3 blocks of
+            accum_kernel<1>.  The dense lists and the disjoint cliques are compared with closed forms, no restatement
+            in between; hypothesis blocks of 16, 64 and 256 are crossed at n_seeds 16 | 17, 64 | 65, 256 | 257.
+  Mixed     a batch of jobs of 0, 0 or 1, at most 4 and some hundred pairs shares the longest job's rows, words and
+            lanes_per_row: it is its single calls bit for bit at any budget and in any order."""
 import numpy as np
 import pytest
 
@@ -182,3 +191,121 @@ def test_the_fpfh_stage_is_untouched(env, oracle_mod, known):
     assert _same(a, b)
     ref = fpfh_cases.known_result("yaw45_2m", oracle_mod)
     assert int(a["n_pairs"][0]) == ref["n_pairs"] and int(a["inliers"][0]) == ref["inliers"]
+
+
+# ---- row widths, closed forms, one handle, mixed batches ----------------------------------------------------------------
+INTEGERS = ("degree", "score", "seeds", "set_sizes", "seed_inliers")
+
+
+@pytest.mark.parametrize("name", K.WIDE)
+def test_row_widths_equal_the_restatement(env, oracle_mod, name):
+    P, Q, _, _ = K.pair_list(name, oracle_mod)
+    _check(env["reg"].pair_graph(P, Q, params=_prm(env["capi"])), K.result(name, oracle_mod), name)
+
+
+def _check_closed_form(g, x, truth, name):
+    """The device against numbers written down without the restatement; the pose against the pure translation."""
+    T = g["T"].astype(np.float64)
+    off = float(np.linalg.norm(T[:3, 3] - truth[:3, 3])), float(np.arccos(np.clip((np.trace(T[:3, :3]) - 1.0) / 2.0, -1.0, 1.0)))
+    print(name, "inliers", g["inliers"], x["inliers"], "rank", g["winner_rank"], "pose off the translation by", off)
+    for k in INTEGERS:
+        assert g[k].dtype == x[k].dtype and (g[k] == x[k]).all(), k
+    assert g["winner_rank"] == x["winner_rank"] and g["inliers"] == x["inliers"] and g["ok"] == x["ok"]
+    assert off[0] <= 1e-4 and off[1] <= 1e-4
+
+
+@pytest.mark.parametrize("m", K.ALL_SIZES)
+def test_dense_lists_are_their_closed_form(env, oracle_mod, m):
+    P, Q, _, truth = K.pair_list("all%d" % m, oracle_mod)
+    _check_closed_form(env["reg"].pair_graph(P, Q, params=_prm(env["capi"])), K.all_expected(m), truth, "all%d" % m)
+
+
+@pytest.mark.parametrize("n_seeds", (64, 272))
+def test_cliques_are_their_closed_form(env, oracle_mod, n_seeds):
+    """64 seeds: all in the largest group.  272: every pair is a seed, every group is seen, the last two ranks are empty."""
+    P, Q, _, truth = K.pair_list("cliques", oracle_mod)
+    g = env["reg"].pair_graph(P, Q, params=_prm(env["capi"], n_seeds=n_seeds))
+    _check_closed_form(g, K.cliques_expected(n_seeds), truth, "cliques")
+    _check(g, K.result("cliques", oracle_mod, n_seeds=n_seeds), "cliques")
+
+
+@pytest.mark.parametrize("n_seeds", (16, 17, 65, 256, 257))
+def test_seed_count_boundaries(env, oracle_mod, n_seeds):
+    """Either side of the hypothesis-block sizes of the scoring launch (16 up to 16 seeds, 64 up to 64, 256 beyond)."""
+    r = K.result("planted1000", oracle_mod, n_seeds=n_seeds)
+    assert r["edge"] == 0
+    P, Q, _, _ = K.pair_list("planted1000", oracle_mod)
+    _check(env["reg"].pair_graph(P, Q, params=_prm(env["capi"], n_seeds=n_seeds)), r, "planted1000")
+
+
+@pytest.mark.parametrize("over", [dict(theta_num=1, theta_den=1), dict(compat_thresh=0.25, inlier_thresh=0.3, theta_num=2, theta_den=3, n_seeds=17)],
+                         ids=("theta1", "tight"))
+def test_parameters_on_streamed_rows(env, oracle_mod, over):
+    r = K.result("planted4097", oracle_mod, **over)
+    assert r["edge"] == 0
+    P, Q, _, _ = K.pair_list("planted4097", oracle_mod)
+    _check(env["reg"].pair_graph(P, Q, params=_prm(env["capi"], **over)), r, "planted4097")
+
+
+def test_one_handle_any_order(capi, oracle_mod):
+    """Long, short, dense, long again on one fresh handle, the seed count changing in between: every call is the
+    restatement (rows or words a longer list left behind would show), and the same list twice gives the same bits."""
+    reg = capi.Registrar()
+    try:
+        got = []
+        for name, n_seeds in (("planted4161", 64), ("planted63", 64), ("all64", 16), ("planted4097", 64), ("planted3", 64), ("planted1000", 64),
+                              ("planted4161", 64)):
+            over = {} if n_seeds == 64 else dict(n_seeds=n_seeds)
+            P, Q, _, _ = K.pair_list(name, oracle_mod)
+            got.append(reg.pair_graph(P, Q, params=_prm(capi, **over)))
+            _check(got[-1], K.result(name, oracle_mod, **over), name)
+        a, b = got[0], got[-1]
+        assert all((a[k] == b[k]).all() for k in INTEGERS) and (bits(a["T"]) == bits(b["T"])).all()
+        assert (a["inliers"], a["winner_rank"], a["ok"]) == (b["inliers"], b["winner_rank"], b["ok"])
+    finally:
+        reg.close()
+
+
+MIXED = ("empty", "true", "n1", "other", "n4", "true")
+
+
+@pytest.mark.parametrize("order", [MIXED, MIXED[::-1], ("true", "other", "empty", "true", "n1", "n4")], ids=("as_listed", "reversed", "empty_opens_a_group"))
+def test_mixed_batch_is_its_single_calls(env, oracle_mod, known, order):
+    """One source against targets of no points, one point, four points and two whole scans: jobs of 0, at most 1, at most 4
+    and some hundred pairs in one batch, at the default budget and at budgets of one and two jobs in flight (groups then
+    start at jobs 1, 2, ... and at 2, 4: short and empty jobs open and close them)."""
+    reg, capi, store = env["reg"], env["capi"], env["store"]
+    s = known["yaw90_3m"][0]
+    small = {n: store.add(fpfh_cases.cloud(n)) for n in ("empty", "n1", "n4")}
+    ids = dict(small, true=known["yaw90_3m"][1], other=known["yaw45_2m"][1])
+    tg = [ids[n] for n in order]
+    prm = _prm(capi)
+    try:
+        singles = [reg.fpfh_graph_batch(s, [t], params=prm) for t in tg]
+        m = max(int(one["n_pairs"][0]) for one in singles)
+        per_job = m * ((m + 63) // 64) * 8 + 8 * prm.n_seeds * m
+        for jobs_in_flight in (0, 1, 2):                     # (0: the default budget)
+            reg.set_option(capi.REG_OPT_PAIRGRAPH_BUDGET, jobs_in_flight * per_job)
+            try:
+                b = reg.fpfh_graph_batch(s, tg, params=prm)
+            finally:
+                reg.set_option(capi.REG_OPT_PAIRGRAPH_BUDGET, 0)
+            print(order, "in flight", jobs_in_flight, "pairs", b["n_pairs"].tolist(), "inliers", b["inliers"].tolist(), "ok", b["ok"].tolist())
+            for c, one in enumerate(singles):
+                assert (bits(one["T"][0]) == bits(b["T"][c])).all() and one["inliers"][0] == b["inliers"][c]
+                assert one["n_pairs"][0] == b["n_pairs"][c] and one["ok"][0] == b["ok"][c]
+            first, second = [c for c, n in enumerate(order) if n == "true"]
+            assert (bits(b["T"][first]) == bits(b["T"][second])).all() and b["inliers"][first] == b["inliers"][second]
+            assert b["n_pairs"][first] == b["n_pairs"][second] and b["ok"][first] == b["ok"][second]
+            r = K.result("known:yaw90_3m", oracle_mod)
+            e = gicp_ref.pose_err(r["T"], b["T"][first])
+            assert int(b["n_pairs"][first]) == r["n_pairs"] and int(b["inliers"][first]) == r["inliers"] and bool(b["ok"][first]) == r["ok"]
+            assert e[0] <= 1e-4 and e[1] <= 1e-4
+            for c, n in enumerate(order):
+                if n in ("empty", "n1"):
+                    assert b["n_pairs"][c] <= 1 and (b["T"][c] == np.eye(4, dtype=np.float32)).all() and not b["ok"][c] and b["inliers"][c] == 0
+                if n == "n4":
+                    assert b["n_pairs"][c] <= 4
+    finally:
+        for t in small.values():
+            store.release(t)

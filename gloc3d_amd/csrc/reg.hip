@@ -116,9 +116,10 @@ struct JobHost {
   const float* init_T;  // 16 floats or null
 };
 
+const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+
 void init_state(CandState& st, const float* T16, uint32_t ransac_iters = 0) {
   memset(&st, 0, sizeof(st));
-  static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   const float* T = T16 ? T16 : I16;
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) {
@@ -132,6 +133,38 @@ void init_state(CandState& st, const float* T16, uint32_t ransac_iters = 0) {
   st.niters = ransac_iters;
   st.last_step = 0.f;
 }
+
+// The fp32 pose of a job's state as a row-major 4 x 4.
+void pose_to_T16(const CandState& st, float* T) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) T[4 * i + j] = st.Tf[3 * i + j];
+    T[4 * i + 3] = st.Tf[9 + i];
+  }
+  T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
+}
+
+// A pair list on the host in the layout the RANSAC kernels read ([ld] x f32x4[2], zero behind the n-th pair):
+// (P[i], Q[i]), or with `corr` (P[i], Q[corr[i]]).
+std::vector<float> pack_pairs(const float* P, const float* Q, const uint32_t* corr, size_t n, size_t ld) {
+  std::vector<float> hp(ld * 8, 0.f);
+  for (size_t i = 0; i < n; ++i)
+    for (int a = 0; a < 3; ++a) {
+      hp[i * 8 + a] = P[3 * i + a];
+      hp[i * 8 + 4 + a] = Q[3 * (corr ? (size_t)corr[i] : i) + a];
+    }
+  return hp;
+}
+
+// What a job on a list of M pairs found: a winner at all, and -- ok -- one with the inliers the stage itself asks for:
+// max(3, ceil(min_inlier_ratio M)), the product in fp64.
+void pair_verdict(const CandState& cs, uint32_t M, float min_inlier_ratio, bool* found, bool* ok) {
+  *found = cs.best_h != 0xFFFFFFFFu && M >= 3;
+  const double need = std::max(3.0, std::ceil((double)min_inlier_ratio * (double)M));
+  *ok = *found && (double)cs.best_inl >= need;
+}
+
+// Source groups (a wave's worth of sources at `cs` per lane) of a scan of n points.
+uint32_t src_groups(size_t n, int cs) { return (uint32_t)((n + 64 * cs - 1) / (64 * cs)); }
 
 struct BatchDims {
   uint32_t n_jobs, max_src, max_groups, n_part;
@@ -158,9 +191,9 @@ struct WsView {
 // Helper wave slots per job of the split plan (NnSplit) for a batch; 0: no plan.  One query alone (20 jobs) is the case
 // that needs it: its launch is as long as its longest wave.  A launch of hundreds of jobs only loses its tail to such waves
 // (5 % at 500 jobs, measured per XCD) and the kernel with the plan in it is 3 % slower: off by default there.
-uint32_t split_helpers(const gloc_reg* h, const BatchDims& bd) {
+uint32_t split_helpers(const gloc_reg* h, uint32_t n_jobs) {
   if (h->nn_mode == 1 || h->nn_split_helpers == 0 || h->nn_split_thresh == 0) return 0;
-  const uint32_t hx = h->nn_split_helpers > 0 ? (uint32_t)h->nn_split_helpers : (bd.n_jobs <= 64 ? 256u : (bd.n_jobs <= 256 ? 64u : 0u));
+  const uint32_t hx = h->nn_split_helpers > 0 ? (uint32_t)h->nn_split_helpers : (n_jobs <= 64 ? 256u : (n_jobs <= 256 ? 64u : 0u));
   return std::min<uint32_t>((hx + NN_WPB - 1) / NN_WPB * NN_WPB, 1u << 12);
 }
 
@@ -395,6 +428,134 @@ int ensure_pinned(gloc_reg* h, uint32_t n_jobs) {
   return GLOC_OK;
 }
 
+// What a batch asks of the handle's workspaces (open_batch).
+struct BatchSpec {
+  uint32_t n_jobs, max_src;
+  uint32_t max_groups;   // source groups of its longest source (0: the batch never searches)
+  bool search;           // it runs launch_nn: corr / d2, the counters, the heavy list
+  bool pairs;            // it runs on pairs: the pairs and, for `hyp` hypotheses per job, Rt / valid / inliers ...
+  size_t hyp;
+  bool alive;            // ... and ransac_alive_kernel's lists
+  uint32_t split_hx;     // helper slots per job of the split plan (split_helpers; 0: none) ...
+  uint32_t warm_passes;  // ... and the passes behind its first that could run chained (batch_chains)
+  // a batch that searches (and no more: RANSAC and the split plan are added by enqueue_jobs) / a batch on pairs alone
+  static BatchSpec searching(uint32_t n_jobs, size_t max_src, uint32_t max_groups) {
+    return BatchSpec{n_jobs, (uint32_t)max_src, max_groups, true, false, 0, false, 0u, 0u};
+  }
+  static BatchSpec on_pairs(uint32_t n_jobs, size_t max_src, size_t hyp, bool alive) {
+    return BatchSpec{n_jobs, (uint32_t)max_src, 0u, false, true, hyp, alive, 0u, 0u};
+  }
+};
+
+// An open batch: its shape, accum_kernel's blocks per job, whether its warm passes are one launch, the workspaces.
+struct Batch {
+  BatchDims bd;
+  uint32_t nblocks;
+  bool chained;
+  WsView v;
+};
+
+// Opens a batch on the handle -- the ONE place where its workspaces are laid out: the shape, the pinned staging, the
+// buffers the spec asks for, fill(jobs, states) into the staging and both tables up, the split plan and the heavy list (or
+// none), the view the launches take.  It also owns what gloc_reg_debug_corr may read afterwards: last_ld / last_jobs
+// describe a searching batch, and a batch on pairs -- whose job table has no scans behind it -- leaves last_jobs = 0, as
+// does a batch that failed to open.
+template <class Fill>
+int open_batch(gloc_reg* h, const BatchSpec& sp, Batch* out, Fill&& fill) {
+  const uint32_t n_jobs = sp.n_jobs;
+  const int cs = h->nn_src_per_lane;
+  hipStream_t s = h->stream;
+  Batch& b = *out;
+  b = Batch{};
+  BatchDims& bd = b.bd;
+  bd = BatchDims{n_jobs, sp.max_src, sp.max_groups, 0, 0};
+  b.nblocks = (bd.max_src + ACC_PER_BLOCK - 1) / ACC_PER_BLOCK;
+  bd.n_part = (std::max<uint32_t>(std::max(bd.max_groups, b.nblocks), 1) + 31u) & ~31u;  // (a job's row of a [job][n_part] table: whole 128-byte lines)
+  bd.ld = ((size_t)bd.max_src + 127) & ~(size_t)127;
+  h->last_jobs = 0;
+  GLOC_TRY(ensure_pinned(h, n_jobs));
+  h->chain_in_batch = false;
+  *h->h_chain_err = 0u;
+  fill(h->h_jobs, h->h_states);
+  WsView& v = b.v;
+  v.s = s;
+  v.n_jobs = n_jobs;
+  GLOC_TRY(h->jobs.ensure(sizeof(Job) * n_jobs, s));
+  GLOC_TRY(h->states.ensure(sizeof(CandState) * n_jobs, s));
+  GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part * n_jobs, s));
+  v.jobs = h->jobs.as<Job>();
+  v.states = h->states.as<CandState>();
+  v.partials = h->partials.as<double>();
+  if (sp.search) {
+    if (!h->counters.p) {
+      GLOC_TRY(h->counters.ensure(8 * NN_STAT_SLOTS, s));
+      GLOC_HIP(hipMemsetAsync(h->counters.p, 0, 8 * NN_STAT_SLOTS, s));
+    }
+    GLOC_TRY(h->corr.ensure(sizeof(uint32_t) * std::max<size_t>(bd.ld, 1) * n_jobs, s));
+    GLOC_TRY(h->d2.ensure(sizeof(float) * std::max<size_t>(bd.ld, 1) * n_jobs, s));
+    v.corr = h->corr.as<uint32_t>();
+    v.d2 = h->d2.as<float>();
+  }
+  if (sp.pairs) {
+    GLOC_TRY(h->pairs.ensure(sizeof(f32x4) * 2 * bd.ld * n_jobs, s));
+    GLOC_TRY(h->Rt.ensure(sizeof(float) * 12 * sp.hyp * n_jobs, s));
+    GLOC_TRY(h->valid.ensure(sizeof(uint32_t) * sp.hyp * n_jobs, s));
+    GLOC_TRY(h->inliers.ensure(sizeof(uint32_t) * sp.hyp * n_jobs, s));
+    v.pairs = h->pairs.as<f32x4>();
+    v.Rt = h->Rt.as<float>();
+    v.valid = h->valid.as<uint32_t>();
+    v.inliers = h->inliers.as<uint32_t>();
+    if (sp.alive) {
+      GLOC_TRY(h->alive.ensure(sizeof(uint32_t) * (sp.hyp + 1) * n_jobs, s));
+      v.a_idx = h->alive.as<uint32_t>();
+      v.a_cnt = v.a_idx + sp.hyp * n_jobs;
+    }
+  }
+  GLOC_HIP(hipMemcpyAsync(v.jobs, h->h_jobs, sizeof(Job) * n_jobs, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(v.states, h->h_states, sizeof(CandState) * n_jobs, hipMemcpyHostToDevice, s));
+  b.chained = batch_chains(h, bd, sp.split_hx, sp.warm_passes);
+  GLOC_TRY(setup_split(h, bd, cs, sp.split_hx, b.chained));  // (no helper slots: h->split = NnSplit{})
+  if (sp.search) GLOC_TRY(setup_heavy(h, bd, cs));
+  else h->heavy = NnHeavy{};
+  v.split = h->split;
+  v.heavy = h->heavy;
+  if (sp.search) {
+    h->last_ld = bd.ld;
+    h->last_jobs = n_jobs;
+  }
+  return GLOC_OK;
+}
+
+// The geometry of ransac_score_kernel's grid.  Pairs per work-group: 4096 -- or 1024 in a small batch (one query alone:
+// 20 jobs x 31 chunks = 620 work-groups for 256 CUs, each walking 16 tiles behind two barriers: 75 us for the first 16
+// hypotheses).
+uint32_t score_chunk_len(uint32_t n_jobs, uint32_t max_src) {
+  static_assert(1024 % SC_STAGE == 0 && SC_CHUNK % SC_STAGE == 0, "whole tiles");
+  return (size_t)n_jobs * ((max_src + SC_CHUNK - 1) / SC_CHUNK) >= 2048 ? (uint32_t)SC_CHUNK : 1024u;
+}
+
+// Hypotheses per work-group for `len` of them: 16 / 64 (its four waves share them and split every staged tile) or
+// thread <-> hypothesis.
+uint32_t score_hpb(uint32_t len) { return len <= 16 ? 16u : (len <= 64 ? 64u : 256u); }
+
+// The refit on the winning hypothesis' inliers among the pairs, behind the scan that chose it.
+int enqueue_refit(gloc_reg* h, const BatchDims& bd, const WsView& v, float thr2, uint32_t nblocks) {
+  const uint32_t n_jobs = v.n_jobs;
+  {
+    ProfScope ps(h->prof, "accum", v.s);
+    hipLaunchKernelGGL(accum_kernel<1>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, v.s, v.jobs, v.states, v.corr, v.d2, v.pairs, bd.ld, thr2,
+                       v.partials, bd.n_part);
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "solve", v.s);
+    hipLaunchKernelGGL(solve_kernel<1>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(SOLVE_THREADS), 0, v.s, v.partials, bd.n_part, false, v.jobs,
+                       v.states, v.split, n_jobs);
+    GLOC_HIP(hipGetLastError());
+  }
+  return GLOC_OK;
+}
+
 // The RANSAC stage on the pairs in v.pairs (jobs[c].n_src of them per job, sampled through jobs[c].src_inv when it is set):
 // hypotheses, scores, the sequential rule with its adaptive stop, the refit on the winner's inliers.  What
 // gloc_reg_batch_* runs behind its pairs pass and gloc_reg_fpfh_batch_ids behind its descriptor matches.
@@ -422,10 +583,7 @@ int enqueue_ransac(gloc_reg* h, const BatchDims& bd, const RansacRule& r, const 
   GLOC_HIP(hipMemsetAsync(v.valid, 0, sizeof(uint32_t) * (size_t)H * n_jobs, s));  // never-generated = invalid
   GLOC_HIP(hipMemsetAsync(v.inliers, 0, sizeof(uint32_t) * (size_t)H * n_jobs, s));
   const float thr2 = r.inlier_thresh * r.inlier_thresh;
-  // pairs per work-group of the scoring: 4096 -- or 1024 in a small batch (one query alone: 20 jobs x 31 chunks = 620
-  // work-groups for 256 CUs, each walking 16 tiles behind two barriers: 75 us for the first 16 hypotheses)
-  const uint32_t chunk_len = (size_t)n_jobs * ((bd.max_src + SC_CHUNK - 1) / SC_CHUNK) >= 2048 ? (uint32_t)SC_CHUNK : 1024u;
-  static_assert(1024 % SC_STAGE == 0 && SC_CHUNK % SC_STAGE == 0, "whole tiles");
+  const uint32_t chunk_len = score_chunk_len(n_jobs, bd.max_src);
   const unsigned cchunks = (bd.max_src + chunk_len - 1) / chunk_len;
   for (int ph = 0; ph < n_ph; ++ph) {
     const uint32_t h0 = bounds[ph], h1 = bounds[ph + 1], len = h1 - h0;
@@ -437,8 +595,7 @@ int enqueue_ransac(gloc_reg* h, const BatchDims& bd, const RansacRule& r, const 
       GLOC_HIP(hipGetLastError());
     }
     ProfScope ps(h->prof, "ransac_score", s);
-    // hypotheses per work-group: 16 / 64 (its four waves share them and split every staged tile) or thread <-> hypothesis
-    const uint32_t hpb = len <= 16 ? 16u : (len <= 64 ? 64u : 256u);
+    const uint32_t hpb = score_hpb(len);
     const unsigned NP = 8;
     if (!adaptive && ph > 0 && len >= 512 && cchunks >= NP) {
       // every hypothesis scored, not every pair of every hypothesis: an eighth of the pairs at a time, the hypotheses
@@ -469,20 +626,7 @@ int enqueue_ransac(gloc_reg* h, const BatchDims& bd, const RansacRule& r, const 
                          r.min_inlier_ratio, v.states);
     GLOC_HIP(hipGetLastError());
   }
-  {
-    ProfScope ps(h->prof, "accum", s);  // refit on the best hypothesis' inliers
-    hipLaunchKernelGGL(accum_kernel<1>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, s, v.jobs,
-                       v.states, v.corr, v.d2,
-                       v.pairs, bd.ld, thr2, v.partials, bd.n_part);
-    GLOC_HIP(hipGetLastError());
-  }
-  {
-    ProfScope ps(h->prof, "solve", s);
-    hipLaunchKernelGGL(solve_kernel<1>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(SOLVE_THREADS), 0, s, v.partials,
-                       bd.n_part, false, v.jobs, v.states, v.split, n_jobs);
-    GLOC_HIP(hipGetLastError());
-  }
-  return GLOC_OK;
+  return enqueue_refit(h, bd, v, thr2, nblocks);
 }
 
 // The launches of a batch: S1 -> S2 (RANSAC + refit) -> S3 (ICP).  chained: its warm passes are one launch (batch_chains).
@@ -530,79 +674,34 @@ int enqueue_jobs(gloc_reg* h, const std::vector<JobHost>& jh, const gloc_reg_par
   const uint32_t n_jobs = (uint32_t)jh.size();
   if (n_jobs == 0) return GLOC_OK;
   const int cs = h->nn_src_per_lane;
-  BatchDims bd{n_jobs, 0, 0, 0, 0};
-  GLOC_TRY(ensure_pinned(h, n_jobs));
-  h->chain_in_batch = false;
-  *h->h_chain_err = 0u;
-  Job* jd = h->h_jobs;
+  uint32_t max_src = 0;
   bool can = false, any_tgt = false;
-  for (uint32_t c = 0; c < n_jobs; ++c) {
-    const DevScan &s = jh[c].src, &t = jh[c].tgt;
-    const uint32_t ng = (uint32_t)((s.n + 64 * cs - 1) / (64 * cs));
-    jd[c] = Job{s.idx.pts, s.order, s.idx.inv, t.xyz, t.idx, (uint32_t)s.n, ng, jh[c].stream_id, 0u};
-    bd.max_src = std::max<uint32_t>(bd.max_src, (uint32_t)s.n);
-    bd.max_groups = std::max(bd.max_groups, ng);
-    can |= s.n >= 3;
-    any_tgt |= t.n >= 1;
+  for (const JobHost& j : jh) {
+    max_src = std::max<uint32_t>(max_src, (uint32_t)j.src.n);
+    can |= j.src.n >= 3;
+    any_tgt |= j.tgt.n >= 1;
   }
-  const uint32_t nblocks = (bd.max_src + ACC_PER_BLOCK - 1) / ACC_PER_BLOCK;
-  bd.n_part = (std::max<uint32_t>(std::max(bd.max_groups, nblocks), 1) + 31u) & ~31u;  // (a job's row of a [job][n_part] table: whole 128-byte lines)
-  bd.ld = ((size_t)bd.max_src + 127) & ~(size_t)127;
-  h->last_ld = bd.ld;
-  h->last_jobs = n_jobs;
-  hipStream_t s = h->stream;
-  for (uint32_t c = 0; c < n_jobs; ++c) {
-    init_state(h->h_states[c], jh[c].init_T, prm->ransac_iters);
-    if (jh[c].src.n < 3) h->h_states[c].frozen = 1;  // nothing to estimate: T stays the initial guess
-  }
-  GLOC_TRY(h->jobs.ensure(sizeof(Job) * n_jobs, s));
-  if (!h->counters.p) {
-    GLOC_TRY(h->counters.ensure(8 * NN_STAT_SLOTS, s));
-    GLOC_HIP(hipMemsetAsync(h->counters.p, 0, 8 * NN_STAT_SLOTS, s));
-  }
-  GLOC_TRY(h->states.ensure(sizeof(CandState) * n_jobs, s));
-  GLOC_TRY(h->corr.ensure(sizeof(uint32_t) * std::max<size_t>(bd.ld, 1) * n_jobs, s));
-  GLOC_TRY(h->d2.ensure(sizeof(float) * std::max<size_t>(bd.ld, 1) * n_jobs, s));
-  GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part * n_jobs, s));
-  GLOC_HIP(hipMemcpyAsync(h->jobs.p, jd, sizeof(Job) * n_jobs, hipMemcpyHostToDevice, s));
-  GLOC_HIP(hipMemcpyAsync(h->states.p, h->h_states, sizeof(CandState) * n_jobs, hipMemcpyHostToDevice, s));
   const bool ransac = can && any_tgt && prm->ransac_iters > 0;
+  const bool adaptive = prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f;
   // the warm passes: the ICP passes behind the batch's first, cold, pass (RANSAC's pairs pass, else the first ICP pass)
   const uint32_t warm_passes = !(can && any_tgt) ? 0u : (ransac ? prm->icp_iters : std::max<uint32_t>(prm->icp_iters, 1u) - 1u);
-  const uint32_t hx = split_helpers(h, bd);
-  const bool chained = batch_chains(h, bd, hx, warm_passes);
-  GLOC_TRY(setup_split(h, bd, cs, hx, chained));
-  const size_t H = prm->ransac_iters;
-  const bool adaptive = prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f;
-  if (ransac) {
-    GLOC_TRY(h->pairs.ensure(sizeof(f32x4) * 2 * bd.ld * n_jobs, s));
-    GLOC_TRY(h->Rt.ensure(sizeof(float) * 12 * H * n_jobs, s));
-    GLOC_TRY(h->valid.ensure(sizeof(uint32_t) * H * n_jobs, s));
-    GLOC_TRY(h->inliers.ensure(sizeof(uint32_t) * H * n_jobs, s));
-    if (!adaptive) GLOC_TRY(h->alive.ensure(sizeof(uint32_t) * (H + 1) * n_jobs, s));
-  }
-  GLOC_TRY(setup_heavy(h, bd, cs));
-  WsView v{};
-  v.s = s;
-  v.n_jobs = n_jobs;
-  v.jobs = h->jobs.as<Job>();
-  v.states = h->states.as<CandState>();
-  v.corr = h->corr.as<uint32_t>();
-  v.d2 = h->d2.as<float>();
-  v.partials = h->partials.as<double>();
-  if (ransac) {
-    v.pairs = h->pairs.as<f32x4>();
-    v.Rt = h->Rt.as<float>();
-    v.valid = h->valid.as<uint32_t>();
-    v.inliers = h->inliers.as<uint32_t>();
-    if (!adaptive) {
-      v.a_idx = h->alive.as<uint32_t>();
-      v.a_cnt = h->alive.as<uint32_t>() + H * n_jobs;
+  BatchSpec spec = BatchSpec::searching(n_jobs, max_src, src_groups(max_src, cs));
+  spec.pairs = ransac;
+  spec.hyp = prm->ransac_iters;
+  spec.alive = !adaptive;
+  spec.split_hx = split_helpers(h, n_jobs);
+  spec.warm_passes = warm_passes;
+  Batch b;
+  GLOC_TRY(open_batch(h, spec, &b, [&](Job* jd, CandState* st) {
+    for (uint32_t c = 0; c < n_jobs; ++c) {
+      const DevScan &s = jh[c].src, &t = jh[c].tgt;
+      jd[c] = Job{s.idx.pts, s.order, s.idx.inv, t.xyz, t.idx, (uint32_t)s.n, src_groups(s.n, cs), jh[c].stream_id, 0u};
+      init_state(st[c], jh[c].init_T, prm->ransac_iters);
+      if (s.n < 3) st[c].frozen = 1;  // nothing to estimate: T stays the initial guess
     }
-  }
-  v.split = h->split;
-  v.heavy = h->heavy;
-  GLOC_TRY(enqueue_pipeline(h, bd, prm, v, can, any_tgt, nblocks, chained));
+  }));
+  hipStream_t s = h->stream;
+  GLOC_TRY(enqueue_pipeline(h, b.bd, prm, b.v, can, any_tgt, b.nblocks, b.chained));
   GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState) * n_jobs, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipEventRecord(h->done_ev, s));
   if (h->chain_in_batch) {  // (a small batch: a few KB)
@@ -651,12 +750,7 @@ int collect_jobs(gloc_reg* h, uint32_t n_jobs, const size_t* n_src_of, float max
   for (uint32_t c = 0; c < n_jobs; ++c) {
     const CandState& st = h->h_states[c];
     const size_t n_src = n_src_of[c];
-    float* T = out_T + 16 * (size_t)c;
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) T[4 * i + j] = st.Tf[3 * i + j];
-      T[4 * i + 3] = st.Tf[9 + i];
-    }
-    T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
+    pose_to_T16(st, out_T + 16 * (size_t)c);
     const float rmse = n_src ? (float)std::sqrt(st.sum_d2 / (double)n_src) : 0.f;
     if (out_rmse) out_rmse[c] = rmse;
     if (out_inliers) out_inliers[c] = st.best_inl;
@@ -739,9 +833,9 @@ struct TempScans {
   }
 };
 
-// Point-to-plane or generalized ICP refinement of one source against n targets (p2l.hip, gicp.hip): the batch is set up as
-// enqueue_jobs sets one up -- job table, fp32 poses in the CandState array the search reads, corr / d2 -- without a split
-// plan (it is solve_kernel that makes one), and `refine` (p2l::run or gicp::run behind their arguments) drives the passes
+// Point-to-plane or generalized ICP refinement of one source against n targets (p2l.hip, gicp.hip): a searching batch
+// (open_batch) -- job table, fp32 poses in the CandState array the search reads, corr / d2 -- without a split plan (it is
+// solve_kernel that makes one), and `refine` (p2l::run or gicp::run behind their arguments) drives the passes
 // through launch_nn.  Synchronous: the scans are pinned for the call.  Targets without normals get them with normal_k, and
 // with src_normals so does the source; `refine` is handed the source's (null without src_normals): DevScan::nrm is in the
 // order of idx.pts whatever that order is (curve or kd: scan_store.hpp), the order of the slots corr is indexed by.
@@ -777,45 +871,23 @@ int run_refine(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, 
   GLOC_REQUIRE(src.n >= 1 && src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
   GLOC_REQUIRE(!src_normals || src.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", src_id);
   const uint32_t n_jobs = (uint32_t)n;
-  const uint32_t ng = (uint32_t)((src.n + 64 * cs - 1) / (64 * cs));
-  BatchDims bd{n_jobs, (uint32_t)src.n, ng, 0, 0};
-  const uint32_t nblocks = (bd.max_src + ACC_PER_BLOCK - 1) / ACC_PER_BLOCK;
-  bd.n_part = (std::max<uint32_t>(std::max(bd.max_groups, nblocks), 1) + 31u) & ~31u;
-  bd.ld = ((size_t)bd.max_src + 127) & ~(size_t)127;
-  h->last_ld = bd.ld;
-  h->last_jobs = n_jobs;
-  GLOC_TRY(ensure_pinned(h, n_jobs));
-  h->chain_in_batch = false;
+  const uint32_t ng = src_groups(src.n, cs);
   std::vector<gloc::p2l::TargetView> tv(n);
   for (uint32_t c = 0; c < n_jobs; ++c) {
     const DevScan& t = scans[1 + c];
     GLOC_REQUIRE(t.n == 0 || t.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", tgt_ids[c]);
-    h->h_jobs[c] = Job{src.idx.pts, src.order, src.idx.inv, t.xyz, t.idx, (uint32_t)src.n, ng, c, 0u};
-    init_state(h->h_states[c], init_T ? init_T + 16 * (size_t)c : nullptr);
     tv[c] = gloc::p2l::TargetView{t.idx.pts, t.nrm, (uint32_t)t.n};
   }
-  GLOC_TRY(h->jobs.ensure(sizeof(Job) * n_jobs, s));
-  if (!h->counters.p) {
-    GLOC_TRY(h->counters.ensure(8 * NN_STAT_SLOTS, s));
-    GLOC_HIP(hipMemsetAsync(h->counters.p, 0, 8 * NN_STAT_SLOTS, s));
-  }
-  GLOC_TRY(h->states.ensure(sizeof(CandState) * n_jobs, s));
-  GLOC_TRY(h->corr.ensure(sizeof(uint32_t) * bd.ld * n_jobs, s));
-  GLOC_TRY(h->d2.ensure(sizeof(float) * bd.ld * n_jobs, s));
-  GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part * n_jobs, s));
-  GLOC_HIP(hipMemcpyAsync(h->jobs.p, h->h_jobs, sizeof(Job) * n_jobs, hipMemcpyHostToDevice, s));
-  GLOC_HIP(hipMemcpyAsync(h->states.p, h->h_states, sizeof(CandState) * n_jobs, hipMemcpyHostToDevice, s));
-  h->split = NnSplit{};
-  GLOC_TRY(setup_heavy(h, bd, cs));
-  P2lPass pass{h, bd, WsView{}};
-  pass.v.s = s;
-  pass.v.n_jobs = n_jobs;
-  pass.v.jobs = h->jobs.as<Job>();
-  pass.v.states = h->states.as<CandState>();
-  pass.v.corr = h->corr.as<uint32_t>();
-  pass.v.d2 = h->d2.as<float>();
-  pass.v.partials = h->partials.as<double>();
-  pass.v.heavy = h->heavy;
+  Batch b;
+  GLOC_TRY(open_batch(h, BatchSpec::searching(n_jobs, src.n, ng), &b, [&](Job* jd, CandState* cst) {
+    for (uint32_t c = 0; c < n_jobs; ++c) {
+      const DevScan& t = scans[1 + c];
+      jd[c] = Job{src.idx.pts, src.order, src.idx.inv, t.xyz, t.idx, (uint32_t)src.n, ng, c, 0u};
+      init_state(cst[c], init_T ? init_T + 16 * (size_t)c : nullptr);
+    }
+  }));
+  const BatchDims& bd = b.bd;
+  P2lPass pass{h, bd, b.v};
   static_assert(sizeof(CandState) % sizeof(float) == 0, "the fp32 poses are a whole number of floats apart");
   gloc::p2l::Ctx x{};
   x.stream = s;
@@ -893,7 +965,6 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
     GLOC_REQUIRE(sc.n == 0 || (sc.fpfh && sc.has_fpfh(prm->normal_k, prm->feature_k)), GLOC_ERR_STATE, "a scan lost its features during the call");
   const uint32_t n_jobs = (uint32_t)n;
   const bool mutual = prm->mutual != 0;
-  static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   for (uint32_t c = 0; c < n_jobs; ++c) {
     memcpy(out_T + 16 * (size_t)c, I16, sizeof(I16));
     if (out_inliers) out_inliers[c] = 0;
@@ -903,10 +974,6 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
   if (src.n < 3) return GLOC_OK;  // fewer than three pairs whatever matches
   GLOC_TRY(ensure_ws(&h->fpfh));
   gloc::fpfh::Ws& w = *h->fpfh;
-  BatchDims bd{n_jobs, (uint32_t)src.n, 0, 0, 0};
-  const uint32_t nblocks = (bd.max_src + ACC_PER_BLOCK - 1) / ACC_PER_BLOCK;
-  bd.n_part = (std::max<uint32_t>(nblocks, 1) + 31u) & ~31u;
-  bd.ld = ((size_t)bd.max_src + 127) & ~(size_t)127;
   // keys: [job][src.n] forward, then each job's backward row of its target's length
   std::vector<size_t> back_off(n_jobs, 0);
   size_t n_keys = (size_t)n_jobs * src.n;
@@ -929,72 +996,43 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
     }
     pj[c] = gloc::fpfh::PairJob{fwd, bwd, src.xyz, t.xyz, (uint32_t)src.n, (uint32_t)t.n};
   }
-  GLOC_TRY(ensure_pinned(h, n_jobs));
-  h->chain_in_batch = false;
-  for (uint32_t c = 0; c < n_jobs; ++c) {
-    h->h_jobs[c] = Job{nullptr, nullptr, nullptr, nullptr, ScanIndexDev{}, 0u, 0u, stream_ids ? stream_ids[c] : c, 0u};
-    init_state(h->h_states[c], nullptr, prm->n_hyp);
-  }
-  const size_t H = prm->n_hyp;
-  const bool adaptive = prm->adaptive;
-  GLOC_TRY(h->jobs.ensure(sizeof(Job) * n_jobs, s));
-  GLOC_TRY(h->states.ensure(sizeof(CandState) * n_jobs, s));
-  GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part * n_jobs, s));
-  GLOC_TRY(h->pairs.ensure(sizeof(f32x4) * 2 * bd.ld * n_jobs, s));
-  GLOC_TRY(h->Rt.ensure(sizeof(float) * 12 * H * n_jobs, s));
-  GLOC_TRY(h->valid.ensure(sizeof(uint32_t) * H * n_jobs, s));
-  GLOC_TRY(h->inliers.ensure(sizeof(uint32_t) * H * n_jobs, s));
-  if (!adaptive) GLOC_TRY(h->alive.ensure(sizeof(uint32_t) * (H + 1) * n_jobs, s));
+  Batch b;
+  GLOC_TRY(open_batch(h, BatchSpec::on_pairs(n_jobs, src.n, prm->n_hyp, !prm->adaptive), &b, [&](Job* jd, CandState* cst) {
+    for (uint32_t c = 0; c < n_jobs; ++c) {
+      jd[c] = Job{nullptr, nullptr, nullptr, nullptr, ScanIndexDev{}, 0u, 0u, stream_ids ? stream_ids[c] : c, 0u};
+      init_state(cst[c], nullptr, prm->n_hyp);
+    }
+  }));
+  const BatchDims& bd = b.bd;
+  const WsView& v = b.v;
   GLOC_TRY(w.counts.ensure(sizeof(uint32_t) * n_jobs, s));
-  GLOC_HIP(hipMemcpyAsync(h->jobs.p, h->h_jobs, sizeof(Job) * n_jobs, hipMemcpyHostToDevice, s));
-  GLOC_HIP(hipMemcpyAsync(h->states.p, h->h_states, sizeof(CandState) * n_jobs, hipMemcpyHostToDevice, s));
   {
     ProfScope ps(h->prof, "fpfh_match", s);
     GLOC_TRY(gloc::fpfh::match(s, w, tasks));
   }
   {
     ProfScope ps(h->prof, "fpfh_pairs", s);
-    GLOC_TRY(gloc::fpfh::pairs(s, w, pj, bd.ld, h->pairs.as<f32x4>(), w.counts.as<uint32_t>()));
+    GLOC_TRY(gloc::fpfh::pairs(s, w, pj, bd.ld, v.pairs, w.counts.as<uint32_t>()));
   }
-  hipLaunchKernelGGL(set_pair_counts_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, s, h->jobs.as<Job>(), w.counts.as<uint32_t>(), n_jobs);
+  hipLaunchKernelGGL(set_pair_counts_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, s, v.jobs, w.counts.as<uint32_t>(), n_jobs);
   GLOC_HIP(hipGetLastError());
   // (the compaction has been waited for: the counts come down here, where the graph stage sizes its workspace by them)
   std::vector<uint32_t> counts(n_jobs);
   GLOC_HIP(hipMemcpyAsync(counts.data(), w.counts.p, sizeof(uint32_t) * n_jobs, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipStreamSynchronize(s));
   const uint32_t m_max = *std::max_element(counts.begin(), counts.end());
-  h->split = NnSplit{};
-  WsView v{};
-  v.s = s;
-  v.n_jobs = n_jobs;
-  v.jobs = h->jobs.as<Job>();
-  v.states = h->states.as<CandState>();
-  v.partials = h->partials.as<double>();
-  v.pairs = h->pairs.as<f32x4>();
-  v.Rt = h->Rt.as<float>();
-  v.valid = h->valid.as<uint32_t>();
-  v.inliers = h->inliers.as<uint32_t>();
-  if (!adaptive) {
-    v.a_idx = h->alive.as<uint32_t>();
-    v.a_cnt = h->alive.as<uint32_t>() + H * n_jobs;
-  }
-  GLOC_TRY(stage(bd, v, nblocks, m_max));
+  GLOC_TRY(stage(bd, v, b.nblocks, m_max));
   GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState) * n_jobs, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipStreamSynchronize(s));
   for (uint32_t c = 0; c < n_jobs; ++c) {
     const CandState& cs = h->h_states[c];
-    float* T = out_T + 16 * (size_t)c;
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) T[4 * i + j] = cs.Tf[3 * i + j];
-      T[4 * i + 3] = cs.Tf[9 + i];
-    }
     const uint32_t M = counts[c];
-    const bool found = cs.best_h != 0xFFFFFFFFu && M >= 3;
+    bool found, ok;
+    pair_verdict(cs, M, prm->min_inlier_ratio, &found, &ok);
+    pose_to_T16(cs, out_T + 16 * (size_t)c);
     if (out_n_pairs) out_n_pairs[c] = M;
     if (out_inliers) out_inliers[c] = found ? cs.best_inl : 0u;
-    // ok by the stage's own statement of the threshold: max(3, ceil(min_inlier_ratio M)), the product in fp64
-    const double need = std::max(3.0, std::ceil((double)prm->min_inlier_ratio * (double)M));
-    if (out_ok) out_ok[c] = found && (double)cs.best_inl >= need;
+    if (out_ok) out_ok[c] = ok;
   }
   return GLOC_OK;
 }
@@ -1050,27 +1088,15 @@ int enqueue_graph(gloc_reg* h, const BatchDims& bd, const gloc_fpfh_graph_params
   const float thr2 = prm->inlier_thresh * prm->inlier_thresh;
   {
     ProfScope ps(h->prof, "ransac_score", s);
-    const uint32_t chunk_len = (size_t)n_jobs * ((bd.max_src + SC_CHUNK - 1) / SC_CHUNK) >= 2048 ? (uint32_t)SC_CHUNK : 1024u;
+    const uint32_t chunk_len = score_chunk_len(n_jobs, bd.max_src), hpb = score_hpb(S);
     const unsigned cchunks = (std::max<uint32_t>(m_max, 1u) + chunk_len - 1) / chunk_len;
-    const uint32_t hpb = S <= 16 ? 16u : (S <= 64 ? 64u : 256u);
     hipLaunchKernelGGL(ransac_score_kernel, dim3((S + hpb - 1) / hpb, cchunks, n_jobs), dim3(256), 0, s, v.pairs, bd.ld, v.jobs, S, 0u, hpb, v.Rt,
                        v.valid, thr2, (const CandState*)nullptr, v.inliers, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, chunk_len);
     hipLaunchKernelGGL(ransac_scan_kernel<true>, dim3(n_jobs), dim3(64), 0, s, v.inliers, v.valid, v.Rt, S, 0u, S, v.jobs, 0.f,
                        prm->min_inlier_ratio, v.states);
     GLOC_HIP(hipGetLastError());
   }
-  {
-    ProfScope ps(h->prof, "accum", s);
-    hipLaunchKernelGGL(accum_kernel<1>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, s, v.jobs, v.states, v.corr, v.d2, v.pairs, bd.ld, thr2,
-                       v.partials, bd.n_part);
-    GLOC_HIP(hipGetLastError());
-  }
-  {
-    ProfScope ps(h->prof, "solve", s);
-    hipLaunchKernelGGL(solve_kernel<1>, dim3(n_jobs), dim3(SOLVE_THREADS), 0, s, v.partials, bd.n_part, false, v.jobs, v.states, NnSplit{}, n_jobs);
-    GLOC_HIP(hipGetLastError());
-  }
-  return GLOC_OK;
+  return enqueue_refit(h, bd, v, thr2, nblocks);  // (a batch on pairs has no split plan: one solve block per job)
 }
 
 int run_fpfh_graph(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const gloc_fpfh_graph_params* prm, float* out_T,
@@ -1087,7 +1113,6 @@ int run_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const 
                    uint64_t* out_score, uint32_t* out_seeds, uint32_t* out_set_sizes, uint32_t* out_seed_inliers, float* out_T,
                    uint32_t* out_inliers, uint32_t* out_winner_rank, int* out_ok) {
   const uint32_t S = prm->n_seeds, M = (uint32_t)m;
-  static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   if (out_T) memcpy(out_T, I16, sizeof(I16));
   if (out_inliers) *out_inliers = 0;
   if (out_winner_rank) *out_winner_rank = 0xFFFFFFFFu;
@@ -1099,45 +1124,18 @@ int run_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const 
   }
   if (M == 0) return GLOC_OK;
   hipStream_t s = h->stream;
-  BatchDims bd{1u, M, 0, 0, 0};
-  const uint32_t nblocks = (M + ACC_PER_BLOCK - 1) / ACC_PER_BLOCK;
-  bd.n_part = (std::max<uint32_t>(nblocks, 1) + 31u) & ~31u;
-  bd.ld = ((size_t)M + 127) & ~(size_t)127;
-  std::vector<float> hp(bd.ld * 8, 0.f);
-  for (size_t i = 0; i < m; ++i)
-    for (int a = 0; a < 3; ++a) {
-      hp[i * 8 + a] = P[3 * i + a];
-      hp[i * 8 + 4 + a] = Q[3 * i + a];
-    }
-  GLOC_TRY(ensure_pinned(h, 1));
-  h->chain_in_batch = false;
-  h->h_jobs[0] = Job{nullptr, nullptr, nullptr, nullptr, ScanIndexDev{}, M, 0u, 0u, 0u};
-  init_state(h->h_states[0], nullptr, S);
-  GLOC_TRY(h->jobs.ensure(sizeof(Job), s));
-  GLOC_TRY(h->states.ensure(sizeof(CandState), s));
-  GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part, s));
-  GLOC_TRY(h->pairs.ensure(sizeof(f32x4) * 2 * bd.ld, s));
-  GLOC_TRY(h->Rt.ensure(sizeof(float) * 12 * (size_t)S, s));
-  GLOC_TRY(h->valid.ensure(sizeof(uint32_t) * (size_t)S, s));
-  GLOC_TRY(h->inliers.ensure(sizeof(uint32_t) * (size_t)S, s));
-  GLOC_HIP(hipMemcpyAsync(h->jobs.p, h->h_jobs, sizeof(Job), hipMemcpyHostToDevice, s));
-  GLOC_HIP(hipMemcpyAsync(h->states.p, h->h_states, sizeof(CandState), hipMemcpyHostToDevice, s));
-  GLOC_HIP(hipMemcpyAsync(h->pairs.p, hp.data(), sizeof(float) * 8 * bd.ld, hipMemcpyHostToDevice, s));
-  h->split = NnSplit{};
-  WsView v{};
-  v.s = s;
-  v.n_jobs = 1;
-  v.jobs = h->jobs.as<Job>();
-  v.states = h->states.as<CandState>();
-  v.partials = h->partials.as<double>();
-  v.pairs = h->pairs.as<f32x4>();
-  v.Rt = h->Rt.as<float>();
-  v.valid = h->valid.as<uint32_t>();
-  v.inliers = h->inliers.as<uint32_t>();
+  Batch b;
+  GLOC_TRY(open_batch(h, BatchSpec::on_pairs(1, M, S, false), &b, [&](Job* jd, CandState* cst) {
+    jd[0] = Job{nullptr, nullptr, nullptr, nullptr, ScanIndexDev{}, M, 0u, 0u, 0u};
+    init_state(cst[0], nullptr, S);
+  }));
+  const WsView& v = b.v;
+  const std::vector<float> hp = pack_pairs(P, Q, nullptr, m, b.bd.ld);
+  GLOC_HIP(hipMemcpyAsync(v.pairs, hp.data(), sizeof(float) * hp.size(), hipMemcpyHostToDevice, s));
   GLOC_TRY(ensure_ws(&h->pgraph));
   GLOC_TRY(h->pgraph->counts.ensure(sizeof(uint32_t), s));
   GLOC_HIP(hipMemcpyAsync(h->pgraph->counts.p, &h->h_jobs[0].n_src, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  GLOC_TRY(enqueue_graph(h, bd, prm, v, h->pgraph->counts.as<uint32_t>(), nblocks, M));
+  GLOC_TRY(enqueue_graph(h, b.bd, prm, v, h->pgraph->counts.as<uint32_t>(), b.nblocks, M));
   const gloc::pairgraph::Ws& w = *h->pgraph;
   GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState), hipMemcpyDeviceToHost, s));
   if (out_degree) GLOC_HIP(hipMemcpyAsync(out_degree, w.degree.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, s));
@@ -1147,18 +1145,17 @@ int run_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const 
   if (out_seed_inliers) GLOC_HIP(hipMemcpyAsync(out_seed_inliers, h->inliers.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipStreamSynchronize(s));  // (hp, too, is done with)
   const CandState& cs = h->h_states[0];
-  const bool found = cs.best_h != 0xFFFFFFFFu && M >= 3;
-  if (out_T)
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) out_T[4 * i + j] = cs.Tf[3 * i + j];
-      out_T[4 * i + 3] = cs.Tf[9 + i];
-    }
+  bool found, ok;
+  pair_verdict(cs, M, prm->min_inlier_ratio, &found, &ok);
+  if (out_T) pose_to_T16(cs, out_T);
   if (out_inliers) *out_inliers = found ? cs.best_inl : 0u;
   if (out_winner_rank) *out_winner_rank = found ? cs.best_h : 0xFFFFFFFFu;
-  const double need = std::max(3.0, std::ceil((double)prm->min_inlier_ratio * (double)M));
-  if (out_ok) *out_ok = found && (double)cs.best_inl >= need;
+  if (out_ok) *out_ok = ok;
   return GLOC_OK;
 }
+
+gloc::ndt::Ctx ndt_ctx(gloc_reg* h) { return gloc::ndt::Ctx{h->store, h->stream, &h->prof, &h->ndt}; }
+gloc::vgicp::Ctx vgicp_ctx(gloc_reg* h) { return gloc::vgicp::Ctx{h->store, h->stream, &h->prof, &h->vgicp, &h->p2l}; }
 
 }  // namespace
 
@@ -1394,7 +1391,7 @@ int gloc_reg_batch_multi_begin(gloc_reg* h, size_t n_queries, const uint32_t* q_
   // rows without a candidate keep the initial guess (identity), not ok
   P.def_T.resize(16 * total);
   for (size_t o = 0; o < total; ++o)
-    for (int i = 0; i < 16; ++i) P.def_T[16 * o + i] = init_T ? init_T[16 * o + i] : ((i % 5 == 0) ? 1.f : 0.f);
+    std::copy_n(init_T ? init_T + 16 * o : I16, 16, P.def_T.begin() + 16 * o);
   P.total = total;
   P.max_rmse = params->max_rmse;
   P.max_final_step = params->icp_iters ? params->max_final_step : 0.f;
@@ -1471,8 +1468,7 @@ int gloc_reg_first_success_multi(gloc_reg* h, size_t n_queries, const uint32_t* 
   for (size_t q = 0; q < n_queries; ++q) {
     GLOC_TRY(store_get(h->store, q_scan_ids[q], h->nn_src_per_lane, &src[q]));
     out_rank[q] = -1;
-    float* T = out_T + 16 * q;
-    for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.f : 0.f;
+    std::copy_n(I16, 16, out_T + 16 * q);
     if (out_rmse) out_rmse[q] = 0.f;
     if (out_inliers) out_inliers[q] = 0;
   }
@@ -1569,48 +1565,29 @@ int gloc_reg_nn(gloc_reg* h, const float* src_xyz, size_t n_src, const float* tg
   hipStream_t s = h->stream;
   TempScans tmp(h->store);
   GLOC_TRY(tmp.add_all(src_xyz, n_src, h->nn_src_per_lane, &tgt_xyz, &n_tgt, 1, h->temp_target_index));
-  const int cs = h->nn_src_per_lane;
-  const uint32_t ng = (uint32_t)((n_src + 64 * cs - 1) / (64 * cs));
-  BatchDims bd{1, (uint32_t)n_src, ng, std::max<uint32_t>(ng, 1), ((size_t)n_src + 127) & ~(size_t)127};
-  auto done = [&](int code) {
-    (void)hipStreamSynchronize(s);
-    return code;
-  };
-  if (h->jobs.ensure(sizeof(Job), s) || h->states.ensure(sizeof(CandState), s) ||
-      h->corr.ensure(sizeof(uint32_t) * bd.ld, s) || h->d2.ensure(sizeof(float) * bd.ld, s) ||
-      h->export_idx.ensure(sizeof(uint32_t) * bd.ld, s) || h->export_d2.ensure(sizeof(float) * bd.ld, s) ||
-      h->partials.ensure(sizeof(double) * ACC_NV * bd.n_part, s))
-    return done(GLOC_ERR_NOMEM);
+  // (whatever happens below, the temporary scans are not freed under a launch that reads them)
+  struct SyncOnExit {
+    hipStream_t s;
+    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+  } sync{s};
   const DevScan &sc = tmp.scans[0], &tg = tmp.scans[1];
-  Job jd{sc.idx.pts, sc.order, sc.idx.inv, tg.xyz, tg.idx, (uint32_t)n_src, ng, 0u, 0u};
-  CandState st;
-  init_state(st, T16);
-  if (hipMemcpyAsync(h->jobs.p, &jd, sizeof(jd), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(h->states.p, &st, sizeof(st), hipMemcpyHostToDevice, s) != hipSuccess)
-    return done(GLOC_ERR_HIP);
-  h->split = NnSplit{};  // (one cold pass: there is no estimate to plan from)
-  if (int rc_h = setup_heavy(h, bd, cs)) return done(rc_h);
-  WsView v{};
-  v.s = s;
-  v.n_jobs = 1;
-  v.jobs = h->jobs.as<Job>();
-  v.states = h->states.as<CandState>();
-  v.corr = h->corr.as<uint32_t>();
-  v.d2 = h->d2.as<float>();
-  v.partials = h->partials.as<double>();
-  v.heavy = h->heavy;
-  int rc = launch_nn(h, bd, v, false, false, 0.f);
-  if (rc != GLOC_OK) return done(rc);
-  hipLaunchKernelGGL(export_corr_kernel, dim3((unsigned)((n_src + 255) / 256), 1), dim3(256), 0, s,
-                     h->jobs.as<Job>(), h->corr.as<uint32_t>(), h->d2.as<float>(), bd.ld,
+  const uint32_t ng = src_groups(n_src, h->nn_src_per_lane);
+  Batch b;  // (one cold pass: there is no estimate to plan a split from)
+  GLOC_TRY(open_batch(h, BatchSpec::searching(1, n_src, ng), &b, [&](Job* jd, CandState* st) {
+    jd[0] = Job{sc.idx.pts, sc.order, sc.idx.inv, tg.xyz, tg.idx, (uint32_t)n_src, ng, 0u, 0u};
+    init_state(st[0], T16);
+  }));
+  const size_t ld = b.bd.ld;
+  GLOC_TRY(h->export_idx.ensure(sizeof(uint32_t) * ld, s));
+  GLOC_TRY(h->export_d2.ensure(sizeof(float) * ld, s));
+  GLOC_TRY(launch_nn(h, b.bd, b.v, false, false, 0.f));
+  hipLaunchKernelGGL(export_corr_kernel, dim3((unsigned)((n_src + 255) / 256), 1), dim3(256), 0, s, b.v.jobs, b.v.corr, b.v.d2, ld,
                      h->export_idx.as<uint32_t>(), h->export_d2.as<float>());
-  if (hipMemcpyAsync(out_idx, h->export_idx.p, sizeof(uint32_t) * n_src, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(out_d2, h->export_d2.p, sizeof(float) * n_src, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    set_err("gloc_reg_nn: copy back failed: %s", hipGetErrorString(hipGetLastError()));
-    return done(GLOC_ERR_HIP);
-  }
-  return done(GLOC_OK);
+  GLOC_HIP(hipGetLastError());
+  GLOC_HIP(hipMemcpyAsync(out_idx, h->export_idx.p, sizeof(uint32_t) * n_src, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipMemcpyAsync(out_d2, h->export_d2.p, sizeof(float) * n_src, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipStreamSynchronize(s));
+  return GLOC_OK;
 }
 
 int gloc_reg_ransac_hypotheses(gloc_reg* h, const float* src_xyz, const float* tgt_xyz,
@@ -1624,43 +1601,31 @@ int gloc_reg_ransac_hypotheses(gloc_reg* h, const float* src_xyz, const float* t
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  const size_t ld = (n + 127) & ~(size_t)127;
   // pairs are built on the host from (src, tgt[corr]) -- src is taken as already moved; slots are the
   // caller's indices (no inverse permutation)
-  std::vector<float> hp(ld * 8, 0.f);
-  for (size_t i = 0; i < n; ++i) {
-    for (int a = 0; a < 3; ++a) {
-      hp[i * 8 + a] = src_xyz[3 * i + a];
-      hp[i * 8 + 4 + a] = tgt_xyz[3 * (size_t)corr[i] + a];
-    }
-  }
-  GLOC_TRY(h->pairs.ensure(sizeof(float) * 8 * ld, s));
-  GLOC_TRY(h->jobs.ensure(sizeof(Job), s));
-  GLOC_TRY(h->Rt.ensure(sizeof(float) * 12 * (size_t)n_hyp, s));
-  GLOC_TRY(h->valid.ensure(sizeof(uint32_t) * (size_t)n_hyp, s));
-  GLOC_TRY(h->inliers.ensure(sizeof(uint32_t) * (size_t)n_hyp, s));
-  Job jd{};
-  jd.n_src = (uint32_t)n;
-  jd.cand_id = cand;
-  GLOC_HIP(hipMemcpyAsync(h->jobs.p, &jd, sizeof(jd), hipMemcpyHostToDevice, s));
-  GLOC_HIP(hipMemcpyAsync(h->pairs.p, hp.data(), sizeof(float) * 8 * ld, hipMemcpyHostToDevice, s));
-  GLOC_HIP(hipMemsetAsync(h->inliers.p, 0, sizeof(uint32_t) * (size_t)n_hyp, s));
-  hipLaunchKernelGGL(ransac_hyp_kernel, dim3((n_hyp + 127) / 128, 1), dim3(128), 0, s,
-                     h->pairs.as<f32x4>(), ld, h->jobs.as<Job>(), seed, n_hyp, 0u, n_hyp,
-                     (const CandState*)nullptr, h->Rt.as<float>(), h->valid.as<uint32_t>());
+  Batch b;
+  GLOC_TRY(open_batch(h, BatchSpec::on_pairs(1, n, n_hyp, false), &b, [&](Job* jd, CandState* st) {
+    jd[0] = Job{};
+    jd[0].n_src = (uint32_t)n;
+    jd[0].cand_id = cand;
+    init_state(st[0], nullptr);  // (not read: the hypotheses are generated and scored, never scanned)
+  }));
+  const WsView& v = b.v;
+  const size_t ld = b.bd.ld;
+  const std::vector<float> hp = pack_pairs(src_xyz, tgt_xyz, corr, n, ld);
+  GLOC_HIP(hipMemcpyAsync(v.pairs, hp.data(), sizeof(float) * hp.size(), hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemsetAsync(v.inliers, 0, sizeof(uint32_t) * (size_t)n_hyp, s));
+  hipLaunchKernelGGL(ransac_hyp_kernel, dim3((n_hyp + 127) / 128, 1), dim3(128), 0, s, v.pairs, ld, v.jobs, seed, n_hyp, 0u, n_hyp,
+                     (const CandState*)nullptr, v.Rt, v.valid);
   GLOC_HIP(hipGetLastError());
   dim3 grid((n_hyp + 255) / 256, (unsigned)((n + SC_CHUNK - 1) / SC_CHUNK), 1);
-  hipLaunchKernelGGL(ransac_score_kernel, grid, dim3(256), 0, s, h->pairs.as<f32x4>(), ld,
-                     h->jobs.as<Job>(), n_hyp, 0u, 256u /* thread <-> hypothesis */, h->Rt.as<float>(),
-                     h->valid.as<uint32_t>(), inlier_thresh * inlier_thresh, (const CandState*)nullptr,
-                     h->inliers.as<uint32_t>(), (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, (uint32_t)SC_CHUNK);
+  hipLaunchKernelGGL(ransac_score_kernel, grid, dim3(256), 0, s, v.pairs, ld, v.jobs, n_hyp, 0u, 256u /* thread <-> hypothesis */, v.Rt,
+                     v.valid, inlier_thresh * inlier_thresh, (const CandState*)nullptr, v.inliers, (const uint32_t*)nullptr,
+                     (const uint32_t*)nullptr, 0u, (uint32_t)SC_CHUNK);
   GLOC_HIP(hipGetLastError());
-  GLOC_HIP(hipMemcpyAsync(out_Rt, h->Rt.p, sizeof(float) * 12 * (size_t)n_hyp,
-                          hipMemcpyDeviceToHost, s));
-  GLOC_HIP(hipMemcpyAsync(out_valid, h->valid.p, sizeof(uint32_t) * (size_t)n_hyp,
-                          hipMemcpyDeviceToHost, s));
-  GLOC_HIP(hipMemcpyAsync(out_inliers, h->inliers.p, sizeof(uint32_t) * (size_t)n_hyp,
-                          hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipMemcpyAsync(out_Rt, v.Rt, sizeof(float) * 12 * (size_t)n_hyp, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipMemcpyAsync(out_valid, v.valid, sizeof(uint32_t) * (size_t)n_hyp, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipMemcpyAsync(out_inliers, v.inliers, sizeof(uint32_t) * (size_t)n_hyp, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipStreamSynchronize(s));
   return GLOC_OK;
 }
@@ -1744,8 +1709,7 @@ int gloc_reg_ndt_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tg
   GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  const gloc::ndt::Ctx x{h->store, h->stream, &h->prof, &h->ndt};
-  return gloc::ndt::run(x, src_scan_id, tgt_scan_ids, n, init_T, nullptr, prm, out_T, out_prob, out_iters, out_converged,
+  return gloc::ndt::run(ndt_ctx(h), src_scan_id, tgt_scan_ids, n, init_T, nullptr, prm, out_T, out_prob, out_iters, out_converged,
                         nullptr);
 }
 
@@ -1754,9 +1718,8 @@ int gloc_reg_ndt_derivatives(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_sca
   GLOC_REQUIRE(h && p6 && out_score && out_grad6 && out_hess36, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  const gloc::ndt::Ctx x{h->store, h->stream, &h->prof, &h->ndt};
   double s[43];
-  GLOC_TRY(gloc::ndt::run(x, src_scan_id, &tgt_scan_id, 1, nullptr, p6, prm, nullptr, nullptr, nullptr, nullptr, s));
+  GLOC_TRY(gloc::ndt::run(ndt_ctx(h), src_scan_id, &tgt_scan_id, 1, nullptr, p6, prm, nullptr, nullptr, nullptr, nullptr, s));
   *out_score = s[0];
   for (int i = 0; i < 6; ++i) out_grad6[i] = s[1 + i];
   for (int i = 0; i < 36; ++i) out_hess36[i] = s[7 + i];
@@ -1768,8 +1731,7 @@ int gloc_reg_ndt_cells(gloc_reg* h, uint32_t scan_id, const gloc_ndt_params* prm
   GLOC_REQUIRE(h && n_cells, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  const gloc::ndt::Ctx x{h->store, h->stream, &h->prof, &h->ndt};
-  return gloc::ndt::cells(x, scan_id, prm, capacity, out_key3, out_count, out_mean3, out_icov9, n_cells);
+  return gloc::ndt::cells(ndt_ctx(h), scan_id, prm, capacity, out_key3, out_count, out_mean3, out_icov9, n_cells);
 }
 
 int gloc_reg_p2l_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
@@ -1817,8 +1779,7 @@ int gloc_reg_vgicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* 
   GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  const gloc::vgicp::Ctx x{h->store, h->stream, &h->prof, &h->vgicp, &h->p2l};
-  return gloc::vgicp::run(x, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
+  return gloc::vgicp::run(vgicp_ctx(h), src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
                           nullptr, nullptr);
 }
 
@@ -1828,8 +1789,7 @@ int gloc_reg_vgicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_i
   GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  const gloc::vgicp::Ctx x{h->store, h->stream, &h->prof, &h->vgicp, &h->p2l};
-  return gloc::vgicp::run(x, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
+  return gloc::vgicp::run(vgicp_ctx(h), src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
                           out_count);
 }
 
@@ -1839,8 +1799,7 @@ int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params
   GLOC_REQUIRE(h && n_voxels, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  const gloc::vgicp::Ctx x{h->store, h->stream, &h->prof, &h->vgicp, &h->p2l};
-  return gloc::vgicp::voxels(x, scan_id, prm, capacity, out_key3, out_count, out_mean3, out_nn6, n_voxels);
+  return gloc::vgicp::voxels(vgicp_ctx(h), scan_id, prm, capacity, out_key3, out_count, out_mean3, out_nn6, n_voxels);
 }
 
 // (the parameters are looked at before the handle, as generalized ICP's are)

@@ -896,6 +896,54 @@ def test_split_groups_decide_ties_by_the_original_index(capi, oracle_mod):
         r.close()
 
 
+def test_debug_corr_describes_what_the_workspaces_hold(capi, scans):
+    """One handle, calls of different kinds back to back.  A batch on pairs (gloc_reg_pair_graph, gloc_reg_fpfh_batch_ids,
+    gloc_reg_ransac_hypotheses) overwrites the job table with jobs that have no scans behind them: gloc_reg_debug_corr is
+    then refused on the host (GLOC_ERR_INVALID), not launched over that table.  gloc_reg_nn leaves ITS single job there.
+    The searching batch run again after each of them returns what it returned the first time, bit for bit."""
+    A, B = scans["A"], scans["B"]
+    store = capi.ScanStore()
+    src = np.ascontiguousarray(B[::300])
+    q = store.add(src)
+    cs = [store.add(np.ascontiguousarray(A[::300])), store.add(np.ascontiguousarray(A[1::310]))]
+    r = capi.Registrar(store=store)
+    prm = capi.default_reg_params(ransac_iters=64, icp_iters=4)
+
+    def searching_batch():
+        out = r.batch_multi([q], [cs], params=prm)
+        return out, [r.debug_corr(j, len(src)) for j in range(2)]
+
+    def same_as_first():
+        out, corr = searching_batch()
+        assert (bits(out["T"]) == bits(out0["T"])).all() and (bits(out["rmse"]) == bits(out0["rmse"])).all()
+        assert (out["inliers"] == out0["inliers"]).all() and (out["ok"] == out0["ok"]).all()
+        for (ai, ad), (bi, bd) in zip(corr, corr0):
+            assert (ai == bi).all() and (bits(ad) == bits(bd)).all()
+
+    out0, corr0 = searching_batch()
+    rng = np.random.default_rng(11)
+    P = (rng.normal(size=(50, 3)) * 5).astype(np.float32)
+    Q = (P @ scans["T"][:3, :3].T + scans["T"][:3, 3]).astype(np.float32)
+    for on_pairs in (lambda: r.pair_graph(P, Q),
+                     lambda: r.fpfh_batch(q, cs),
+                     lambda: r.ransac_hypotheses(P, Q, np.arange(50, dtype=np.uint32), 1, 0, 16, 0.6)):
+        on_pairs()
+        with pytest.raises(capi.GlocError) as ei:
+            r.debug_corr(0, 16)
+        assert ei.value.code == 1, ei.value                # GLOC_ERR_INVALID
+        same_as_first()
+    tgt = np.ascontiguousarray(A[2::290])
+    idx, d2 = r.nn(src[:129], tgt)
+    ai, ad = r.debug_corr(0, 129)                          # the nn call's job, not job 0 of the batch before it
+    assert (ai == idx).all() and (bits(ad) == bits(d2)).all()
+    with pytest.raises(capi.GlocError) as ei:
+        r.debug_corr(1, 16)
+    assert ei.value.code == 1, ei.value
+    same_as_first()
+    r.close()
+    store.close()
+
+
 def test_begin_end_pipeline_on_a_shared_stream(capi, scans):
     """gloc_reg_batch_multi_begin / _end: two handles with their own workspaces on ONE stream, batch i + 1 enqueued
     before batch i's results are waited for (bench.py's registration pipeline).  Every batch equals the blocking call

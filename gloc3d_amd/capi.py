@@ -126,6 +126,11 @@ class CoarseParams(C.Structure):
                 ("top_yaw", C.c_uint32), ("refine", C.c_uint32), ("min_overlap", C.c_float), ("reserved_", C.c_uint32)]
 
 
+class ScParams(C.Structure):
+    _fields_ = [("n_rings", C.c_uint32), ("n_sectors", C.c_uint32), ("max_radius", C.c_float), ("sensor_height", C.c_float),
+                ("min_common_columns", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class GroundParams(C.Structure):
     _fields_ = [("near_range2", C.c_float), ("knn", C.c_uint32), ("plane_thresh", C.c_float),
                 ("ransac_iters", C.c_uint32), ("ransac_conf", C.c_float), ("reserved_", C.c_uint32),
@@ -315,6 +320,30 @@ _PROTOS = [
     ("gloc_coarse_release", _i, [_vp, _u32]),
     ("gloc_coarse_cells", _i, [_vp, _u32, C.POINTER(_u32), _vp, _sz]),
     ("gloc_coarse_match", _i, [_vp, _u32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_sc_default_params", _i, [C.POINTER(ScParams)]),
+    ("gloc_sc_create", _i, [_i, C.POINTER(ScParams), C.POINTER(_vp)]),
+    ("gloc_sc_destroy", _i, [_vp]),
+    ("gloc_sc_set_stream", _i, [_vp, _vp]),
+    ("gloc_sc_synchronize", _i, [_vp]),
+    ("gloc_sc_describe", _i, [_vp, _vp, _sz, _sz, _vp]),
+    ("gloc_sc_describe_store_scans", _i, [_vp, _vp, _vp, _sz, _vp]),
+    ("gloc_sc_add", _i, [_vp, _vp, _sz]),
+    ("gloc_sc_add_scan", _i, [_vp, _vp, _sz, _sz, C.POINTER(_u64)]),
+    ("gloc_sc_add_store_scans", _i, [_vp, _vp, _vp, _sz, C.POINTER(_u64)]),
+    ("gloc_sc_size", _i, [_vp, C.POINTER(_sz)]),
+    ("gloc_sc_clear", _i, [_vp]),
+    ("gloc_sc_reserve", _i, [_vp, _sz]),
+    ("gloc_sc_rows", _i, [_vp, _sz, _sz, _vp]),
+    ("gloc_sc_ring_keys", _i, [_vp, _sz, _sz, _vp]),
+    ("gloc_sc_save", _i, [_vp, C.c_char_p]),
+    ("gloc_sc_load", _i, [_vp, C.c_char_p]),
+    ("gloc_sc_search", _i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp]),
+    ("gloc_sc_search_store_scans", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp]),
+    ("gloc_sc_distances", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gloc_sc_shift_to_yaw", _i, [C.POINTER(ScParams), _u32, C.POINTER(C.c_float)]),
+    ("gloc_sc_set_profile", _i, [_vp, _i]),
+    ("gloc_sc_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
+    ("gloc_sc_profile_reset", _i, [_vp]),
     ("gloc_ground_default_params", _i, [_vp]),
     ("gloc_ground_create", _i, [_i, C.POINTER(_vp)]),
     ("gloc_ground_destroy", _i, [_vp]),
@@ -1531,6 +1560,136 @@ class CoarseMatcher(_Handle):
         check(lib().gloc_coarse_match(self._h, int(q_grid), _np_ptr(ids), n, C.byref(self.params), _np_ptr(xyyaw),
                                       _np_ptr(ratio), _np_ptr(ok), _np_ptr(self.last_scale)))
         return xyyaw, ratio, ok.astype(bool)
+
+
+def default_sc_params(**over):
+    p = ScParams()
+    check(lib().gloc_sc_default_params(C.byref(p)))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def sc_shift_to_yaw(params, shift):
+    """The yaw (radians, in (-pi, pi]) of a query in the frame of the place it matched at `shift`."""
+    yaw = C.c_float()
+    check(lib().gloc_sc_shift_to_yaw(C.byref(params), int(shift), C.byref(yaw)))
+    return yaw.value
+
+
+class ScanContext(_Handle):
+    """Scan Context place descriptors (Kim & Kim, IROS 2018): built from host or resident scans, kept as a resident
+    database, searched exhaustively with the column shift that aligns the two scans' yaw (gloc_sc_* of include/gloc3d.h)."""
+
+    _C = "sc"
+    set_stream, synchronize = _set_stream, _synchronize
+    set_profile, profile, profile_reset = _set_profile, _profile, _profile_reset
+
+    def __init__(self, device=0, params=None):
+        self._h = C.c_void_p()
+        self.params = params or default_sc_params()
+        check(lib().gloc_sc_create(device, C.byref(self.params), C.byref(self._h)))
+        self.shape = (int(self.params.n_rings), int(self.params.n_sectors))
+
+    def _desc(self, d, n=None):
+        d = np.ascontiguousarray(d, np.float32).reshape((-1,) + self.shape)
+        assert n is None or d.shape[0] == n
+        return d
+
+    @staticmethod
+    def _ids(scan_ids):
+        return np.ascontiguousarray(scan_ids, np.uint32).reshape(-1)
+
+    def describe(self, pts):
+        pts = np.ascontiguousarray(pts, np.float32)
+        out = np.empty(self.shape, np.float32)
+        check(lib().gloc_sc_describe(self._h, _np_ptr(pts), pts.shape[0], pts.shape[1], _np_ptr(out)))
+        return out
+
+    def describe_store_scans(self, store, scan_ids):
+        ids = self._ids(scan_ids)
+        out = np.empty((ids.shape[0],) + self.shape, np.float32)
+        check(lib().gloc_sc_describe_store_scans(self._h, store._h, _np_ptr(ids), ids.shape[0], _np_ptr(out)))
+        return out
+
+    def add(self, desc):
+        d = self._desc(desc)
+        check(lib().gloc_sc_add(self._h, _np_ptr(d), d.shape[0]))
+
+    def add_scan(self, pts):
+        pts = np.ascontiguousarray(pts, np.float32)
+        row = C.c_uint64()
+        check(lib().gloc_sc_add_scan(self._h, _np_ptr(pts), pts.shape[0], pts.shape[1], C.byref(row)))
+        return row.value
+
+    def add_store_scans(self, store, scan_ids):
+        """Returns the row index of the first of the scans; the others follow it in order."""
+        ids = self._ids(scan_ids)
+        first = C.c_uint64()
+        check(lib().gloc_sc_add_store_scans(self._h, store._h, _np_ptr(ids), ids.shape[0], C.byref(first)))
+        return first.value
+
+    def __len__(self):
+        n = C.c_size_t()
+        check(lib().gloc_sc_size(self._h, C.byref(n)))
+        return n.value
+
+    def clear(self):
+        check(lib().gloc_sc_clear(self._h))
+
+    def reserve(self, n):
+        check(lib().gloc_sc_reserve(self._h, n))
+
+    def rows(self, first=0, n=None):
+        n = len(self) - first if n is None else n
+        out = np.empty((n,) + self.shape, np.float32)
+        check(lib().gloc_sc_rows(self._h, first, n, _np_ptr(out)))
+        return out
+
+    def ring_keys(self, first=0, n=None):
+        n = len(self) - first if n is None else n
+        out = np.empty((n, self.shape[0]), np.float32)
+        check(lib().gloc_sc_ring_keys(self._h, first, n, _np_ptr(out)))
+        return out
+
+    def save(self, path):
+        check(lib().gloc_sc_save(self._h, os.fsencode(path)))
+
+    def load(self, path):
+        check(lib().gloc_sc_load(self._h, os.fsencode(path)))
+
+    @staticmethod
+    def _search_outs(nq, k):
+        return np.empty((nq, k), np.uint64), np.empty((nq, k), np.float32), np.empty((nq, k), np.uint32)
+
+    def search(self, q_desc, k, row_begin=0, row_end=None):
+        """(row indices, distances, shifts), each [nq, k], ascending by (distance, row index)."""
+        q = self._desc(q_desc)
+        idx, dist, shift = self._search_outs(q.shape[0], k)
+        check(lib().gloc_sc_search(self._h, _np_ptr(q), q.shape[0], k, row_begin, SIZE_MAX if row_end is None else row_end,
+                                   _np_ptr(idx), _np_ptr(dist), _np_ptr(shift)))
+        return idx, dist, shift
+
+    def search_store_scans(self, store, q_scan_ids, k, row_begin=0, row_end=None):
+        ids = self._ids(q_scan_ids)
+        idx, dist, shift = self._search_outs(ids.shape[0], k)
+        check(lib().gloc_sc_search_store_scans(self._h, store._h, _np_ptr(ids), ids.shape[0], k, row_begin,
+                                               SIZE_MAX if row_end is None else row_end, _np_ptr(idx), _np_ptr(dist),
+                                               _np_ptr(shift)))
+        return idx, dist, shift
+
+    def distances(self, q_desc, rows, by_shift=False):
+        """One descriptor against the listed rows: (distances, shifts[, the distance at every shift [n, n_sectors]])."""
+        q = self._desc(q_desc, 1)
+        r = np.ascontiguousarray(rows, np.uint64).reshape(-1)
+        dist, shift = np.empty(r.shape[0], np.float32), np.empty(r.shape[0], np.uint32)
+        by = np.empty((r.shape[0], self.shape[1]), np.float32) if by_shift else None
+        check(lib().gloc_sc_distances(self._h, _np_ptr(q), _np_ptr(r), r.shape[0], _np_ptr(dist), _np_ptr(shift),
+                                      _np_ptr(by) if by_shift else None))
+        return (dist, shift, by) if by_shift else (dist, shift)
+
+    def shift_to_yaw(self, shift):
+        return sc_shift_to_yaw(self.params, shift)
 
 
 def default_ground_params(**over):

@@ -1020,6 +1020,83 @@ int gloc_coarse_match_pairs(gloc_coarse* h, const uint32_t* q_grids, const uint3
                             const gloc_coarse_params* params, float* out_xy_yaw, float* out_ratio,
                             int* out_ok, float* out_scale);
 
+/* ============================ Scan Context place descriptor ================================= *
+ * NO COUNTERPART IN THE REFERENCE, whose descriptors come from trained networks (gloc_vgg_*, gloc_pillar_*): this is
+ * the training-free LiDAR place descriptor of Kim & Kim, "Scan Context", IROS 2018, so that scan -> descriptor ->
+ * retrieval -> registration runs on what the repository holds.  tests/sc_ref.py restates the contract in numpy.
+ *
+ * Descriptor [n_rings][n_sectors] fp32: for every finite point, r = hypot(x, y) (dropped when r >= max_radius),
+ * ring = min(floor(r / max_radius * n_rings), n_rings - 1), theta = atan2(y, x) in [0, 2 pi),
+ * sector = min(floor(theta / 2 pi * n_sectors), n_sectors - 1); a bin holds the maximum of max(z + sensor_height, 0)
+ * (one fp32 addition) over its points, 0 when empty.  The same bits on every run and in every batch.
+ * Ring key [n_rings]: the fp32 mean of each ring, summed in sector order.  (The paper's sector key, the mean of each
+ * column, is not kept: nothing here reads it.)
+ *
+ * distance(q, c) = min over shift s of 1 - mean over the sectors j where column (j - s) mod n_sectors of q and column j
+ * of c both hold a height above 0, of the cosine of the two columns -- np.roll(q, s, axis=1) against c; a shift with
+ * fewer than max(min_common_columns, 1) such sectors scores 1.0; the lowest shift wins among equal fp32 distances, so a
+ * descriptor without a non-empty column has distance 1.0 at shift 0.  Distances are fp32 in [0, 1], within 1e-5 of the
+ * fp64 value; a pair's distance depends on the pair alone (any batch, any run: the same bits).  A query whose yaw in the
+ * place's frame is +90 degrees matches at s = n_sectors / 4 (gloc_sc_shift_to_yaw): the seed of the 3-D stage for
+ * reverse-direction revisits.  The search is exhaustive over the window, with no ring-key prefilter. */
+typedef struct gloc_sc gloc_sc;
+
+typedef struct gloc_sc_params {
+  uint32_t n_rings;            /* 20 (1..32) */
+  uint32_t n_sectors;          /* 60 (2..64) */
+  float max_radius;            /* 80 m, finite and positive */
+  float sensor_height;         /* 2.0 m, finite: added to z so that the ground is near 0 */
+  uint32_t min_common_columns; /* 1 */
+  uint32_t reserved_;
+} gloc_sc_params;
+
+int gloc_sc_default_params(gloc_sc_params* p);
+/* The parameters are fixed for the handle's life; they are checked before the device is (GLOC_ERR_INVALID). */
+int gloc_sc_create(int device, const gloc_sc_params* params, gloc_sc** out);
+int gloc_sc_destroy(gloc_sc* h);
+int gloc_sc_set_stream(gloc_sc* h, void* hip_stream);
+int gloc_sc_synchronize(gloc_sc* h);
+/* One host scan (x y z first in every stride_floats floats) -> out_desc [n_rings][n_sectors]; nothing is added. */
+int gloc_sc_describe(gloc_sc* h, const float* xyz, size_t n, size_t stride_floats, float* out_desc);
+/* n (<= 4096) scans resident in a store on the same device, one launch sequence, the points stay on the device. */
+int gloc_sc_describe_store_scans(gloc_sc* h, gloc_scan_store* store, const uint32_t* scan_ids, size_t n,
+                                 float* out_desc);
+/* Append rows: given descriptors (finite, >= 0: GLOC_ERR_INVALID otherwise), a host scan (row: its index, may be
+ * NULL), resident scans (first_row: the index of the first, may be NULL).  Rows are searchable when the call returns. */
+int gloc_sc_add(gloc_sc* h, const float* desc, size_t n);
+int gloc_sc_add_scan(gloc_sc* h, const float* xyz, size_t n, size_t stride_floats, uint64_t* row);
+int gloc_sc_add_store_scans(gloc_sc* h, gloc_scan_store* store, const uint32_t* scan_ids, size_t n,
+                            uint64_t* first_row);
+int gloc_sc_size(const gloc_sc* h, size_t* n_rows);
+int gloc_sc_clear(gloc_sc* h);
+int gloc_sc_reserve(gloc_sc* h, size_t n_rows);
+int gloc_sc_rows(gloc_sc* h, size_t first, size_t n, float* out_desc);
+int gloc_sc_ring_keys(gloc_sc* h, size_t first, size_t n, float* out_keys /* [n][n_rings] */);
+/* File: "GLOCSCTX", u32 version = 1, u32 rows, the gloc_sc_params block, rows x n_rings x n_sectors fp32.  load APPENDS;
+ * a file written with other parameters than the handle's is refused (GLOC_ERR_INVALID). */
+int gloc_sc_save(gloc_sc* h, const char* path);
+int gloc_sc_load(gloc_sc* h, const char* path);
+/* The k (1..64) nearest rows of [row_begin, row_end) for each of nq descriptors, ascending by (distance, row index);
+ * out_shift (may be NULL): the shift of each.  The window is the SLAM-mode exclusion, as in gloc_knn_search: row_end is
+ * clamped to the size (SIZE_MAX = all), and where the window holds fewer than k rows the tail is idx = UINT64_MAX,
+ * dist = FLT_MAX, shift = 0. */
+int gloc_sc_search(gloc_sc* h, const float* q_desc, size_t nq, size_t k, size_t row_begin, size_t row_end,
+                   uint64_t* out_idx, float* out_dist, uint32_t* out_shift);
+/* The same with the queries taken from resident scans: describe + search without a host round trip of the points. */
+int gloc_sc_search_store_scans(gloc_sc* h, gloc_scan_store* store, const uint32_t* q_scan_ids, size_t nq, size_t k,
+                               size_t row_begin, size_t row_end, uint64_t* out_idx, float* out_dist,
+                               uint32_t* out_shift);
+/* One descriptor against the listed rows only (rows may repeat): out_dist / out_shift [n], and, unless NULL,
+ * out_by_shift [n][n_sectors]: the distance at every shift.  The test hook of the distance kernel. */
+int gloc_sc_distances(gloc_sc* h, const float* q_desc, const uint64_t* rows, size_t n, float* out_dist,
+                      uint32_t* out_shift, float* out_by_shift);
+/* shift * 2 pi / n_sectors wrapped to (-pi, pi]: the query's yaw in the matched place's frame.  Host only. */
+int gloc_sc_shift_to_yaw(const gloc_sc_params* params, uint32_t shift, float* yaw);
+int gloc_sc_set_profile(gloc_sc* h, int enable);
+/* kernel families: "sc_scatter", "sc_finish", "sc_dist", "sc_select" */
+int gloc_sc_profile(gloc_sc* h, const char* kernel, double* total_ms, uint64_t* launches);
+int gloc_sc_profile_reset(gloc_sc* h);
+
 /* ============================ ground pre-alignment ("next" row N3) ========================= *
  * Replaces GroundEstimator::EsitmateGroundAndTransform (registration/ground_estimator.cpp:196-228),
  * the optional 4th-argument mode of global_localization (registration/global_localization.cpp:431-436,

@@ -152,23 +152,6 @@ int launch_dist_exact(gloc_knn* h, const float* d_q, int nq, size_t first, int n
   return GLOC_OK;
 }
 
-// Per-query top-K of h->dist: chunked threshold selection + merge(s).  MODE as select_chunk_kernel.
-constexpr int SELECT_ONE_BLOCK_MAX = 16384;  // rows one work-group per query selects from in one launch
-
-// Windows above 16 384 rows: S slices of L rows (a multiple of 64, <= 16 384), one work-group per (slice, query);
-// more slices than the window needs while the launch would leave CUs idle.
-struct SlicePlan {
-  int S, L;
-};
-bool plan_slices(int n_range, int nq, int K, SlicePlan* out) {
-  long long s = ((long long)n_range + SELQ_MAX_ROWS - 1) / SELQ_MAX_ROWS;
-  while (s * nq < 512 && n_range / (s * 2) >= 4096 && s * 2 * K <= SELQ_MAX_ROWS) s *= 2;
-  const int L = (int)((((long long)n_range + s - 1) / s + 63) & ~63ll);
-  const int S = (n_range + L - 1) / L;  // (no empty slice)
-  if ((long long)S * K > SELQ_MAX_ROWS || S > 65535) return false;  // the lists no longer fit one work-group's registers
-  *out = SlicePlan{S, L};
-  return true;
-}
 template <int MODE>
 int launch_slices(gloc_knn* h, const float* d_q, int nq, int K, size_t first, int n_range, size_t ld, size_t strideP,
                   int n_splits, const SlicePlan& sl, const int* only_flagged) {
@@ -191,29 +174,30 @@ int launch_slices(gloc_knn* h, const float* d_q, int nq, int K, size_t first, in
   return GLOC_OK;
 }
 
+const FinalOut KEYS_ONLY{nullptr, nullptr, 0, 1};
+
+// Per-query top-K of h->dist in the form `sp` names (knn_plan.hpp: plan_select).  MODE as select_chunk_kernel.  Window and
+// Slices also write the result through `fo` when it is given; Chunks leaves the keys alone (through_fo below).
 template <int MODE>
-int run_select(gloc_knn* h, const float* d_q, int nq, int K, size_t first, int n_range, size_t ld, size_t strideP,
-               int n_splits, uint64_t* d_keys_out, const int* only_flagged = nullptr,
-               const FinalOut& fo = FinalOut{nullptr, nullptr, 0, 1}, bool* finalized = nullptr) {
-  if (finalized) *finalized = false;
+int run_select(gloc_knn* h, const SelectPlan& sp, const float* d_q, int nq, int K, size_t first, int n_range, size_t ld,
+               size_t strideP, int n_splits, uint64_t* d_keys_out, const int* only_flagged = nullptr,
+               const FinalOut& fo = KEYS_ONLY) {
   ProfScope ps(h->prof, "select", h->stream);
-  if (n_range <= SELQ_MAX_ROWS && K <= 64) {  // one launch, one work-group per query
+  if (sp.form == Selection::Window) {
     hipLaunchKernelGGL(select_query_kernel<MODE>, dim3(nq), dim3(SELQ_THREADS), 0, h->stream, h->dist.as<float>(), ld,
                        strideP, n_splits, h->qnorm.as<float>(), d_q, (int)h->dim, h->db->norms.as<float>(), first, n_range,
                        K, d_keys_out, only_flagged, fo);
     GLOC_HIP(hipGetLastError());
-    if (finalized) *finalized = fo.idx != nullptr;
     return GLOC_OK;
   }
-  SlicePlan sl;
-  if (K <= 64 && plan_slices(n_range, nq, K, &sl)) {  // two launches: slices, then their lists
+  if (sp.form == Selection::Slices) {
+    const SlicePlan& sl = sp.sl;
     GLOC_TRY(launch_slices<MODE>(h, d_q, nq, K, first, n_range, ld, strideP, n_splits, sl, only_flagged));
     hipLaunchKernelGGL(select_query_kernel<2>, dim3(nq), dim3(SELQ_THREADS), 0, h->stream,
                        reinterpret_cast<const float*>(h->klists.as<uint64_t>()), (size_t)2 * sl.S * K, (size_t)0, 1,
                        (float*)nullptr, (const float*)nullptr, (int)h->dim, (const float*)nullptr, (size_t)0, sl.S * K, K,
                        d_keys_out, only_flagged, fo);
     GLOC_HIP(hipGetLastError());
-    if (finalized) *finalized = fo.idx != nullptr;
     return GLOC_OK;
   }
   const int per_group = SEL_LIST / K;  // lists one merge can take
@@ -253,90 +237,20 @@ int run_select(gloc_knn* h, const float* d_q, int nq, int K, size_t first, int n
   return GLOC_OK;
 }
 
-int run_exact(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_range,
-              uint64_t* d_keys_out, const FinalOut& fo = FinalOut{nullptr, nullptr, 0, 1}, bool* finalized = nullptr) {
+// *through_fo (here and in run_mfma): the result (indices, distances) has been written through `fo` already -- no finalize
+// launch; else it is the keys in d_keys_out
+int run_exact(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_range, uint64_t* d_keys_out,
+              const FinalOut& fo, bool* through_fo) {
   const size_t ld = ((size_t)n_range + 63) & ~(size_t)63;
+  const SelectPlan sp = plan_select(n_range, nq, k);
   GLOC_TRY(h->dist.ensure((size_t)nq * ld * sizeof(float), h->stream));
   GLOC_TRY(launch_dist_exact(h, d_q, nq, first, n_range, ld));
-  return run_select<0>(h, d_q, nq, k, first, n_range, ld, 0, 1, d_keys_out, nullptr, fo, finalized);
+  GLOC_TRY(run_select<0>(h, sp, d_q, nq, k, first, n_range, ld, 0, 1, d_keys_out, nullptr, fo));
+  *through_fo = fo.idx && sp.form != Selection::Chunks;
+  return GLOC_OK;
 }
 
 // ---- MFMA path -------------------------------------------------------------------------------
-struct MfmaPlan {
-  int WQ, NT, KS, BQ, BN;
-  int t32 = 0;  // 1: the 32 x 32 x 2 tiles (dist_mfma32_kernel: BQ = 64, BN = 128, one plan)
-  int b3 = 0;   // 1: the split-bf16 form (dist_bf16x3_tiled_kernel: BQ = 64, BN = 64 * NT)
-};
-
-MfmaPlan plan_mfma(int nq, int n_range, int dim, bool fp32_only) {
-  // The split-bf16 coarse pass (round 4): the matrix cores stop being the bound, the rows' stream from HBM is.  Tiles of
-  // 64 queries x 128 rows when those alone fill the CUs twice, 64 rows otherwise; K split until ~512 work-groups.
-  if (!fp32_only && dim % 8 == 0 && dim >= 8) {
-    const int qblocks = (nq + 63) / 64;
-    const int nt = ((long long)((n_range + 127) / 128) * qblocks >= 512) ? 2 : 1;
-    const long long tiles = (long long)((n_range + 64 * nt - 1) / (64 * nt)) * qblocks;
-    int ks = 1;
-    while (tiles * ks < 512 && ks < 16 && (dim % (64 * ks * 2)) == 0 && dim / (ks * 2) >= 128) ks *= 2;
-    MfmaPlan b{4, nt, ks, 64, 64 * nt};
-    b.b3 = 1;
-    return b;
-  }
-  MfmaPlan best{};
-  double best_cost = 1e300;
-  const int WQ = nq <= 16 ? 1 : (nq <= 32 ? 2 : 4);
-  static const int NT4[] = {2, 3, 4, 5, 6, 8}, NT2[] = {2, 4}, NT1[] = {1, 2};
-  const int* nts = WQ == 4 ? NT4 : (WQ == 2 ? NT2 : NT1);
-  const int n_nts = WQ == 4 ? 6 : 2;
-  const int BQ = 16 * WQ;
-  const int qblocks = (nq + BQ - 1) / BQ;
-  for (int i = 0; i < n_nts; ++i) {
-    const int NT = nts[i], BN = 16 * NT * (4 / WQ);
-    const long long tiles = (long long)((n_range + BN - 1) / BN) * qblocks;
-    // split K only when the tiles alone cannot give every CU a work-group (the partial sums cost
-    // KS x Q x N x 8 B of extra traffic and a longer rounding chain)
-    int KS = 1;
-    // (one block of queries over >= 64 row tiles: two work-groups per CU overlap each other's LDS hand-offs;
-    // measured at 64 x 10 000 and 25 x 4541 x 4096: -4 / -3 us; 128 x 16 000 and 32 x 2000: +4 us, so not there)
-    const long long want_wgs = (qblocks == 1 && tiles >= 64) ? 400 : 200;
-    while (tiles * KS < want_wgs && KS < 16 && (dim % (64 * KS * 2)) == 0 && dim / (KS * 2) >= 128) KS *= 2;
-    const int klen = (dim + KS - 1) / KS;
-    const long long wgs = tiles * KS;
-    const long long rounds = (wgs + 255) / 256;
-    // per-WG time ~ klen * (MFMA issue for BN rows + staging of BQ+BN rows)
-    const double per_wg = (double)klen * ((double)BN * 1.0 + (double)(BQ + BN) * 0.35);
-    const double cost = (double)rounds * per_wg * (1.0 + 0.03 * (KS - 1)) + (wgs < 128 ? 1e7 : 0);
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = MfmaPlan{WQ, NT, KS, BQ, BN};
-    }
-  }
-  // Many rounds of work-groups per CU (a shard of a large database): the 32 x 32 x 2 tiles -- half the LDS operand reads
-  // per flop.  Measured at 64 x 125 000 x 4096: 794 us against 922 with the 16 x 16 x 4 tiles (BN = 128, K-step 32, three
-  // work-groups per CU).  At 64 x 10 000 the launch is ONE round of work-groups and the tile that divides 10 000 rows
-  // into 500 of them (BN = 80, split-K 4) wins: 82 us against 92 - 116 for every 32-wide plan.
-  if (nq > 32 && (long long)((n_range + 127) / 128) * ((nq + 63) / 64) >= 3 * 256) {
-    best = MfmaPlan{4, 2, 1, 64, 128};
-    best.t32 = 1;
-  }
-  return best;
-}
-
-template <int WQ, int NT>
-void launch_mfma_inst(gloc_knn* h, const MfmaPlan& p, const float* d_q, int nq, size_t first,
-                      int n_range, size_t ld, size_t strideP) {
-  dim3 grid((unsigned)((n_range + p.BN - 1) / p.BN), (unsigned)((nq + p.BQ - 1) / p.BQ),
-            (unsigned)p.KS);
-  const int kps = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
-  if (kps < 128)
-    hipLaunchKernelGGL((dist_mfma_kernel<WQ, NT, 8>), grid, dim3(256), 0, h->stream,
-                       h->db->rows.as<float>(), d_q, h->dist.as<float>(), (int)h->dim, first, n_range,
-                       nq, kps, ld, strideP);
-  else
-    hipLaunchKernelGGL((dist_mfma_kernel<WQ, NT, 16>), grid, dim3(256), 0, h->stream,
-                       h->db->rows.as<float>(), d_q, h->dist.as<float>(), (int)h->dim, first, n_range,
-                       nq, kps, ld, strideP);
-}
-
 // The split-bf16 coarse pass over the mirror.  Its LDS image may exceed the 48-KB default, and the attribute that allows
 // more belongs to the device's copy of the kernel: set once per kernel and device.
 template <auto KERNEL>
@@ -349,201 +263,157 @@ int allow_lds(int device, int bytes) {
   }
   return GLOC_OK;
 }
-template <int NT, bool QRAW>
-int launch_bf16x3(gloc_knn* h, dim3 grid, const float* qsrc, size_t first, int n_range, int nq, int kps, size_t ld,
-                  size_t strideP, bool use_bmin, int n_blocks) {
+template <int NT, bool QRAW, bool BMIN>
+int launch_bf16x3(gloc_knn* h, const SearchPlan& p, dim3 grid, const float* qsrc, size_t first, int n_range, int nq) {
   constexpr int lds_bytes = b3_lds_bytes<NT>();
-  if (use_bmin) {
-    GLOC_TRY((allow_lds<dist_bf16x3_tiled_kernel<NT, QRAW, true>>(h->device, lds_bytes)));
-    hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT, QRAW, true>), grid, dim3(256), lds_bytes, h->stream, h->db->mirror.as<u32x4>(),
-                       qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps, ld, strideP, h->db->norms.as<float>(),
-                       h->bmin.as<float>(), n_blocks);
-  } else {
-    GLOC_TRY((allow_lds<dist_bf16x3_tiled_kernel<NT, QRAW>>(h->device, lds_bytes)));
-    hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT, QRAW>), grid, dim3(256), lds_bytes, h->stream, h->db->mirror.as<u32x4>(),
-                       qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps, ld, strideP, (const float*)nullptr,
-                       (float*)nullptr, 0);
-  }
-  GLOC_HIP(hipGetLastError());
+  GLOC_TRY((allow_lds<dist_bf16x3_tiled_kernel<NT, QRAW, BMIN>>(h->device, lds_bytes)));
+  hipLaunchKernelGGL((dist_bf16x3_tiled_kernel<NT, QRAW, BMIN>), grid, dim3(256), lds_bytes, h->stream, h->db->mirror.as<u32x4>(),
+                     qsrc, h->dist.as<float>(), (int)h->dim, first, n_range, nq, p.kps, p.ld, p.strideP,
+                     BMIN ? h->db->norms.as<float>() : (const float*)nullptr, BMIN ? h->bmin.as<float>() : (float*)nullptr,
+                     BMIN ? p.n_blocks : 0);
   return GLOC_OK;
 }
 
-// *finalized: the result (indices, distances) has been written through `fo` already -- no finalize launch
-int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_range,
-             uint64_t* d_keys_out, const FinalOut& fo, bool* finalized, bool fp32_only) {
-  *finalized = false;
-  const MfmaPlan p = plan_mfma(nq, n_range, (int)h->dim, fp32_only);
-  const int KC = std::max(h->candidates, std::min(64, k + 12));
-  const size_t ld = ((size_t)n_range + 63) & ~(size_t)63;
-  const size_t qpad = (size_t)((nq + p.BQ - 1) / p.BQ) * p.BQ;
-  const size_t strideP = qpad * ld;
-  GLOC_TRY(h->dist.ensure((size_t)p.KS * strideP * sizeof(float), h->stream));
+// The steps of a coarse search, in the order run_mfma takes them; every decision is the plan's (knn_plan.hpp).
+// 1. the workspaces (the slices' and the redo's lists are sized where they are launched)
+int ensure_search_ws(gloc_knn* h, const SearchPlan& p, int nq) {
+  GLOC_TRY(h->dist.ensure((size_t)p.tile.KS * p.strideP * sizeof(float), h->stream));
   GLOC_TRY(h->qnorm.ensure((size_t)nq * sizeof(float), h->stream));
-  GLOC_TRY(h->keys.ensure((size_t)nq * KC * sizeof(uint64_t), h->stream));
+  GLOC_TRY(h->keys.ensure((size_t)nq * p.KC * sizeof(uint64_t), h->stream));
   GLOC_TRY(h->flags.ensure((size_t)nq * sizeof(int), h->stream));
   if (!h->n_incomplete.p) {
     GLOC_TRY(h->n_incomplete.ensure(sizeof(unsigned long long), h->stream));
     GLOC_HIP(hipMemsetAsync(h->n_incomplete.p, 0, sizeof(unsigned long long), h->stream));
   }
-  bool use_bmin = false;
-  int n_blocks = 0;
-  if (p.b3) {
-    // few work-groups: each splits its queries itself; many: once, ahead of the launch
-    const dim3 grid((unsigned)((n_range + p.BN - 1) / p.BN), (unsigned)((nq + p.BQ - 1) / p.BQ), (unsigned)p.KS);
-    const bool qraw = (long long)grid.x * grid.y * grid.z <= 768;  // (64 x 125 000, 977 work-groups: 456 us split ahead, 461 in-kernel)
-    const float* qsrc = d_q;
-    if (!qraw) {
-      ProfScope ps(h->prof, "split_queries", h->stream);
-      GLOC_TRY(h->qsplit.ensure((size_t)nq * h->dim * sizeof(float), h->stream));
-      const size_t n8 = (size_t)nq * h->dim / 8;
-      hipLaunchKernelGGL(split_queries_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, h->stream, d_q, n8,
-                         h->qsplit.as<float>());
-      qsrc = h->qsplit.as<float>();
-    }
-    ProfScope ps(h->prof, "dist_mfma", h->stream);
+  if (p.tile.b3 && !p.qraw) GLOC_TRY(h->qsplit.ensure((size_t)nq * h->dim * sizeof(float), h->stream));
+  if (p.use_bmin) {
+    GLOC_TRY(h->bmin.ensure((size_t)nq * p.n_blocks * sizeof(float), h->stream));
+    GLOC_TRY(h->klists.ensure((size_t)nq * SELB_LIST * sizeof(uint64_t), h->stream));
+  }
+  if (!p.fused) GLOC_TRY(h->exact.ensure((size_t)nq * p.KC * sizeof(float), h->stream));
+  return GLOC_OK;
+}
+
+// 2. the coarse pass: the partial dots of every (K split, query, row) into h->dist
+int coarse_pass(gloc_knn* h, const SearchPlan& p, const float* d_q, int nq, size_t first, int n_range) {
+  const dim3 grid(p.gx, p.gy, p.gz);
+  const float* qsrc = d_q;
+  if (p.tile.b3 && !p.qraw) {
+    ProfScope ps(h->prof, "split_queries", h->stream);
+    const size_t n8 = (size_t)nq * h->dim / 8;
+    hipLaunchKernelGGL(split_queries_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, h->stream, d_q, n8,
+                       h->qsplit.as<float>());
+    qsrc = h->qsplit.as<float>();
+  }
+  ProfScope ps(h->prof, "dist_mfma", h->stream);
+  if (p.tile.b3) {
     // the rows from their tiled, pre-split mirror (round 6), which every add keeps when dim % 8 == 0
     GLOC_REQUIRE(h->db->mirror.p, GLOC_ERR_STATE, "internal: the split-bf16 coarse pass without the rows' mirror");
-    const int kps3 = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
-    const dim3 tgrid((unsigned)((first % MIR_ROWS + (size_t)n_range + p.BN - 1) / p.BN), grid.y, grid.z);
-    // a large window in one K-split: the epilogue leaves block minima for the selection (select_blocks_body)
-    n_blocks = (int)tgrid.x * (p.BN / 32);
-    use_bmin = n_range > SELQ_MAX_ROWS && p.KS == 1 && n_blocks <= SELQ_MAX_ROWS && KC <= SRR_KC && (int)h->dim <= 4 * SRR_G;
-    if (use_bmin) GLOC_TRY(h->bmin.ensure((size_t)nq * n_blocks * sizeof(float), h->stream));
-#define B3T(NT_, QR_) launch_bf16x3<NT_, QR_>(h, tgrid, qsrc, first, n_range, nq, kps3, ld, strideP, use_bmin, n_blocks)
-    if (p.NT == 1) GLOC_TRY(qraw ? B3T(1, true) : B3T(1, false));
-    else GLOC_TRY(qraw ? B3T(2, true) : B3T(2, false));
+#define B3T(NT_, QR_) \
+  (p.use_bmin ? launch_bf16x3<NT_, QR_, true>(h, p, grid, qsrc, first, n_range, nq) : launch_bf16x3<NT_, QR_, false>(h, p, grid, qsrc, first, n_range, nq))
+    if (p.tile.NT == 1) GLOC_TRY(p.qraw ? B3T(1, true) : B3T(1, false));
+    else GLOC_TRY(p.qraw ? B3T(2, true) : B3T(2, false));
 #undef B3T
-  } else if (p.t32) {
-    ProfScope ps(h->prof, "dist_mfma", h->stream);
-    // (plan_mfma's one 32 x 32 plan: NT = 2, and steps of 32 k)
-    dim3 grid((unsigned)((n_range + p.BN - 1) / p.BN), (unsigned)((nq + p.BQ - 1) / p.BQ), (unsigned)p.KS);
-    const int kps32 = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
-    hipLaunchKernelGGL((dist_mfma32_kernel<2, 8>), grid, dim3(256), 0, h->stream, h->db->rows.as<float>(), d_q,
-                       h->dist.as<float>(), (int)h->dim, first, n_range, nq, kps32, ld, strideP);
-    GLOC_HIP(hipGetLastError());
   } else {
-    ProfScope ps(h->prof, "dist_mfma", h->stream);
-#define MF(WQ_, NT_)                                                        \
-  if (p.WQ == WQ_ && p.NT == NT_) {                                         \
-    launch_mfma_inst<WQ_, NT_>(h, p, d_q, nq, first, n_range, ld, strideP); \
+    // the fp32 forms: plan_mfma's one 32 x 32 plan (NT = 2, steps of 32 k), else the 16 x 16 tiles <WQ, NT> in steps of 32 or 64 k
+#define FP32(...)                                                                                                       \
+  hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(256), 0, h->stream, h->db->rows.as<float>(), d_q, h->dist.as<float>(), \
+                     (int)h->dim, first, n_range, nq, p.kps, p.ld, p.strideP)
+#define MF(WQ_, NT_)                                                   \
+  if (p.tile.WQ == WQ_ && p.tile.NT == NT_) {                          \
+    if (p.kps < 128) FP32(dist_mfma_kernel<WQ_, NT_, 8>);              \
+    else FP32(dist_mfma_kernel<WQ_, NT_, 16>);                         \
   } else
-    MF(4, 2) MF(4, 3) MF(4, 4) MF(4, 5) MF(4, 6) MF(4, 8) MF(2, 2) MF(2, 4) MF(1, 1) MF(1, 2) {
-      set_err("internal: no MFMA instance for WQ=%d NT=%d", p.WQ, p.NT);
+    if (p.tile.t32) FP32(dist_mfma32_kernel<2, 8>);
+    else MF(4, 2) MF(4, 3) MF(4, 4) MF(4, 5) MF(4, 6) MF(4, 8) MF(2, 2) MF(2, 4) MF(1, 1) MF(1, 2) {
+      set_err("internal: no MFMA instance for WQ=%d NT=%d", p.tile.WQ, p.tile.NT);
       return GLOC_ERR_STATE;
     }
+#undef FP32
 #undef MF
-    GLOC_HIP(hipGetLastError());
   }
-  // rounding bound of the coarse distance against the reference-order distance:
-  //   reference chain          (D/4 + 4) u d2
-  //   MFMA chains of <= 64 fma, nch partial sums, KS split sums, norms (D/64 + 6), 3 final ops
-  const float u = 5.9604645e-8f;
-  const int kps = (((int)h->dim + p.KS - 1) / p.KS + 63) & ~63;
-  const float eps_rel_d = 1.05f * u * (float)(h->dim / 4 + 4);
-  //   split-bf16 form: the dropped product terms 3.03 * 2^-16 = 776 u (knn_kernels.hpp), and its chains are 3 x 64
-  //   products long with the accumulation inside an MFMA priced as truncating adds (2 u each): 384 for the 64
-  const float chain_u = p.b3 ? 776.f + 384.f : 64.f;
-  const float eps_rel_n = 1.05f * u * (chain_u + (float)((kps + 63) / 64 + p.KS + h->dim / 64 + 6 + 3 + 4));
-  const bool large = n_range > SELQ_MAX_ROWS;  // slices first; an incomplete query is flagged for the host
-  SlicePlan sl{1, 0};
-  const bool fused = (!large || use_bmin || plan_slices(n_range, nq, KC, &sl)) && KC <= SRR_KC && (int)h->dim <= 4 * SRR_G;
-  if (fused) {
-    // select + re-rank + completeness check in one launch, one work-group per query
-    if (large && use_bmin) {  // round 6: from the coarse kernel's block minima -- 32 x KC partial dots per query, not the window's:
-      // inside the select + re-rank launch itself (select_blocks_body)
-      GLOC_TRY(h->klists.ensure((size_t)nq * SELB_LIST * sizeof(uint64_t), h->stream));
-    } else if (large) {
-      ProfScope ps(h->prof, "select", h->stream);
-      GLOC_TRY(launch_slices<1>(h, d_q, nq, KC, first, n_range, ld, strideP, p.KS, sl, nullptr));
-    }
-    ProfScope ps(h->prof, "select_rerank", h->stream);
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+// 3. selection, re-rank and completeness check: the keys in d_keys_out, the unproven queries' flags in h->flags.
+// Fused: ONE launch, one work-group per query, which also writes the result through `fo`.
+int select_rerank_fused(gloc_knn* h, const SearchPlan& p, const float* d_q, int nq, int k, size_t first, int n_range,
+                        uint64_t* d_keys_out, const FinalOut& fo) {
+  if (p.sel.form == Selection::Slices) {
+    ProfScope ps(h->prof, "select", h->stream);
+    GLOC_TRY(launch_slices<1>(h, d_q, nq, p.KC, first, n_range, p.ld, p.strideP, p.tile.KS, p.sel.sl, nullptr));
+  }
+  ProfScope ps(h->prof, "select_rerank", h->stream);
 #define SRR_ARGS                                                                                                          \
-  dim3(nq), dim3(SELQ_THREADS), 0, h->stream, h->dist.as<float>(), ld, strideP, p.KS, d_q, (int)h->dim,                  \
-      h->db->norms.as<float>(), first, n_range, KC, k, h->db->rows.as<float>(), h->db->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n, \
+  dim3(nq), dim3(SELQ_THREADS), 0, h->stream, h->dist.as<float>(), p.ld, p.strideP, p.tile.KS, d_q, (int)h->dim,         \
+      h->db->norms.as<float>(), first, n_range, p.KC, k, h->db->rows.as<float>(), h->db->dn_max.as<uint32_t>(), p.eps_rel_d, p.eps_rel_n, \
       h->qnorm.as<float>(), d_keys_out, h->flags.as<int>(), h->n_incomplete.as<unsigned long long>(), fo,                \
       h->dist.as<float>()
-    if (large)
-      hipLaunchKernelGGL(select_rerank_kernel<true>, SRR_ARGS, h->klists.as<uint64_t>(), use_bmin ? SELB_LIST : sl.S * KC,
-                         use_bmin ? h->bmin.as<float>() : (const float*)nullptr, n_blocks, h->klists.as<uint64_t>());
-    else
+  switch (p.sel.form) {
+    case Selection::BlockMinima:  // selected inside the launch itself (select_blocks_body), which leaves the blocks' keys in h->klists
+      hipLaunchKernelGGL(select_rerank_kernel<true>, SRR_ARGS, h->klists.as<uint64_t>(), SELB_LIST, h->bmin.as<float>(), p.n_blocks,
+                         h->klists.as<uint64_t>());
+      break;
+    case Selection::Slices:  // from their lists
+      hipLaunchKernelGGL(select_rerank_kernel<true>, SRR_ARGS, h->klists.as<uint64_t>(), p.sel.sl.S * p.KC, (const float*)nullptr,
+                         p.n_blocks, h->klists.as<uint64_t>());
+      break;
+    default:  // Window: from the partial dots
       hipLaunchKernelGGL(select_rerank_kernel<false>, SRR_ARGS, (const uint64_t*)nullptr, 0, (const float*)nullptr, 0, (uint64_t*)nullptr);
+  }
 #undef SRR_ARGS
-    GLOC_HIP(hipGetLastError());
-    // (incomplete queries -- rare -- are redone exactly by their own work-group inside the same launch: no
-    // read-back, no host synchronisation, no further launch)
-    h->stats.last_n_tile = (uint32_t)p.BN;
-    h->stats.last_k_split = (uint32_t)p.KS;
-    h->stats.last_candidates = (uint32_t)KC;
-    if (!large) {
-      *finalized = fo.idx != nullptr;
-      return GLOC_OK;
-    }
-    // (large windows: on to the flagged-only exact pass below -- a work-group per query cannot redo a window of that size)
-  } else {
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+// Not fused (more than SRR_KC candidates, dim > 4 * SRR_G, or a window whose slices' lists fit no work-group): launch by launch
+int select_then_rerank(gloc_knn* h, const SearchPlan& p, const float* d_q, int nq, int k, size_t first, int n_range,
+                       uint64_t* d_keys_out) {
   // (the query norms of the coarse form are made by the select kernel, which leaves them in h->qnorm)
-  GLOC_TRY(run_select<1>(h, d_q, nq, KC, first, n_range, ld, strideP, p.KS, h->keys.as<uint64_t>()));
-  {
-    // rounding bound of the coarse distance against the reference-order distance:
-    //   reference chain          (D/4 + 4) u d2
-    //   MFMA chains of <= 64 fma, nch partial sums, KS split sums, norms (D/64 + 6), 3 final ops
-    ProfScope ps(h->prof, "rerank", h->stream);
-    GLOC_TRY(h->exact.ensure((size_t)nq * KC * sizeof(float), h->stream));
-    hipLaunchKernelGGL(rerank_dist_kernel, dim3((KC + RR - 1) / RR, nq), dim3(64), 0, h->stream,
-                       h->db->rows.as<float>(), d_q, (int)h->dim, h->keys.as<uint64_t>(), KC, k,
-                       h->qnorm.as<float>(), h->db->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n,
-                       h->exact.as<float>());
-    hipLaunchKernelGGL(rerank_final_kernel, dim3(nq), dim3(64), 0, h->stream,
-                       h->keys.as<uint64_t>(), h->exact.as<float>(), KC, k, n_range,
-                       h->qnorm.as<float>(), h->db->dn_max.as<uint32_t>(), eps_rel_d, eps_rel_n,
-                       d_keys_out, h->flags.as<int>(), h->n_incomplete.as<unsigned long long>());
-    GLOC_HIP(hipGetLastError());
-  }
-  }
-  h->stats.last_n_tile = (uint32_t)p.BN;
-  h->stats.last_k_split = (uint32_t)p.KS;
-  h->stats.last_candidates = (uint32_t)KC;
-  SlicePlan fb_sl;
-  if ((n_range <= SELECT_ONE_BLOCK_MAX && k <= 2048 / std::max(1, (n_range + 255) / 256)) ||
-      (k <= 64 && plan_slices(n_range, nq, k, &fb_sl))) {
-    // Incomplete queries are redone on the exact path ON THE DEVICE: the kernels are always
-    // launched and leave at once unless the query's flag is set -- no read-back, no host synchronisation
-    // (windows above 16 384 rows too since round 4: the read-back of the flags stalled the launches of a run of searches
-    // behind a host synchronisation, ~35 us of a 460-us search over a 125 000-row shard).
-    // (The coarse partial dots in h->dist are dead by now: the exact distances of the flagged queries
-    // reuse the buffer, row q at q * ld.)
-    if (fused && large && k <= 64) {
-      // ONE launch (round 6): every work-group walks the flags and leaves when none is set; a flagged query's exact
-      // distances, slice selections and final selection happen inside it (flagged_redo_kernel)
-      int S = std::max(1, (n_range + 2047) / 2048);
-      while ((long long)S * k > SELQ_MAX_ROWS) S = (S + 1) / 2;
-      int L = (((n_range + S - 1) / S) + 63) & ~63;
-      S = (n_range + L - 1) / L;  // (no empty slice)
-      if (L <= SELQ_MAX_ROWS) {
-        const size_t before = h->redo_tickets.cap;
-        GLOC_TRY(h->redo_tickets.ensure((size_t)nq * sizeof(unsigned int), h->stream));
-        if (h->redo_tickets.cap != before) GLOC_HIP(hipMemsetAsync(h->redo_tickets.p, 0, h->redo_tickets.cap, h->stream));
-        GLOC_TRY(h->klists.ensure((size_t)nq * S * k * sizeof(uint64_t), h->stream));
-        ProfScope ps(h->prof, "dist_exact", h->stream);
-        hipLaunchKernelGGL(flagged_redo_kernel, dim3((unsigned)S), dim3(SELQ_THREADS), 0, h->stream, h->db->rows.as<float>(), d_q,
-                           (int)h->dim, first, n_range, L, k, h->dist.as<float>(), ld, h->klists.as<uint64_t>(),
-                           h->redo_tickets.as<unsigned int>(), h->flags.as<int>(), nq, d_keys_out, fo);
-        GLOC_HIP(hipGetLastError());
-        *finalized = fo.idx != nullptr;
-        return GLOC_OK;
-      }
-    }
-    GLOC_TRY(launch_dist_exact(h, d_q, nq, first, n_range, ld, h->flags.as<int>()));
-    if (fused && large) {  // the fused kernel has written the result through `fo`: the flagged queries' is replaced
-      bool fin = false;
-      GLOC_TRY(run_select<0>(h, d_q, nq, k, first, n_range, ld, 0, 1, d_keys_out, h->flags.as<int>(), fo, &fin));
-      *finalized = fo.idx != nullptr;
-    } else {
-      GLOC_TRY(run_select<0>(h, d_q, nq, k, first, n_range, ld, 0, 1, d_keys_out, h->flags.as<int>()));
-    }
-    return GLOC_OK;
-  }
-  // windows too large for that (the slices' lists no longer fit one work-group): completeness flags -> host;
-  // incomplete queries are redone on the exact path
+  GLOC_TRY(run_select<1>(h, p.sel, d_q, nq, p.KC, first, n_range, p.ld, p.strideP, p.tile.KS, h->keys.as<uint64_t>()));
+  ProfScope ps(h->prof, "rerank", h->stream);
+  hipLaunchKernelGGL(rerank_dist_kernel, dim3((p.KC + RR - 1) / RR, nq), dim3(64), 0, h->stream,
+                     h->db->rows.as<float>(), d_q, (int)h->dim, h->keys.as<uint64_t>(), p.KC, k,
+                     h->qnorm.as<float>(), h->db->dn_max.as<uint32_t>(), p.eps_rel_d, p.eps_rel_n,
+                     h->exact.as<float>());
+  hipLaunchKernelGGL(rerank_final_kernel, dim3(nq), dim3(64), 0, h->stream,
+                     h->keys.as<uint64_t>(), h->exact.as<float>(), p.KC, k, n_range,
+                     h->qnorm.as<float>(), h->db->dn_max.as<uint32_t>(), p.eps_rel_d, p.eps_rel_n,
+                     d_keys_out, h->flags.as<int>(), h->n_incomplete.as<unsigned long long>());
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+// 4. the redo of the unproven queries behind a search that has not done it in its own launch (Redo::InLaunch), in one of
+// three forms.  (The coarse partial dots in h->dist are dead by now: the exact distances of the flagged queries reuse
+// the buffer, row q at q * ld.)
+int redo_one_launch(gloc_knn* h, const SearchPlan& p, const float* d_q, int nq, int k, size_t first, int n_range,
+                    uint64_t* d_keys_out, const FinalOut& fo) {
+  const SlicePlan& sl = p.redo.sl;
+  const size_t before = h->redo_tickets.cap;
+  GLOC_TRY(h->redo_tickets.ensure((size_t)nq * sizeof(unsigned int), h->stream));
+  if (h->redo_tickets.cap != before) GLOC_HIP(hipMemsetAsync(h->redo_tickets.p, 0, h->redo_tickets.cap, h->stream));
+  GLOC_TRY(h->klists.ensure((size_t)nq * sl.S * k * sizeof(uint64_t), h->stream));
+  ProfScope ps(h->prof, "dist_exact", h->stream);
+  hipLaunchKernelGGL(flagged_redo_kernel, dim3((unsigned)sl.S), dim3(SELQ_THREADS), 0, h->stream, h->db->rows.as<float>(), d_q,
+                     (int)h->dim, first, n_range, sl.L, k, h->dist.as<float>(), p.ld, h->klists.as<uint64_t>(),
+                     h->redo_tickets.as<unsigned int>(), h->flags.as<int>(), nq, d_keys_out, fo);
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int redo_flagged_exact(gloc_knn* h, const SearchPlan& p, const float* d_q, int nq, int k, size_t first, int n_range,
+                       uint64_t* d_keys_out, const FinalOut& fo) {
+  GLOC_TRY(launch_dist_exact(h, d_q, nq, first, n_range, p.ld, h->flags.as<int>()));
+  // (behind the fused launch, which has written the result through `fo`: the flagged queries' is replaced there too)
+  return run_select<0>(h, p.redo, d_q, nq, k, first, n_range, p.ld, 0, 1, d_keys_out, h->flags.as<int>(), p.fused ? fo : KEYS_ONLY);
+}
+
+// Reached only when the lists of the redo's slices no longer fit one work-group, S * k > 16 384 -- by plan_slices a
+// window above roughly 5 million rows at k = 52 (16 384 / 52 = 315 slices of 16 384 rows): the completeness flags go to the
+// host behind a synchronisation, and each flagged query takes the exact path on its own, leaving keys.
+int redo_on_host(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_range, uint64_t* d_keys_out, bool* redone) {
   if (h->h_flags_cap < (size_t)nq) {
     if (h->h_flags) (void)hipHostFree(h->h_flags);
     h->h_flags = nullptr;
@@ -553,15 +423,35 @@ int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_r
   GLOC_HIP(hipMemcpyAsync(h->h_flags, h->flags.p, sizeof(int) * (size_t)nq,
                           hipMemcpyDeviceToHost, h->stream));
   GLOC_HIP(hipStreamSynchronize(h->stream));
-  bool redone = false;
   for (int q = 0; q < nq; ++q) {
     if (h->h_flags[q]) {
-      GLOC_TRY(run_exact(h, d_q + (size_t)q * h->dim, 1, k, first, n_range,
-                         d_keys_out + (size_t)q * k));
-      redone = true;
+      bool ignored;  // (keys only: nothing goes through a FinalOut here)
+      GLOC_TRY(run_exact(h, d_q + (size_t)q * h->dim, 1, k, first, n_range, d_keys_out + (size_t)q * k, KEYS_ONLY, &ignored));
+      *redone = true;
     }
   }
-  if (fused && !redone) *finalized = fo.idx != nullptr;  // the fused kernel's own result stands
+  return GLOC_OK;
+}
+
+int run_mfma(gloc_knn* h, const float* d_q, int nq, int k, size_t first, int n_range, uint64_t* d_keys_out,
+             const FinalOut& fo, bool fp32_only, bool* through_fo) {
+  const SearchPlan p = plan_search(nq, n_range, (int)(first % MIR_ROWS), (int)h->dim, k, h->candidates, fp32_only);
+  GLOC_TRY(ensure_search_ws(h, p, nq));
+  GLOC_TRY(coarse_pass(h, p, d_q, nq, first, n_range));
+  GLOC_TRY(p.fused ? select_rerank_fused(h, p, d_q, nq, k, first, n_range, d_keys_out, fo)
+                   : select_then_rerank(h, p, d_q, nq, k, first, n_range, d_keys_out));
+  h->stats.last_n_tile = (uint32_t)p.tile.BN;
+  h->stats.last_k_split = (uint32_t)p.tile.KS;
+  h->stats.last_candidates = (uint32_t)p.KC;
+  bool redone_on_host = false;
+  switch (p.how_redo) {
+    case Redo::InLaunch: break;
+    case Redo::OneLaunch: GLOC_TRY(redo_one_launch(h, p, d_q, nq, k, first, n_range, d_keys_out, fo)); break;
+    case Redo::FlaggedExact: GLOC_TRY(redo_flagged_exact(h, p, d_q, nq, k, first, n_range, d_keys_out, fo)); break;
+    case Redo::HostReadBack: GLOC_TRY(redo_on_host(h, d_q, nq, k, first, n_range, d_keys_out, &redone_on_host)); break;
+  }
+  // the fused launch and the device redos behind it write through `fo`; the re-rank kernels and the host's redo leave keys
+  *through_fo = p.fused && !redone_on_host;
   return GLOC_OK;
 }
 
@@ -607,22 +497,16 @@ int search_device_impl(gloc_knn* h, const float* d_q, size_t nq, size_t k, size_
         tracked = !h->inc_pending;
       }
     }
+    const bool coarse = algo == GLOC_KNN_ALGO_MFMA || algo == GLOC_KNN_ALGO_MFMA_FP32;
     for (size_t q0 = 0; q0 < nq; q0 += qblk) {
       const int cnt = (int)std::min(qblk, nq - q0);
-      if (algo == GLOC_KNN_ALGO_MFMA || algo == GLOC_KNN_ALGO_MFMA_FP32) {
-        h->stats.searches_mfma++;
-        bool fin = false;
-        const FinalOut fo{d_idx + q0 * k, d_d2 + q0 * k, index_offset, index_stride};
-        GLOC_TRY(run_mfma(h, d_q + q0 * h->dim, cnt, (int)k, first_row, (int)range, keys_out + q0 * k, fo, &fin,
-                          algo == GLOC_KNN_ALGO_MFMA_FP32));
-        all_final = all_final && fin;
-      } else {
-        h->stats.searches_exact++;
-        bool fin = false;
-        const FinalOut fo{d_idx + q0 * k, d_d2 + q0 * k, index_offset, index_stride};
-        GLOC_TRY(run_exact(h, d_q + q0 * h->dim, cnt, (int)k, first_row, (int)range, keys_out + q0 * k, fo, &fin));
-        all_final = all_final && fin;
-      }
+      const FinalOut fo{d_idx + q0 * k, d_d2 + q0 * k, index_offset, index_stride};
+      bool fin = false;
+      (coarse ? h->stats.searches_mfma : h->stats.searches_exact)++;
+      GLOC_TRY(coarse ? run_mfma(h, d_q + q0 * h->dim, cnt, (int)k, first_row, (int)range, keys_out + q0 * k, fo,
+                                 algo == GLOC_KNN_ALGO_MFMA_FP32, &fin)
+                      : run_exact(h, d_q + q0 * h->dim, cnt, (int)k, first_row, (int)range, keys_out + q0 * k, fo, &fin));
+      all_final = all_final && fin;
     }
     if (tracked && h->n_incomplete.p) {  // the fallback count as of this search, for the next one to look at
       if (!h->h_inc) {

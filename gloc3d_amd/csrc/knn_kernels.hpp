@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knn_plan.hpp"
 #include "lane_ops.hpp"
 
 namespace gloc {
@@ -638,7 +639,6 @@ __global__ __launch_bounds__(256) void split_queries_kernel(const float* __restr
 // costs the database's size again in HBM (16 GB at a million rows of 288 GB) and is kept current by every add
 // (mirror_rows_kernel); the fp32 rows stay what the exact kernels and the re-rank read.  The rows are split once, at the
 // add, not by every search (3 VALU operations per element).
-constexpr int MIR_ROWS = 64;  // rows per tile
 __host__ __device__ __forceinline__ size_t mirror_tile_u32x4(int dim) { return (size_t)(dim / 8) * 2 * MIR_ROWS; }  // 16-B slots per tile
 
 // rows [first, first + count) of the fp32 database -> their places in the mirror.  One thread per (row, 8 k): rows fastest
@@ -896,7 +896,6 @@ __global__ __launch_bounds__(256) void dist_bf16x3_tiled_kernel(const u32x4* __r
 // Keys are (ordered(d) << 32 | row): one integer order = (distance, row).
 // MODE 0: dist holds final distances.  MODE 1: dist holds MFMA partial dots; the coarse distance
 // (qn + dn[j]) - 2 * sum_splits P is formed here.
-constexpr int SEL_LIST = 2048;
 
 __device__ __forceinline__ void bitonic_sort_lds(uint64_t* buf, int n /* pow2 */, int tid,
                                                  int nthreads) {
@@ -1013,9 +1012,6 @@ __global__ __launch_bounds__(256) void select_chunk_kernel(
 //      registers, more -- rare -- through the LDS sort) and writes the first K.
 // The round-1 form (256 threads, two LDS bitonic sorts with a barrier per step, five chunk lists and a
 // merge launch) took 21.9 + 9.9 us at 64 x 10 000; this one launch replaces both.
-constexpr int SELQ_THREADS = 1024;
-constexpr int SELQ_EPT = 16;                             // keys per thread
-constexpr int SELQ_MAX_ROWS = SELQ_THREADS * SELQ_EPT;   // 16 384
 
 // one compare-exchange step of the bitonic network at lane distance STRIDE inside blocks of SIZE
 template <int SIZE, int STRIDE>
@@ -1325,8 +1321,6 @@ __global__ __launch_bounds__(SELQ_THREADS) void flagged_redo_kernel(
 // included; more than SELB_MAX_BLOCKS of them: the query is flagged for the exact redo), and writes the coarse keys of
 // those blocks' rows -- (|q|^2 + |d|^2) - 2 q.d exactly as selq_select<1> forms them -- as a list of 32 x SELB_MAX_BLOCKS
 // ready keys for the selection + re-rank that follows.  Replaces select_slices_kernel<1> there (which read the whole window again).
-constexpr int SELB_MAX_BLOCKS = 64;
-constexpr int SELB_LIST = 32 * SELB_MAX_BLOCKS;
 // (A device function of select_rerank_kernel<true> since the same round: as a kernel of its own it cost a launch floor and a
 // round trip of the list through memory -- 14.3 + 27.1 us in two launches against ~36 in one.)  Returns whether more blocks
 // tied at the threshold than the list holds (uniform over the work-group); ends with a barrier.
@@ -1567,8 +1561,6 @@ __global__ __launch_bounds__(64) void rerank_final_kernel(
 //   R2  4 waves x 8 lanes run the chains (one wave per SIMD: a chain is 1024 dependent adds whichever
 //       lanes are active, so the chains of a SIMD should share instructions, not waves);
 //   F   wave 0 ranks the exact keys.
-constexpr int SRR_KC = 32;
-constexpr int SRR_G = 1024;          // groups of 4 dims held per candidate
 static_assert(SEL_LIST * 8 >= 4 * SRR_G * 4, "the selection's key list doubles as the staged query");
 constexpr int SRR_LD = SRR_G + 4;    // floats per candidate row: 16 bytes of shift spread the chains' reads over the banks
 

@@ -104,7 +104,9 @@ def test_forced_fallback_still_exact(capi, oracle_mod):
     assert (bits(d2) == bits(od)).all() and (idx == oi).all()
     assert ix.stats()["queries_fallback"] > 0
     ix.close()
-    # the same above the device-side limit (flags read back, exact path per flagged query)
+    # the same above 16384 rows with 64 candidates: selection over slices, the re-rank kernels, and the flagged queries
+    # redone by the exact pass on the device (the flags are read back by the host only when the redo's slice lists
+    # fit no work-group: a window above roughly 5 million rows at k = 52)
     db = synth.descriptors_iid(33, 0, 17000, 64)
     q = synth.descriptors_iid(34, 0, 12, 64)
     ix = _index(capi, db, 2)
@@ -367,8 +369,8 @@ def test_sliced_select_above_16384_rows(capi, oracle_mod, algo, N, first, Q):
 @pytest.mark.parametrize("algo", [2, 3])
 def test_unproven_queries_above_16384_rows_are_redone_on_the_device(capi, oracle_mod, algo):
     """Rows closer to each other than the coarse form can resolve, in a window above 16 384 rows: the fused selection +
-    re-rank over the slices' lists flags the queries, and the exact pass (distances, slices, list selection -- launched
-    for flagged queries only) replaces their results, with no read-back of the flags."""
+    re-rank over the slices' lists flags the queries, and one redo launch (flagged_redo_kernel: exact distances, slice
+    selections and the final selection of the flagged queries only) replaces their results, with no read-back of the flags."""
     from gloc3d_amd import synth
     N, D, Q = 20000, 256, 9
     base = synth.descriptors_iid(71, 0, 1, D)

@@ -56,6 +56,18 @@ class NdtParams(C.Structure):
                 ("min_covar_eigvalue_mult", C.c_float)]
 
 
+class SubmapParams(C.Structure):
+    _fields_ = [("leaf", C.c_float), ("min_points", C.c_uint32), ("min_scans", C.c_uint32), ("max_range", C.c_float),
+                ("group_points", C.c_uint32)]
+
+
+class SubmapInfo(C.Structure):
+    _fields_ = [("points_in", C.c_uint64), ("points_used", C.c_uint64), ("cells", C.c_uint32), ("kept", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class P2lParams(C.Structure):
     _fields_ = [("max_iters", C.c_uint32), ("max_corr_dist", C.c_float), ("trans_eps", C.c_float), ("rot_eps", C.c_float),
                 ("normal_k", C.c_uint32), ("reserved_", C.c_uint32)]
@@ -258,6 +270,10 @@ _PROTOS = [
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
     ("gloc_scan_store_add_approx_voxel", _i, [_vp, _u32, C.c_float, C.POINTER(_u32)]),
+    ("gloc_submap_default_params", None, [C.POINTER(SubmapParams)]),
+    ("gloc_scan_store_add_submap", _i, [_vp, _vp, _vp, _sz, C.POINTER(SubmapParams), C.POINTER(_u32), _vp]),
+    ("gloc_scan_store_add_submaps", _i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(SubmapParams), _vp, _vp]),
+    ("gloc_reg_scan_add_submaps", _i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(SubmapParams), _vp, _vp]),
     ("gloc_vlad_create", _i, [_i, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)]),
     ("gloc_vlad_set_gating", _i, [_vp, _vp, _vp, _vp]),
     ("gloc_vlad_destroy", _i, [_vp]),
@@ -614,6 +630,41 @@ def default_ndt_params(**over):
     return p
 
 
+def default_submap_params(**over):
+    """gloc_submap_params as gloc_submap_default_params leaves them (leaf 0.2 m, every occupied cell kept, no range limit),
+    then `over`."""
+    p = SubmapParams()
+    lib().gloc_submap_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
+def _submap_args(submaps):
+    """[(member ids, poses [n, 4, 4])] -> the flat arrays of gloc_scan_store_add_submaps: ids, poses [sum n, 16], first."""
+    ids = [np.ascontiguousarray(m[0], np.uint32).reshape(-1) for m in submaps]
+    Ts = [np.ascontiguousarray(m[1], np.float32).reshape(-1, 16) for m in submaps]
+    for i, t in zip(ids, Ts):
+        if i.shape[0] != t.shape[0]:
+            raise ValueError(f"{i.shape[0]} member ids but {t.shape[0]} poses")
+    first = np.zeros(len(submaps) + 1, np.uint32)
+    first[1:] = np.cumsum([i.shape[0] for i in ids])
+    cat_i = np.ascontiguousarray(np.concatenate(ids + [np.zeros(0, np.uint32)]))
+    cat_T = np.ascontiguousarray(np.concatenate(Ts + [np.zeros((0, 16), np.float32)]))
+    return cat_i, cat_T, first
+
+
+def _add_submaps(fn, handle, submaps, params, want_info):
+    ids, T, first = _submap_args(submaps)
+    n = len(submaps)
+    prm = params or default_submap_params()
+    new = np.empty(n, np.uint32)
+    info = (SubmapInfo * max(n, 1))()
+    check(fn(handle, _np_ptr(ids), _np_ptr(T), _np_ptr(first), n, C.byref(prm), _np_ptr(new), C.cast(info, C.c_void_p)))
+    out = [int(i) for i in new]
+    return (out, [info[i].as_dict() for i in range(n)]) if want_info else out
+
+
 def default_p2l_params(**over):
     """gloc_p2l_params as gloc_p2l_default_params leaves them (30 passes, no rejection, no early stop, k = 10), then `over`."""
     p = P2lParams()
@@ -779,6 +830,25 @@ class ScanStore(_Handle):
         check(lib().gloc_scan_store_add_approx_voxel(self._h, int(base_id), float(leaf), C.byref(sid)))
         return sid.value
 
+    def add_submap(self, ids, T, params=None, want_info=False):
+        """A new scan: the member scans `ids` brought into one frame by the poses T [n, 4, 4] (member -> submap frame) and
+        thinned by an exact voxel grid (gloc_scan_store_add_submap).  One id with the identity pose is the exact voxel-grid
+        filter of a scan.  Returns its id, with want_info (id, dict(points_in, points_used, cells, kept))."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), np.uint32).reshape(-1)
+        Tp = np.ascontiguousarray(T, np.float32).reshape(-1, 16)
+        if ids.shape[0] != Tp.shape[0]:
+            raise ValueError(f"{ids.shape[0]} member ids but {Tp.shape[0]} poses")
+        prm = params or default_submap_params()
+        sid, info = C.c_uint32(), SubmapInfo()
+        check(lib().gloc_scan_store_add_submap(self._h, _np_ptr(ids), _np_ptr(Tp), ids.shape[0], C.byref(prm), C.byref(sid),
+                                               C.cast(C.pointer(info), C.c_void_p)))
+        return (sid.value, info.as_dict()) if want_info else sid.value
+
+    def add_submaps(self, submaps, params=None, want_info=False):
+        """Several submaps, [(ids, T [n, 4, 4]), ...], in one batch call (gloc_scan_store_add_submaps): each equals its
+        add_submap, bit for bit.  Returns the ids, with want_info (ids, [info dict])."""
+        return _add_submaps(lib().gloc_scan_store_add_submaps, self._h, submaps, params, want_info)
+
     def download(self, scan_id):
         n = self.points(scan_id)
         out = np.empty((n, 3), np.float32)
@@ -896,6 +966,10 @@ class Registrar(_Handle):
     def scan_build_target_index(self, scan_id):
         check(lib().gloc_reg_scan_build_target_index(self._h, int(scan_id)))
         return scan_id
+
+    def scan_add_submaps(self, submaps, params=None, want_info=False):
+        """ScanStore.add_submaps over the handle's current store (gloc_reg_scan_add_submaps)."""
+        return _add_submaps(lib().gloc_reg_scan_add_submaps, self._h, submaps, params, want_info)
 
     def scan_count(self):
         n = C.c_size_t()

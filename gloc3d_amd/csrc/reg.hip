@@ -1288,6 +1288,14 @@ int gloc_reg_scan_upload(gloc_reg* h, const float* pts, size_t n, size_t stride_
   return gloc_scan_store_add(h->store, pts, n, stride_floats, scan_id);
 }
 
+int gloc_reg_scan_add_submaps(gloc_reg* h, const uint32_t* member_ids, const float* member_T, const uint32_t* first, size_t count,
+                              const gloc_submap_params* prm, uint32_t* new_ids, gloc_submap_info* info) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
+  GLOC_REQUIRE(h->store, GLOC_ERR_INVALID, "no scan store: upload the member scans or attach a store first");
+  GLOC_HIP(hipSetDevice(h->device));
+  return gloc_scan_store_add_submaps(h->store, member_ids, member_T, first, count, prm, new_ids, info);
+}
+
 int gloc_reg_scan_build_target_index(gloc_reg* h, uint32_t scan_id) {
   GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
   GLOC_REQUIRE(h->store, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);

@@ -1073,6 +1073,14 @@ int add_common(gloc_scan_store* st, const float* pts, size_t n, size_t stride, b
 
 int gloc::reg::store_insert_scan(gloc_scan_store* st, const DevScan& s, uint32_t* id) { return store_insert(st, s, id); }
 
+void gloc::reg::store_remove_scan(gloc_scan_store* st, uint32_t id) {
+  DevScan& s = st->scans[id];
+  st->live_count--;
+  st->live_bytes -= s.block_bytes + s.nrm_bytes() + s.fpfh_bytes();
+  store_free_scan(st, s, true);
+  st->free_ids.push_back(id);
+}
+
 extern "C" {
 
 int gloc_scan_store_create(int device, gloc_scan_store** out) { return create_handle(device, out); }
@@ -1276,10 +1284,7 @@ int gloc_scan_store_release(gloc_scan_store* st, uint32_t scan_id) {
   GLOC_REQUIRE(st->scans[scan_id].pins == 0, GLOC_ERR_STATE,
                "scan %u is read by %d registration batch(es) in flight (gloc_reg_batch_multi_begin without _end)", scan_id,
                st->scans[scan_id].pins);
-  st->live_count--;
-  st->live_bytes -= st->scans[scan_id].block_bytes + st->scans[scan_id].nrm_bytes() + st->scans[scan_id].fpfh_bytes();
-  store_free_scan(st, st->scans[scan_id], true);
-  st->free_ids.push_back(scan_id);
+  store_remove_scan(st, scan_id);
   return GLOC_OK;
 }
 

@@ -51,6 +51,13 @@ struct DevScan {
                     // it may not be re-sorted in place meanwhile (store_pin / store_unpin, under the store's mutex)
 };
 
+namespace gloc {
+namespace submap {
+struct Ws;  // the scratch of gloc_scan_store_add_submaps (submap.hip), made on first use
+void free_ws(Ws* w);
+}  // namespace submap
+}  // namespace gloc
+
 struct gloc_scan_store : gloc::Handle {  // (always on its own stream; the base's profiler stays idle)
   std::mutex mu;  // guards the tables, the store's stream and its scratch
   std::vector<DevScan> scans;
@@ -65,8 +72,10 @@ struct gloc_scan_store : gloc::Handle {  // (always on its own stream; the base'
   gloc::ground::NormalsScratch nrm_ws;  // the normals' k-NN lists and staging (gloc_scan_store_build_normals)
   gloc::DevBuf nrm_tmp;                 // normals in original order, between the normal kernel / a download and the sorted copy
   gloc::DevBuf fpfh_tmp, spfh_tmp;      // features in original order (as nrm_tmp) and the SPFH counts they are summed from
+  gloc::submap::Ws* submap_ws = nullptr;
   std::atomic<int> attached{0};  // registration handles using this store
   ~gloc_scan_store() {
+    gloc::submap::free_ws(submap_ws);
     for (auto& s : scans) {
       if (s.block) (void)hipFree(s.block);
       if (s.nrm) (void)hipFree(s.nrm);
@@ -89,6 +98,8 @@ int store_make_scans(gloc_scan_store* st, size_t count, const float* const* pts,
 void store_free_scan(gloc_scan_store* st, DevScan& s, bool cache_block);
 // Give a scan made by store_make_scan an id (a recycled one first).  Caller holds store->mu.
 int store_insert_scan(gloc_scan_store* st, const DevScan& s, uint32_t* id);
+// Take a live, unpinned scan out again (its block goes to the cache, its id is free).  Caller holds store->mu.
+void store_remove_scan(gloc_scan_store* st, uint32_t id);
 // Re-sort an indexed scan into kd order (target index) and rebuild everything that depends on the order.
 // Caller holds store->mu; nothing may be reading the scan; returns after the work has completed.
 int store_build_target_index(gloc_scan_store* st, DevScan& s);

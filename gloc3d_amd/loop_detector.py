@@ -23,6 +23,7 @@ class RpyPCLoopDetector:
         self._index = capi.KnnIndex(k_dim, device)
         self._reg = capi.Registrar(device)
         self._db_scan_ids = []
+        self._db_submap_ids = []                 # build_submaps(): place i's registration target, where it has one
         self._last_descriptor = None
         self.reg_params = capi.default_reg_params()
         self.high_resolution_max_range_ = 100.0  # loop_detector.h:115
@@ -104,6 +105,36 @@ class RpyPCLoopDetector:
         self._db_grid_ids.append(self._coarse.add_scan(scan))   # loop_detector.cpp:16-19: the place's grid
         self._last_descriptor = d
 
+    def build_submaps(self, db_poses, half_window=2, max_member_dist=5.0, params=None):
+        """Give every place a local submap as its registration target: the scans of the places j in [i - half_window,
+        i + half_window] within max_member_dist metres of place i, brought into place i's frame by the trajectory
+        (db_poses [n, 4, 4], world <- place) and voxel-filtered (capi.default_submap_params; one batch call).  Poses that
+        match() returns stay query -> place frame.  Calling it again replaces the submaps; a place added afterwards is
+        matched against its own scan until the next call.  The 2-D coarse match stays on the per-place grids."""
+        P = np.asarray(db_poses, np.float64).reshape(-1, 4, 4)
+        n = len(self)
+        if P.shape[0] != n:
+            raise ValueError(f"{P.shape[0]} poses for {n} places")
+        if n == 0:
+            return []
+        t = P[:, :3, 3]
+        submaps = []
+        for i in range(n):
+            inv_i = np.linalg.inv(P[i])
+            js = [j for j in range(max(0, i - int(half_window)), min(n, i + int(half_window) + 1))
+                  if np.linalg.norm(t[j] - t[i]) <= max_member_dist]
+            submaps.append(([self._db_scan_ids[j] for j in js], np.stack([inv_i @ P[j] for j in js]).astype(np.float32)))
+        new = self._reg.scan_add_submaps(submaps, params)
+        for sid in new:
+            self._reg.scan_build_target_index(sid)
+        old, self._db_submap_ids = self._db_submap_ids, new
+        for sid in old:
+            self._reg.scan_release(sid)
+        return new
+
+    def _target_id(self, i):
+        return self._db_submap_ids[i] if i < len(self._db_submap_ids) else self._db_scan_ids[i]
+
     def detect(self, q_descriptor):
         """Global localization (loop_detector.cpp:22-46): (indices, squared distances), or two
         empty arrays when the database is too small (:27-30)."""
@@ -156,7 +187,7 @@ class RpyPCLoopDetector:
         (rank of the first successful candidate or -1, its 4x4 pose query->db, full result).
         Unless the caller gives initial poses, every candidate whose coarse 2-D match succeeds starts
         from it (the reference composes its pose from that match, global_localization.cpp:519-572)."""
-        ids = [self._db_scan_ids[int(i)] for i in db_indices]
+        ids = [self._target_id(int(i)) for i in db_indices]
         q = np.ascontiguousarray(q_scan, np.float32)
         if init_T is None and self.use_coarse_match and len(ids):
             xy_yaw, _, ok2d = self.match_2d(q, db_indices)

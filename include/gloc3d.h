@@ -473,6 +473,58 @@ int gloc_reg_ndt_cells(gloc_reg* h, uint32_t scan_id, const gloc_ndt_params* prm
  * Rows come out in (slot, first point) order. */
 int gloc_scan_store_add_approx_voxel(gloc_scan_store* st, uint32_t base_id, float leaf, uint32_t* new_id);
 
+/* ---- local submaps --------------------------------------------------------------------------------------- *
+ * A registration target made of several resident scans: the members brought into one frame by their poses and thinned by
+ * an EXACT voxel grid (one centroid per occupied cell).  Such a target has no ring pattern of its own, covers what one
+ * view occludes and overlaps a query that stands between two places.  The reference has no counterpart; the executable
+ * contract is the numpy restatement tests/submap_ref.py, bit for bit:
+ *   - member m = a resident scan id and a 4x4 row-major fp32 pose T_m, member frame -> submap frame (rows 0..2 are used);
+ *   - point p = (x, y, z) of the member's original-order xyz (the result never depends on a member's target index) is
+ *     left out if a coordinate is not finite, or if max_range > 0 and (x x + y y) + z z > max_range^2;
+ *   - q_a = ((T[a][0] x + T[a][1] y) + T[a][2] z) + T[a][3], every product and sum rounded to fp32 on its own;
+ *   - k_a = floorf(q_a * (1.0f / leaf)); the point is left out if q is not finite or |k_a| >= 2^20 on an axis;
+ *   - cells ascend in (kx, ky, kz); inside a cell the points are in (position in the member list, point index) order;
+ *   - centroid = fp32(sum / count), the sum accumulated in fp64 in that order, the division in fp64;
+ *   - a cell stays iff count >= max(min_points, 1) and the number of distinct member positions in it >= max(min_scans, 1)
+ *     (an id listed twice counts twice);
+ *   - the centroids that stay, in cell order, become a new resident scan, exactly the scan gloc_scan_store_add_device
+ *     makes of those points.
+ * One member with the identity pose is the exact voxel-grid filter of one scan (its rows in cell order, independent of
+ * the point order -- unlike gloc_scan_store_add_approx_voxel). */
+typedef struct gloc_submap_params {
+  float leaf;            /* 0.2 m */
+  uint32_t min_points;   /* 1 */
+  uint32_t min_scans;    /* 1; 2 drops what only one member saw (moving objects) -- at the price of most cells of a sparse map */
+  float max_range;       /* <= 0: off; else member points farther than this from their own sensor are left out */
+  uint32_t group_points; /* 0: 8 M.  Input points per launch sequence of the batch call; results never depend on it */
+} gloc_submap_params;
+
+typedef struct gloc_submap_info {
+  uint64_t points_in;   /* points of the members */
+  uint64_t points_used; /* ... that fell into a cell */
+  uint32_t cells;       /* occupied cells */
+  uint32_t kept;        /* cells that stayed = points of the new scan */
+} gloc_submap_info;
+
+void gloc_submap_default_params(gloc_submap_params* p);
+
+/* One submap of n members (member_T: n x 16); *new_id: the new scan.  info may be NULL.  The members are only read
+ * (scans pinned by batches in flight are fine); the call holds the store's mutex and returns when the scan is complete.
+ * GLOC_ERR_INVALID, before any device work: a null argument, n = 0, an unknown or released id, leaf not positive and
+ * finite, a non-finite pose entry, members that hold 2^31 points or more (or none), more than 65535 members; and, after
+ * the device work, a submap in which no cell stays.  A call that fails adds nothing. */
+int gloc_scan_store_add_submap(gloc_scan_store* st, const uint32_t* member_ids, const float* member_T, size_t n,
+                               const gloc_submap_params* prm, uint32_t* new_id, gloc_submap_info* info);
+/* `count` submaps at once: submap s has members first[s] .. first[s + 1] - 1 of the two arrays (first: count + 1 entries,
+ * strictly ascending).  One launch sequence per group of submaps of at most prm->group_points input points, however many
+ * submaps the group holds; every submap equals the single call, bit for bit.  new_ids: count; info: count, or NULL.  A
+ * batch that fails for any reason -- one empty submap included -- leaves the store as it found it. */
+int gloc_scan_store_add_submaps(gloc_scan_store* st, const uint32_t* member_ids, const float* member_T, const uint32_t* first,
+                                size_t count, const gloc_submap_params* prm, uint32_t* new_ids, gloc_submap_info* info);
+/* The same over the handle's current store, as gloc_reg_scan_upload is. */
+int gloc_reg_scan_add_submaps(gloc_reg* h, const uint32_t* member_ids, const float* member_T, const uint32_t* first,
+                              size_t count, const gloc_submap_params* prm, uint32_t* new_ids, gloc_submap_info* info);
+
 /* ---- point-to-plane ICP refinement -------------------------------------------------------------------- *
  * The linearised point-to-plane step (Chen & Medioni; pcl::IterativeClosestPointWithNormals, Open3D's
  * TransformationEstimationPointToPlane) behind the exact 1-NN search of the ICP above, on the TARGET's normals

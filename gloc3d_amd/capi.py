@@ -96,6 +96,11 @@ class FpfhGraphParams(C.Structure):
                 ("theta_num", C.c_uint32), ("theta_den", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class FpfhRadiusParams(C.Structure):
+    _fields_ = [("normal_radius", C.c_float), ("normal_max_nn", C.c_uint32), ("normal_min_nn", C.c_uint32),
+                ("feature_radius", C.c_float), ("feature_max_nn", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 FPFH_DIM = 33          # floats per feature row
 FPFH_MATCH_TILE = 128  # target rows per tile of the matcher (csrc/fpfh.hpp MATCH_TILE_ROWS)
 
@@ -266,6 +271,13 @@ _PROTOS = [
     ("gloc_fpfh_graph_default_params", None, [C.POINTER(FpfhGraphParams)]),
     ("gloc_reg_fpfh_graph_batch_ids", _i, [_vp, _u32, _vp, _sz, C.POINTER(FpfhGraphParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_pair_graph", _i, [_vp, _vp, _vp, _sz, C.POINTER(FpfhGraphParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_fpfh_radius_default_params", None, [C.POINTER(FpfhRadiusParams)]),
+    ("gloc_scan_store_radius_neighbors", _i, [_vp, _u32, C.c_float, _u32, _vp, _vp, _vp, _sz]),
+    ("gloc_scan_store_build_normals_radius", _i, [_vp, _u32, C.c_float, _u32, _u32]),
+    ("gloc_scan_store_build_fpfh_radius", _i, [_vp, _u32, C.POINTER(FpfhRadiusParams)]),
+    ("gloc_scan_store_spfh_radius", _i, [_vp, _u32, C.c_float, _u32, _vp, _vp, _sz]),
+    ("gloc_reg_fpfh_batch_ids_radius", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FpfhParams), C.POINTER(FpfhRadiusParams), _vp, _vp, _vp, _vp]),
+    ("gloc_reg_fpfh_graph_batch_ids_radius", _i, [_vp, _u32, _vp, _sz, C.POINTER(FpfhGraphParams), C.POINTER(FpfhRadiusParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
@@ -714,6 +726,16 @@ def default_fpfh_graph_params(**over):
     return p
 
 
+def default_fpfh_radius_params(**over):
+    """gloc_fpfh_radius_params as gloc_fpfh_radius_default_params leaves them (normals from 30 neighbours within 1.0 m, at
+    least 5; features from 100 within 2.5 m), then `over`."""
+    p = FpfhRadiusParams()
+    lib().gloc_fpfh_radius_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
 class ScanStore(_Handle):
     """Resident scans + their search index, shared by any number of Registrars."""
 
@@ -883,6 +905,32 @@ class ScanStore(_Handle):
         n = self.points(scan_id)
         counts, used = np.empty((n, FPFH_DIM), np.uint16), np.empty(n, np.uint32)
         check(lib().gloc_scan_store_spfh(self._h, int(scan_id), int(feature_k), _np_ptr(counts), _np_ptr(used), n))
+        return counts, used
+
+    def radius_neighbors(self, scan_id, radius, max_nn):
+        """The scan's radius lists (gloc_scan_store_radius_neighbors): idx [n, max_nn] uint32 and d2 [n, max_nn] float32, the
+        max_nn nearest points within `radius` of each point in ascending (d2, index), padded with 0xFFFFFFFF / FLT_MAX, and
+        count [n] uint32, the size of the whole neighbourhood."""
+        n = self.points(scan_id)
+        idx, d2, cnt = np.empty((n, int(max_nn)), np.uint32), np.empty((n, int(max_nn)), np.float32), np.empty(n, np.uint32)
+        check(lib().gloc_scan_store_radius_neighbors(self._h, int(scan_id), float(radius), int(max_nn), _np_ptr(idx), _np_ptr(d2), _np_ptr(cnt), n))
+        return idx, d2, cnt
+
+    def build_normals_radius(self, scan_id, radius=1.0, max_nn=30, min_nn=5):
+        """Per-point normals from the neighbours within `radius` (gloc_scan_store_build_normals_radius): at most max_nn of
+        them, no normal below min_nn."""
+        check(lib().gloc_scan_store_build_normals_radius(self._h, int(scan_id), float(radius), int(max_nn), int(min_nn)))
+
+    def build_fpfh_radius(self, scan_id, support=None):
+        """FPFH features over a metric support (gloc_scan_store_build_fpfh_radius; default_fpfh_radius_params when None)."""
+        prm = support or default_fpfh_radius_params()
+        check(lib().gloc_scan_store_build_fpfh_radius(self._h, int(scan_id), C.byref(prm)))
+
+    def spfh_radius(self, scan_id, radius=2.5, max_nn=100):
+        """Diagnostic: spfh() over the radius list of (radius, max_nn)."""
+        n = self.points(scan_id)
+        counts, used = np.empty((n, FPFH_DIM), np.uint16), np.empty(n, np.uint32)
+        check(lib().gloc_scan_store_spfh_radius(self._h, int(scan_id), float(radius), int(max_nn), _np_ptr(counts), _np_ptr(used), n))
         return counts, used
 
 
@@ -1082,31 +1130,41 @@ class Registrar(_Handle):
                                         _np_ptr(d2) if d2.size else None))
         return idx, d2
 
-    def fpfh_batch(self, src_id, tgt_ids, stream_ids=None, params=None):
+    def fpfh_batch(self, src_id, tgt_ids, stream_ids=None, params=None, support=None):
         """Feature-based global registration of scan src_id against each of tgt_ids (gloc_reg_fpfh_batch_ids), no initial
         guess: returns dict(T [n, 4, 4] float32 source -> target, inliers [n], n_pairs [n], ok [n] bool).  T is a start for
-        p2l_batch / gicp_batch / batch_ids(init_T=...), not a refined pose."""
+        p2l_batch / gicp_batch / batch_ids(init_T=...), not a refined pose.  support: a FpfhRadiusParams -- features over
+        that metric support (gloc_reg_fpfh_batch_ids_radius) instead of the k-NN lists of params."""
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
         n = ids.shape[0]
         prm = params or default_fpfh_params()
         sid = None if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32).reshape(n)
         T = np.empty((n, 4, 4), np.float32)
         inl, npairs, ok = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int32)
-        check(lib().gloc_reg_fpfh_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if sid is None else _np_ptr(sid), C.byref(prm),
-                                            _np_ptr(T), _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
+        if support is None:
+            check(lib().gloc_reg_fpfh_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if sid is None else _np_ptr(sid), C.byref(prm),
+                                                _np_ptr(T), _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
+        else:
+            check(lib().gloc_reg_fpfh_batch_ids_radius(self._h, int(src_id), _np_ptr(ids), n, None if sid is None else _np_ptr(sid),
+                                                       C.byref(prm), C.byref(support), _np_ptr(T), _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
         return dict(T=T, inliers=inl, n_pairs=npairs, ok=ok.astype(bool))
 
-    def fpfh_graph_batch(self, src_id, tgt_ids, params=None):
+    def fpfh_graph_batch(self, src_id, tgt_ids, params=None, support=None):
         """Feature-based global registration through the correspondence graph (gloc_reg_fpfh_graph_batch_ids): the matches of
         fpfh_batch, the pose from their second-order compatibility instead of RANSAC.  Returns dict(T [n, 4, 4] float32
-        source -> target, inliers [n], n_pairs [n], ok [n] bool); T is a start for a refinement, as fpfh_batch's."""
+        source -> target, inliers [n], n_pairs [n], ok [n] bool); T is a start for a refinement, as fpfh_batch's.  support: as
+        fpfh_batch's (gloc_reg_fpfh_graph_batch_ids_radius)."""
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
         n = ids.shape[0]
         prm = params or default_fpfh_graph_params()
         T = np.empty((n, 4, 4), np.float32)
         inl, npairs, ok = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int32)
-        check(lib().gloc_reg_fpfh_graph_batch_ids(self._h, int(src_id), _np_ptr(ids), n, C.byref(prm), _np_ptr(T), _np_ptr(inl),
-                                                  _np_ptr(npairs), _np_ptr(ok)))
+        if support is None:
+            check(lib().gloc_reg_fpfh_graph_batch_ids(self._h, int(src_id), _np_ptr(ids), n, C.byref(prm), _np_ptr(T), _np_ptr(inl),
+                                                      _np_ptr(npairs), _np_ptr(ok)))
+        else:
+            check(lib().gloc_reg_fpfh_graph_batch_ids_radius(self._h, int(src_id), _np_ptr(ids), n, C.byref(prm), C.byref(support), _np_ptr(T),
+                                                             _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
         return dict(T=T, inliers=inl, n_pairs=npairs, ok=ok.astype(bool))
 
     def pair_graph(self, P, Q, params=None):

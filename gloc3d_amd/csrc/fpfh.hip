@@ -3,6 +3,8 @@
 // in 3-D.  Host side of fpfh_kernels.hpp; tests/fpfh_ref.py is the contract.  The features live with the scans
 // (scan_store.hip builds and keeps them through the functions here); the C entry points that match and register are in
 // reg.hip, which owns the handle and runs its RANSAC stage on the pairs this file compacts.
+#include <cmath>
+
 #include "fpfh.hpp"
 #include "fpfh_kernels.hpp"
 
@@ -40,6 +42,38 @@ int build_fpfh(hipStream_t s, ground::NormalsScratch& w, const uint8_t* spfh, ui
   if (n == 0) return GLOC_OK;
   hipLaunchKernelGGL(fpfh_kernel, dim3((n + 255) / 256), dim3(256), 0, s, spfh, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>(), n,
                      (int)k, out);
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int check_radius_params(const gloc_fpfh_radius_params* p) {
+  GLOC_REQUIRE(p, GLOC_ERR_INVALID, "radius params is null");
+  GLOC_REQUIRE(p->normal_radius > 0.f && std::isfinite(p->normal_radius), GLOC_ERR_INVALID, "normal_radius = %g must be positive and finite",
+               (double)p->normal_radius);
+  GLOC_REQUIRE(p->normal_min_nn >= 4 && p->normal_min_nn <= p->normal_max_nn, GLOC_ERR_INVALID, "normal_min_nn = %u outside [4, normal_max_nn = %u]",
+               p->normal_min_nn, p->normal_max_nn);
+  GLOC_REQUIRE(p->normal_max_nn <= 128, GLOC_ERR_INVALID, "normal_max_nn = %u outside [normal_min_nn, 128]", p->normal_max_nn);
+  GLOC_REQUIRE(p->feature_radius > 0.f && std::isfinite(p->feature_radius), GLOC_ERR_INVALID, "feature_radius = %g must be positive and finite",
+               (double)p->feature_radius);
+  GLOC_REQUIRE(p->feature_max_nn >= 4 && p->feature_max_nn <= 128, GLOC_ERR_INVALID, "feature_max_nn = %u outside [4, 128]", p->feature_max_nn);
+  GLOC_REQUIRE(p->reserved_ == 0, GLOC_ERR_INVALID, "reserved_ = %u must be 0", p->reserved_);
+  return GLOC_OK;
+}
+
+int build_spfh_radius(hipStream_t s, ground::NormalsScratch& w, const reg::f32x4* spts, const float* nrm_orig, uint32_t n, float radius,
+                      uint32_t max_nn, uint8_t* spfh) {
+  if (n == 0) return GLOC_OK;
+  GLOC_TRY(ground::scan_radius(s, w, spts, n, radius, max_nn));
+  hipLaunchKernelGGL(spfh_wide_kernel, dim3((n + 3) / 4), dim3(256), 0, s, w.pts.as<f32x4>(), nrm_orig, w.knn_idx.as<uint32_t>(),
+                     w.knn_d2.as<float>(), n, (int)max_nn, spfh);
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int build_fpfh_wide(hipStream_t s, ground::NormalsScratch& w, const uint8_t* spfh, uint32_t n, uint32_t max_nn, float* out) {
+  if (n == 0) return GLOC_OK;
+  hipLaunchKernelGGL(fpfh_wide_kernel, dim3((n + 3) / 4), dim3(256), 0, s, spfh, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>(), n,
+                     (int)max_nn, out);
   GLOC_HIP(hipGetLastError());
   return GLOC_OK;
 }
@@ -102,6 +136,16 @@ void gloc_fpfh_default_params(gloc_fpfh_params* p) {
   p->ransac_confidence = 0.99f;
   p->reserved_ = 0;
   p->seed = 1234;
+}
+
+void gloc_fpfh_radius_default_params(gloc_fpfh_radius_params* p) {
+  if (!p) return;
+  p->normal_radius = 1.0f;   // 2 x the 0.5 m leaf the stage runs behind
+  p->normal_max_nn = 30;
+  p->normal_min_nn = 5;
+  p->feature_radius = 2.5f;  // 5 x the leaf
+  p->feature_max_nn = 100;
+  p->reserved_ = 0;
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // Compiled in fpfh.hip.
 //   F1 spfh_kernel        thread per point: Darboux-frame pair features against the point's k-NN list, 3 x 11 counts
 //   F2 fpfh_kernel        thread per point: 1/d2-weighted sum of the neighbours' SPFH, each sub-histogram rescaled to 100
+//      spfh_wide_kernel / fpfh_wide_kernel  the same two over lists wider than 16 (the radius support), a wave per point
 //   F3 fpfh_match_kernel  thread per source row, target rows streamed through LDS as wave-uniform broadcasts; the
 //                         un-fused fp32 distance on packed pairs of target rows; slices of the targets folded with a
 //                         64-bit atomicMin on (d2 bits, original target index)
@@ -36,6 +37,40 @@ __device__ __forceinline__ bool entry_ok(uint32_t i, uint32_t j, float d2, uint3
   return j != i && j < n && d2 > 0.f && isfinite(d2);
 }
 
+// The pair feature of F1 for point i (p, normal ni) and its list entry j (q, normal nj), both finite with non-zero normals:
+// false when the pair is skipped (coincident points, dp parallel to n1), else the three bins.  fp64 from the fp32 inputs.
+__device__ __forceinline__ bool pair_bins(const f32x4 p, float nix, float niy, float niz, const f32x4 q, float njx, float njy, float njz,
+                                          int* b1, int* b2, int* b3) {
+  const double ni[3] = {(double)nix, (double)niy, (double)niz}, nj[3] = {(double)njx, (double)njy, (double)njz};
+  double dp[3] = {(double)q.x - (double)p.x, (double)q.y - (double)p.y, (double)q.z - (double)p.z};
+  const double f4 = sqrt((dp[0] * dp[0] + dp[1] * dp[1]) + dp[2] * dp[2]);
+  if (!(f4 > 0.0)) return false;
+  const double a1 = ((ni[0] * dp[0] + ni[1] * dp[1]) + ni[2] * dp[2]) / f4;
+  const double a2 = ((nj[0] * dp[0] + nj[1] * dp[1]) + nj[2] * dp[2]) / f4;
+  const bool swap = acos(fmin(fabs(a1), 1.0)) > acos(fmin(fabs(a2), 1.0));
+  const double* n1 = swap ? nj : ni;
+  const double* n2 = swap ? ni : nj;
+  const double f3 = swap ? -a2 : a1;
+  if (swap) { dp[0] = -dp[0]; dp[1] = -dp[1]; dp[2] = -dp[2]; }
+  double v[3] = {dp[1] * n1[2] - dp[2] * n1[1], dp[2] * n1[0] - dp[0] * n1[2], dp[0] * n1[1] - dp[1] * n1[0]};
+  const double vl = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+  if (!(vl > 0.0)) return false;
+  v[0] = v[0] / vl; v[1] = v[1] / vl; v[2] = v[2] / vl;
+  const double w[3] = {n1[1] * v[2] - n1[2] * v[1], n1[2] * v[0] - n1[0] * v[2], n1[0] * v[1] - n1[1] * v[0]};
+  const double f2 = (v[0] * n2[0] + v[1] * n2[1]) + v[2] * n2[2];
+  const double f1 = atan2((w[0] * n2[0] + w[1] * n2[1]) + w[2] * n2[2], (n1[0] * n2[0] + n1[1] * n2[1]) + n1[2] * n2[2]);
+  const double s1 = 11.0 * (f1 + 3.14159265358979323846) / (2.0 * 3.14159265358979323846);
+  const double s2 = 11.0 * (f2 + 1.0) / 2.0, s3 = 11.0 * (f3 + 1.0) / 2.0;
+  auto bin = [](double x) {
+    const double f = floor(x);
+    return f >= 1.0 ? (f > 10.0 ? 10 : (int)f) : 0;  // (a NaN lands in bin 0; the restatement says the same)
+  };
+  *b1 = bin(s1); *b2 = bin(s2); *b3 = bin(s3);
+  return true;
+}
+
+__device__ __forceinline__ bool has_normal(float x, float y, float z) { return x != 0.f || y != 0.f || z != 0.f; }
+
 // F1.  pts / nrm / lists in ORIGINAL order (the order the k-NN lists are written in).
 __global__ __launch_bounds__(256) void spfh_kernel(const f32x4* __restrict__ pts, const float* __restrict__ nrm,
                                                     const uint32_t* __restrict__ nb, const float* __restrict__ nb_d2, uint32_t n, int k,
@@ -48,38 +83,15 @@ __global__ __launch_bounds__(256) void spfh_kernel(const f32x4* __restrict__ pts
   uint32_t used = 0;
   const f32x4 p = pts[i];
   const float nix = nrm[3 * (size_t)i], niy = nrm[3 * (size_t)i + 1], niz = nrm[3 * (size_t)i + 2];
-  const bool have_i = finite3(p.x, p.y, p.z) && (nix != 0.f || niy != 0.f || niz != 0.f);
+  const bool have_i = finite3(p.x, p.y, p.z) && has_normal(nix, niy, niz);
   for (int s = 0; s < k && have_i; ++s) {
     const uint32_t j = nb[(size_t)i * k + s];
     if (!entry_ok(i, j, nb_d2[(size_t)i * k + s], n)) continue;
     const f32x4 q = pts[j];
     const float njx = nrm[3 * (size_t)j], njy = nrm[3 * (size_t)j + 1], njz = nrm[3 * (size_t)j + 2];
-    if (!finite3(q.x, q.y, q.z) || !(njx != 0.f || njy != 0.f || njz != 0.f)) continue;
-    const double ni[3] = {(double)nix, (double)niy, (double)niz}, nj[3] = {(double)njx, (double)njy, (double)njz};
-    double dp[3] = {(double)q.x - (double)p.x, (double)q.y - (double)p.y, (double)q.z - (double)p.z};
-    const double f4 = sqrt((dp[0] * dp[0] + dp[1] * dp[1]) + dp[2] * dp[2]);
-    if (!(f4 > 0.0)) continue;
-    const double a1 = ((ni[0] * dp[0] + ni[1] * dp[1]) + ni[2] * dp[2]) / f4;
-    const double a2 = ((nj[0] * dp[0] + nj[1] * dp[1]) + nj[2] * dp[2]) / f4;
-    const bool swap = acos(fmin(fabs(a1), 1.0)) > acos(fmin(fabs(a2), 1.0));
-    const double* n1 = swap ? nj : ni;
-    const double* n2 = swap ? ni : nj;
-    const double f3 = swap ? -a2 : a1;
-    if (swap) { dp[0] = -dp[0]; dp[1] = -dp[1]; dp[2] = -dp[2]; }
-    double v[3] = {dp[1] * n1[2] - dp[2] * n1[1], dp[2] * n1[0] - dp[0] * n1[2], dp[0] * n1[1] - dp[1] * n1[0]};
-    const double vl = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-    if (!(vl > 0.0)) continue;
-    v[0] = v[0] / vl; v[1] = v[1] / vl; v[2] = v[2] / vl;
-    const double w[3] = {n1[1] * v[2] - n1[2] * v[1], n1[2] * v[0] - n1[0] * v[2], n1[0] * v[1] - n1[1] * v[0]};
-    const double f2 = (v[0] * n2[0] + v[1] * n2[1]) + v[2] * n2[2];
-    const double f1 = atan2((w[0] * n2[0] + w[1] * n2[1]) + w[2] * n2[2], (n1[0] * n2[0] + n1[1] * n2[1]) + n1[2] * n2[2]);
-    const double s1 = 11.0 * (f1 + 3.14159265358979323846) / (2.0 * 3.14159265358979323846);
-    const double s2 = 11.0 * (f2 + 1.0) / 2.0, s3 = 11.0 * (f3 + 1.0) / 2.0;
-    auto bin = [](double x) {
-      const double f = floor(x);
-      return f >= 1.0 ? (f > 10.0 ? 10 : (int)f) : 0;  // (a NaN lands in bin 0; the restatement says the same)
-    };
-    const int b1 = bin(s1), b2 = bin(s2), b3 = bin(s3);
+    if (!finite3(q.x, q.y, q.z) || !has_normal(njx, njy, njz)) continue;
+    int b1, b2, b3;
+    if (!pair_bins(p, nix, niy, niz, q, njx, njy, njz, &b1, &b2, &b3)) continue;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       cnt[b] += (b == b1) ? 1u : 0u;
@@ -94,6 +106,44 @@ __global__ __launch_bounds__(256) void spfh_kernel(const f32x4* __restrict__ pts
   o[33] = (uint8_t)used;
   o[34] = 0;
   o[35] = 0;
+}
+
+// F1 over wide lists (the radius support: up to 128 entries): one wave per point, a lane per list entry, so that the fp64
+// pair features of a list run side by side instead of one thread crawling 128 scattered neighbours.  The counts are summed
+// across the lanes by ballots -- integer sums, exact in any order -- and lane b writes byte b of the row.
+__global__ __launch_bounds__(256) void spfh_wide_kernel(const f32x4* __restrict__ pts, const float* __restrict__ nrm,
+                                                         const uint32_t* __restrict__ nb, const float* __restrict__ nb_d2, uint32_t n, int k,
+                                                         uint8_t* __restrict__ out /* [n][SPFH_STRIDE] */) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;  // (the whole wave)
+  const f32x4 p = pts[i];
+  const float nix = nrm[3 * (size_t)i], niy = nrm[3 * (size_t)i + 1], niz = nrm[3 * (size_t)i + 2];
+  const bool have_i = finite3(p.x, p.y, p.z) && has_normal(nix, niy, niz);
+  uint32_t mine = 0;  // lane b < 33: count b; lane 33: the pairs counted
+  for (int s0 = 0; s0 < k && have_i; s0 += 64) {
+    const int s = s0 + lane;
+    bool ok = false;
+    int b1 = 0, b2 = 0, b3 = 0;
+    if (s < k) {
+      const uint32_t j = nb[(size_t)i * k + s];
+      if (entry_ok(i, j, nb_d2[(size_t)i * k + s], n)) {
+        const f32x4 q = pts[j];
+        const float njx = nrm[3 * (size_t)j], njy = nrm[3 * (size_t)j + 1], njz = nrm[3 * (size_t)j + 2];
+        if (finite3(q.x, q.y, q.z) && has_normal(njx, njy, njz)) ok = pair_bins(p, nix, niy, niz, q, njx, njy, njz, &b1, &b2, &b3);
+      }
+    }
+    for (int b = 0; b < NB; ++b) {
+      const uint32_t c1 = (uint32_t)__popcll(__ballot(ok && b1 == b)), c2 = (uint32_t)__popcll(__ballot(ok && b2 == b)),
+                     c3 = (uint32_t)__popcll(__ballot(ok && b3 == b));
+      if (lane == b) mine += c1;
+      if (lane == NB + b) mine += c2;
+      if (lane == 2 * NB + b) mine += c3;
+    }
+    const uint32_t u = (uint32_t)__popcll(__ballot(ok));
+    if (lane == DIM) mine += u;
+  }
+  if (lane < SPFH_STRIDE) out[(size_t)i * SPFH_STRIDE + lane] = (uint8_t)mine;  // (lanes 34, 35: the padding, zero)
 }
 
 // F2.  out [n][DIM] in ORIGINAL order; the all-zero row = no feature.
@@ -129,6 +179,46 @@ __global__ __launch_bounds__(256) void fpfh_kernel(const uint8_t* __restrict__ s
 #pragma unroll
     for (int b = 0; b < NB; ++b) o[h * NB + b] = (float)(acc[h * NB + b] * sc);
   }
+}
+
+// F2 over wide lists: one wave per point.  The list is read once, a lane per entry (with the neighbour's `used`), and then
+// walked in order with lane b < 33 adding bin b: each of the 33 fp64 sums is taken in list order, as F2 defines it, and the
+// three sub-histogram totals in bin order.
+__global__ __launch_bounds__(256) void fpfh_wide_kernel(const uint8_t* __restrict__ spfh, const uint32_t* __restrict__ nb,
+                                                         const float* __restrict__ nb_d2, uint32_t n, int k, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;  // (the whole wave)
+  const int bl = lane < DIM ? lane : 0;
+  double acc = 0.0;
+  bool any = false;
+  if (spfh[(size_t)i * SPFH_STRIDE + 33] != 0) {
+    for (int s0 = 0; s0 < k; s0 += 64) {
+      const int s = s0 + lane;
+      uint32_t j = NONE, uj = 0;
+      float d2 = 0.f;
+      if (s < k) {
+        j = nb[(size_t)i * k + s];
+        d2 = nb_d2[(size_t)i * k + s];
+        if (entry_ok(i, j, d2, n)) uj = spfh[(size_t)j * SPFH_STRIDE + 33];  // (0: a neighbour without an SPFH)
+      }
+      unsigned long long todo = __ballot(uj != 0);
+      while (todo) {  // ascending lanes = list order
+        const int t = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const uint32_t jt = (uint32_t)__builtin_amdgcn_readlane((int)j, t), ut = (uint32_t)__builtin_amdgcn_readlane((int)uj, t);
+        const float dt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d2), t));
+        const double wgt = 1.0 / (double)dt, du = (double)ut;
+        acc += (((double)spfh[(size_t)jt * SPFH_STRIDE + bl] * 100.0) / du) * wgt;
+        any = true;
+      }
+    }
+  }
+  const int h = bl / NB;
+  double sum = 0.0;
+  for (int b = 0; b < NB; ++b) sum += __shfl(acc, h * NB + b);
+  const double sc = (any && sum > 0.0) ? 100.0 / sum : 0.0;
+  if (lane < DIM) out[(size_t)i * DIM + lane] = (float)(acc * sc);
 }
 
 // rows of `width` floats between original order and the order of the sorted points (pts[i].w = original index of i)

@@ -9,6 +9,7 @@
 #include "common.hpp"
 #include "ground_kernels.hpp"
 #include "ground_normals.hpp"
+#include "radius_kernels.hpp"
 #include "seg_sort.hpp"
 
 using namespace gloc;
@@ -345,6 +346,41 @@ int scan_normals(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m
   GLOC_HIP(hipMemsetAsync(w.hist.p, 0, sizeof(uint32_t) * 18, s));
   hipLaunchKernelGGL(normals_kernel, dim3((m + 255) / 256), dim3(256), 0, s, w.pts.as<f32x4>(), m, w.knn_idx.as<uint32_t>(),
                      (int)k, out_normals, w.bins.as<uint8_t>(), w.hist.as<uint32_t>());
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int scan_radius(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, float r, uint32_t max_nn) {
+  GLOC_REQUIRE(r > 0.f && std::isfinite(r), GLOC_ERR_INVALID, "radius = %g must be positive and finite", (double)r);
+  GLOC_REQUIRE(max_nn >= 1 && max_nn <= (uint32_t)RADIUS_MAX_NN, GLOC_ERR_INVALID, "max_nn = %u outside [1, %d]", max_nn, RADIUS_MAX_NN);
+  if (m == 0) return GLOC_OK;
+  const uint32_t nch = (m + KCH - 1) / KCH;
+  GLOC_TRY(w.pts.ensure(sizeof(f32x4) * m, s));
+  GLOC_TRY(w.knn_idx.ensure(sizeof(uint32_t) * (size_t)m * max_nn, s));
+  GLOC_TRY(w.knn_d2.ensure(sizeof(float) * (size_t)m * max_nn, s));
+  GLOC_TRY(w.knn_cnt.ensure(sizeof(uint32_t) * (size_t)m, s));
+  GLOC_TRY(w.cbox_lo.ensure(sizeof(f32x4) * nch, s));
+  GLOC_TRY(w.cbox_hi.ensure(sizeof(f32x4) * nch, s));
+  hipLaunchKernelGGL(unsort_f4_kernel, dim3((m + 255) / 256), dim3(256), 0, s, spts, m, w.pts.as<f32x4>());
+  hipLaunchKernelGGL(kchunk_boxes_kernel, dim3(nch), dim3(64), 0, s, spts, m, w.cbox_lo.as<f32x4>(), w.cbox_hi.as<f32x4>());
+  // a wave's lists: 64 lanes x max_nn keys of 8 bytes (64 KiB at 128, the most a launch may ask for without opting in)
+  hipLaunchKernelGGL(radius_self_kernel, dim3(nch), dim3(64), (size_t)max_nn * 64 * sizeof(unsigned long long), s, spts, m,
+                     w.cbox_lo.as<f32x4>(), w.cbox_hi.as<f32x4>(), nch, r * r, (int)max_nn, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>(),
+                     w.knn_cnt.as<uint32_t>());
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int scan_normals_radius(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, float r, uint32_t max_nn, uint32_t min_nn,
+                        float* out_normals) {
+  GLOC_TRY(scan_radius(s, w, spts, m, r, max_nn));
+  if (m == 0) return GLOC_OK;
+  GLOC_TRY(w.bins.ensure(std::max<uint32_t>(m, 16), s));
+  GLOC_TRY(w.hist.ensure(sizeof(uint32_t) * 18, s));
+  GLOC_HIP(hipMemsetAsync(w.hist.p, 0, sizeof(uint32_t) * 18, s));
+  hipLaunchKernelGGL(normals_kernel, dim3((m + 255) / 256), dim3(256), 0, s, w.pts.as<f32x4>(), m, w.knn_idx.as<uint32_t>(), (int)max_nn,
+                     out_normals, w.bins.as<uint8_t>(), w.hist.as<uint32_t>());
+  hipLaunchKernelGGL(normals_min_nn_kernel, dim3((m + 255) / 256), dim3(256), 0, s, m, w.knn_cnt.as<uint32_t>(), max_nn, min_nn, out_normals);
   GLOC_HIP(hipGetLastError());
   return GLOC_OK;
 }

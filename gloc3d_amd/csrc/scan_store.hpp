@@ -11,6 +11,15 @@
 #include "ground_normals.hpp"
 #include "scan_index.hpp"
 
+// The metric support a scan's normals or features were built from (gloc_fpfh_radius_params): every neighbour within r,
+// the max_nn nearest of them, no normal below min_nn (0 for features).
+struct RadiusSupport {
+  float r = 0.f;
+  uint32_t max_nn = 0, min_nn = 0;
+  bool operator==(const RadiusSupport& o) const { return r == o.r && max_nn == o.max_nn && min_nn == o.min_nn; }
+};
+constexpr uint32_t SUPPORT_BY_RADIUS = 0xFFFFFFFFu;  // in the place of a k: the support is the RadiusSupport beside it
+
 // A scan resident in HBM: original-order xyz plus its search index (Hilbert-sorted copy with the
 // original indices, boxes, sorted keys, inverse permutation, launch order).  ONE allocation per scan.
 struct DevScan {
@@ -36,15 +45,21 @@ struct DevScan {
   // order of idx.pts -- the order the 1-NN search reports its matches in -- so that a correspondence reads its normal at
   // the index it got.  Built once per (scan, k); re-ordered with the points by the kd re-sort; zero = no normal.
   float* nrm = nullptr;
-  uint32_t nrm_k = 0;  // the k they were built with (0: none)
+  uint32_t nrm_k = 0;  // the k they were built with (0: none; SUPPORT_BY_RADIUS: nrm_rad)
+  RadiusSupport nrm_rad{};
   size_t nrm_bytes() const { return nrm ? 12 * n : 0; }
   // FPFH features (gloc_scan_store_build_fpfh), an OPTIONAL THIRD allocation of 132 B per point: rows of 33 floats in the
   // order of idx.pts, as the normals are, and re-ordered with them.  Built once per (scan, normal_k, feature_k); valid for
   // the normals they were built from only (fpfh_nk = that nrm_k); the zero row = no feature.
   float* fpfh = nullptr;
-  uint32_t fpfh_nk = 0, fpfh_fk = 0;  // the k's they were built with (0: none)
+  uint32_t fpfh_nk = 0, fpfh_fk = 0;  // the k's they were built with (0: none; both SUPPORT_BY_RADIUS: fpfh_nrad, fpfh_rad)
+  RadiusSupport fpfh_nrad{}, fpfh_rad{};
   size_t fpfh_bytes() const { return fpfh ? 132 * n : 0; }
-  bool has_fpfh(uint32_t nk, uint32_t fk) const { return fpfh_fk == fk && fpfh_nk == nk && nrm_k == nk; }
+  bool has_fpfh(uint32_t nk, uint32_t fk) const { return fpfh_fk == fk && fpfh_nk == nk && nrm_k == nk; }  // (k's: never the radius tag)
+  bool has_normals_radius(const RadiusSupport& ns) const { return nrm_k == SUPPORT_BY_RADIUS && nrm_rad == ns; }
+  bool has_fpfh_radius(const RadiusSupport& ns, const RadiusSupport& fs) const {
+    return fpfh_fk == SUPPORT_BY_RADIUS && fpfh_nk == SUPPORT_BY_RADIUS && fpfh_nrad == ns && fpfh_rad == fs && has_normals_radius(ns);
+  }
   bool live = false;
   bool kd = false;  // the index is in kd order (target index)
   int pins = 0;     // batches in flight (gloc_reg_batch_multi_begin .. _end) whose jobs hold a by-value view of THIS scan:
@@ -126,6 +141,13 @@ int store_build_normals(gloc_scan_store* st, DevScan& s, uint32_t k);
 int store_build_fpfh(gloc_scan_store* st, DevScan& s, uint32_t normal_k, uint32_t feature_k);
 // ... for a list of ids (takes store->mu).  GLOC_ERR_INVALID for an unknown id.
 int store_ensure_fpfh(gloc_scan_store* st, const uint32_t* ids, size_t n, uint32_t normal_k, uint32_t feature_k);
+// The same three for a metric support (gloc_fpfh_radius_params; include/gloc3d.h R1 - R3), under the same rules: one set of
+// normals and one of features per scan, whichever support they were built from.
+int store_build_normals_radius(gloc_scan_store* st, DevScan& s, const RadiusSupport& ns);
+int store_build_fpfh_radius(gloc_scan_store* st, DevScan& s, const gloc_fpfh_radius_params& prm);
+int store_ensure_fpfh_radius(gloc_scan_store* st, const uint32_t* ids, size_t n, const gloc_fpfh_radius_params& prm);
+inline RadiusSupport normal_support(const gloc_fpfh_radius_params& p) { return RadiusSupport{p.normal_radius, p.normal_max_nn, p.normal_min_nn}; }
+inline RadiusSupport feature_support(const gloc_fpfh_radius_params& p) { return RadiusSupport{p.feature_radius, p.feature_max_nn, 0u}; }
 // The pins' release (delta = -1) once the batch's event has been waited for.  Ids no longer live are skipped.
 void store_pin(gloc_scan_store* st, const uint32_t* ids, size_t count, int delta);
 // Scans without normals get them from k neighbours (takes store->mu; an allocation beside the scan: nothing a batch in

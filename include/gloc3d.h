@@ -799,6 +799,66 @@ int gloc_reg_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, c
                         uint32_t* out_degree, uint64_t* out_score, uint32_t* out_seeds, uint32_t* out_set_sizes,
                         uint32_t* out_seed_inliers, float* out_T, uint32_t* out_inliers, uint32_t* out_winner_rank, int* out_ok);
 
+/* ---- Radius-support FPFH ------------------------------------------------------------------------------------- *
+ * The features above take every normal and every histogram from a k-NN list of at most 16 entries.  FPFH is customarily
+ * used with a METRIC support instead -- all neighbours within a radius, capped at max_nn (pcl::Feature::setRadiusSearch,
+ * Open3D's KDTreeSearchParamHybrid), about 2 x the voxel leaf for the normals and 5 x for the features, 30 and 100
+ * neighbours.  These entries build the same features over such lists; F3, F4 and G1 - G4 are untouched.  A scan carries
+ * ONE set of normals and ONE set of features, each tagged with the support it was built from -- k, or (radius, max_nn,
+ * min_nn): a request for another support rebuilds, under the rule of gloc_scan_store_build_normals (GLOC_ERR_STATE while
+ * a batch in flight may read them), a repeated request is a no-op, and radius features are valid only for the radius
+ * normals they were built from.  The refinements that need normals (p2l, gicp) use whatever normals a scan has.  The
+ * executable contract is tests/fpfh_radius_ref.py.
+ *
+ * R1  Lists.  d2(i, j) = ((dx dx + dy dy) + dz dz) in fp32, un-fused, as the k-NN lists compute it.  j belongs to i's
+ *     neighbourhood iff d2 <= r2, r2 = r * r rounded to fp32.  A NaN distance is never inside: a point with a non-finite
+ *     coordinate has an empty neighbourhood, itself included, and is in nobody's.  A finite point is always in its own;
+ *     exact duplicates count with d2 = 0.  The list is the max_nn smallest entries of the neighbourhood in ascending
+ *     (d2, index) order, the rest of the row 0xFFFFFFFF / FLT_MAX (the k-NN lists' padding).  count(i) is the size of the
+ *     whole neighbourhood, before the cap.  Indices are upload-order indices; nothing depends on a target index.
+ * R2  Normals.  The list of (normal_radius, normal_max_nn).  A point whose list holds fewer than normal_min_nn entries,
+ *     self included, has no normal (zero row); every other point gets what gloc_scan_store_build_normals computes from
+ *     that list: fp64 mean and covariance in list order, cyclic Jacobi, smallest eigenvalue with ties to the lower
+ *     column, the flip towards the origin.  normal_min_nn >= 4 is part of the contract: three points span an exact
+ *     plane, the normal is then perpendicular to every in-plane difference up to rounding, and F1's role test
+ *     (acos|a1| > acos|a2|) hangs on the last bit.
+ * R3  Features.  F1 and F2 word for word over the list of (feature_radius, feature_max_nn) and the normals of R2.  A row
+ *     of all zeros still means "no feature". */
+typedef struct gloc_fpfh_radius_params {
+  float normal_radius;      /* default 1.0 m (2 x the 0.5 m leaf); > 0, finite */
+  uint32_t normal_max_nn;   /* default 30;  normal_min_nn .. 128 */
+  uint32_t normal_min_nn;   /* default 5;   4 .. normal_max_nn */
+  float feature_radius;     /* default 2.5 m (5 x the leaf); > 0, finite */
+  uint32_t feature_max_nn;  /* default 100; 4 .. 128 */
+  uint32_t reserved_;       /* 0 */
+} gloc_fpfh_radius_params;  /* 24 bytes */
+
+void gloc_fpfh_radius_default_params(gloc_fpfh_radius_params* p);
+
+/* R1 on a resident scan (a building block and diagnostic, nothing is kept): out_idx / out_d2 [n][max_nn], out_count [n],
+ * in upload order; each may be NULL.  The arguments are checked before the handle.  GLOC_ERR_INVALID: radius not positive
+ * and finite, max_nn outside [1, 128], a null store, an unknown id, capacity_points below the scan's size. */
+int gloc_scan_store_radius_neighbors(gloc_scan_store* st, uint32_t scan_id, float radius, uint32_t max_nn, uint32_t* out_idx, float* out_d2,
+                                     uint32_t* out_count, size_t capacity_points);
+/* R2: the scan's normals from the lists of (radius, max_nn), none below min_nn entries; as gloc_scan_store_build_normals
+ * otherwise (one set per scan: normals of another support are rebuilt, the features built from them dropped).
+ * GLOC_ERR_INVALID: radius not positive and finite, min_nn outside [4, max_nn], max_nn above 128, a null store, an unknown id. */
+int gloc_scan_store_build_normals_radius(gloc_scan_store* st, uint32_t scan_id, float radius, uint32_t max_nn, uint32_t min_nn);
+/* R2 + R3: as gloc_scan_store_build_fpfh with this support; gloc_scan_store_fpfh downloads the features. */
+int gloc_scan_store_build_fpfh_radius(gloc_scan_store* st, uint32_t scan_id, const gloc_fpfh_radius_params* prm);
+/* as gloc_scan_store_spfh, over the radius list of (radius, max_nn in [4, 128]); needs normals (GLOC_ERR_STATE without) */
+int gloc_scan_store_spfh_radius(gloc_scan_store* st, uint32_t scan_id, float radius, uint32_t max_nn, uint16_t* out_counts,
+                                uint32_t* out_used, size_t capacity_points);
+/* gloc_reg_fpfh_batch_ids / gloc_reg_fpfh_graph_batch_ids with features of this support: prm's normal_k and feature_k
+ * are checked and not used; everything else is theirs, argument for argument.  Both parameter blocks are checked before
+ * the handle. */
+int gloc_reg_fpfh_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
+                                   const gloc_fpfh_params* prm, const gloc_fpfh_radius_params* support, float* out_T, uint32_t* out_inliers,
+                                   uint32_t* out_n_pairs, int* out_ok);
+int gloc_reg_fpfh_graph_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n,
+                                         const gloc_fpfh_graph_params* prm, const gloc_fpfh_radius_params* support, float* out_T,
+                                         uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok);
+
 /* ============================ NetVLAD-FC pooling head ("next" row N2) ===================== *
  * Replaces NetVLAD.forward of the reference (model/netvlad_fc.py:73-109, built without gating at
  * main.py:594) -- the tail of the TorchScript module RpyPCLoopDetector::get_place_feature runs

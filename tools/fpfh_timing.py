@@ -4,9 +4,15 @@ table commits (tests/fpfh_cases.py LEAF): feature build per scan, the matcher pe
 stage, a 20-candidate batch end to end -- and how many of the 40 jobs are located within 1 m / 5 degrees of ground truth,
 beside the RANSAC stage of gloc_reg_batch_ids on the same filtered scans from the identity guess.
 
-    python tools/fpfh_timing.py [--queries 2] [--reps 5] [--leaf 0.5] [--out FILE]
+    python tools/fpfh_timing.py [--queries 2] [--reps 5] [--leaf 0.5] [--out FILE] [--support] [--build-only]
 
 Medians of --reps runs on one box; host time of synchronous calls unless a line says "profiler".
+
+--support adds the radius-support features (gloc_fpfh_radius_params) beside the k-NN ones, everything from the same run:
+the feature build on a filtered scan at the default support and on a raw scan at SUPPORTS["raw"], each next to the k-mode
+build of the same scan, and the 40 jobs under the supports of SUPPORTS through RANSAC and through the correspondence graph --
+located within 1 m / 5 degrees, median error, inlier populations of the two groups -- beside k-mode's.  --build-only stops
+after the builds: what a `rocprofv3 --kernel-trace --stats` run of its own wraps to split the build by kernel.
 """
 import argparse
 import os
@@ -19,6 +25,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 OK_T, OK_R = 1.0, 5.0
+# name -> gloc_fpfh_radius_params fields; "default" is gloc_fpfh_radius_default_params (2 x and 5 x the 0.5 m leaf)
+SUPPORTS = {"default": {},
+            "tight": dict(normal_radius=0.75, feature_radius=1.5, normal_max_nn=32, feature_max_nn=64),
+            "raw": dict(normal_radius=0.5, feature_radius=1.0)}
 PEAK_FP32_VECTOR = 157.3e12   # MI355X, fp32 vector, an fma counted as two operations
 
 
@@ -44,6 +54,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--leaf", type=float, default=0.5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--support", action="store_true", help="add the radius-support measurements")
+    ap.add_argument("--build-only", action="store_true", help="with --support: the feature builds alone (for a kernel trace)")
     a = ap.parse_args()
     from gloc3d_amd import capi, synth
     traj, xy = synth.loop_trajectory(400, 328.0)
@@ -95,6 +107,12 @@ def main():
         t_raw.append((time.perf_counter() - t0) * 1e3)
         store.release(s)
     say(f"feature build on an unfiltered scan ({store.points(r['raw'][0])} points), normals + features: median {np.median(t_raw[1:]):.3f} ms")
+    if a.support:
+        radius_builds(a, capi, store, r, say)
+    if a.build_only:
+        reg.close()
+        store.close()
+        return
     for row in rows:
         for t in [row["q"]] + row["db"]:
             store.build_fpfh(t, 10, 16)
@@ -152,11 +170,78 @@ def main():
         % (np.median([e[0] for e in errs]), max(e[0] for e in errs), np.median([e[1] for e in errs]), max(e[1] for e in errs)))
     mb, lob = med(lambda: reg.batch_ids(rows[0]["q"], rows[0]["db"], params=capi.default_reg_params(icp_iters=0)), a.reps)
     say(f"baseline, the RANSAC stage of gloc_reg_batch_ids on the same filtered scans from the identity, 20 candidates: median {mb:.2f} ms (min {lob:.2f})")
+    if a.support:
+        radius_jobs(a, capi, store, reg, rows, located, say)
     reg.close()
     store.close()
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+
+
+def radius_builds(a, capi, store, r, say):
+    """Build time, k-mode and radius support side by side on the same scans: a warm-up, then the median of --reps."""
+    def timed(make, build):
+        t = []
+        for _ in range(a.reps + 1):
+            s = make()
+            t0 = time.perf_counter()
+            build(s)
+            t.append((time.perf_counter() - t0) * 1e3)
+            store.release(s)
+        return float(np.median(t[1:]))
+
+    dflt, raw = capi.default_fpfh_radius_params(**SUPPORTS["default"]), capi.default_fpfh_radius_params(**SUPPORTS["raw"])
+    filt = lambda: store.add_approx_voxel(r["raw"][1], a.leaf)  # noqa: E731
+    full = lambda: store.add_variant(r["raw"][1])  # noqa: E731
+    n_f, n_r = store.points(r["db"][0]), store.points(r["raw"][1])
+    say(f"radius support, feature build (normals + lists + SPFH + FPFH, host time, synchronous), warm-up + median of {a.reps}:")
+    k_f, r_f = timed(filt, lambda s: store.build_fpfh(s, 10, 16)), timed(filt, lambda s: store.build_fpfh_radius(s, dflt))
+    say(f"  filtered scan ({n_f} points): k-mode (10, 16) {k_f:.3f} ms; radius default (1.0 m / 30, 2.5 m / 100) {r_f:.3f} ms = {r_f / k_f:.1f} x")
+    k_r, r_r = timed(full, lambda s: store.build_fpfh(s, 10, 16)), timed(full, lambda s: store.build_fpfh_radius(s, raw))
+    say(f"  raw scan ({n_r} points): k-mode (10, 16) {k_r:.3f} ms; radius raw (0.5 m / 30, 1.0 m / 100) {r_r:.3f} ms = {r_r / k_r:.1f} x")
+    s = filt()
+    idx, _, cnt = store.radius_neighbors(s, dflt.feature_radius, dflt.feature_max_nn)
+    _, _, ncnt = store.radius_neighbors(s, dflt.normal_radius, dflt.normal_max_nn)
+    say(f"  filtered scan, default support: neighbourhood sizes median (max) normals {int(np.median(ncnt))} ({int(ncnt.max())}), features "
+        f"{int(np.median(cnt))} ({int(cnt.max())}); lists cut by max_nn: normals {100.0 * np.mean(ncnt > dflt.normal_max_nn):.1f} %, features "
+        f"{100.0 * np.mean(cnt > dflt.feature_max_nn):.1f} %; points below normal_min_nn {100.0 * np.mean(ncnt < dflt.normal_min_nn):.1f} %")
+    store.release(s)
+
+
+def radius_jobs(a, capi, store, reg, rows, located, say):
+    """The 40 jobs under each support, through RANSAC and through the graph, beside k-mode from the same scans."""
+    n_same = 10 * a.queries
+
+    def run(label, call):
+        loc = acc = 0
+        errs, inl_same, inl_diff = [], [], []
+        for row in rows:
+            g = call(row)
+            loc += located(g["T"], g["ok"], row["truth"])
+            acc += int(np.sum(g["ok"][10:]))
+            errs += [pose_error(g["T"][c], row["truth"][c]) for c in range(10)]
+            inl_same += g["inliers"][:10].tolist()
+            inl_diff += g["inliers"][10:].tolist()
+        say(f"  {label:28s} located {loc:2d} of {n_same}; error median {np.median([e[0] for e in errs]):.3f} m {np.median([e[1] for e in errs]):.3f} deg; "
+            f"inliers same-world median {int(np.median(inl_same))} ({min(inl_same)} .. {max(inl_same)}), different-world median "
+            f"{int(np.median(inl_diff))} ({min(inl_diff)} .. {max(inl_diff)}); different-world ok {acc} of {n_same}")
+
+    say(f"located within {OK_T} m / {OK_R} deg of the {n_same} same-world jobs, k-mode and radius supports, same scans, same run:")
+    run("k-mode (10, 16), RANSAC", lambda row: reg.fpfh_batch(row["q"], row["db"]))
+    run("k-mode (10, 16), graph", lambda row: reg.fpfh_graph_batch(row["q"], row["db"]))
+    for name in ("default", "tight"):
+        sup = capi.default_fpfh_radius_params(**SUPPORTS[name])
+        tag = f"{sup.normal_radius:g} m / {sup.normal_max_nn}, {sup.feature_radius:g} m / {sup.feature_max_nn}"
+        run(f"radius {tag}, RANSAC", lambda row: reg.fpfh_batch(row["q"], row["db"], support=sup))
+        run(f"radius {tag}, graph", lambda row: reg.fpfh_graph_batch(row["q"], row["db"], support=sup))
+        m20, lo20 = med(lambda: reg.fpfh_batch(rows[0]["q"], rows[0]["db"], support=sup), a.reps)
+        say(f"  radius {tag}: end to end (features present), 20 candidates, RANSAC: median {m20:.2f} ms (min {lo20:.2f})")
+    for row in rows:                                                      # (leave the scans as the tool's other lines expect them)
+        for t in [row["q"]] + row["db"]:
+            store.build_fpfh(t, 10, 16)
+    m20, lo20 = med(lambda: reg.fpfh_batch(rows[0]["q"], rows[0]["db"]), a.reps)
+    say(f"  k-mode: end to end (features present), 20 candidates, RANSAC: median {m20:.2f} ms (min {lo20:.2f})")
 
 
 if __name__ == "__main__":

@@ -900,12 +900,15 @@ class ScanStore(_Handle):
         check(lib().gloc_scan_store_fpfh(self._h, int(scan_id), _np_ptr(out), n))
         return out
 
-    def spfh(self, scan_id, feature_k=16):
-        """Diagnostic: the SPFH counts [n, 33] uint16 and the pairs counted [n] uint32 (0: no SPFH) from the scan's normals."""
+    def _spfh(self, fn, scan_id, *support):
         n = self.points(scan_id)
         counts, used = np.empty((n, FPFH_DIM), np.uint16), np.empty(n, np.uint32)
-        check(lib().gloc_scan_store_spfh(self._h, int(scan_id), int(feature_k), _np_ptr(counts), _np_ptr(used), n))
+        check(fn(self._h, int(scan_id), *support, _np_ptr(counts), _np_ptr(used), n))
         return counts, used
+
+    def spfh(self, scan_id, feature_k=16):
+        """Diagnostic: the SPFH counts [n, 33] uint16 and the pairs counted [n] uint32 (0: no SPFH) from the scan's normals."""
+        return self._spfh(lib().gloc_scan_store_spfh, scan_id, int(feature_k))
 
     def radius_neighbors(self, scan_id, radius, max_nn):
         """The scan's radius lists (gloc_scan_store_radius_neighbors): idx [n, max_nn] uint32 and d2 [n, max_nn] float32, the
@@ -928,10 +931,7 @@ class ScanStore(_Handle):
 
     def spfh_radius(self, scan_id, radius=2.5, max_nn=100):
         """Diagnostic: spfh() over the radius list of (radius, max_nn)."""
-        n = self.points(scan_id)
-        counts, used = np.empty((n, FPFH_DIM), np.uint16), np.empty(n, np.uint32)
-        check(lib().gloc_scan_store_spfh_radius(self._h, int(scan_id), float(radius), int(max_nn), _np_ptr(counts), _np_ptr(used), n))
-        return counts, used
+        return self._spfh(lib().gloc_scan_store_spfh_radius, scan_id, float(radius), int(max_nn))
 
 
 class Registrar(_Handle):
@@ -1130,24 +1130,26 @@ class Registrar(_Handle):
                                         _np_ptr(d2) if d2.size else None))
         return idx, d2
 
+    def _fpfh_jobs(self, entry, src_id, ids, blocks, support):
+        """What fpfh_batch and fpfh_graph_batch share: entry(handle, source, targets, n, *blocks, T, inliers, n_pairs, ok), or
+        its _radius form with the support block behind the others."""
+        n = ids.shape[0]
+        T = np.empty((n, 4, 4), np.float32)
+        inl, npairs, ok = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        fn = getattr(lib(), entry if support is None else entry + "_radius")
+        blocks = blocks if support is None else blocks + [C.byref(support)]
+        check(fn(self._h, int(src_id), _np_ptr(ids), n, *blocks, _np_ptr(T), _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
+        return dict(T=T, inliers=inl, n_pairs=npairs, ok=ok.astype(bool))
+
     def fpfh_batch(self, src_id, tgt_ids, stream_ids=None, params=None, support=None):
         """Feature-based global registration of scan src_id against each of tgt_ids (gloc_reg_fpfh_batch_ids), no initial
         guess: returns dict(T [n, 4, 4] float32 source -> target, inliers [n], n_pairs [n], ok [n] bool).  T is a start for
         p2l_batch / gicp_batch / batch_ids(init_T=...), not a refined pose.  support: a FpfhRadiusParams -- features over
         that metric support (gloc_reg_fpfh_batch_ids_radius) instead of the k-NN lists of params."""
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
-        n = ids.shape[0]
         prm = params or default_fpfh_params()
-        sid = None if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32).reshape(n)
-        T = np.empty((n, 4, 4), np.float32)
-        inl, npairs, ok = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int32)
-        if support is None:
-            check(lib().gloc_reg_fpfh_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if sid is None else _np_ptr(sid), C.byref(prm),
-                                                _np_ptr(T), _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
-        else:
-            check(lib().gloc_reg_fpfh_batch_ids_radius(self._h, int(src_id), _np_ptr(ids), n, None if sid is None else _np_ptr(sid),
-                                                       C.byref(prm), C.byref(support), _np_ptr(T), _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
-        return dict(T=T, inliers=inl, n_pairs=npairs, ok=ok.astype(bool))
+        sid = None if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32).reshape(ids.shape[0])
+        return self._fpfh_jobs("gloc_reg_fpfh_batch_ids", src_id, ids, [None if sid is None else _np_ptr(sid), C.byref(prm)], support)
 
     def fpfh_graph_batch(self, src_id, tgt_ids, params=None, support=None):
         """Feature-based global registration through the correspondence graph (gloc_reg_fpfh_graph_batch_ids): the matches of
@@ -1155,17 +1157,8 @@ class Registrar(_Handle):
         source -> target, inliers [n], n_pairs [n], ok [n] bool); T is a start for a refinement, as fpfh_batch's.  support: as
         fpfh_batch's (gloc_reg_fpfh_graph_batch_ids_radius)."""
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
-        n = ids.shape[0]
         prm = params or default_fpfh_graph_params()
-        T = np.empty((n, 4, 4), np.float32)
-        inl, npairs, ok = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int32)
-        if support is None:
-            check(lib().gloc_reg_fpfh_graph_batch_ids(self._h, int(src_id), _np_ptr(ids), n, C.byref(prm), _np_ptr(T), _np_ptr(inl),
-                                                      _np_ptr(npairs), _np_ptr(ok)))
-        else:
-            check(lib().gloc_reg_fpfh_graph_batch_ids_radius(self._h, int(src_id), _np_ptr(ids), n, C.byref(prm), C.byref(support), _np_ptr(T),
-                                                             _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
-        return dict(T=T, inliers=inl, n_pairs=npairs, ok=ok.astype(bool))
+        return self._fpfh_jobs("gloc_reg_fpfh_graph_batch_ids", src_id, ids, [C.byref(prm)], support)
 
     def pair_graph(self, P, Q, params=None):
         """The correspondence graph of a pair list P, Q [m, 3] (gloc_reg_pair_graph): dict(degree [m] uint32, score [m] uint64,

@@ -1,7 +1,7 @@
 // fpfh.hip -- FPFH feature-based global registration (Rusu, Blodow & Beetz; pcl::FPFHEstimation in its k-nearest form,
 // pcl::SampleConsensusPrerejective's idea of RANSAC over descriptor matches): the one stage that needs no initial guess
 // in 3-D.  Host side of fpfh_kernels.hpp; tests/fpfh_ref.py is the contract.  The features live with the scans
-// (scan_store.hip builds and keeps them through the functions here); the C entry points that match and register are in
+// (scan_features.hip builds and keeps them through the functions here); the C entry points that match and register are in
 // reg.hip, which owns the handle and runs its RANSAC stage on the pairs this file compacts.
 #include <cmath>
 
@@ -20,60 +20,38 @@ void ws_free(Ws* w) { delete w; }
 
 int check_params(const gloc_fpfh_params* p) {
   GLOC_REQUIRE(p, GLOC_ERR_INVALID, "params is null");
-  GLOC_REQUIRE(p->normal_k >= 3 && p->normal_k <= 16, GLOC_ERR_INVALID, "normal_k = %u outside [3, 16]", p->normal_k);
-  GLOC_REQUIRE(p->feature_k >= 4 && p->feature_k <= 16, GLOC_ERR_INVALID, "feature_k = %u outside [4, 16]", p->feature_k);
+  GLOC_TRY(check_support(Support::nearest(p->normal_k), SupportOf::NORMALS, SupportNames{"normal_k"}));
+  GLOC_TRY(check_support(Support::nearest(p->feature_k), SupportOf::FEATURES, SupportNames{"feature_k"}));
   GLOC_REQUIRE(p->ransac_iters >= 1 && p->ransac_iters <= (1u << 20), GLOC_ERR_INVALID, "ransac_iters = %u outside [1, 2^20]",
                p->ransac_iters);
   GLOC_REQUIRE(p->inlier_thresh > 0.f, GLOC_ERR_INVALID, "inlier_thresh = %g must be > 0", (double)p->inlier_thresh);
   return GLOC_OK;
 }
 
-int build_spfh(hipStream_t s, ground::NormalsScratch& w, const reg::f32x4* spts, const float* nrm_orig, uint32_t n, uint32_t k,
-               uint8_t* spfh) {
-  if (n == 0) return GLOC_OK;
-  GLOC_TRY(ground::scan_knn(s, w, spts, n, k));
-  hipLaunchKernelGGL(spfh_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w.pts.as<f32x4>(), nrm_orig, w.knn_idx.as<uint32_t>(),
-                     w.knn_d2.as<float>(), n, (int)k, spfh);
-  GLOC_HIP(hipGetLastError());
-  return GLOC_OK;
-}
-
-int build_fpfh(hipStream_t s, ground::NormalsScratch& w, const uint8_t* spfh, uint32_t n, uint32_t k, float* out) {
-  if (n == 0) return GLOC_OK;
-  hipLaunchKernelGGL(fpfh_kernel, dim3((n + 255) / 256), dim3(256), 0, s, spfh, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>(), n,
-                     (int)k, out);
-  GLOC_HIP(hipGetLastError());
-  return GLOC_OK;
-}
-
 int check_radius_params(const gloc_fpfh_radius_params* p) {
   GLOC_REQUIRE(p, GLOC_ERR_INVALID, "radius params is null");
-  GLOC_REQUIRE(p->normal_radius > 0.f && std::isfinite(p->normal_radius), GLOC_ERR_INVALID, "normal_radius = %g must be positive and finite",
-               (double)p->normal_radius);
-  GLOC_REQUIRE(p->normal_min_nn >= 4 && p->normal_min_nn <= p->normal_max_nn, GLOC_ERR_INVALID, "normal_min_nn = %u outside [4, normal_max_nn = %u]",
-               p->normal_min_nn, p->normal_max_nn);
-  GLOC_REQUIRE(p->normal_max_nn <= 128, GLOC_ERR_INVALID, "normal_max_nn = %u outside [normal_min_nn, 128]", p->normal_max_nn);
-  GLOC_REQUIRE(p->feature_radius > 0.f && std::isfinite(p->feature_radius), GLOC_ERR_INVALID, "feature_radius = %g must be positive and finite",
-               (double)p->feature_radius);
-  GLOC_REQUIRE(p->feature_max_nn >= 4 && p->feature_max_nn <= 128, GLOC_ERR_INVALID, "feature_max_nn = %u outside [4, 128]", p->feature_max_nn);
+  GLOC_TRY(check_support(Support::normals_of(*p), SupportOf::NORMALS, SupportNames{nullptr, "normal_radius", "normal_max_nn", "normal_min_nn"}));
+  GLOC_TRY(check_support(Support::features_of(*p), SupportOf::FEATURES, SupportNames{nullptr, "feature_radius", "feature_max_nn"}));
   GLOC_REQUIRE(p->reserved_ == 0, GLOC_ERR_INVALID, "reserved_ = %u must be 0", p->reserved_);
   return GLOC_OK;
 }
 
-int build_spfh_radius(hipStream_t s, ground::NormalsScratch& w, const reg::f32x4* spts, const float* nrm_orig, uint32_t n, float radius,
-                      uint32_t max_nn, uint8_t* spfh) {
+int build_spfh(hipStream_t s, ground::NormalsScratch& w, const reg::f32x4* spts, const float* nrm_orig, uint32_t n, const Support& sup,
+               uint8_t* spfh) {
   if (n == 0) return GLOC_OK;
-  GLOC_TRY(ground::scan_radius(s, w, spts, n, radius, max_nn));
-  hipLaunchKernelGGL(spfh_wide_kernel, dim3((n + 3) / 4), dim3(256), 0, s, w.pts.as<f32x4>(), nrm_orig, w.knn_idx.as<uint32_t>(),
-                     w.knn_d2.as<float>(), n, (int)max_nn, spfh);
+  GLOC_TRY(ground::scan_lists(s, w, spts, n, sup));
+  const bool wide = sup.by_radius();
+  hipLaunchKernelGGL(wide ? spfh_wide_kernel : spfh_kernel, dim3(wide ? (n + 3) / 4 : (n + 255) / 256), dim3(256), 0, s, w.pts.as<f32x4>(),
+                     nrm_orig, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>(), n, (int)sup.width(), spfh);
   GLOC_HIP(hipGetLastError());
   return GLOC_OK;
 }
 
-int build_fpfh_wide(hipStream_t s, ground::NormalsScratch& w, const uint8_t* spfh, uint32_t n, uint32_t max_nn, float* out) {
+int build_fpfh(hipStream_t s, ground::NormalsScratch& w, const uint8_t* spfh, uint32_t n, const Support& sup, float* out) {
   if (n == 0) return GLOC_OK;
-  hipLaunchKernelGGL(fpfh_wide_kernel, dim3((n + 3) / 4), dim3(256), 0, s, spfh, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>(), n,
-                     (int)max_nn, out);
+  const bool wide = sup.by_radius();
+  hipLaunchKernelGGL(wide ? fpfh_wide_kernel : fpfh_kernel, dim3(wide ? (n + 3) / 4 : (n + 255) / 256), dim3(256), 0, s, spfh,
+                     w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>(), n, (int)sup.width(), out);
   GLOC_HIP(hipGetLastError());
   return GLOC_OK;
 }

@@ -1,4 +1,4 @@
-// fpfh.hpp -- what scan_store.hip (which owns the scans' features) and reg.hip (which owns the registration handle and
+// fpfh.hpp -- what scan_features.hip (which owns the scans' features) and reg.hip (which owns the registration handle and
 // the RANSAC stage) call of fpfh.hip.
 #pragma once
 #include <vector>
@@ -39,17 +39,13 @@ void ws_free(Ws* w);
 int check_params(const gloc_fpfh_params* prm);
 int check_radius_params(const gloc_fpfh_radius_params* prm);
 
-// SPFH of the n points of `spts` (the store's sorted points) from their k-NN lists, which this builds into w (scan_knn),
-// and the normals `nrm_orig` (original order): spfh [n][SPFH_BYTES] by original index.  Enqueued on s.
-int build_spfh(hipStream_t s, ground::NormalsScratch& w, const reg::f32x4* spts, const float* nrm_orig, uint32_t n, uint32_t k,
+// SPFH of the n points of `spts` (the store's sorted points) from their neighbour lists of `sup`, which this builds into w
+// (ground::scan_lists), and the normals `nrm_orig` (original order): spfh [n][SPFH_BYTES] by original index.  Enqueued on s.
+int build_spfh(hipStream_t s, ground::NormalsScratch& w, const reg::f32x4* spts, const float* nrm_orig, uint32_t n, const Support& sup,
                uint8_t* spfh);
-// ... and the FPFH rows from them and the same lists (still in w): out [n][FEAT_DIM] by original index.
-int build_fpfh(hipStream_t s, ground::NormalsScratch& w, const uint8_t* spfh, uint32_t n, uint32_t k, float* out);
-// The same two over the radius lists of (radius, max_nn), which build_spfh_radius builds into w (scan_radius): the wide-list
-// kernels, a wave per point.
-int build_spfh_radius(hipStream_t s, ground::NormalsScratch& w, const reg::f32x4* spts, const float* nrm_orig, uint32_t n, float radius,
-                      uint32_t max_nn, uint8_t* spfh);
-int build_fpfh_wide(hipStream_t s, ground::NormalsScratch& w, const uint8_t* spfh, uint32_t n, uint32_t max_nn, float* out);
+// ... and the FPFH rows from them and the same lists (still in w): out [n][FEAT_DIM] by original index.  Both run a thread
+// per point over k-NN lists and the wide-list kernels, a wave per point, over radius lists.
+int build_fpfh(hipStream_t s, ground::NormalsScratch& w, const uint8_t* spfh, uint32_t n, const Support& sup, float* out);
 // Rows of `width` floats between original order and the order of the sorted points.
 int reorder_rows(hipStream_t s, const reg::f32x4* spts, uint32_t n, const float* in, float* out, uint32_t width, bool to_sorted);
 

@@ -306,11 +306,26 @@ int estimate_device(gloc_ground* h, const float* d_xyz, size_t n, size_t stride,
 
 }  // namespace
 
-// ---- per-point normals of a whole resident scan (scan_store.hip: gloc_scan_store_build_normals) -----------------------
+// ---- per-point normals of a whole resident scan (scan_features.hip: gloc_scan_store_build_normals) --------------------
 // The kernels of G2 - G4 on a cloud that already has a spatially sorted copy: the exact k-NN is exact in whatever order
 // the points are cut into chunks, so the store's own sorted copy stands in for the Hilbert sort of knn_device and the
 // lists -- hence the normals -- are those of gloc_ground_normals on the same points, bit for bit.
 namespace gloc {
+
+int check_support(const Support& s, SupportOf what, const SupportNames& nm) {
+  if (nm.k && !s.by_radius()) {
+    const uint32_t lo = what == SupportOf::FEATURES ? 4u : 3u;
+    GLOC_REQUIRE(s.k >= lo && s.k <= (uint32_t)KMAX, GLOC_ERR_INVALID, "%s = %u outside [%u, %d]", nm.k, s.k, lo, KMAX);
+    return GLOC_OK;
+  }
+  GLOC_REQUIRE(s.r > 0.f && std::isfinite(s.r), GLOC_ERR_INVALID, "%s = %g must be positive and finite", nm.r, (double)s.r);
+  if (what == SupportOf::NORMALS)
+    GLOC_REQUIRE(s.min_nn >= 4 && s.min_nn <= s.max_nn, GLOC_ERR_INVALID, "%s = %u outside [4, %s = %u]", nm.min_nn, s.min_nn, nm.max_nn, s.max_nn);
+  const uint32_t lo = what == SupportOf::SEARCH ? 1u : 4u;
+  GLOC_REQUIRE(s.max_nn >= lo && s.max_nn <= (uint32_t)RADIUS_MAX_NN, GLOC_ERR_INVALID, "%s = %u outside [%u, %d]", nm.max_nn, s.max_nn, lo, RADIUS_MAX_NN);
+  return GLOC_OK;
+}
+
 namespace ground {
 
 __global__ __launch_bounds__(256) void unsort_f4_kernel(const f32x4* __restrict__ spts, uint32_t m, f32x4* __restrict__ pts) {
@@ -321,66 +336,42 @@ __global__ __launch_bounds__(256) void unsort_f4_kernel(const f32x4* __restrict_
   if (o < m) pts[o] = f32x4{p.x, p.y, p.z, 0.f};
 }
 
-int scan_knn(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, uint32_t k) {
-  GLOC_REQUIRE(k >= 3 && k <= (uint32_t)KMAX, GLOC_ERR_INVALID, "k must be in [3, %d]", KMAX);
+int scan_lists(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, const Support& sup) {
+  GLOC_TRY(check_support(sup, SupportOf::SEARCH, SupportNames{"k", "radius", "max_nn", "min_nn"}));
   if (m == 0) return GLOC_OK;
-  const uint32_t nch = (m + KCH - 1) / KCH;
+  const uint32_t nch = (m + KCH - 1) / KCH, width = sup.width();
   GLOC_TRY(w.pts.ensure(sizeof(f32x4) * m, s));
-  GLOC_TRY(w.knn_idx.ensure(sizeof(uint32_t) * (size_t)m * k, s));
-  GLOC_TRY(w.knn_d2.ensure(sizeof(float) * (size_t)m * k, s));
+  GLOC_TRY(w.knn_idx.ensure(sizeof(uint32_t) * (size_t)m * width, s));
+  GLOC_TRY(w.knn_d2.ensure(sizeof(float) * (size_t)m * width, s));
+  if (sup.by_radius()) GLOC_TRY(w.knn_cnt.ensure(sizeof(uint32_t) * (size_t)m, s));
   GLOC_TRY(w.cbox_lo.ensure(sizeof(f32x4) * nch, s));
   GLOC_TRY(w.cbox_hi.ensure(sizeof(f32x4) * nch, s));
   hipLaunchKernelGGL(unsort_f4_kernel, dim3((m + 255) / 256), dim3(256), 0, s, spts, m, w.pts.as<f32x4>());
   hipLaunchKernelGGL(kchunk_boxes_kernel, dim3(nch), dim3(64), 0, s, spts, m, w.cbox_lo.as<f32x4>(), w.cbox_hi.as<f32x4>());
-  hipLaunchKernelGGL(knn_culled_kernel, dim3((nch + 3) / 4), dim3(256), 0, s, spts, m, w.cbox_lo.as<f32x4>(),
-                     w.cbox_hi.as<f32x4>(), nch, (int)k, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>());
+  if (sup.by_radius()) {
+    // a wave's lists: 64 lanes x max_nn keys of 8 bytes (64 KiB at 128, the most a launch may ask for without opting in)
+    hipLaunchKernelGGL(radius_self_kernel, dim3(nch), dim3(64), (size_t)width * 64 * sizeof(unsigned long long), s, spts, m,
+                       w.cbox_lo.as<f32x4>(), w.cbox_hi.as<f32x4>(), nch, sup.r * sup.r, (int)width, w.knn_idx.as<uint32_t>(),
+                       w.knn_d2.as<float>(), w.knn_cnt.as<uint32_t>());
+  } else {
+    hipLaunchKernelGGL(knn_culled_kernel, dim3((nch + 3) / 4), dim3(256), 0, s, spts, m, w.cbox_lo.as<f32x4>(),
+                       w.cbox_hi.as<f32x4>(), nch, (int)width, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>());
+  }
   GLOC_HIP(hipGetLastError());
   return GLOC_OK;
 }
 
-int scan_normals(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, uint32_t k, float* out_normals) {
-  GLOC_TRY(scan_knn(s, w, spts, m, k));
+int scan_normals(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, const Support& sup, float* out_normals) {
+  GLOC_TRY(scan_lists(s, w, spts, m, sup));
   if (m == 0) return GLOC_OK;
   GLOC_TRY(w.bins.ensure(std::max<uint32_t>(m, 16), s));
   GLOC_TRY(w.hist.ensure(sizeof(uint32_t) * 18, s));
   GLOC_HIP(hipMemsetAsync(w.hist.p, 0, sizeof(uint32_t) * 18, s));
   hipLaunchKernelGGL(normals_kernel, dim3((m + 255) / 256), dim3(256), 0, s, w.pts.as<f32x4>(), m, w.knn_idx.as<uint32_t>(),
-                     (int)k, out_normals, w.bins.as<uint8_t>(), w.hist.as<uint32_t>());
-  GLOC_HIP(hipGetLastError());
-  return GLOC_OK;
-}
-
-int scan_radius(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, float r, uint32_t max_nn) {
-  GLOC_REQUIRE(r > 0.f && std::isfinite(r), GLOC_ERR_INVALID, "radius = %g must be positive and finite", (double)r);
-  GLOC_REQUIRE(max_nn >= 1 && max_nn <= (uint32_t)RADIUS_MAX_NN, GLOC_ERR_INVALID, "max_nn = %u outside [1, %d]", max_nn, RADIUS_MAX_NN);
-  if (m == 0) return GLOC_OK;
-  const uint32_t nch = (m + KCH - 1) / KCH;
-  GLOC_TRY(w.pts.ensure(sizeof(f32x4) * m, s));
-  GLOC_TRY(w.knn_idx.ensure(sizeof(uint32_t) * (size_t)m * max_nn, s));
-  GLOC_TRY(w.knn_d2.ensure(sizeof(float) * (size_t)m * max_nn, s));
-  GLOC_TRY(w.knn_cnt.ensure(sizeof(uint32_t) * (size_t)m, s));
-  GLOC_TRY(w.cbox_lo.ensure(sizeof(f32x4) * nch, s));
-  GLOC_TRY(w.cbox_hi.ensure(sizeof(f32x4) * nch, s));
-  hipLaunchKernelGGL(unsort_f4_kernel, dim3((m + 255) / 256), dim3(256), 0, s, spts, m, w.pts.as<f32x4>());
-  hipLaunchKernelGGL(kchunk_boxes_kernel, dim3(nch), dim3(64), 0, s, spts, m, w.cbox_lo.as<f32x4>(), w.cbox_hi.as<f32x4>());
-  // a wave's lists: 64 lanes x max_nn keys of 8 bytes (64 KiB at 128, the most a launch may ask for without opting in)
-  hipLaunchKernelGGL(radius_self_kernel, dim3(nch), dim3(64), (size_t)max_nn * 64 * sizeof(unsigned long long), s, spts, m,
-                     w.cbox_lo.as<f32x4>(), w.cbox_hi.as<f32x4>(), nch, r * r, (int)max_nn, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>(),
-                     w.knn_cnt.as<uint32_t>());
-  GLOC_HIP(hipGetLastError());
-  return GLOC_OK;
-}
-
-int scan_normals_radius(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, float r, uint32_t max_nn, uint32_t min_nn,
-                        float* out_normals) {
-  GLOC_TRY(scan_radius(s, w, spts, m, r, max_nn));
-  if (m == 0) return GLOC_OK;
-  GLOC_TRY(w.bins.ensure(std::max<uint32_t>(m, 16), s));
-  GLOC_TRY(w.hist.ensure(sizeof(uint32_t) * 18, s));
-  GLOC_HIP(hipMemsetAsync(w.hist.p, 0, sizeof(uint32_t) * 18, s));
-  hipLaunchKernelGGL(normals_kernel, dim3((m + 255) / 256), dim3(256), 0, s, w.pts.as<f32x4>(), m, w.knn_idx.as<uint32_t>(), (int)max_nn,
-                     out_normals, w.bins.as<uint8_t>(), w.hist.as<uint32_t>());
-  hipLaunchKernelGGL(normals_min_nn_kernel, dim3((m + 255) / 256), dim3(256), 0, s, m, w.knn_cnt.as<uint32_t>(), max_nn, min_nn, out_normals);
+                     (int)sup.width(), out_normals, w.bins.as<uint8_t>(), w.hist.as<uint32_t>());
+  if (sup.by_radius())
+    hipLaunchKernelGGL(normals_min_nn_kernel, dim3((m + 255) / 256), dim3(256), 0, s, m, w.knn_cnt.as<uint32_t>(), sup.max_nn, sup.min_nn,
+                       out_normals);
   GLOC_HIP(hipGetLastError());
   return GLOC_OK;
 }

@@ -938,10 +938,10 @@ __global__ void set_pair_counts_kernel(Job* __restrict__ jobs, const uint32_t* _
 // What the two stages that turn the match list into a pose differ in, as the shared part below sees it: the features'
 // and the matcher's parameters, the hypotheses per job, and whether all of them are scored (the alive lists).
 struct FpfhFront {
-  uint32_t normal_k, feature_k, mutual, n_hyp;
+  Support normal, feature;  // what the scans' normals and features are built from
+  uint32_t mutual, n_hyp;
   bool adaptive;
   float min_inlier_ratio;
-  const gloc_fpfh_radius_params* radius;  // the features' metric support; null: the k's above
 };
 
 // stage(bd, v, nblocks, m_max): the launches from the pairs in v.pairs (M of job c in jobs[c].n_src; none above m_max) to
@@ -956,20 +956,14 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
   std::vector<uint32_t> ids(1 + n);
   ids[0] = src_id;
   std::copy(tgt_ids, tgt_ids + n, ids.begin() + 1);
-  if (prm->radius)
-    GLOC_TRY(store_ensure_fpfh_radius(st, ids.data(), ids.size(), *prm->radius));
-  else
-    GLOC_TRY(store_ensure_fpfh(st, ids.data(), ids.size(), prm->normal_k, prm->feature_k));
+  GLOC_TRY(store_ensure_fpfh(st, ids.data(), ids.size(), prm->normal, prm->feature));
   ScopedPins pins(st, s);
   GLOC_TRY(pins.pin(ids.data(), nullptr, ids.size()));
   const std::vector<DevScan>& scans = pins.scans;
   const DevScan& src = scans[0];
   GLOC_REQUIRE(src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is too large");
-  for (const DevScan& sc : scans) {
-    const bool has = prm->radius ? sc.has_fpfh_radius(normal_support(*prm->radius), feature_support(*prm->radius))
-                                 : sc.has_fpfh(prm->normal_k, prm->feature_k);
-    GLOC_REQUIRE(sc.n == 0 || (sc.fpfh && has), GLOC_ERR_STATE, "a scan lost its features during the call");
-  }
+  for (const DevScan& sc : scans)
+    GLOC_REQUIRE(sc.n == 0 || (sc.fpfh && sc.has_fpfh(prm->normal, prm->feature)), GLOC_ERR_STATE, "a scan lost its features during the call");
   const uint32_t n_jobs = (uint32_t)n;
   const bool mutual = prm->mutual != 0;
   for (uint32_t c = 0; c < n_jobs; ++c) {
@@ -1045,9 +1039,9 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
 }
 
 int run_fpfh(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const uint32_t* stream_ids, const gloc_fpfh_params* prm,
-             const gloc_fpfh_radius_params* radius, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
-  const FpfhFront f{prm->normal_k, prm->feature_k, prm->mutual, prm->ransac_iters, prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f,
-                    prm->min_inlier_ratio, radius};
+             const Support& normal, const Support& feature, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+  const FpfhFront f{normal, feature, prm->mutual, prm->ransac_iters, prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f,
+                    prm->min_inlier_ratio};
   return run_fpfh_pairs(h, src_id, tgt_ids, n, stream_ids, &f, out_T, out_inliers, out_n_pairs, out_ok,
                         [&](const BatchDims& bd, const WsView& v, uint32_t nblocks, uint32_t) {
                           return enqueue_ransac(h, bd, RansacRule{prm->ransac_iters, prm->inlier_thresh, prm->min_inlier_ratio,
@@ -1107,8 +1101,8 @@ int enqueue_graph(gloc_reg* h, const BatchDims& bd, const gloc_fpfh_graph_params
 }
 
 int run_fpfh_graph(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const gloc_fpfh_graph_params* prm,
-                   const gloc_fpfh_radius_params* radius, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
-  const FpfhFront f{prm->normal_k, prm->feature_k, prm->mutual, prm->n_seeds, true, prm->min_inlier_ratio, radius};
+                   const Support& normal, const Support& feature, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+  const FpfhFront f{normal, feature, prm->mutual, prm->n_seeds, true, prm->min_inlier_ratio};
   return run_fpfh_pairs(h, src_id, tgt_ids, n, nullptr, &f, out_T, out_inliers, out_n_pairs, out_ok,
                         [&](const BatchDims& bd, const WsView& v, uint32_t nblocks, uint32_t m_max) {
                           return enqueue_graph(h, bd, prm, v, h->fpfh->counts.as<uint32_t>(), nblocks, m_max);
@@ -1824,7 +1818,8 @@ int gloc_reg_fpfh_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* t
   GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return run_fpfh(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, nullptr, out_T, out_inliers, out_n_pairs, out_ok);
+  return run_fpfh(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, Support::nearest(prm->normal_k), Support::nearest(prm->feature_k), out_T,
+                  out_inliers, out_n_pairs, out_ok);
 }
 
 int gloc_reg_fpfh_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
@@ -1835,7 +1830,8 @@ int gloc_reg_fpfh_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, const uint
   GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return run_fpfh(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, support, out_T, out_inliers, out_n_pairs, out_ok);
+  return run_fpfh(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, Support::normals_of(*support), Support::features_of(*support), out_T,
+                  out_inliers, out_n_pairs, out_ok);
 }
 
 int gloc_reg_fpfh_graph_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n,
@@ -1845,7 +1841,8 @@ int gloc_reg_fpfh_graph_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint3
   GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return run_fpfh_graph(h, src_scan_id, tgt_scan_ids, n, prm, nullptr, out_T, out_inliers, out_n_pairs, out_ok);
+  return run_fpfh_graph(h, src_scan_id, tgt_scan_ids, n, prm, Support::nearest(prm->normal_k), Support::nearest(prm->feature_k), out_T,
+                        out_inliers, out_n_pairs, out_ok);
 }
 
 int gloc_reg_fpfh_graph_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n,
@@ -1856,7 +1853,8 @@ int gloc_reg_fpfh_graph_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, cons
   GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return run_fpfh_graph(h, src_scan_id, tgt_scan_ids, n, prm, support, out_T, out_inliers, out_n_pairs, out_ok);
+  return run_fpfh_graph(h, src_scan_id, tgt_scan_ids, n, prm, Support::normals_of(*support), Support::features_of(*support), out_T,
+                        out_inliers, out_n_pairs, out_ok);
 }
 
 int gloc_reg_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const gloc_fpfh_graph_params* prm,

@@ -7,6 +7,7 @@
 // the segmented radix sort of seg_sort.hpp with one segment per scan.  Adding the 25 query scans of a step is
 // one sequence of ~35 launches (round 2: ~25 launches per scan, a third of them inside hipCUB's merge sort);
 // re-sorting a KITTI-00-sized database into kd order is 71 batches of 64 scans.
+// The scans' normals and features are scan_features.hip's; the re-sort here only carries them along with the points.
 #include <algorithm>
 #include <new>
 
@@ -603,167 +604,6 @@ void store_free_scan(gloc_scan_store* st, DevScan& s, bool cache_block) {
   s = DevScan{};
 }
 
-// normals between original order and the order of the sorted points (pts[i].w = original index of sorted position i)
-__global__ __launch_bounds__(256) void normals_reorder_kernel(const f32x4* __restrict__ pts, uint32_t n, const float* __restrict__ in,
-                                                              float* __restrict__ out, bool to_sorted) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t o = __float_as_uint(pts[i].w);
-  if (o >= n) return;
-  const size_t src = 3 * (size_t)(to_sorted ? o : i), dst = 3 * (size_t)(to_sorted ? i : o);
-  out[dst + 0] = in[src + 0];
-  out[dst + 1] = in[src + 1];
-  out[dst + 2] = in[src + 2];
-}
-
-static void describe_normals(const DevScan& s, char* buf, size_t cap);
-
-int store_build_normals(gloc_scan_store* st, DevScan& s, uint32_t k) {
-  GLOC_REQUIRE(k >= 3 && k <= 16, GLOC_ERR_INVALID, "k = %u outside [3, 16]", k);
-  if (s.nrm_k == k || s.n == 0) {
-    s.nrm_k = k;
-    return GLOC_OK;
-  }
-  char have[96];
-  describe_normals(s, have, sizeof(have));
-  GLOC_REQUIRE(!s.nrm || s.pins == 0, GLOC_ERR_STATE, "the scan's normals (%s) may be read by %d batch(es) in flight: not rebuilt with k = %u", have,
-               s.pins, k);
-  hipStream_t q = st->stream;
-  const uint32_t n = (uint32_t)s.n;
-  if (!s.nrm) {
-    GLOC_HIP(hipMalloc(reinterpret_cast<void**>(&s.nrm), 12 * s.n));
-    if (s.live) st->live_bytes += 12 * s.n;
-  }
-  s.nrm_k = 0;
-  s.fpfh_nk = s.fpfh_fk = 0;  // (features of the old normals: rebuilt on the next request)
-  GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
-  GLOC_TRY(gloc::ground::scan_normals(q, st->nrm_ws, s.idx.pts, n, k, st->nrm_tmp.as<float>()));
-  hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, s.idx.pts, n, st->nrm_tmp.as<float>(), s.nrm, true);
-  GLOC_HIP(hipGetLastError());
-  GLOC_HIP(hipStreamSynchronize(q));
-  s.nrm_k = k;
-  return GLOC_OK;
-}
-
-// SPFH of a scan with normals into st->spfh_tmp (original order); the lists stay in st->nrm_ws for build_fpfh.
-static int store_spfh(gloc_scan_store* st, const DevScan& s, uint32_t feature_k) {
-  hipStream_t q = st->stream;
-  const uint32_t n = (uint32_t)s.n;
-  GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
-  GLOC_TRY(st->spfh_tmp.ensure((size_t)gloc::fpfh::SPFH_BYTES * s.n, q));
-  hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, s.idx.pts, n, s.nrm, st->nrm_tmp.as<float>(), false);
-  GLOC_HIP(hipGetLastError());
-  return gloc::fpfh::build_spfh(q, st->nrm_ws, s.idx.pts, st->nrm_tmp.as<float>(), n, feature_k, st->spfh_tmp.as<uint8_t>());
-}
-
-int store_build_fpfh(gloc_scan_store* st, DevScan& s, uint32_t normal_k, uint32_t feature_k) {
-  GLOC_REQUIRE(normal_k >= 3 && normal_k <= 16, GLOC_ERR_INVALID, "normal_k = %u outside [3, 16]", normal_k);
-  GLOC_REQUIRE(feature_k >= 4 && feature_k <= 16, GLOC_ERR_INVALID, "feature_k = %u outside [4, 16]", feature_k);
-  if (s.n == 0) {
-    s.nrm_k = s.fpfh_nk = normal_k;
-    s.fpfh_fk = feature_k;
-    return GLOC_OK;
-  }
-  if (s.has_fpfh(normal_k, feature_k)) return GLOC_OK;
-  GLOC_REQUIRE(!s.fpfh || s.pins == 0, GLOC_ERR_STATE,
-               "the scan's features (normal_k = %u, feature_k = %u) may be read by %d batch(es) in flight: not rebuilt with %u, %u", s.fpfh_nk,
-               s.fpfh_fk, s.pins, normal_k, feature_k);
-  GLOC_TRY(store_build_normals(st, s, normal_k));
-  hipStream_t q = st->stream;
-  const uint32_t n = (uint32_t)s.n;
-  if (!s.fpfh) {
-    GLOC_HIP(hipMalloc(reinterpret_cast<void**>(&s.fpfh), 132 * s.n));
-    if (s.live) st->live_bytes += 132 * s.n;
-  }
-  s.fpfh_nk = s.fpfh_fk = 0;
-  GLOC_TRY(st->fpfh_tmp.ensure(132 * s.n, q));
-  GLOC_TRY(store_spfh(st, s, feature_k));
-  GLOC_TRY(gloc::fpfh::build_fpfh(q, st->nrm_ws, st->spfh_tmp.as<uint8_t>(), n, feature_k, st->fpfh_tmp.as<float>()));
-  GLOC_TRY(gloc::fpfh::reorder_rows(q, s.idx.pts, n, st->fpfh_tmp.as<float>(), s.fpfh, gloc::fpfh::FEAT_DIM, true));
-  GLOC_HIP(hipStreamSynchronize(q));
-  s.fpfh_nk = normal_k;
-  s.fpfh_fk = feature_k;
-  return GLOC_OK;
-}
-
-static void describe_normals(const DevScan& s, char* buf, size_t cap) {
-  if (s.nrm_k == SUPPORT_BY_RADIUS)
-    snprintf(buf, cap, "radius = %g, max_nn = %u, min_nn = %u", (double)s.nrm_rad.r, s.nrm_rad.max_nn, s.nrm_rad.min_nn);
-  else
-    snprintf(buf, cap, "k = %u", s.nrm_k);
-}
-
-int store_build_normals_radius(gloc_scan_store* st, DevScan& s, const RadiusSupport& ns) {
-  if (s.has_normals_radius(ns) || s.n == 0) {
-    s.nrm_k = SUPPORT_BY_RADIUS;
-    s.nrm_rad = ns;
-    return GLOC_OK;
-  }
-  char have[96];
-  describe_normals(s, have, sizeof(have));
-  GLOC_REQUIRE(!s.nrm || s.pins == 0, GLOC_ERR_STATE,
-               "the scan's normals (%s) may be read by %d batch(es) in flight: not rebuilt with radius = %g, max_nn = %u, min_nn = %u", have, s.pins,
-               (double)ns.r, ns.max_nn, ns.min_nn);
-  hipStream_t q = st->stream;
-  const uint32_t n = (uint32_t)s.n;
-  if (!s.nrm) {
-    GLOC_HIP(hipMalloc(reinterpret_cast<void**>(&s.nrm), 12 * s.n));
-    if (s.live) st->live_bytes += 12 * s.n;
-  }
-  s.nrm_k = 0;
-  s.fpfh_nk = s.fpfh_fk = 0;  // (features of the old normals: rebuilt on the next request)
-  GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
-  GLOC_TRY(gloc::ground::scan_normals_radius(q, st->nrm_ws, s.idx.pts, n, ns.r, ns.max_nn, ns.min_nn, st->nrm_tmp.as<float>()));
-  hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, s.idx.pts, n, st->nrm_tmp.as<float>(), s.nrm, true);
-  GLOC_HIP(hipGetLastError());
-  GLOC_HIP(hipStreamSynchronize(q));
-  s.nrm_k = SUPPORT_BY_RADIUS;
-  s.nrm_rad = ns;
-  return GLOC_OK;
-}
-
-// store_spfh over the radius lists of (radius, max_nn), which stay in st->nrm_ws for build_fpfh_wide.
-static int store_spfh_radius(gloc_scan_store* st, const DevScan& s, float radius, uint32_t max_nn) {
-  hipStream_t q = st->stream;
-  const uint32_t n = (uint32_t)s.n;
-  GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
-  GLOC_TRY(st->spfh_tmp.ensure((size_t)gloc::fpfh::SPFH_BYTES * s.n, q));
-  hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, s.idx.pts, n, s.nrm, st->nrm_tmp.as<float>(), false);
-  GLOC_HIP(hipGetLastError());
-  return gloc::fpfh::build_spfh_radius(q, st->nrm_ws, s.idx.pts, st->nrm_tmp.as<float>(), n, radius, max_nn, st->spfh_tmp.as<uint8_t>());
-}
-
-int store_build_fpfh_radius(gloc_scan_store* st, DevScan& s, const gloc_fpfh_radius_params& prm) {
-  GLOC_TRY(gloc::fpfh::check_radius_params(&prm));
-  const RadiusSupport ns = normal_support(prm), fs = feature_support(prm);
-  if (s.n == 0) {
-    s.nrm_k = s.fpfh_nk = s.fpfh_fk = SUPPORT_BY_RADIUS;
-    s.nrm_rad = s.fpfh_nrad = ns;
-    s.fpfh_rad = fs;
-    return GLOC_OK;
-  }
-  if (s.has_fpfh_radius(ns, fs)) return GLOC_OK;
-  GLOC_REQUIRE(!s.fpfh || s.pins == 0, GLOC_ERR_STATE, "the scan's features may be read by %d batch(es) in flight: not rebuilt with another support",
-               s.pins);
-  GLOC_TRY(store_build_normals_radius(st, s, ns));
-  hipStream_t q = st->stream;
-  const uint32_t n = (uint32_t)s.n;
-  if (!s.fpfh) {
-    GLOC_HIP(hipMalloc(reinterpret_cast<void**>(&s.fpfh), 132 * s.n));
-    if (s.live) st->live_bytes += 132 * s.n;
-  }
-  s.fpfh_nk = s.fpfh_fk = 0;
-  GLOC_TRY(st->fpfh_tmp.ensure(132 * s.n, q));
-  GLOC_TRY(store_spfh_radius(st, s, fs.r, fs.max_nn));
-  GLOC_TRY(gloc::fpfh::build_fpfh_wide(q, st->nrm_ws, st->spfh_tmp.as<uint8_t>(), n, fs.max_nn, st->fpfh_tmp.as<float>()));
-  GLOC_TRY(gloc::fpfh::reorder_rows(q, s.idx.pts, n, st->fpfh_tmp.as<float>(), s.fpfh, gloc::fpfh::FEAT_DIM, true));
-  GLOC_HIP(hipStreamSynchronize(q));
-  s.fpfh_nk = s.fpfh_fk = SUPPORT_BY_RADIUS;
-  s.fpfh_nrad = ns;
-  s.fpfh_rad = fs;
-  return GLOC_OK;
-}
-
 int store_build_order(gloc_scan_store* st, DevScan& s, int cs) {
   if (cs == 0) {
     s.order = nullptr;
@@ -1003,8 +843,7 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
       if (todo[i]->nrm) {
         const uint32_t n = (uint32_t)todo[i]->n;
         GLOC_TRY(nrm_keep[i].ensure(12 * (size_t)n, q));
-        hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, todo[i]->idx.pts, n, todo[i]->nrm,
-                           nrm_keep[i].as<float>(), false);
+        GLOC_TRY(store_reorder_normals(q, todo[i]->idx.pts, n, todo[i]->nrm, nrm_keep[i].as<float>(), false));
       }
     std::vector<DevBuf> fpfh_keep(cnt);  // (and so do the features)
     for (uint32_t i = 0; i < cnt; ++i)
@@ -1029,11 +868,7 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
     hipLaunchKernelGGL(kd_finish_kernel, dim3((max_np + 255) / 256, cnt), dim3(256), 0, q, d_k, pp[cur], hh[cur]);
     launch_boxes(q, st->builds.as<ScanBuild>(), cnt, max_nch, max_npairs, max_nsup);
     for (uint32_t i = 0; i < cnt; ++i)
-      if (todo[i]->nrm) {
-        const uint32_t n = (uint32_t)todo[i]->n;
-        hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, todo[i]->idx.pts, n,
-                           nrm_keep[i].as<float>(), todo[i]->nrm, true);
-      }
+      if (todo[i]->nrm) GLOC_TRY(store_reorder_normals(q, todo[i]->idx.pts, (uint32_t)todo[i]->n, nrm_keep[i].as<float>(), todo[i]->nrm, true));
     for (uint32_t i = 0; i < cnt; ++i)
       if (todo[i]->fpfh)
         GLOC_TRY(gloc::fpfh::reorder_rows(q, todo[i]->idx.pts, (uint32_t)todo[i]->n, fpfh_keep[i].as<float>(), todo[i]->fpfh,
@@ -1097,34 +932,6 @@ void store_pin(gloc_scan_store* st, const uint32_t* ids, size_t count, int delta
   std::lock_guard<std::mutex> lk(st->mu);
   for (size_t i = 0; i < count; ++i)
     if (ids[i] < st->scans.size() && st->scans[ids[i]].live) st->scans[ids[i]].pins += delta;
-}
-
-int store_ensure_normals(gloc_scan_store* st, const uint32_t* ids, size_t n, uint32_t k) {
-  std::lock_guard<std::mutex> lk(st->mu);
-  for (size_t c = 0; c < n; ++c) {
-    GLOC_REQUIRE(ids[c] < st->scans.size() && st->scans[ids[c]].live, GLOC_ERR_INVALID, "unknown scan id %u", ids[c]);
-    DevScan& s = st->scans[ids[c]];
-    if (s.nrm_k == 0) GLOC_TRY(store_build_normals(st, s, k));
-  }
-  return GLOC_OK;
-}
-
-int store_ensure_fpfh(gloc_scan_store* st, const uint32_t* ids, size_t n, uint32_t normal_k, uint32_t feature_k) {
-  std::lock_guard<std::mutex> lk(st->mu);
-  for (size_t c = 0; c < n; ++c) {
-    GLOC_REQUIRE(ids[c] < st->scans.size() && st->scans[ids[c]].live, GLOC_ERR_INVALID, "unknown scan id %u", ids[c]);
-    GLOC_TRY(store_build_fpfh(st, st->scans[ids[c]], normal_k, feature_k));
-  }
-  return GLOC_OK;
-}
-
-int store_ensure_fpfh_radius(gloc_scan_store* st, const uint32_t* ids, size_t n, const gloc_fpfh_radius_params& prm) {
-  std::lock_guard<std::mutex> lk(st->mu);
-  for (size_t c = 0; c < n; ++c) {
-    GLOC_REQUIRE(ids[c] < st->scans.size() && st->scans[ids[c]].live, GLOC_ERR_INVALID, "unknown scan id %u", ids[c]);
-    GLOC_TRY(store_build_fpfh_radius(st, st->scans[ids[c]], prm));
-  }
-  return GLOC_OK;
 }
 
 }  // namespace reg
@@ -1472,156 +1279,6 @@ int gloc_scan_store_download(gloc_scan_store* st, uint32_t scan_id, float* out_x
   if (s.n) {
     GLOC_HIP(hipMemcpyAsync(out_xyz, s.xyz, sizeof(float) * 3 * s.n, hipMemcpyDeviceToHost, st->stream));
     GLOC_HIP(hipStreamSynchronize(st->stream));
-  }
-  return GLOC_OK;
-}
-
-int gloc_scan_store_build_normals(gloc_scan_store* st, uint32_t scan_id, uint32_t k) {
-  GLOC_REQUIRE(k >= 3 && k <= 16, GLOC_ERR_INVALID, "k = %u outside [3, 16]", k);
-  GLOC_REQUIRE(st, GLOC_ERR_INVALID, "null store");
-  GLOC_HIP(hipSetDevice(st->device));
-  std::lock_guard<std::mutex> lk(st->mu);
-  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  return store_build_normals(st, st->scans[scan_id], k);
-}
-
-int gloc_scan_store_normals(gloc_scan_store* st, uint32_t scan_id, float* out_nxyz, size_t capacity_points) {
-  GLOC_REQUIRE(st && out_nxyz, GLOC_ERR_INVALID, "null argument");
-  GLOC_HIP(hipSetDevice(st->device));
-  std::lock_guard<std::mutex> lk(st->mu);
-  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  const DevScan& s = st->scans[scan_id];
-  GLOC_REQUIRE(s.nrm_k != 0, GLOC_ERR_STATE, "scan %u has no normals: call gloc_scan_store_build_normals first", scan_id);
-  GLOC_REQUIRE(capacity_points >= s.n, GLOC_ERR_INVALID, "buffer holds %zu points, the scan has %zu", capacity_points, s.n);
-  if (s.n) {
-    hipStream_t q = st->stream;
-    const uint32_t n = (uint32_t)s.n;
-    GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
-    hipLaunchKernelGGL(normals_reorder_kernel, dim3((n + 255) / 256), dim3(256), 0, q, s.idx.pts, n, s.nrm, st->nrm_tmp.as<float>(), false);
-    GLOC_HIP(hipGetLastError());
-    GLOC_HIP(hipMemcpyAsync(out_nxyz, st->nrm_tmp.p, 12 * s.n, hipMemcpyDeviceToHost, q));
-    GLOC_HIP(hipStreamSynchronize(q));
-  }
-  return GLOC_OK;
-}
-
-int gloc_scan_store_build_fpfh(gloc_scan_store* st, uint32_t scan_id, uint32_t normal_k, uint32_t feature_k) {
-  GLOC_REQUIRE(normal_k >= 3 && normal_k <= 16, GLOC_ERR_INVALID, "normal_k = %u outside [3, 16]", normal_k);
-  GLOC_REQUIRE(feature_k >= 4 && feature_k <= 16, GLOC_ERR_INVALID, "feature_k = %u outside [4, 16]", feature_k);
-  GLOC_REQUIRE(st, GLOC_ERR_INVALID, "null store");
-  GLOC_HIP(hipSetDevice(st->device));
-  std::lock_guard<std::mutex> lk(st->mu);
-  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  return store_build_fpfh(st, st->scans[scan_id], normal_k, feature_k);
-}
-
-int gloc_scan_store_fpfh(gloc_scan_store* st, uint32_t scan_id, float* out_feat, size_t capacity_points) {
-  GLOC_REQUIRE(st && out_feat, GLOC_ERR_INVALID, "null argument");
-  GLOC_HIP(hipSetDevice(st->device));
-  std::lock_guard<std::mutex> lk(st->mu);
-  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  const DevScan& s = st->scans[scan_id];
-  GLOC_REQUIRE(s.fpfh_fk != 0, GLOC_ERR_STATE, "scan %u has no features: call gloc_scan_store_build_fpfh first", scan_id);
-  GLOC_REQUIRE(capacity_points >= s.n, GLOC_ERR_INVALID, "buffer holds %zu points, the scan has %zu", capacity_points, s.n);
-  if (s.n) {
-    hipStream_t q = st->stream;
-    GLOC_TRY(st->fpfh_tmp.ensure(132 * s.n, q));
-    GLOC_TRY(gloc::fpfh::reorder_rows(q, s.idx.pts, (uint32_t)s.n, s.fpfh, st->fpfh_tmp.as<float>(), gloc::fpfh::FEAT_DIM, false));
-    GLOC_HIP(hipMemcpyAsync(out_feat, st->fpfh_tmp.p, 132 * s.n, hipMemcpyDeviceToHost, q));
-    GLOC_HIP(hipStreamSynchronize(q));
-  }
-  return GLOC_OK;
-}
-
-int gloc_scan_store_spfh(gloc_scan_store* st, uint32_t scan_id, uint32_t feature_k, uint16_t* out_counts, uint32_t* out_used,
-                         size_t capacity_points) {
-  GLOC_REQUIRE(feature_k >= 4 && feature_k <= 16, GLOC_ERR_INVALID, "feature_k = %u outside [4, 16]", feature_k);
-  GLOC_REQUIRE(st && out_counts && out_used, GLOC_ERR_INVALID, "null argument");
-  GLOC_HIP(hipSetDevice(st->device));
-  std::lock_guard<std::mutex> lk(st->mu);
-  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  const DevScan& s = st->scans[scan_id];
-  GLOC_REQUIRE(s.nrm_k != 0, GLOC_ERR_STATE, "scan %u has no normals: call gloc_scan_store_build_normals first", scan_id);
-  GLOC_REQUIRE(capacity_points >= s.n, GLOC_ERR_INVALID, "buffer holds %zu points, the scan has %zu", capacity_points, s.n);
-  if (s.n) {
-    GLOC_TRY(store_spfh(st, s, feature_k));
-    std::vector<uint8_t> raw((size_t)gloc::fpfh::SPFH_BYTES * s.n);
-    GLOC_HIP(hipMemcpyAsync(raw.data(), st->spfh_tmp.p, raw.size(), hipMemcpyDeviceToHost, st->stream));
-    GLOC_HIP(hipStreamSynchronize(st->stream));
-    for (size_t i = 0; i < s.n; ++i) {
-      for (uint32_t b = 0; b < gloc::fpfh::FEAT_DIM; ++b) out_counts[i * gloc::fpfh::FEAT_DIM + b] = raw[i * gloc::fpfh::SPFH_BYTES + b];
-      out_used[i] = raw[i * gloc::fpfh::SPFH_BYTES + gloc::fpfh::FEAT_DIM];
-    }
-  }
-  return GLOC_OK;
-}
-
-static int check_radius(float radius, uint32_t max_nn, uint32_t lo) {
-  GLOC_REQUIRE(radius > 0.f && std::isfinite(radius), GLOC_ERR_INVALID, "radius = %g must be positive and finite", (double)radius);
-  GLOC_REQUIRE(max_nn >= lo && max_nn <= 128, GLOC_ERR_INVALID, "max_nn = %u outside [%u, 128]", max_nn, lo);
-  return GLOC_OK;
-}
-
-int gloc_scan_store_radius_neighbors(gloc_scan_store* st, uint32_t scan_id, float radius, uint32_t max_nn, uint32_t* out_idx, float* out_d2,
-                                     uint32_t* out_count, size_t capacity_points) {
-  GLOC_TRY(check_radius(radius, max_nn, 1));
-  GLOC_REQUIRE(st, GLOC_ERR_INVALID, "null store");
-  GLOC_HIP(hipSetDevice(st->device));
-  std::lock_guard<std::mutex> lk(st->mu);
-  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  const DevScan& s = st->scans[scan_id];
-  GLOC_REQUIRE(capacity_points >= s.n, GLOC_ERR_INVALID, "buffers hold %zu points, the scan has %zu", capacity_points, s.n);
-  if (s.n) {
-    hipStream_t q = st->stream;
-    GLOC_TRY(gloc::ground::scan_radius(q, st->nrm_ws, s.idx.pts, (uint32_t)s.n, radius, max_nn));
-    const size_t e = s.n * (size_t)max_nn;
-    if (out_idx) GLOC_HIP(hipMemcpyAsync(out_idx, st->nrm_ws.knn_idx.p, sizeof(uint32_t) * e, hipMemcpyDeviceToHost, q));
-    if (out_d2) GLOC_HIP(hipMemcpyAsync(out_d2, st->nrm_ws.knn_d2.p, sizeof(float) * e, hipMemcpyDeviceToHost, q));
-    if (out_count) GLOC_HIP(hipMemcpyAsync(out_count, st->nrm_ws.knn_cnt.p, sizeof(uint32_t) * s.n, hipMemcpyDeviceToHost, q));
-    GLOC_HIP(hipStreamSynchronize(q));
-  }
-  return GLOC_OK;
-}
-
-int gloc_scan_store_build_normals_radius(gloc_scan_store* st, uint32_t scan_id, float radius, uint32_t max_nn, uint32_t min_nn) {
-  GLOC_REQUIRE(radius > 0.f && std::isfinite(radius), GLOC_ERR_INVALID, "radius = %g must be positive and finite", (double)radius);
-  GLOC_REQUIRE(min_nn >= 4 && min_nn <= max_nn, GLOC_ERR_INVALID, "min_nn = %u outside [4, max_nn = %u]", min_nn, max_nn);
-  GLOC_REQUIRE(max_nn <= 128, GLOC_ERR_INVALID, "max_nn = %u outside [min_nn, 128]", max_nn);
-  GLOC_REQUIRE(st, GLOC_ERR_INVALID, "null store");
-  GLOC_HIP(hipSetDevice(st->device));
-  std::lock_guard<std::mutex> lk(st->mu);
-  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  return store_build_normals_radius(st, st->scans[scan_id], RadiusSupport{radius, max_nn, min_nn});
-}
-
-int gloc_scan_store_build_fpfh_radius(gloc_scan_store* st, uint32_t scan_id, const gloc_fpfh_radius_params* prm) {
-  GLOC_TRY(gloc::fpfh::check_radius_params(prm));
-  GLOC_REQUIRE(st, GLOC_ERR_INVALID, "null store");
-  GLOC_HIP(hipSetDevice(st->device));
-  std::lock_guard<std::mutex> lk(st->mu);
-  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  return store_build_fpfh_radius(st, st->scans[scan_id], *prm);
-}
-
-int gloc_scan_store_spfh_radius(gloc_scan_store* st, uint32_t scan_id, float radius, uint32_t max_nn, uint16_t* out_counts,
-                                uint32_t* out_used, size_t capacity_points) {
-  GLOC_TRY(check_radius(radius, max_nn, 4));
-  GLOC_REQUIRE(st && out_counts && out_used, GLOC_ERR_INVALID, "null argument");
-  GLOC_HIP(hipSetDevice(st->device));
-  std::lock_guard<std::mutex> lk(st->mu);
-  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
-  const DevScan& s = st->scans[scan_id];
-  GLOC_REQUIRE(s.nrm_k != 0, GLOC_ERR_STATE, "scan %u has no normals: call gloc_scan_store_build_normals_radius first", scan_id);
-  GLOC_REQUIRE(capacity_points >= s.n, GLOC_ERR_INVALID, "buffer holds %zu points, the scan has %zu", capacity_points, s.n);
-  if (s.n) {
-    GLOC_TRY(store_spfh_radius(st, s, radius, max_nn));
-    std::vector<uint8_t> raw((size_t)gloc::fpfh::SPFH_BYTES * s.n);
-    GLOC_HIP(hipMemcpyAsync(raw.data(), st->spfh_tmp.p, raw.size(), hipMemcpyDeviceToHost, st->stream));
-    GLOC_HIP(hipStreamSynchronize(st->stream));
-    for (size_t i = 0; i < s.n; ++i) {
-      for (uint32_t b = 0; b < gloc::fpfh::FEAT_DIM; ++b) out_counts[i * gloc::fpfh::FEAT_DIM + b] = raw[i * gloc::fpfh::SPFH_BYTES + b];
-      out_used[i] = raw[i * gloc::fpfh::SPFH_BYTES + gloc::fpfh::FEAT_DIM];
-    }
   }
   return GLOC_OK;
 }

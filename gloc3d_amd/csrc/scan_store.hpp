@@ -1,5 +1,6 @@
 // scan_store.hpp -- host-side view of the resident scan store (gloc_scan_store of include/gloc3d.h),
-// shared by scan_store.hip (which owns it) and reg.hip (whose registration handles read it).
+// shared by scan_store.hip (which owns it and indexes the scans), scan_features.hip (which gives the scans their normals
+// and features) and reg.hip (whose registration handles read it).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -10,15 +11,6 @@
 #include "common.hpp"
 #include "ground_normals.hpp"
 #include "scan_index.hpp"
-
-// The metric support a scan's normals or features were built from (gloc_fpfh_radius_params): every neighbour within r,
-// the max_nn nearest of them, no normal below min_nn (0 for features).
-struct RadiusSupport {
-  float r = 0.f;
-  uint32_t max_nn = 0, min_nn = 0;
-  bool operator==(const RadiusSupport& o) const { return r == o.r && max_nn == o.max_nn && min_nn == o.min_nn; }
-};
-constexpr uint32_t SUPPORT_BY_RADIUS = 0xFFFFFFFFu;  // in the place of a k: the support is the RadiusSupport beside it
 
 // A scan resident in HBM: original-order xyz plus its search index (Hilbert-sorted copy with the
 // original indices, boxes, sorted keys, inverse permutation, launch order).  ONE allocation per scan.
@@ -43,23 +35,18 @@ struct DevScan {
   }
   // Per-point normals (gloc_scan_store_build_normals), an OPTIONAL SECOND allocation of 12 B per point: packed xyz in the
   // order of idx.pts -- the order the 1-NN search reports its matches in -- so that a correspondence reads its normal at
-  // the index it got.  Built once per (scan, k); re-ordered with the points by the kd re-sort; zero = no normal.
+  // the index it got.  Built once per (scan, support); re-ordered with the points by the kd re-sort; zero = no normal.
   float* nrm = nullptr;
-  uint32_t nrm_k = 0;  // the k they were built with (0: none; SUPPORT_BY_RADIUS: nrm_rad)
-  RadiusSupport nrm_rad{};
+  gloc::Support nrm_sup;  // what they were built from (none: no normals)
   size_t nrm_bytes() const { return nrm ? 12 * n : 0; }
   // FPFH features (gloc_scan_store_build_fpfh), an OPTIONAL THIRD allocation of 132 B per point: rows of 33 floats in the
-  // order of idx.pts, as the normals are, and re-ordered with them.  Built once per (scan, normal_k, feature_k); valid for
-  // the normals they were built from only (fpfh_nk = that nrm_k); the zero row = no feature.
+  // order of idx.pts, as the normals are, and re-ordered with them.  Built once per (scan, normals' support, features'
+  // support); valid for the normals they were built from only (fpfh_nsup = that nrm_sup); the zero row = no feature.
   float* fpfh = nullptr;
-  uint32_t fpfh_nk = 0, fpfh_fk = 0;  // the k's they were built with (0: none; both SUPPORT_BY_RADIUS: fpfh_nrad, fpfh_rad)
-  RadiusSupport fpfh_nrad{}, fpfh_rad{};
+  gloc::Support fpfh_nsup, fpfh_fsup;  // the supports of the normals they were built on and of their own lists (none: no features)
   size_t fpfh_bytes() const { return fpfh ? 132 * n : 0; }
-  bool has_fpfh(uint32_t nk, uint32_t fk) const { return fpfh_fk == fk && fpfh_nk == nk && nrm_k == nk; }  // (k's: never the radius tag)
-  bool has_normals_radius(const RadiusSupport& ns) const { return nrm_k == SUPPORT_BY_RADIUS && nrm_rad == ns; }
-  bool has_fpfh_radius(const RadiusSupport& ns, const RadiusSupport& fs) const {
-    return fpfh_fk == SUPPORT_BY_RADIUS && fpfh_nk == SUPPORT_BY_RADIUS && fpfh_nrad == ns && fpfh_rad == fs && has_normals_radius(ns);
-  }
+  bool has_normals(const gloc::Support& ns) const { return nrm_sup == ns; }
+  bool has_fpfh(const gloc::Support& ns, const gloc::Support& fs) const { return fpfh_nsup == ns && fpfh_fsup == fs && nrm_sup == ns; }
   bool live = false;
   bool kd = false;  // the index is in kd order (target index)
   int pins = 0;     // batches in flight (gloc_reg_batch_multi_begin .. _end) whose jobs hold a by-value view of THIS scan:
@@ -131,27 +118,24 @@ int store_get(gloc_scan_store* st, uint32_t id, int cs, DevScan* out);
 // pins nothing.  ids may repeat (pins are counted).  gloc_scan_store_build_target_index refuses a pinned scan that still
 // needs the re-sort, gloc_scan_store_release refuses any pinned scan.
 int store_get_pinned(gloc_scan_store* st, const uint32_t* ids, const int* cs, size_t count, DevScan* out);
-// Give a scan its normals from k neighbours (no-op when it has them with this k).  Caller holds store->mu; returns after
-// the work has completed.  Adds an allocation and moves nothing: safe on a pinned scan, except that normals a batch may
-// be reading are not rebuilt with another k (GLOC_ERR_STATE).
-int store_build_normals(gloc_scan_store* st, DevScan& s, uint32_t k);
-// Give a scan its FPFH features from feature_k neighbours and normals of normal_k (built or rebuilt first when the scan's
-// differ: store_build_normals and its rule); no-op when it has them with these k's.  Caller holds store->mu; returns after
-// the work has completed.  Features a batch may be reading are not rebuilt (GLOC_ERR_STATE).
-int store_build_fpfh(gloc_scan_store* st, DevScan& s, uint32_t normal_k, uint32_t feature_k);
+// Give a scan its normals from the support ns (no-op when it has them from it).  Caller holds store->mu; returns after the
+// work has completed.  Adds an allocation and moves nothing: safe on a pinned scan, except that normals a batch may be
+// reading are not rebuilt from another support (GLOC_ERR_STATE).  One set of normals and one of features per scan,
+// whichever support they were built from.
+int store_build_normals(gloc_scan_store* st, DevScan& s, const Support& ns);
+// Give a scan its FPFH features from the support fs and normals of ns (built or rebuilt first when the scan's differ:
+// store_build_normals and its rule); no-op when it has them from these two.  Caller holds store->mu; returns after the
+// work has completed.  Features a batch may be reading are not rebuilt (GLOC_ERR_STATE).
+int store_build_fpfh(gloc_scan_store* st, DevScan& s, const Support& ns, const Support& fs);
 // ... for a list of ids (takes store->mu).  GLOC_ERR_INVALID for an unknown id.
-int store_ensure_fpfh(gloc_scan_store* st, const uint32_t* ids, size_t n, uint32_t normal_k, uint32_t feature_k);
-// The same three for a metric support (gloc_fpfh_radius_params; include/gloc3d.h R1 - R3), under the same rules: one set of
-// normals and one of features per scan, whichever support they were built from.
-int store_build_normals_radius(gloc_scan_store* st, DevScan& s, const RadiusSupport& ns);
-int store_build_fpfh_radius(gloc_scan_store* st, DevScan& s, const gloc_fpfh_radius_params& prm);
-int store_ensure_fpfh_radius(gloc_scan_store* st, const uint32_t* ids, size_t n, const gloc_fpfh_radius_params& prm);
-inline RadiusSupport normal_support(const gloc_fpfh_radius_params& p) { return RadiusSupport{p.normal_radius, p.normal_max_nn, p.normal_min_nn}; }
-inline RadiusSupport feature_support(const gloc_fpfh_radius_params& p) { return RadiusSupport{p.feature_radius, p.feature_max_nn, 0u}; }
+int store_ensure_fpfh(gloc_scan_store* st, const uint32_t* ids, size_t n, const Support& ns, const Support& fs);
+// A scan's normals between original order and the order of its sorted points (`pts`, n of them): what the builders, the
+// downloads and the target-index re-sort, which moves the points under them, all go through.  Enqueued on q.
+int store_reorder_normals(hipStream_t q, const f32x4* pts, uint32_t n, const float* in, float* out, bool to_sorted);
 // The pins' release (delta = -1) once the batch's event has been waited for.  Ids no longer live are skipped.
 void store_pin(gloc_scan_store* st, const uint32_t* ids, size_t count, int delta);
-// Scans without normals get them from k neighbours (takes store->mu; an allocation beside the scan: nothing a batch in
-// flight reads moves).  GLOC_ERR_INVALID for an unknown id.
+// Scans without normals get them from k neighbours -- normals from any other support are used as they are (takes
+// store->mu; an allocation beside the scan: nothing a batch in flight reads moves).  GLOC_ERR_INVALID for an unknown id.
 int store_ensure_normals(gloc_scan_store* st, const uint32_t* ids, size_t n, uint32_t k);
 
 // The scans of a synchronous call, pinned for as long as the holder lives: pin() is store_get_pinned (cs null: no launch

@@ -150,6 +150,49 @@ def test_k_then_radius_then_k_each_equals_a_fresh_scan(env, oracle_mod):
         store.release(s)
 
 
+def test_normals_alone_k_radius_k_radius_each_equal_a_fresh_scan(env):
+    """The normals-only transitions: k -> radius -> k -> the radius with another min_nn on one scan.  After each step the
+    normals are, bit for bit, those of a fresh scan built directly from that support (which the tests above tie to the
+    restatement), in the allocation the first step made; the features asked for afterwards are the fresh k scan's.  An
+    empty scan takes the same calls and allocates nothing."""
+    store = env["store"]
+    xyz = RK.cloud("a_vox")
+    nr, _, nmax, _, nmin = RK.S_A
+    steps = [("k", 10), ("radius", nmin), ("k", 10), ("radius", nmin + 3)]
+
+    def build(s, step):
+        if step[0] == "k":
+            store.build_normals(s, step[1])
+        else:
+            store.build_normals_radius(s, nr, nmax, step[1])
+
+    fresh = {}
+    for step in steps[1:]:
+        fresh[step] = store.add(xyz)
+        build(fresh[step], step)
+    want = {step: store.normals(f) for step, f in fresh.items()}
+    differ = [(bits(want[a]) != bits(want[b])).any() for a, b in ((steps[0], steps[1]), (steps[0], steps[3]), (steps[1], steps[3]))]
+    print("points", len(xyz), "the three supports give three sets of normals", differ)
+    assert all(differ)
+    store.build_fpfh(fresh[steps[0]], 10, 16)
+    fk = store.fpfh(fresh[steps[0]])
+    sid, empty = store.add(xyz), store.add(RK.cloud("empty"))
+    before = store.bytes()[0]
+    for step in steps:
+        build(sid, step)
+        build(empty, step)
+        assert store.bytes()[0] == before + 12 * len(xyz)
+        assert (bits(store.normals(sid)) == bits(want[step])).all(), step
+        assert store.normals(empty).shape == (0, 3)
+    store.build_fpfh(sid, 10, 16)
+    store.build_fpfh(empty, 10, 16)
+    assert store.bytes()[0] == before + (12 + 132) * len(xyz)
+    assert (bits(store.fpfh(sid)) == bits(fk)).all() and (bits(store.normals(sid)) == bits(want[steps[0]])).all()
+    assert store.fpfh(empty).shape == (0, 33)
+    for s in [sid, empty] + list(fresh.values()):
+        store.release(s)
+
+
 def test_features_follow_the_target_index_with_their_tags(env):
     store, capi = env["store"], env["capi"]
     prm = _sup(capi, "S_RAW")

@@ -101,6 +101,11 @@ class FpfhRadiusParams(C.Structure):
                 ("feature_radius", C.c_float), ("feature_max_nn", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class IssParams(C.Structure):
+    _fields_ = [("salient_radius", C.c_float), ("max_nn", C.c_uint32), ("min_nn", C.c_uint32), ("non_max_radius", C.c_float),
+                ("gamma_21", C.c_float), ("gamma_32", C.c_float)]
+
+
 FPFH_DIM = 33          # floats per feature row
 FPFH_MATCH_TILE = 128  # target rows per tile of the matcher (csrc/fpfh.hpp MATCH_TILE_ROWS)
 
@@ -278,6 +283,16 @@ _PROTOS = [
     ("gloc_scan_store_spfh_radius", _i, [_vp, _u32, C.c_float, _u32, _vp, _vp, _sz]),
     ("gloc_reg_fpfh_batch_ids_radius", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FpfhParams), C.POINTER(FpfhRadiusParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_fpfh_graph_batch_ids_radius", _i, [_vp, _u32, _vp, _sz, C.POINTER(FpfhGraphParams), C.POINTER(FpfhRadiusParams), _vp, _vp, _vp, _vp]),
+    ("gloc_iss_default_params", None, [C.POINTER(IssParams)]),
+    ("gloc_scan_store_iss_saliency", _i, [_vp, _u32, C.POINTER(IssParams), _vp, _vp, _sz]),
+    ("gloc_scan_store_build_keypoints", _i, [_vp, _u32, C.POINTER(IssParams)]),
+    ("gloc_scan_store_keypoint_count", _i, [_vp, _u32, C.POINTER(C.c_size_t)]),
+    ("gloc_scan_store_keypoints", _i, [_vp, _u32, _vp, _sz]),
+    ("gloc_scan_store_keypoint_fpfh", _i, [_vp, _u32, _vp, _sz]),
+    ("gloc_reg_fpfh_batch_ids_keypoints", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FpfhParams), C.POINTER(FpfhRadiusParams), C.POINTER(IssParams),
+                                           _vp, _vp, _vp, _vp]),
+    ("gloc_reg_fpfh_graph_batch_ids_keypoints", _i, [_vp, _u32, _vp, _sz, C.POINTER(FpfhGraphParams), C.POINTER(FpfhRadiusParams),
+                                                 C.POINTER(IssParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
@@ -736,6 +751,16 @@ def default_fpfh_radius_params(**over):
     return p
 
 
+def default_iss_params(**over):
+    """gloc_iss_params as gloc_iss_default_params leaves them (saliency from 128 neighbours within 3.0 m, at least 5;
+    suppression within 2.0 m; both eigenvalue ratios below 0.975), then `over`."""
+    p = IssParams()
+    lib().gloc_iss_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
 class ScanStore(_Handle):
     """Resident scans + their search index, shared by any number of Registrars."""
 
@@ -932,6 +957,37 @@ class ScanStore(_Handle):
     def spfh_radius(self, scan_id, radius=2.5, max_nn=100):
         """Diagnostic: spfh() over the radius list of (radius, max_nn)."""
         return self._spfh(lib().gloc_scan_store_spfh_radius, scan_id, float(radius), int(max_nn))
+
+    def iss_saliency(self, scan_id, params=None):
+        """Diagnostic: the ISS saliency [n] float32 (0: not salient) and the sorted covariance eigenvalues [n, 3] float64 of
+        every point (gloc_scan_store_iss_saliency), in original order; nothing is kept."""
+        prm = params or default_iss_params()
+        n = self.points(scan_id)
+        sal, eig = np.empty(n, np.float32), np.empty((n, 3), np.float64)
+        check(lib().gloc_scan_store_iss_saliency(self._h, int(scan_id), C.byref(prm), _np_ptr(sal), _np_ptr(eig), n))
+        return sal, eig
+
+    def build_keypoints(self, scan_id, params=None):
+        """Give a resident scan its ISS keypoints (gloc_scan_store_build_keypoints; default_iss_params when None)."""
+        prm = params or default_iss_params()
+        check(lib().gloc_scan_store_build_keypoints(self._h, int(scan_id), C.byref(prm)))
+
+    def keypoints(self, scan_id):
+        """The scan's keypoints [K] uint32: original indices in ascending order (gloc_scan_store_keypoints)."""
+        k = C.c_size_t(0)
+        check(lib().gloc_scan_store_keypoint_count(self._h, int(scan_id), C.byref(k)))
+        out = np.empty(k.value, np.uint32)
+        check(lib().gloc_scan_store_keypoints(self._h, int(scan_id), _np_ptr(out) if k.value else None, k.value))
+        return out
+
+    def keypoint_fpfh(self, scan_id):
+        """Diagnostic: the keypoints' feature rows [K, 33] float32 as the keypoint matcher reads them
+        (gloc_scan_store_keypoint_fpfh)."""
+        k = C.c_size_t(0)
+        check(lib().gloc_scan_store_keypoint_count(self._h, int(scan_id), C.byref(k)))
+        out = np.empty((k.value, FPFH_DIM), np.float32)
+        check(lib().gloc_scan_store_keypoint_fpfh(self._h, int(scan_id), _np_ptr(out) if k.value else None, k.value))
+        return out
 
 
 class Registrar(_Handle):
@@ -1130,35 +1186,41 @@ class Registrar(_Handle):
                                         _np_ptr(d2) if d2.size else None))
         return idx, d2
 
-    def _fpfh_jobs(self, entry, src_id, ids, blocks, support):
+    def _fpfh_jobs(self, entry, src_id, ids, blocks, support, keypoints=None):
         """What fpfh_batch and fpfh_graph_batch share: entry(handle, source, targets, n, *blocks, T, inliers, n_pairs, ok), or
-        its _radius form with the support block behind the others."""
+        its _radius form with the support block behind the others, or its _keypoints form with the support block (or null)
+        and the keypoint block behind them."""
         n = ids.shape[0]
         T = np.empty((n, 4, 4), np.float32)
         inl, npairs, ok = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.int32)
-        fn = getattr(lib(), entry if support is None else entry + "_radius")
-        blocks = blocks if support is None else blocks + [C.byref(support)]
+        if keypoints is not None:
+            fn = getattr(lib(), entry + "_keypoints")
+            blocks = blocks + [None if support is None else C.byref(support), C.byref(keypoints)]
+        else:
+            fn = getattr(lib(), entry if support is None else entry + "_radius")
+            blocks = blocks if support is None else blocks + [C.byref(support)]
         check(fn(self._h, int(src_id), _np_ptr(ids), n, *blocks, _np_ptr(T), _np_ptr(inl), _np_ptr(npairs), _np_ptr(ok)))
         return dict(T=T, inliers=inl, n_pairs=npairs, ok=ok.astype(bool))
 
-    def fpfh_batch(self, src_id, tgt_ids, stream_ids=None, params=None, support=None):
+    def fpfh_batch(self, src_id, tgt_ids, stream_ids=None, params=None, support=None, keypoints=None):
         """Feature-based global registration of scan src_id against each of tgt_ids (gloc_reg_fpfh_batch_ids), no initial
         guess: returns dict(T [n, 4, 4] float32 source -> target, inliers [n], n_pairs [n], ok [n] bool).  T is a start for
         p2l_batch / gicp_batch / batch_ids(init_T=...), not a refined pose.  support: a FpfhRadiusParams -- features over
-        that metric support (gloc_reg_fpfh_batch_ids_radius) instead of the k-NN lists of params."""
+        that metric support (gloc_reg_fpfh_batch_ids_radius) instead of the k-NN lists of params.  keypoints: an IssParams --
+        match the scans' ISS keypoints alone (gloc_reg_fpfh_batch_ids_keypoints); None: every point, today's calls."""
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
         prm = params or default_fpfh_params()
         sid = None if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32).reshape(ids.shape[0])
-        return self._fpfh_jobs("gloc_reg_fpfh_batch_ids", src_id, ids, [None if sid is None else _np_ptr(sid), C.byref(prm)], support)
+        return self._fpfh_jobs("gloc_reg_fpfh_batch_ids", src_id, ids, [None if sid is None else _np_ptr(sid), C.byref(prm)], support, keypoints)
 
-    def fpfh_graph_batch(self, src_id, tgt_ids, params=None, support=None):
+    def fpfh_graph_batch(self, src_id, tgt_ids, params=None, support=None, keypoints=None):
         """Feature-based global registration through the correspondence graph (gloc_reg_fpfh_graph_batch_ids): the matches of
         fpfh_batch, the pose from their second-order compatibility instead of RANSAC.  Returns dict(T [n, 4, 4] float32
         source -> target, inliers [n], n_pairs [n], ok [n] bool); T is a start for a refinement, as fpfh_batch's.  support: as
-        fpfh_batch's (gloc_reg_fpfh_graph_batch_ids_radius)."""
+        fpfh_batch's (gloc_reg_fpfh_graph_batch_ids_radius); keypoints: as fpfh_batch's (gloc_reg_fpfh_graph_batch_ids_keypoints)."""
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
         prm = params or default_fpfh_graph_params()
-        return self._fpfh_jobs("gloc_reg_fpfh_graph_batch_ids", src_id, ids, [C.byref(prm)], support)
+        return self._fpfh_jobs("gloc_reg_fpfh_graph_batch_ids", src_id, ids, [C.byref(prm)], support, keypoints)
 
     def pair_graph(self, P, Q, params=None):
         """The correspondence graph of a pair list P, Q [m, 3] (gloc_reg_pair_graph): dict(degree [m] uint32, score [m] uint64,

@@ -29,6 +29,10 @@ struct PairJob {
   const float* src_xyz;
   const float* tgt_xyz;
   uint32_t n_src, n_tgt;
+  // keypoint-restricted matching (I4): the keys are by keypoint RANK, and these lists turn a rank into the original index
+  // whose xyz is fetched (null: the keys are by original index already)
+  const uint32_t* src_map = nullptr;
+  const uint32_t* tgt_map = nullptr;
 };
 
 struct Ws {  // a registration handle's workspace, made on first use

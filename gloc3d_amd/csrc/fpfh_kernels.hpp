@@ -297,7 +297,8 @@ __global__ __launch_bounds__(MATCH_THREADS) void fpfh_match_kernel(const MatchTa
 }
 
 // A job of F4: the forward keys of the source's rows, the backward keys of the target's (null: not mutual), the scans'
-// points in original order (packed xyz).
+// points in original order (packed xyz); for a job on keypoints the rows are keypoint ranks and src_map / tgt_map the
+// keypoints' original indices.
 
 // F4.  One work-group per job; pairs[(job * ld + m) * 2 + {0, 1}] = (source point, matched target point) of the m-th kept
 // source in ascending original index; the count goes to counts[job].
@@ -331,8 +332,9 @@ __global__ __launch_bounds__(1024) void fpfh_pairs_kernel(const PairJob* __restr
     }
     if (keep) {
       const size_t slot = (size_t)job * ld + off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      pairs[slot * 2 + 0] = f32x4{J.src_xyz[3 * (size_t)i], J.src_xyz[3 * (size_t)i + 1], J.src_xyz[3 * (size_t)i + 2], 0.f};
-      pairs[slot * 2 + 1] = f32x4{J.tgt_xyz[3 * (size_t)j], J.tgt_xyz[3 * (size_t)j + 1], J.tgt_xyz[3 * (size_t)j + 2], 0.f};
+      const size_t pi = J.src_map ? J.src_map[i] : i, qj = J.tgt_map ? J.tgt_map[j] : j;  // (keypoint rank -> original index)
+      pairs[slot * 2 + 0] = f32x4{J.src_xyz[3 * pi], J.src_xyz[3 * pi + 1], J.src_xyz[3 * pi + 2], 0.f};
+      pairs[slot * 2 + 1] = f32x4{J.tgt_xyz[3 * qj], J.tgt_xyz[3 * qj + 1], J.tgt_xyz[3 * qj + 2], 0.f};
     }
     __syncthreads();
     if (tid == 0) base_s += tot;

@@ -328,6 +328,8 @@ int check_support(const Support& s, SupportOf what, const SupportNames& nm) {
 
 namespace ground {
 
+static_assert(KCH == LIST_CHUNK, "the lists' chunks are the ones ground_normals.hpp announces");
+
 __global__ __launch_bounds__(256) void unsort_f4_kernel(const f32x4* __restrict__ spts, uint32_t m, f32x4* __restrict__ pts) {
   const uint32_t s = blockIdx.x * 256 + threadIdx.x;
   if (s >= m) return;

@@ -37,6 +37,10 @@ int check_support(const Support& s, SupportOf what, const SupportNames& names);
 
 namespace ground {
 
+// scan_lists cuts the sorted points into chunks of this many and leaves one box per chunk in cbox_lo / cbox_hi (corners):
+// what a kernel that sweeps the same chunks after it (iss_kernels.hpp) goes by.
+constexpr int LIST_CHUNK = 64;
+
 struct NormalsScratch {
   DevBuf pts, knn_idx, knn_d2, knn_cnt, cbox_lo, cbox_hi, bins, hist;
 };

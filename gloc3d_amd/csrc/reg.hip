@@ -942,6 +942,7 @@ struct FpfhFront {
   uint32_t mutual, n_hyp;
   bool adaptive;
   float min_inlier_ratio;
+  const gloc_iss_params* iss = nullptr;  // match the scans' keypoints of these parameters alone (I4); null: every point
 };
 
 // stage(bd, v, nblocks, m_max): the launches from the pairs in v.pairs (M of job c in jobs[c].n_src; none above m_max) to
@@ -957,13 +958,23 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
   ids[0] = src_id;
   std::copy(tgt_ids, tgt_ids + n, ids.begin() + 1);
   GLOC_TRY(store_ensure_fpfh(st, ids.data(), ids.size(), prm->normal, prm->feature));
+  if (prm->iss) GLOC_TRY(store_ensure_keypoints(st, ids.data(), ids.size(), *prm->iss));
   ScopedPins pins(st, s);
   GLOC_TRY(pins.pin(ids.data(), nullptr, ids.size()));
   const std::vector<DevScan>& scans = pins.scans;
   const DevScan& src = scans[0];
   GLOC_REQUIRE(src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is too large");
-  for (const DevScan& sc : scans)
+  for (const DevScan& sc : scans) {
     GLOC_REQUIRE(sc.n == 0 || (sc.fpfh && sc.has_fpfh(prm->normal, prm->feature)), GLOC_ERR_STATE, "a scan lost its features during the call");
+    GLOC_REQUIRE(!prm->iss || (sc.has_keypoints(*prm->iss) && (sc.kp_n == 0 || (sc.kp && sc.kp_feat))), GLOC_ERR_STATE,
+                 "a scan lost its keypoints during the call");
+  }
+  // On keypoints the searches run in RANK space: the rows are the scans' gathered tables, already in ascending original
+  // index, so a row's number is its rank, the smaller rank is the smaller original index (F3's tie rule as it stands), and
+  // the compaction turns ranks into points through the keypoint lists.
+  const bool on_kp = prm->iss != nullptr;
+  auto rows_of = [&](const DevScan& sc) { return on_kp ? sc.kp_n : sc.n; };
+  const size_t src_rows = rows_of(src);
   const uint32_t n_jobs = (uint32_t)n;
   const bool mutual = prm->mutual != 0;
   for (uint32_t c = 0; c < n_jobs; ++c) {
@@ -972,15 +983,15 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
     if (out_n_pairs) out_n_pairs[c] = 0;
     if (out_ok) out_ok[c] = 0;
   }
-  if (src.n < 3) return GLOC_OK;  // fewer than three pairs whatever matches
+  if (src_rows < 3) return GLOC_OK;  // fewer than three pairs whatever matches
   GLOC_TRY(ensure_ws(&h->fpfh));
   gloc::fpfh::Ws& w = *h->fpfh;
   // keys: [job][src.n] forward, then each job's backward row of its target's length
   std::vector<size_t> back_off(n_jobs, 0);
-  size_t n_keys = (size_t)n_jobs * src.n;
+  size_t n_keys = (size_t)n_jobs * src_rows;
   for (uint32_t c = 0; c < n_jobs && mutual; ++c) {
     back_off[c] = n_keys;
-    n_keys += scans[1 + c].n;
+    n_keys += rows_of(scans[1 + c]);
   }
   GLOC_TRY(w.keys.ensure(sizeof(unsigned long long) * n_keys, s));
   GLOC_HIP(hipMemsetAsync(w.keys.p, 0xFF, sizeof(unsigned long long) * n_keys, s));
@@ -989,8 +1000,16 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
   std::vector<gloc::fpfh::PairJob> pj(n_jobs);
   for (uint32_t c = 0; c < n_jobs; ++c) {
     const DevScan& t = scans[1 + c];
-    unsigned long long* fwd = keys + (size_t)c * src.n;
+    unsigned long long* fwd = keys + (size_t)c * src_rows;
     unsigned long long* bwd = mutual ? keys + back_off[c] : nullptr;
+    if (on_kp) {
+      if (t.kp_n) {
+        tasks.push_back(gloc::fpfh::MatchTask{src.kp_feat, nullptr, t.kp_feat, nullptr, fwd, (uint32_t)src.kp_n, (uint32_t)t.kp_n});
+        if (mutual) tasks.push_back(gloc::fpfh::MatchTask{t.kp_feat, nullptr, src.kp_feat, nullptr, bwd, (uint32_t)t.kp_n, (uint32_t)src.kp_n});
+      }
+      pj[c] = gloc::fpfh::PairJob{fwd, bwd, src.xyz, t.xyz, (uint32_t)src.kp_n, (uint32_t)t.kp_n, src.kp, t.kp};
+      continue;
+    }
     if (t.n) {
       tasks.push_back(gloc::fpfh::MatchTask{src.fpfh, src.idx.pts, t.fpfh, t.idx.pts, fwd, (uint32_t)src.n, (uint32_t)t.n});
       if (mutual) tasks.push_back(gloc::fpfh::MatchTask{t.fpfh, t.idx.pts, src.fpfh, src.idx.pts, bwd, (uint32_t)t.n, (uint32_t)src.n});
@@ -998,7 +1017,7 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
     pj[c] = gloc::fpfh::PairJob{fwd, bwd, src.xyz, t.xyz, (uint32_t)src.n, (uint32_t)t.n};
   }
   Batch b;
-  GLOC_TRY(open_batch(h, BatchSpec::on_pairs(n_jobs, src.n, prm->n_hyp, !prm->adaptive), &b, [&](Job* jd, CandState* cst) {
+  GLOC_TRY(open_batch(h, BatchSpec::on_pairs(n_jobs, src_rows, prm->n_hyp, !prm->adaptive), &b, [&](Job* jd, CandState* cst) {
     for (uint32_t c = 0; c < n_jobs; ++c) {
       jd[c] = Job{nullptr, nullptr, nullptr, nullptr, ScanIndexDev{}, 0u, 0u, stream_ids ? stream_ids[c] : c, 0u};
       init_state(cst[c], nullptr, prm->n_hyp);
@@ -1039,9 +1058,10 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
 }
 
 int run_fpfh(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const uint32_t* stream_ids, const gloc_fpfh_params* prm,
-             const Support& normal, const Support& feature, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+             const Support& normal, const Support& feature, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok,
+             const gloc_iss_params* iss = nullptr) {
   const FpfhFront f{normal, feature, prm->mutual, prm->ransac_iters, prm->ransac_confidence > 0.f && prm->ransac_confidence < 1.f,
-                    prm->min_inlier_ratio};
+                    prm->min_inlier_ratio, iss};
   return run_fpfh_pairs(h, src_id, tgt_ids, n, stream_ids, &f, out_T, out_inliers, out_n_pairs, out_ok,
                         [&](const BatchDims& bd, const WsView& v, uint32_t nblocks, uint32_t) {
                           return enqueue_ransac(h, bd, RansacRule{prm->ransac_iters, prm->inlier_thresh, prm->min_inlier_ratio,
@@ -1101,8 +1121,9 @@ int enqueue_graph(gloc_reg* h, const BatchDims& bd, const gloc_fpfh_graph_params
 }
 
 int run_fpfh_graph(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const gloc_fpfh_graph_params* prm,
-                   const Support& normal, const Support& feature, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
-  const FpfhFront f{normal, feature, prm->mutual, prm->n_seeds, true, prm->min_inlier_ratio};
+                   const Support& normal, const Support& feature, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok,
+                   const gloc_iss_params* iss = nullptr) {
+  const FpfhFront f{normal, feature, prm->mutual, prm->n_seeds, true, prm->min_inlier_ratio, iss};
   return run_fpfh_pairs(h, src_id, tgt_ids, n, nullptr, &f, out_T, out_inliers, out_n_pairs, out_ok,
                         [&](const BatchDims& bd, const WsView& v, uint32_t nblocks, uint32_t m_max) {
                           return enqueue_graph(h, bd, prm, v, h->fpfh->counts.as<uint32_t>(), nblocks, m_max);
@@ -1855,6 +1876,35 @@ int gloc_reg_fpfh_graph_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, cons
   GLOC_HIP(hipSetDevice(h->device));
   return run_fpfh_graph(h, src_scan_id, tgt_scan_ids, n, prm, Support::normals_of(*support), Support::features_of(*support), out_T,
                         out_inliers, out_n_pairs, out_ok);
+}
+
+// (support == NULL: the k-mode features of prm)
+int gloc_reg_fpfh_batch_ids_keypoints(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
+                                      const gloc_fpfh_params* prm, const gloc_fpfh_radius_params* support, const gloc_iss_params* iss,
+                                      float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+  GLOC_TRY(gloc::fpfh::check_params(prm));
+  if (support) GLOC_TRY(gloc::fpfh::check_radius_params(support));
+  GLOC_TRY(check_iss_params(iss));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_fpfh(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, support ? Support::normals_of(*support) : Support::nearest(prm->normal_k),
+                  support ? Support::features_of(*support) : Support::nearest(prm->feature_k), out_T, out_inliers, out_n_pairs, out_ok, iss);
+}
+
+int gloc_reg_fpfh_graph_batch_ids_keypoints(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n,
+                                            const gloc_fpfh_graph_params* prm, const gloc_fpfh_radius_params* support,
+                                            const gloc_iss_params* iss, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs,
+                                            int* out_ok) {
+  GLOC_TRY(gloc::pairgraph::check_params(prm));
+  if (support) GLOC_TRY(gloc::fpfh::check_radius_params(support));
+  GLOC_TRY(check_iss_params(iss));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_fpfh_graph(h, src_scan_id, tgt_scan_ids, n, prm, support ? Support::normals_of(*support) : Support::nearest(prm->normal_k),
+                        support ? Support::features_of(*support) : Support::nearest(prm->feature_k), out_T, out_inliers, out_n_pairs, out_ok,
+                        iss);
 }
 
 int gloc_reg_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const gloc_fpfh_graph_params* prm,

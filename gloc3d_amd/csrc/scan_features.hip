@@ -56,6 +56,7 @@ int store_build_normals(gloc_scan_store* st, DevScan& s, const Support& ns) {
   }
   s.nrm_sup = Support{};
   s.fpfh_nsup = s.fpfh_fsup = Support{};  // (features of the old normals: rebuilt on the next request)
+  store_drop_keypoint_rows(st, s);        // (and the keypoints' rows gathered from them)
   GLOC_TRY(st->nrm_tmp.ensure(12 * s.n, q));
   GLOC_TRY(gloc::ground::scan_normals(q, st->nrm_ws, s.idx.pts, n, ns, st->nrm_tmp.as<float>()));
   GLOC_TRY(store_reorder_normals(q, s.idx.pts, n, st->nrm_tmp.as<float>(), s.nrm, true));
@@ -95,6 +96,7 @@ int store_build_fpfh(gloc_scan_store* st, DevScan& s, const Support& ns, const S
     if (s.live) st->live_bytes += 132 * s.n;
   }
   s.fpfh_nsup = s.fpfh_fsup = Support{};
+  store_drop_keypoint_rows(st, s);  // (gathered from the old features; the next keypoint request gathers from the new)
   GLOC_TRY(st->fpfh_tmp.ensure(132 * s.n, q));
   GLOC_TRY(store_spfh(st, s, fs));
   GLOC_TRY(gloc::fpfh::build_fpfh(q, st->nrm_ws, st->spfh_tmp.as<uint8_t>(), n, fs, st->fpfh_tmp.as<float>()));

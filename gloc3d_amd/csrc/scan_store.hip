@@ -601,6 +601,8 @@ void store_free_scan(gloc_scan_store* st, DevScan& s, bool cache_block) {
   }
   if (s.nrm) (void)hipFree(s.nrm);
   if (s.fpfh) (void)hipFree(s.fpfh);
+  if (s.kp) (void)hipFree(s.kp);
+  if (s.kp_feat) (void)hipFree(s.kp_feat);
   s = DevScan{};
 }
 
@@ -952,7 +954,7 @@ int store_insert(gloc_scan_store* st, const DevScan& s, uint32_t* id) {
     *id = (uint32_t)(st->scans.size() - 1);
   }
   st->live_count++;
-  st->live_bytes += s.block_bytes + s.nrm_bytes() + s.fpfh_bytes();
+  st->live_bytes += s.block_bytes + s.nrm_bytes() + s.fpfh_bytes() + s.kp_bytes();
   return GLOC_OK;
 }
 
@@ -974,7 +976,7 @@ int gloc::reg::store_insert_scan(gloc_scan_store* st, const DevScan& s, uint32_t
 void gloc::reg::store_remove_scan(gloc_scan_store* st, uint32_t id) {
   DevScan& s = st->scans[id];
   st->live_count--;
-  st->live_bytes -= s.block_bytes + s.nrm_bytes() + s.fpfh_bytes();
+  st->live_bytes -= s.block_bytes + s.nrm_bytes() + s.fpfh_bytes() + s.kp_bytes();
   store_free_scan(st, s, true);
   st->free_ids.push_back(id);
 }
@@ -1195,6 +1197,8 @@ int gloc_scan_store_clear(gloc_scan_store* st) {
     if (s.block) (void)hipFree(s.block);
     if (s.nrm) (void)hipFree(s.nrm);
     if (s.fpfh) (void)hipFree(s.fpfh);
+    if (s.kp) (void)hipFree(s.kp);
+    if (s.kp_feat) (void)hipFree(s.kp_feat);
   }
   for (auto& kv : st->free_blocks) (void)hipFree(kv.second);
   st->scans.clear();

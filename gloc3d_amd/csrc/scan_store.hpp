@@ -47,6 +47,21 @@ struct DevScan {
   size_t fpfh_bytes() const { return fpfh ? 132 * n : 0; }
   bool has_normals(const gloc::Support& ns) const { return nrm_sup == ns; }
   bool has_fpfh(const gloc::Support& ns, const gloc::Support& fs) const { return fpfh_nsup == ns && fpfh_fsup == fs && nrm_sup == ns; }
+  // ISS keypoints (gloc_scan_store_build_keypoints), an OPTIONAL allocation of 4 B per keypoint: their ORIGINAL indices in
+  // ascending order -- nothing the kd re-sort moves -- K known to the host, tagged with the parameters they were built from.
+  // kp_feat: the keypoints' feature rows [K][33] in list order, what the keypoint-restricted matcher reads; valid for the
+  // features it was gathered from only, so dropped whenever the features or the keypoints are rebuilt and gathered again
+  // on the next request.
+  uint32_t* kp = nullptr;
+  float* kp_feat = nullptr;
+  size_t kp_n = 0;
+  bool kp_built = false;  // (K = 0 is a keypoint set too)
+  gloc_iss_params kp_prm{};
+  size_t kp_bytes() const { return (kp ? 4 * kp_n : 0) + (kp_feat ? 132 * kp_n : 0); }
+  bool has_keypoints(const gloc_iss_params& p) const {
+    return kp_built && kp_prm.salient_radius == p.salient_radius && kp_prm.max_nn == p.max_nn && kp_prm.min_nn == p.min_nn &&
+           kp_prm.non_max_radius == p.non_max_radius && kp_prm.gamma_21 == p.gamma_21 && kp_prm.gamma_32 == p.gamma_32;
+  }
   bool live = false;
   bool kd = false;  // the index is in kd order (target index)
   int pins = 0;     // batches in flight (gloc_reg_batch_multi_begin .. _end) whose jobs hold a by-value view of THIS scan:
@@ -74,6 +89,7 @@ struct gloc_scan_store : gloc::Handle {  // (always on its own stream; the base'
   gloc::ground::NormalsScratch nrm_ws;  // the normals' k-NN lists and staging (gloc_scan_store_build_normals)
   gloc::DevBuf nrm_tmp;                 // normals in original order, between the normal kernel / a download and the sorted copy
   gloc::DevBuf fpfh_tmp, spfh_tmp;      // features in original order (as nrm_tmp) and the SPFH counts they are summed from
+  gloc::DevBuf iss_sal, iss_sal_sorted, iss_eig, iss_flag, iss_list, iss_count;  // the keypoint detector's scratch (iss.hip)
   gloc::submap::Ws* submap_ws = nullptr;
   std::atomic<int> attached{0};  // registration handles using this store
   ~gloc_scan_store() {
@@ -82,6 +98,8 @@ struct gloc_scan_store : gloc::Handle {  // (always on its own stream; the base'
       if (s.block) (void)hipFree(s.block);
       if (s.nrm) (void)hipFree(s.nrm);
       if (s.fpfh) (void)hipFree(s.fpfh);
+      if (s.kp) (void)hipFree(s.kp);
+      if (s.kp_feat) (void)hipFree(s.kp_feat);
     }
     for (auto& kv : free_blocks) (void)hipFree(kv.second);
   }
@@ -129,6 +147,15 @@ int store_build_normals(gloc_scan_store* st, DevScan& s, const Support& ns);
 int store_build_fpfh(gloc_scan_store* st, DevScan& s, const Support& ns, const Support& fs);
 // ... for a list of ids (takes store->mu).  GLOC_ERR_INVALID for an unknown id.
 int store_ensure_fpfh(gloc_scan_store* st, const uint32_t* ids, size_t n, const Support& ns, const Support& fs);
+// Give a scan its ISS keypoints of prm (iss.hip; no-op when it has them from these parameters), and the table of their
+// feature rows when the scan has features.  Caller holds store->mu; returns after the work has completed.  Keypoints a
+// batch may be reading are not rebuilt (GLOC_ERR_STATE).
+int store_build_keypoints(gloc_scan_store* st, DevScan& s, const gloc_iss_params& prm);
+// ... for a list of ids whose features exist (takes store->mu).  GLOC_ERR_INVALID for an unknown id.
+int store_ensure_keypoints(gloc_scan_store* st, const uint32_t* ids, size_t n, const gloc_iss_params& prm);
+// Let go of the table of the keypoints' feature rows: what every rebuild of the features or the normals under them calls.
+void store_drop_keypoint_rows(gloc_scan_store* st, DevScan& s);
+int check_iss_params(const gloc_iss_params* prm);
 // A scan's normals between original order and the order of its sorted points (`pts`, n of them): what the builders, the
 // downloads and the target-index re-sort, which moves the points under them, all go through.  Enqueued on q.
 int store_reorder_normals(hipStream_t q, const f32x4* pts, uint32_t n, const float* in, float* out, bool to_sorted);

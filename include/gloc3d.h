@@ -859,6 +859,66 @@ int gloc_reg_fpfh_graph_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, cons
                                          const gloc_fpfh_graph_params* prm, const gloc_fpfh_radius_params* support, float* out_T,
                                          uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok);
 
+/* ---- ISS keypoints and keypoint-restricted FPFH matching ----------------------------------------------------- *
+ * F3 compares every source row with every target row.  FPFH registration is customarily run on KEYPOINTS instead:
+ * Intrinsic Shape Signatures (Zhong 2009; pcl::ISSKeypoint3D, Open3D's compute_iss_keypoints) keeps the points whose
+ * neighbourhood spreads in all three directions and distinctly so, and the matcher's work falls with K_src x K_tgt.
+ * Opt-in: a scan gets keypoints only when asked, and only the two _keypoints batch entries read them.  The executable
+ * contract is tests/iss_ref.py.
+ *
+ * I1  Saliency.  The list of point i is R1's list for (salient_radius, max_nn).  A point whose list holds fewer than
+ *     min_nn entries, and any non-finite point (its list is empty), has saliency 0.  Otherwise, in fp64 from the fp32
+ *     inputs and in list order: mean = sum / count; the covariance is the unnormalised sum of the outer products of
+ *     (q - mean), its six upper-triangle sums formed as gloc_scan_store_build_normals forms them and mirrored; the
+ *     eigenvalues are the diagonal the same cyclic Jacobi leaves, sorted l1 >= l2 >= l3.  The point is salient iff
+ *     l3 > 0 && l2 < g21 l1 && l3 < g32 l2 (the fp32 gammas widened to fp64); its saliency is (float)l3, else 0.
+ * I2  Non-maximum suppression, over the WHOLE neighbourhood (no capped list).  i is a keypoint iff its saliency is
+ *     positive and no j != i with d2(i, j) <= r2 (R1's d2 and r2, from non_max_radius) has a larger saliency, or an equal
+ *     one and j < i: among equal saliencies within the radius the lower upload index wins.
+ * I3  The keypoint set is the keypoints in ascending upload-order index, K long.  A keypoint whose FPFH row is all zeros
+ *     stays in the set and has "no feature", as before.
+ * I4  Matching.  F3 word for word on feature tables in which every non-keypoint row counts as "no feature", on both
+ *     sides and in the backward search of `mutual`; ties still go to the smaller target upload index.  F4's list is the
+ *     kept pairs in ascending source index; F4 and G1 - G4 are unchanged.  K_src < 3: the identity, ok = 0, 0 inliers. */
+typedef struct gloc_iss_params {
+  float salient_radius;  /* default 3.0 m (6 x the 0.5 m leaf); > 0, finite */
+  uint32_t max_nn;       /* default 128; min_nn .. 128 */
+  uint32_t min_nn;       /* default 5;   3 .. max_nn */
+  float non_max_radius;  /* default 2.0 m (4 x the leaf); > 0, finite */
+  float gamma_21;        /* default 0.975; (0, 1] */
+  float gamma_32;        /* default 0.975; (0, 1] */
+} gloc_iss_params;       /* 24 bytes */
+
+void gloc_iss_default_params(gloc_iss_params* p);
+
+/* I1 as a diagnostic in upload order, nothing is kept: out_saliency [n], out_eig [n][3] the sorted fp64 eigenvalues (all
+ * zeros where the list is too short); either may be NULL.  The parameters are checked before the handle.
+ * GLOC_ERR_INVALID: a parameter outside its range, a null store, an unknown id, capacity_points below the scan's size. */
+int gloc_scan_store_iss_saliency(gloc_scan_store* st, uint32_t scan_id, const gloc_iss_params* prm, float* out_saliency, double* out_eig,
+                                 size_t capacity_points);
+/* I1 - I3: the scan keeps its keypoint list (4 bytes per keypoint, and 132 more for the keypoints' feature rows gathered
+ * into a table of their own whenever the scan has features; both counted by gloc_scan_store_bytes, freed with the scan),
+ * tagged with the six parameters: a repeated request is a no-op, another parameter set rebuilds, GLOC_ERR_STATE while a
+ * batch in flight may read the keypoints.  The list holds upload-order indices: building a target index does not change it. */
+int gloc_scan_store_build_keypoints(gloc_scan_store* st, uint32_t scan_id, const gloc_iss_params* prm);
+/* K, and the list in ascending order.  GLOC_ERR_STATE: the scan has no keypoints. */
+int gloc_scan_store_keypoint_count(gloc_scan_store* st, uint32_t scan_id, size_t* out_k);
+int gloc_scan_store_keypoints(gloc_scan_store* st, uint32_t scan_id, uint32_t* out_idx, size_t capacity);
+/* Diagnostic: the keypoints' feature rows [K][33] in list order, as the matcher reads them (gathered again first when a
+ * rebuild of the features dropped the table).  GLOC_ERR_STATE: the scan has no keypoints or no features. */
+int gloc_scan_store_keypoint_fpfh(gloc_scan_store* st, uint32_t scan_id, float* out_feat, size_t capacity);
+/* gloc_reg_fpfh_batch_ids_radius / gloc_reg_fpfh_graph_batch_ids_radius on the keypoints of `iss` alone (I4), argument
+ * for argument; support == NULL: the k-mode features of prm.  Features and keypoints a scan lacks are built first.  All
+ * parameter blocks are checked before the handle; job c equals its single call bit for bit, and the result does not
+ * depend on target indices. */
+int gloc_reg_fpfh_batch_ids_keypoints(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
+                                      const gloc_fpfh_params* prm, const gloc_fpfh_radius_params* support, const gloc_iss_params* iss,
+                                      float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok);
+int gloc_reg_fpfh_graph_batch_ids_keypoints(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n,
+                                            const gloc_fpfh_graph_params* prm, const gloc_fpfh_radius_params* support,
+                                            const gloc_iss_params* iss, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs,
+                                            int* out_ok);
+
 /* ============================ NetVLAD-FC pooling head ("next" row N2) ===================== *
  * Replaces NetVLAD.forward of the reference (model/netvlad_fc.py:73-109, built without gating at
  * main.py:594) -- the tail of the TorchScript module RpyPCLoopDetector::get_place_feature runs

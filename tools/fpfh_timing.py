@@ -4,7 +4,7 @@ table commits (tests/fpfh_cases.py LEAF): feature build per scan, the matcher pe
 stage, a 20-candidate batch end to end -- and how many of the 40 jobs are located within 1 m / 5 degrees of ground truth,
 beside the RANSAC stage of gloc_reg_batch_ids on the same filtered scans from the identity guess.
 
-    python tools/fpfh_timing.py [--queries 2] [--reps 5] [--leaf 0.5] [--out FILE] [--support] [--build-only]
+    python tools/fpfh_timing.py [--queries 2] [--reps 5] [--leaf 0.5] [--out FILE] [--support] [--keypoints] [--build-only]
 
 Medians of --reps runs on one box; host time of synchronous calls unless a line says "profiler".
 
@@ -13,6 +13,11 @@ the feature build on a filtered scan at the default support and on a raw scan at
 build of the same scan, and the 40 jobs under the supports of SUPPORTS through RANSAC and through the correspondence graph --
 located within 1 m / 5 degrees, median error, inlier populations of the two groups -- beside k-mode's.  --build-only stops
 after the builds: what a `rocprofv3 --kernel-trace --stats` run of its own wraps to split the build by kernel.
+
+--keypoints adds the ISS keypoints (gloc_iss_params at their defaults), everything from the same run: the keypoint build on a
+filtered scan beside the feature builds, K per scan, the matcher and the pair compaction per 20 candidates with and without
+keypoints (profiler) and the batch end to end, and the six rows of the localization table -- k-mode and the two radius
+supports, through RANSAC and through the graph -- each without and with keypoints.
 """
 import argparse
 import os
@@ -55,7 +60,8 @@ def main():
     ap.add_argument("--leaf", type=float, default=0.5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--support", action="store_true", help="add the radius-support measurements")
-    ap.add_argument("--build-only", action="store_true", help="with --support: the feature builds alone (for a kernel trace)")
+    ap.add_argument("--keypoints", action="store_true", help="add the ISS keypoint measurements")
+    ap.add_argument("--build-only", action="store_true", help="with --support / --keypoints: the builds alone (for a kernel trace)")
     a = ap.parse_args()
     from gloc3d_amd import capi, synth
     traj, xy = synth.loop_trajectory(400, 328.0)
@@ -109,6 +115,8 @@ def main():
     say(f"feature build on an unfiltered scan ({store.points(r['raw'][0])} points), normals + features: median {np.median(t_raw[1:]):.3f} ms")
     if a.support:
         radius_builds(a, capi, store, r, say)
+    if a.keypoints:
+        keypoint_builds(a, capi, store, r, say)
     if a.build_only:
         reg.close()
         store.close()
@@ -172,6 +180,8 @@ def main():
     say(f"baseline, the RANSAC stage of gloc_reg_batch_ids on the same filtered scans from the identity, 20 candidates: median {mb:.2f} ms (min {lob:.2f})")
     if a.support:
         radius_jobs(a, capi, store, reg, rows, located, say)
+    if a.keypoints:
+        keypoint_jobs(a, capi, store, reg, rows, located, say)
     reg.close()
     store.close()
     if a.out:
@@ -209,23 +219,27 @@ def radius_builds(a, capi, store, r, say):
     store.release(s)
 
 
+def table_row(rows, located, n_same, say, label, call):
+    """One row of the localization table: the 40 jobs through call(row)."""
+    loc = acc = 0
+    errs, inl_same, inl_diff, pairs = [], [], [], []
+    for row in rows:
+        g = call(row)
+        loc += located(g["T"], g["ok"], row["truth"])
+        acc += int(np.sum(g["ok"][10:]))
+        errs += [pose_error(g["T"][c], row["truth"][c]) for c in range(10)]
+        inl_same += g["inliers"][:10].tolist()
+        inl_diff += g["inliers"][10:].tolist()
+        pairs += g["n_pairs"].tolist()
+    say(f"  {label:28s} located {loc:2d} of {n_same}; error median {np.median([e[0] for e in errs]):.3f} m {np.median([e[1] for e in errs]):.3f} deg; "
+        f"inliers same-world median {int(np.median(inl_same))} ({min(inl_same)} .. {max(inl_same)}), different-world median "
+        f"{int(np.median(inl_diff))} ({min(inl_diff)} .. {max(inl_diff)}); different-world ok {acc} of {n_same}; pairs median {int(np.median(pairs))}")
+
+
 def radius_jobs(a, capi, store, reg, rows, located, say):
     """The 40 jobs under each support, through RANSAC and through the graph, beside k-mode from the same scans."""
     n_same = 10 * a.queries
-
-    def run(label, call):
-        loc = acc = 0
-        errs, inl_same, inl_diff = [], [], []
-        for row in rows:
-            g = call(row)
-            loc += located(g["T"], g["ok"], row["truth"])
-            acc += int(np.sum(g["ok"][10:]))
-            errs += [pose_error(g["T"][c], row["truth"][c]) for c in range(10)]
-            inl_same += g["inliers"][:10].tolist()
-            inl_diff += g["inliers"][10:].tolist()
-        say(f"  {label:28s} located {loc:2d} of {n_same}; error median {np.median([e[0] for e in errs]):.3f} m {np.median([e[1] for e in errs]):.3f} deg; "
-            f"inliers same-world median {int(np.median(inl_same))} ({min(inl_same)} .. {max(inl_same)}), different-world median "
-            f"{int(np.median(inl_diff))} ({min(inl_diff)} .. {max(inl_diff)}); different-world ok {acc} of {n_same}")
+    run = lambda label, call: table_row(rows, located, n_same, say, label, call)  # noqa: E731
 
     say(f"located within {OK_T} m / {OK_R} deg of the {n_same} same-world jobs, k-mode and radius supports, same scans, same run:")
     run("k-mode (10, 16), RANSAC", lambda row: reg.fpfh_batch(row["q"], row["db"]))
@@ -242,6 +256,91 @@ def radius_jobs(a, capi, store, reg, rows, located, say):
             store.build_fpfh(t, 10, 16)
     m20, lo20 = med(lambda: reg.fpfh_batch(rows[0]["q"], rows[0]["db"]), a.reps)
     say(f"  k-mode: end to end (features present), 20 candidates, RANSAC: median {m20:.2f} ms (min {lo20:.2f})")
+
+
+def keypoint_builds(a, capi, store, r, say):
+    """The keypoint build on a filtered scan beside the feature builds of the same run: a warm-up, then the median of --reps."""
+    def timed(make, build):
+        t = []
+        for _ in range(a.reps + 1):
+            s = make()
+            t0 = time.perf_counter()
+            build(s)
+            t.append((time.perf_counter() - t0) * 1e3)
+            store.release(s)
+        return float(np.median(t[1:]))
+
+    iss, dflt = capi.default_iss_params(), capi.default_fpfh_radius_params()
+    filt = lambda: store.add_approx_voxel(r["raw"][1], a.leaf)  # noqa: E731
+
+    def with_features():
+        s = filt()
+        store.build_fpfh(s, 10, 16)
+        return s
+
+    n_f = store.points(r["db"][0])
+    k_f, r_f = timed(filt, lambda s: store.build_fpfh(s, 10, 16)), timed(filt, lambda s: store.build_fpfh_radius(s, dflt))
+    kp, kp_g = timed(filt, lambda s: store.build_keypoints(s, iss)), timed(with_features, lambda s: store.build_keypoints(s, iss))
+    say(f"ISS keypoints (salient {iss.salient_radius:g} m / {iss.max_nn}, min {iss.min_nn}, non-max {iss.non_max_radius:g} m, gammas {iss.gamma_21:g} "
+        f"{iss.gamma_32:g}), build on a filtered scan ({n_f} points), host time, synchronous, warm-up + median of {a.reps}:")
+    say(f"  keypoints (search + saliency + suppression + list) {kp:.3f} ms; with features present (+ the gather of their rows) {kp_g:.3f} ms; "
+        f"feature build of the same run: k-mode (10, 16) {k_f:.3f} ms, radius default {r_f:.3f} ms")
+    s = filt()
+    sal, _ = store.iss_saliency(s, iss)
+    _, _, cnt = store.radius_neighbors(s, iss.salient_radius, iss.max_nn)
+    store.build_keypoints(s, iss)
+    say(f"  that scan: neighbourhood within {iss.salient_radius:g} m median {int(np.median(cnt))} (max {int(cnt.max())}), lists cut by max_nn "
+        f"{100.0 * np.mean(cnt > iss.max_nn):.1f} %, below min_nn {100.0 * np.mean(cnt < iss.min_nn):.1f} %; salient {int((sal > 0).sum())} of {len(sal)}; "
+        f"K = {len(store.keypoints(s))}")
+    store.release(s)
+
+
+def keypoint_jobs(a, capi, store, reg, rows, located, say):
+    """Matcher and batch time with and without keypoints, and the six rows of the localization table each without and with."""
+    n_same = 10 * a.queries
+    iss = capi.default_iss_params()
+    r = rows[0]
+    for row in rows:
+        for t in [row["q"]] + row["db"]:
+            store.build_fpfh(t, 10, 16)
+            store.build_keypoints(t, iss)
+    ks = [[len(store.keypoints(t)) for t in [row["q"]] + row["db"]] for row in rows]
+    say(f"keypoints per scan at the defaults: queries {[k[0] for k in ks]}, places {min(min(k[1:]) for k in ks)} .. {max(max(k[1:]) for k in ks)} "
+        f"(median {int(np.median([x for k in ks for x in k[1:]]))}) of {store.points(r['q'])} / {min(store.points(t) for t in r['db'])} .. "
+        f"{max(store.points(t) for t in r['db'])} points")
+    reg.set_option(capi.REG_OPT_PROFILE, 1)
+    for label, kw in (("all points", {}), ("keypoints", dict(keypoints=iss))):
+        reg.fpfh_batch(r["q"], r["db"], **kw)
+        reg.profile_reset()
+        for _ in range(a.reps):
+            reg.fpfh_batch(r["q"], r["db"], **kw)
+        parts = {k: reg.profile(k)[0] / a.reps for k in ("fpfh_match", "fpfh_pairs", "ransac_hyp", "ransac_score", "accum", "solve")}
+        say(f"20 candidates, k-mode features, mutual = 1, profiler on, per batch, {label}: fpfh_match {parts['fpfh_match']:.3f} ms, fpfh_pairs "
+            f"{parts['fpfh_pairs']:.3f} ms, ransac_hyp {parts['ransac_hyp']:.3f}, ransac_score {parts['ransac_score']:.3f}, refit "
+            f"{parts['accum'] + parts['solve']:.3f}")
+    reg.set_option(capi.REG_OPT_PROFILE, 0)
+    for label, kw in (("all points", {}), ("keypoints", dict(keypoints=iss))):
+        m20, lo20 = med(lambda: reg.fpfh_batch(r["q"], r["db"], **kw), a.reps)
+        m1, lo1 = med(lambda: reg.fpfh_batch(r["q"], r["db"][:1], **kw), a.reps)
+        g20, glo20 = med(lambda: reg.fpfh_graph_batch(r["q"], r["db"], **kw), a.reps)
+        say(f"end to end (features and keypoints present), k-mode, {label}: RANSAC 20 candidates median {m20:.2f} ms (min {lo20:.2f}), 1 candidate "
+            f"{m1:.2f} ms (min {lo1:.2f}); graph 20 candidates median {g20:.2f} ms (min {glo20:.2f})")
+    say(f"located within {OK_T} m / {OK_R} deg of the {n_same} same-world jobs, each row without and with keypoints, same scans, same run:")
+    run = lambda label, call: table_row(rows, located, n_same, say, label, call)  # noqa: E731
+    for kp_label, kw in (("", {}), (" + keypoints", dict(keypoints=iss))):
+        run("k-mode (10, 16), RANSAC" + kp_label, lambda row: reg.fpfh_batch(row["q"], row["db"], **kw))
+        run("k-mode (10, 16), graph" + kp_label, lambda row: reg.fpfh_graph_batch(row["q"], row["db"], **kw))
+    for name in ("default", "tight"):
+        sup = capi.default_fpfh_radius_params(**SUPPORTS[name])
+        tag = f"{sup.normal_radius:g} m / {sup.normal_max_nn}, {sup.feature_radius:g} m / {sup.feature_max_nn}"
+        for kp_label, kw in (("", {}), (" + keypoints", dict(keypoints=iss))):
+            run(f"radius {tag}, RANSAC" + kp_label, lambda row: reg.fpfh_batch(row["q"], row["db"], support=sup, **kw))
+            run(f"radius {tag}, graph" + kp_label, lambda row: reg.fpfh_graph_batch(row["q"], row["db"], support=sup, **kw))
+        m20, lo20 = med(lambda: reg.fpfh_batch(r["q"], r["db"], support=sup, keypoints=iss), a.reps)
+        say(f"  radius {tag} + keypoints: end to end, 20 candidates, RANSAC: median {m20:.2f} ms (min {lo20:.2f})")
+    for row in rows:                                                      # (leave the scans as the tool's other lines expect them)
+        for t in [row["q"]] + row["db"]:
+            store.build_fpfh(t, 10, 16)
 
 
 if __name__ == "__main__":

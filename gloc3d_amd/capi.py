@@ -84,6 +84,13 @@ class VgicpParams(C.Structure):
                 ("min_points", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class RobustParams(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("scale", C.c_float), ("scale_start", C.c_float), ("anneal", C.c_float)]
+
+
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_GEMAN_MCCLURE = range(5)
+
+
 class FpfhParams(C.Structure):
     _fields_ = [("normal_k", C.c_uint32), ("feature_k", C.c_uint32), ("mutual", C.c_uint32), ("ransac_iters", C.c_uint32),
                 ("inlier_thresh", C.c_float), ("min_inlier_ratio", C.c_float), ("ransac_confidence", C.c_float),
@@ -267,6 +274,18 @@ _PROTOS = [
     ("gloc_reg_vgicp_system", _i, [_vp, _u32, _u32, _vp, C.POINTER(VgicpParams), _vp, _vp, C.POINTER(C.c_double),
                                C.POINTER(C.c_uint64)]),
     ("gloc_reg_vgicp_voxels", _i, [_vp, _u32, C.POINTER(VgicpParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
+    ("gloc_robust_default_params", None, [C.POINTER(RobustParams)]),
+    ("gloc_robust_scale", _i, [C.POINTER(RobustParams), _u32, C.POINTER(C.c_double)]),
+    ("gloc_robust_weight", _i, [C.POINTER(RobustParams), _u32, C.c_double, C.POINTER(C.c_double)]),
+    ("gloc_reg_p2l_batch_ids_robust", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(P2lParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_gicp_batch_ids_robust", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(GicpParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_vgicp_batch_ids_robust", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(VgicpParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_p2l_system_robust", _i, [_vp, _u32, _u32, _vp, C.POINTER(P2lParams), C.POINTER(RobustParams), _u32, _vp, _vp, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("gloc_reg_gicp_system_robust", _i, [_vp, _u32, _u32, _vp, C.POINTER(GicpParams), C.POINTER(RobustParams), _u32, _vp, _vp, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("gloc_reg_vgicp_system_robust", _i, [_vp, _u32, _u32, _vp, C.POINTER(VgicpParams), C.POINTER(RobustParams), _u32, _vp, _vp, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     ("gloc_fpfh_default_params", None, [C.POINTER(FpfhParams)]),
     ("gloc_scan_store_build_fpfh", _i, [_vp, _u32, _u32, _u32]),
     ("gloc_scan_store_fpfh", _i, [_vp, _u32, _vp, _sz]),
@@ -721,6 +740,29 @@ def default_vgicp_params(**over):
     return p
 
 
+def default_robust_params(**over):
+    """gloc_robust_params as gloc_robust_default_params leaves them (kind NONE, zeros), then `over`."""
+    p = RobustParams()
+    lib().gloc_robust_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
+def robust_scale(robust, k):
+    """c(k) of the block's schedule, as the device uses it (gloc_robust_scale)."""
+    c = C.c_double()
+    check(lib().gloc_robust_scale(C.byref(robust), int(k), C.byref(c)))
+    return c.value
+
+
+def robust_weight(robust, k, s2):
+    """The weight of a squared residual s2 at c(k), as the device computes it (gloc_robust_weight)."""
+    w = C.c_double()
+    check(lib().gloc_robust_weight(C.byref(robust), int(k), float(s2), C.byref(w)))
+    return w.value
+
+
 def default_fpfh_params(**over):
     """gloc_fpfh_params as gloc_fpfh_default_params leaves them (normal_k = 10, feature_k = 16, mutual matches, 3000
     hypotheses at most, 0.6 m inliers, confidence 0.99, seed 1234), then `over`."""
@@ -1130,47 +1172,76 @@ class Registrar(_Handle):
                                            C.byref(prm), _np_ptr(T), _np_ptr(prob), _np_ptr(iters), _np_ptr(conv)))
         return T, prob, iters, conv.astype(bool)
 
-    def p2l_batch(self, src_id, tgt_ids, init_T=None, params=None):
+    def p2l_batch(self, src_id, tgt_ids, init_T=None, params=None, robust=None):
         """Point-to-plane ICP of scan src_id against each of tgt_ids (gloc_reg_p2l_batch_ids): returns T [n, 4, 4] float32,
-        rmse [n] float32 (point-to-plane, at the final pose), iterations [n], status [n] (0 cap, 1 converged, 2 degenerate)."""
+        rmse [n] float32 (point-to-plane, at the final pose), iterations [n], status [n] (0 cap, 1 converged, 2 degenerate).
+        robust: a RobustParams -- every pair weighted by its residual (gloc_reg_p2l_batch_ids_robust); then also weight [n]
+        float32, the mean weight of the final evaluation."""
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
         n = ids.shape[0]
         prm = params or default_p2l_params()
         it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
         T = np.empty((n, 4, 4), np.float32)
         rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        if robust is not None:
+            weight = np.empty(n, np.float32)
+            check(lib().gloc_reg_p2l_batch_ids_robust(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
+                                                      C.byref(prm), C.byref(robust), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters),
+                                                      _np_ptr(status), _np_ptr(weight)))
+            return T, rmse, iters, status, weight
         check(lib().gloc_reg_p2l_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
                                            C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
         return T, rmse, iters, status
 
-    def p2l_system(self, src_id, tgt_id, T=None, params=None):
-        """One evaluation of the point-to-plane normal equations at T: H [6, 6], g [6], sum r^2, pairs used."""
+    def p2l_system(self, src_id, tgt_id, T=None, params=None, robust=None, robust_pass=0):
+        """One evaluation of the point-to-plane normal equations at T: H [6, 6], g [6], sum r^2, pairs used.  robust: as
+        p2l_batch, weighted at c(robust_pass) (gloc_reg_p2l_system_robust); then also the weights' sum."""
         prm = params or default_p2l_params()
         t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
         H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
+        if robust is not None:
+            ws = C.c_double()
+            check(lib().gloc_reg_p2l_system_robust(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
+                                                   C.byref(robust), int(robust_pass), _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c),
+                                                   C.byref(ws)))
+            return H, g, s.value, c.value, ws.value
         check(lib().gloc_reg_p2l_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
                                         _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
         return H, g, s.value, c.value
 
-    def gicp_batch(self, src_id, tgt_ids, init_T=None, params=None):
+    def gicp_batch(self, src_id, tgt_ids, init_T=None, params=None, robust=None):
         """Generalized ICP of scan src_id against each of tgt_ids (gloc_reg_gicp_batch_ids): returns T [n, 4, 4] float32,
         rmse [n] float32 (sqrt of the mean e^T M e at the final pose), iterations [n], status [n] (0 cap, 1 converged,
-        2 degenerate)."""
+        2 degenerate).  robust: a RobustParams (gloc_reg_gicp_batch_ids_robust); then also weight [n] float32, the mean
+        weight of the final evaluation."""
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
         n = ids.shape[0]
         prm = params or default_gicp_params()
         it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
         T = np.empty((n, 4, 4), np.float32)
         rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        if robust is not None:
+            weight = np.empty(n, np.float32)
+            check(lib().gloc_reg_gicp_batch_ids_robust(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
+                                                       C.byref(prm), C.byref(robust), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters),
+                                                       _np_ptr(status), _np_ptr(weight)))
+            return T, rmse, iters, status, weight
         check(lib().gloc_reg_gicp_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
                                             C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
         return T, rmse, iters, status
 
-    def gicp_system(self, src_id, tgt_id, T=None, params=None):
-        """One evaluation of the generalized ICP normal equations at T: H [6, 6], g [6], sum e^T M e, pairs used."""
+    def gicp_system(self, src_id, tgt_id, T=None, params=None, robust=None, robust_pass=0):
+        """One evaluation of the generalized ICP normal equations at T: H [6, 6], g [6], sum e^T M e, pairs used.  robust: as
+        gicp_batch, weighted at c(robust_pass) (gloc_reg_gicp_system_robust); then also the weights' sum."""
         prm = params or default_gicp_params()
         t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
         H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
+        if robust is not None:
+            ws = C.c_double()
+            check(lib().gloc_reg_gicp_system_robust(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
+                                                    C.byref(robust), int(robust_pass), _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c),
+                                                    C.byref(ws)))
+            return H, g, s.value, c.value, ws.value
         check(lib().gloc_reg_gicp_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
                                          _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
         return H, g, s.value, c.value
@@ -1241,26 +1312,40 @@ class Registrar(_Handle):
         return dict(degree=deg[:m], score=score[:m], seeds=seeds, set_sizes=sizes, seed_inliers=sinl, T=T, inliers=inl.value,
                     winner_rank=rank.value, ok=bool(ok.value))
 
-    def vgicp_batch(self, src_id, tgt_ids, init_T=None, params=None):
+    def vgicp_batch(self, src_id, tgt_ids, init_T=None, params=None, robust=None):
         """Voxelized generalized ICP of scan src_id against each of tgt_ids (gloc_reg_vgicp_batch_ids): returns
         T [n, 4, 4] float32, rmse [n] float32 (sqrt of the weighted e^T M e per pair at the final pose), iterations [n],
-        status [n] (0 cap, 1 converged, 2 degenerate)."""
+        status [n] (0 cap, 1 converged, 2 degenerate).  robust: a RobustParams (gloc_reg_vgicp_batch_ids_robust); then also
+        weight [n] float32, the mean weight of the final evaluation."""
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
         n = ids.shape[0]
         prm = params or default_vgicp_params()
         it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
         T = np.empty((n, 4, 4), np.float32)
         rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        if robust is not None:
+            weight = np.empty(n, np.float32)
+            check(lib().gloc_reg_vgicp_batch_ids_robust(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
+                                                        C.byref(prm), C.byref(robust), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters),
+                                                        _np_ptr(status), _np_ptr(weight)))
+            return T, rmse, iters, status, weight
         check(lib().gloc_reg_vgicp_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
                                              C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
         return T, rmse, iters, status
 
-    def vgicp_system(self, src_id, tgt_id, T=None, params=None):
+    def vgicp_system(self, src_id, tgt_id, T=None, params=None, robust=None, robust_pass=0):
         """One evaluation of the voxelized generalized ICP normal equations at T: H [6, 6], g [6], the weighted sum of
-        e^T M e, pairs used."""
+        e^T M e, pairs used.  robust: as vgicp_batch, weighted at c(robust_pass) (gloc_reg_vgicp_system_robust); then also
+        the weights' sum."""
         prm = params or default_vgicp_params()
         t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
         H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
+        if robust is not None:
+            ws = C.c_double()
+            check(lib().gloc_reg_vgicp_system_robust(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
+                                                     C.byref(robust), int(robust_pass), _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c),
+                                                     C.byref(ws)))
+            return H, g, s.value, c.value, ws.value
         check(lib().gloc_reg_vgicp_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
                                           _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
         return H, g, s.value, c.value

@@ -14,6 +14,12 @@
 //   ww = -A [p]x  (row i: p x A_i.),   wv = A,   vv = M,      and J^T M e = (p x M e ; M e).
 // About 150 fp64 operations and one division per pair; the 1-NN search of the same pass is two orders above that.
 //
+// KIND (robust.hpp; 0: none, the plain entries' instantiation, whose arithmetic is what it was before there were kinds):
+// the lane that owns the pair takes s2 = e^T M e from the adjugate -- (e^T adj e) / det -- and the weight w of the pass's
+// scale, which then rides on M (w / det), so that the 27 contributions to H and g come out weighted; e^T M e (s2 itself)
+// and the count are left alone; slot 29 gets the weight.  One more division (a square root with it for Huber) beside the
+// pair's own.
+//
 // The reduction of the sums, the solve kernel and the note on registers are in gn6_kernels.hpp, shared with the
 // point-to-plane refinement.  The correspondences are the registration's own exact 1-NN pass (reg.hip: launch_nn).
 #pragma once
@@ -38,12 +44,14 @@ struct Target {  // of a job
   uint32_t n, pad_;
 };
 
+template <int KIND>
 __global__ __launch_bounds__(ACC_THREADS) void gicp_accum_kernel(const f32x4* __restrict__ src_pts, const float* __restrict__ src_nrm,
                                                                  uint32_t n_src, const Target* __restrict__ tgts,
                                                                  const float* __restrict__ pose_f32, size_t pose_stride /* floats */,
                                                                  const State* __restrict__ states, const uint32_t* __restrict__ corr,
                                                                  const float* __restrict__ d2in, size_t ld, float gate2, double a,
-                                                                 bool skip_stopped, double* __restrict__ partials /* [job][n_blk][NSLOT] */) {
+                                                                 bool skip_stopped, double* __restrict__ partials /* [job][n_blk][NSLOT] */,
+                                                                 gn6::Scale2 sc) {
   __shared__ double red[ACC_THREADS / 64][NSLOT];
   const uint32_t job = blockIdx.y;
   if (skip_stopped && states[job].stopped) return;  // (uniform; the solve does not read a stopped job's partials)
@@ -77,7 +85,17 @@ __global__ __launch_bounds__(ACC_THREADS) void gicp_accum_kernel(const f32x4* __
       const double syz = -a * (B[1] * B[2] + m[1] * m[2]), szz = 2.0 - a * (B[2] * B[2] + m[2] * m[2]);
       const double cxx = syy * szz - syz * syz, cxy = sxz * syz - sxy * szz, cxz = sxy * syz - sxz * syy;
       const double cyy = sxx * szz - sxz * sxz, cyz = sxy * sxz - sxx * syz, czz = sxx * syy - sxy * sxy;
-      const double inv = 1.0 / ((sxx * cxx + sxy * cxy) + sxz * cxz);
+      double inv = 1.0 / ((sxx * cxx + sxy * cxy) + sxz * cxz);
+      double s2 = 0.0;
+      if (KIND != GLOC_ROBUST_NONE) {
+        // s2 = e^T M e from the adjugate, before the weight rides on M
+        const double ce[3] = {(cxx * E[0] + cxy * E[1]) + cxz * E[2], (cxy * E[0] + cyy * E[1]) + cyz * E[2],
+                              (cxz * E[0] + cyz * E[1]) + czz * E[2]};
+        s2 = ((E[0] * ce[0] + E[1] * ce[1]) + E[2] * ce[2]) * inv;
+        const double w = robust::weight<KIND>(s2, gn6::scale2_of(sc, states[job]));
+        inv = w * inv;
+        v[gn6::WSLOT] = w;
+      }
       const double M[3][3] = {{cxx * inv, cxy * inv, cxz * inv}, {cxy * inv, cyy * inv, cyz * inv}, {cxz * inv, cyz * inv, czz * inv}};
       double Me[3];
 #pragma unroll
@@ -104,7 +122,7 @@ __global__ __launch_bounds__(ACC_THREADS) void gicp_accum_kernel(const f32x4* __
       v[20] = M[2][2];
       v[21] = gw[0]; v[22] = gw[1]; v[23] = gw[2];
       v[24] = Me[0]; v[25] = Me[1]; v[26] = Me[2];
-      v[27] = (E[0] * Me[0] + E[1] * Me[1]) + E[2] * Me[2];
+      v[27] = KIND != GLOC_ROBUST_NONE ? s2 : (E[0] * Me[0] + E[1] * Me[1]) + E[2] * Me[2];
       v[28] = 1.0;
     }
   }

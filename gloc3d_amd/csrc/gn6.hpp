@@ -8,6 +8,7 @@
 // and an event -- to cut the tail once every job has stopped.
 #pragma once
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "gn6_kernels.hpp"
@@ -17,7 +18,7 @@ namespace gloc {
 namespace p2l {
 
 struct Ws {  // (one per handle, whichever refinement runs: the calls are synchronous)
-  DevBuf tgts, states, partials, done, exp;
+  DevBuf tgts, states, partials, done, exp, c2tab;
   uint32_t* h_done = nullptr;  // pinned
   hipEvent_t ev = nullptr;
   ~Ws() {
@@ -32,6 +33,18 @@ namespace gn6 {
 
 constexpr uint32_t LOOK_EVERY = 4;
 
+// f(std::integral_constant<int, KIND>) for the robust kind of a call: the accumulate kernels are templates on it
+template <class F>
+void for_kind(uint32_t kind, F&& f) {
+  switch (kind) {
+    case GLOC_ROBUST_HUBER: f(std::integral_constant<int, GLOC_ROBUST_HUBER>()); break;
+    case GLOC_ROBUST_CAUCHY: f(std::integral_constant<int, GLOC_ROBUST_CAUCHY>()); break;
+    case GLOC_ROBUST_TUKEY: f(std::integral_constant<int, GLOC_ROBUST_TUKEY>()); break;
+    case GLOC_ROBUST_GEMAN_MCCLURE: f(std::integral_constant<int, GLOC_ROBUST_GEMAN_MCCLURE>()); break;
+    default: f(std::integral_constant<int, GLOC_ROBUST_NONE>());
+  }
+}
+
 struct Loop {  // what the refinements' parameter blocks have in common
   uint32_t max_iters;
   float max_corr_dist, trans_eps, rot_eps;
@@ -40,11 +53,16 @@ struct Loop {  // what the refinements' parameter blocks have in common
 
 // Refines every job from init_T ([n][16] or null: identity); any of the last four non-null: ONE evaluation at init_T of
 // job 0 instead.  `tgts`: the jobs' targets as the accumulate kernel takes them, copied to the device; accum(targets on
-// the device, states, gate^2, skip_stopped, partials, n_blk) enqueues that kernel.  Returns after the results have been
-// copied out.
+// the device, states, gate^2, skip_stopped, partials, n_blk, the pass's Scale2) enqueues that kernel.  Returns after the
+// results have been copied out.
+//
+// rb (robust.hpp): with a kind other than NONE accum is also handed the pass's scale -- the table of c(k)^2 made here
+// with the host helper's own function, indexed by each job's update count, during the loop; scale^2 for the evaluation
+// after it; c(pass)^2 for the system form -- and the solve kernel the first update index at which the stop test counts.
 template <class Target, class Accum>
 int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, const float* init_T, Accum&& accum, float* out_T,
-        float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count) {
+        float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count,
+        const p2l::RobustArgs& rb = p2l::RobustArgs()) {
   if (!*x.ws) {
     *x.ws = new (std::nothrow) p2l::Ws;
     GLOC_REQUIRE(*x.ws, GLOC_ERR_NOMEM, "host allocation failed");
@@ -52,7 +70,8 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
   p2l::Ws& w = **x.ws;
   const hipStream_t q = x.stream;
   const uint32_t n = x.n_jobs;
-  const bool system = out_H36 || out_g6 || out_sum || out_count;
+  const bool system = out_H36 || out_g6 || out_sum || out_count || rb.out_wsum;
+  const bool weighted = rb.kind() != GLOC_ROBUST_NONE;
   const uint32_t n_blk = std::max<uint32_t>(1, (x.n_src + ACC_THREADS - 1) / ACC_THREADS);
   std::vector<State> hs(n);
   static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -75,6 +94,31 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
   GLOC_HIP(hipMemcpyAsync(w.tgts.p, tgts.data(), sizeof(Target) * n, hipMemcpyHostToDevice, q));
   GLOC_HIP(hipMemcpyAsync(w.states.p, hs.data(), sizeof(State) * n, hipMemcpyHostToDevice, q));
   GLOC_HIP(hipMemsetAsync(w.done.p, 0, 16, q));
+  // the scales: c(k)^2 for k = 0 .. the last update index a job can have, cut where the schedule has settled
+  std::vector<double> c2;
+  uint32_t stop_from = 0;
+  Scale2 loop_sc{nullptr, 0, 0.0}, end_sc{nullptr, 0, 0.0};
+  if (weighted) {
+    if (system) {
+      const double c = robust::scale_at(rb.prm, rb.pass);
+      end_sc.fixed = c * c;
+    } else {
+      stop_from = 0xFFFFFFFFu;  // (a schedule that has not settled by the last update: no update's stop test counts)
+      double c = robust::scale_first(rb.prm);
+      for (uint32_t k = 0; k < lp.max_iters; ++k, c = robust::scale_next(rb.prm, c)) {
+        c2.push_back(c * c);
+        if (c == (double)rb.prm->scale) {
+          stop_from = k;
+          break;
+        }
+      }
+      const uint32_t n_tab = (uint32_t)c2.size();
+      GLOC_TRY(w.c2tab.ensure(sizeof(double) * n_tab, q));
+      GLOC_HIP(hipMemcpyAsync(w.c2tab.p, c2.data(), sizeof(double) * n_tab, hipMemcpyHostToDevice, q));
+      loop_sc = Scale2{w.c2tab.template as<double>(), n_tab, 0.0};
+      end_sc.fixed = (double)rb.prm->scale * (double)rb.prm->scale;
+    }
+  }
   GLOC_HIP(hipStreamSynchronize(q));  // (tgts and hs are host vectors)
   const float gate2 = lp.max_corr_dist > 0.f ? lp.max_corr_dist * lp.max_corr_dist : 0.f;
   bool warm = false;
@@ -84,12 +128,14 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
     warm = true;
     {
       ProfScope ps(*x.prof, lp.accum_name, q);
-      accum(w.tgts.template as<Target>(), w.states.template as<State>(), gate2, mode == 0, w.partials.template as<double>(), n_blk);
+      accum(w.tgts.template as<Target>(), w.states.template as<State>(), gate2, mode == 0, w.partials.template as<double>(), n_blk,
+            mode == 0 ? loop_sc : end_sc);
     }
     {
       ProfScope ps(*x.prof, lp.solve_name, q);
-      hipLaunchKernelGGL(solve_kernel, dim3(n), dim3(64), 0, q, w.partials.template as<double>(), n_blk, w.states.template as<State>(),
-                         x.pose_f32, x.pose_stride, (double)lp.trans_eps, (double)lp.rot_eps, mode, w.done.template as<uint32_t>(), exp);
+      hipLaunchKernelGGL(solve_kernel, dim3(n), dim3(64), 0, q, w.partials.template as<double>(), n_blk, stop_from,
+                         w.states.template as<State>(), x.pose_f32, x.pose_stride, (double)lp.trans_eps, (double)lp.rot_eps, mode,
+                         w.done.template as<uint32_t>(), exp);
     }
     GLOC_HIP(hipGetLastError());
     return GLOC_OK;
@@ -98,6 +144,7 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
     GLOC_TRY(pass(1, w.exp.template as<double>()));
     double s[NSUM];
     GLOC_HIP(hipMemcpyAsync(s, w.exp.p, sizeof(double) * NSUM, hipMemcpyDeviceToHost, q));
+    GLOC_HIP(hipMemcpyAsync(hs.data(), w.states.p, sizeof(State), hipMemcpyDeviceToHost, q));
     GLOC_HIP(hipStreamSynchronize(q));
     if (out_H36) {
       int e = 0;
@@ -107,6 +154,7 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
     if (out_g6) std::copy(s + 21, s + 27, out_g6);
     if (out_sum) *out_sum = s[27];
     if (out_count) *out_count = (uint64_t)s[28];
+    if (rb.out_wsum) *rb.out_wsum = weighted ? hs[0].wsum : s[28];  // (kind NONE: every pair's weight is 1)
     return GLOC_OK;
   }
   const bool can_converge = lp.trans_eps > 0.f && lp.rot_eps > 0.f;
@@ -135,6 +183,7 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
     if (out_rmse) out_rmse[c] = (float)s.rmse;
     if (out_iters) out_iters[c] = s.iters;
     if (out_status) out_status[c] = s.status;
+    if (rb.out_weight) rb.out_weight[c] = s.count == 0 ? 0.f : weighted ? (float)(s.wsum / (double)s.count) : 1.f;
   }
   return GLOC_OK;
 }

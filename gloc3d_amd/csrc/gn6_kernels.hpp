@@ -1,6 +1,7 @@
 // gn6_kernels.hpp -- what the Gauss-Newton refinements on 6 pose parameters share on the device (gfx950): point-to-plane
-// (p2l_kernels.hpp) and generalized ICP (gicp_kernels.hpp).  Each has its own accumulate kernel -- one lane per source
-// point, the pair's 29 fp64 contributions -- and ends it with reduce_store() here; solve_kernel here takes it from there.
+// (p2l_kernels.hpp), generalized ICP (gicp_kernels.hpp) and its voxelized form (vgicp_kernels.hpp).  Each has its own
+// accumulate kernel -- one lane per source point, the pair's 29 fp64 contributions, a 30th (the robust weight: robust.hpp)
+// from the robust instantiations -- and ends it with reduce_store() here; solve_kernel here takes it from there.
 //
 //   reduce_store    the 29 sums of a pass (21 entries of the upper triangle of H, 6 of g, the squared residual, the count):
 //                   a reduce-scatter over the wave, the work-group's waves in LDS, one partial per work-group
@@ -19,6 +20,7 @@
 #include <stdint.h>
 
 #include "lane_ops.hpp"
+#include "robust.hpp"
 
 namespace gloc {
 namespace gn6 {
@@ -26,6 +28,7 @@ namespace gn6 {
 constexpr int ACC_THREADS = 256;  // source points per work-group
 constexpr int NSUM = 29;          // H upper triangle 21 (row-major), g 6, the squared residual, count
 constexpr int NSLOT = 32;         // a partial's row (256 B)
+constexpr int WSLOT = 29;         // ... whose slot behind the sums holds the robust weights' sum (0 from a plain kernel)
 
 // per-job state beside the fp32 pose the search reads
 struct State {
@@ -37,7 +40,21 @@ struct State {
   int status;   // 0 iteration cap, 1 converged, 2 degenerate
   int stopped;  // frozen: later passes leave the job alone
   int pad_;
+  double wsum;  // of the last evaluation: the robust weights' sum (0 from a plain kernel)
 };
+
+// The scale of a robust accumulate kernel's pass, squared: the table's entry at the job's update index (the last entry
+// from there on), or `fixed` without a table -- the evaluation after the loop and the system form.
+struct Scale2 {
+  const double* tab;
+  uint32_t n_tab;
+  double fixed;
+};
+__device__ __forceinline__ double scale2_of(const Scale2& s, const State& st) {
+  if (!s.tab) return s.fixed;
+  const uint32_t k = st.iters < s.n_tab - 1 ? st.iters : s.n_tab - 1;
+  return s.tab[k];
+}
 
 // keep the half of v[0 .. 2H) this lane owns at the step that exchanges with lane ^ O, add the partner's share of it
 template <int O, int H>
@@ -70,9 +87,11 @@ __device__ __forceinline__ void reduce_store(double* v, double (*red)[NSLOT] /* 
   }
 }
 
-// mode 0: a pass (solve, update, stop test).  mode 1: evaluation only (sum_r2, count, rmse; `exp`, if given, gets the
-// job's 29 sums).
-static __global__ __launch_bounds__(64) void solve_kernel(const double* __restrict__ partials, uint32_t n_blk, State* __restrict__ states,
+// mode 0: a pass (solve, update, stop test).  mode 1: evaluation only (sum_r2, count, rmse, wsum; `exp`, if given, gets
+// the job's 29 sums).  stop_from: the first update index at which the stop test counts (0: every update; a robust
+// schedule's first index at its final scale).
+static __global__ __launch_bounds__(64) void solve_kernel(const double* __restrict__ partials, uint32_t n_blk, uint32_t stop_from,
+                                                          State* __restrict__ states,
                                                           float* __restrict__ pose_f32, size_t pose_stride, double trans_eps, double rot_eps,
                                                           int mode, uint32_t* __restrict__ done, double* __restrict__ exp) {
   __shared__ double tot[NSLOT];
@@ -93,6 +112,7 @@ static __global__ __launch_bounds__(64) void solve_kernel(const double* __restri
   st.sum_r2 = tot[27];
   st.count = (uint64_t)cnt;
   st.rmse = cnt > 0.0 ? sqrt(tot[27] / cnt) : 0.0;
+  st.wsum = tot[WSLOT];
   if (mode != 0) return;
   auto stop = [&](int status) {
     st.status = status;
@@ -168,9 +188,10 @@ static __global__ __launch_bounds__(64) void solve_kernel(const double* __restri
     st.Td[k] = Tn[k];
     pose_f32[(size_t)job * pose_stride + k] = (float)Tn[k];
   }
-  st.iters += 1;
+  const uint32_t k = st.iters;
+  st.iters = k + 1;
   const double vn = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
-  if (trans_eps > 0.0 && rot_eps > 0.0 && vn < trans_eps && th < rot_eps) stop(1);
+  if (trans_eps > 0.0 && rot_eps > 0.0 && vn < trans_eps && th < rot_eps && k >= stop_from) stop(1);
 }
 
 }  // namespace gn6

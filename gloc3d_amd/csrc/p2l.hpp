@@ -33,11 +33,22 @@ struct Ctx {
   void* self;
 };
 
+// The robust half of a call (the _robust entries; include/gloc3d.h): the block, the pass the system form evaluates at and
+// the outputs the plain entries do not have.  prm null or of kind NONE: the plain kernels.
+struct RobustArgs {
+  const gloc_robust_params* prm = nullptr;
+  uint32_t pass = 0;
+  float* out_weight = nullptr;  // [n]: the weights' sum over the count of the final evaluation
+  double* out_wsum = nullptr;   // system form
+  uint32_t kind() const { return prm ? prm->kind : (uint32_t)GLOC_ROBUST_NONE; }
+};
+
 int check_params(const gloc_p2l_params* prm);
 // Refines every job from init_T ([n][16] or null: identity).  system36/g6/sum_r2/count non-null: ONE evaluation at init_T
 // of job 0 instead (gloc_reg_p2l_system).  Returns after the results have been copied out.
 int run(const Ctx& x, const TargetView* tgts, const float* init_T, const gloc_p2l_params* prm, float* out_T, float* out_rmse,
-        uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum_r2, uint64_t* out_count);
+        uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum_r2, uint64_t* out_count,
+        const RobustArgs& rb = RobustArgs());
 
 }  // namespace p2l
 }  // namespace gloc

@@ -4,6 +4,10 @@
 //                      target point and its normal, r = n.(p - q), J = [p x n ; n]; the 29 sums of a pass (21 entries of
 //                      the upper triangle of J J^T, 6 of J r, r^2, the count) in fp64, one partial per work-group
 //
+// KIND (robust.hpp; 0: none, the plain entries' instantiation, whose arithmetic is what it was before there were kinds):
+// the lane that owns the pair takes s2 = r^2 and the weight w of the pass's scale, and forms its 27 contributions to H
+// and g from w J in place of one J -- (w J) J^T and (w J) r -- leaving r^2 and the count alone; slot 29 gets the weight.
+//
 // The reduction of those sums, the solve kernel and the note on registers are in gn6_kernels.hpp, shared with the
 // generalized ICP.  The correspondences are the registration's own exact 1-NN pass (reg.hip: launch_nn), unchanged.
 #pragma once
@@ -28,11 +32,13 @@ struct Target {  // of a job
   uint32_t n, pad_;
 };
 
+template <int KIND>
 __global__ __launch_bounds__(ACC_THREADS) void p2l_accum_kernel(const f32x4* __restrict__ src_pts, uint32_t n_src,
                                                                 const Target* __restrict__ tgts, const float* __restrict__ pose_f32,
                                                                 size_t pose_stride /* floats */, const State* __restrict__ states,
                                                                 const uint32_t* __restrict__ corr, const float* __restrict__ d2in, size_t ld,
-                                                                float gate2, bool skip_stopped, double* __restrict__ partials /* [job][n_blk][NSLOT] */) {
+                                                                float gate2, bool skip_stopped, double* __restrict__ partials /* [job][n_blk][NSLOT] */,
+                                                                gn6::Scale2 sc) {
   __shared__ double red[ACC_THREADS / 64][NSLOT];
   const uint32_t job = blockIdx.y;
   if (skip_stopped && states[job].stopped) return;  // (uniform; the solve does not read a stopped job's partials)
@@ -61,15 +67,25 @@ __global__ __launch_bounds__(ACC_THREADS) void p2l_accum_kernel(const f32x4* __r
         double J[6];
         reg::cross3(P, N, J);
         J[3] = N[0]; J[4] = N[1]; J[5] = N[2];
+        v[27] = r * r;
+        v[28] = 1.0;
+        double Jw[6];  // w J: the weight rides on one factor of J J^T and of J r (the plain kernel: J itself)
+        if (KIND != GLOC_ROBUST_NONE) {
+          const double w = robust::weight<KIND>(v[27], gn6::scale2_of(sc, states[job]));
+#pragma unroll
+          for (int a = 0; a < 6; ++a) Jw[a] = J[a] * w;
+          v[gn6::WSLOT] = w;
+        } else {
+#pragma unroll
+          for (int a = 0; a < 6; ++a) Jw[a] = J[a];
+        }
         int e = 0;
 #pragma unroll
         for (int a = 0; a < 6; ++a)
 #pragma unroll
-          for (int b = a; b < 6; ++b) v[e++] = J[a] * J[b];
+          for (int b = a; b < 6; ++b) v[e++] = Jw[a] * J[b];
 #pragma unroll
-        for (int a = 0; a < 6; ++a) v[21 + a] = J[a] * r;
-        v[27] = r * r;
-        v[28] = 1.0;
+        for (int a = 0; a < 6; ++a) v[21 + a] = Jw[a] * r;
       }
     }
   }

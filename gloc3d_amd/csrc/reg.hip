@@ -16,6 +16,7 @@
 #include "p2l.hpp"
 #include "pairgraph.hpp"
 #include "reg_kernels.hpp"
+#include "robust.hpp"
 #include "scan_store.hpp"
 #include "vgicp.hpp"
 
@@ -908,21 +909,22 @@ int run_refine(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, 
 
 int run_p2l(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_p2l_params* prm,
             float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6,
-            double* out_sum_r2, uint64_t* out_count) {
+            double* out_sum_r2, uint64_t* out_count, const gloc::p2l::RobustArgs& rb = gloc::p2l::RobustArgs()) {
   GLOC_TRY(gloc::p2l::check_params(prm));
   return run_refine(h, src_id, tgt_ids, n, init_T, prm->normal_k, false,
                     [&](const gloc::p2l::Ctx& x, const float*, const gloc::p2l::TargetView* tv) {
-                      return gloc::p2l::run(x, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum_r2, out_count);
+                      return gloc::p2l::run(x, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum_r2, out_count,
+                                            rb);
                     });
 }
 
 int run_gicp(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_gicp_params* prm,
              float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum,
-             uint64_t* out_count) {
+             uint64_t* out_count, const gloc::p2l::RobustArgs& rb = gloc::p2l::RobustArgs()) {
   return run_refine(h, src_id, tgt_ids, n, init_T, prm->normal_k, true,
                     [&](const gloc::p2l::Ctx& x, const float* src_nrm, const gloc::p2l::TargetView* tv) {
                       return gloc::gicp::run(x, src_nrm, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum,
-                                             out_count);
+                                             out_count, rb);
                     });
 }
 
@@ -1821,6 +1823,100 @@ int gloc_reg_vgicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_i
   GLOC_HIP(hipSetDevice(h->device));
   return gloc::vgicp::run(vgicp_ctx(h), src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
                           out_count);
+}
+
+// The robust entries (robust.hpp): the plain ones' calls with the robust half of the arguments behind them.  Both blocks
+// are looked at before the handle.
+int gloc_reg_p2l_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                                  const gloc_p2l_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse,
+                                  uint32_t* out_iters, int* out_status, float* out_weight) {
+  GLOC_TRY(gloc::p2l::check_params(prm));
+  GLOC_TRY(gloc::robust::check_params(robust));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  gloc::p2l::RobustArgs rb;
+  rb.prm = robust;
+  rb.out_weight = out_weight;
+  return run_p2l(h, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+                 nullptr, rb);
+}
+
+int gloc_reg_p2l_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_p2l_params* prm,
+                               const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6, double* out_sum_r2,
+                               uint64_t* out_count, double* out_wsum) {
+  GLOC_TRY(gloc::p2l::check_params(prm));
+  GLOC_TRY(gloc::robust::check_params(robust));
+  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum_r2 && out_count && out_wsum, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  gloc::p2l::RobustArgs rb;
+  rb.prm = robust;
+  rb.pass = pass;
+  rb.out_wsum = out_wsum;
+  return run_p2l(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum_r2, out_count,
+                 rb);
+}
+
+int gloc_reg_gicp_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                                   const gloc_gicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse,
+                                   uint32_t* out_iters, int* out_status, float* out_weight) {
+  GLOC_TRY(gloc::gicp::check_params(prm));
+  GLOC_TRY(gloc::robust::check_params(robust));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  gloc::p2l::RobustArgs rb;
+  rb.prm = robust;
+  rb.out_weight = out_weight;
+  return run_gicp(h, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+                  nullptr, rb);
+}
+
+int gloc_reg_gicp_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_gicp_params* prm,
+                                const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6, double* out_sum,
+                                uint64_t* out_count, double* out_wsum) {
+  GLOC_TRY(gloc::gicp::check_params(prm));
+  GLOC_TRY(gloc::robust::check_params(robust));
+  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count && out_wsum, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  gloc::p2l::RobustArgs rb;
+  rb.prm = robust;
+  rb.pass = pass;
+  rb.out_wsum = out_wsum;
+  return run_gicp(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum, out_count, rb);
+}
+
+int gloc_reg_vgicp_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                                    const gloc_vgicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse,
+                                    uint32_t* out_iters, int* out_status, float* out_weight) {
+  GLOC_TRY(gloc::vgicp::check_params(prm));
+  GLOC_TRY(gloc::robust::check_params(robust));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  gloc::p2l::RobustArgs rb;
+  rb.prm = robust;
+  rb.out_weight = out_weight;
+  return gloc::vgicp::run(vgicp_ctx(h), src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
+                          nullptr, nullptr, rb);
+}
+
+int gloc_reg_vgicp_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16,
+                                 const gloc_vgicp_params* prm, const gloc_robust_params* robust, uint32_t pass, double* out_H36,
+                                 double* out_g6, double* out_sum, uint64_t* out_count, double* out_wsum) {
+  GLOC_TRY(gloc::vgicp::check_params(prm));
+  GLOC_TRY(gloc::robust::check_params(robust));
+  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count && out_wsum, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  gloc::p2l::RobustArgs rb;
+  rb.prm = robust;
+  rb.pass = pass;
+  rb.out_wsum = out_wsum;
+  return gloc::vgicp::run(vgicp_ctx(h), src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
+                          out_count, rb);
 }
 
 int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3,

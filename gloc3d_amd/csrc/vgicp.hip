@@ -60,7 +60,7 @@ int check_params(const gloc_vgicp_params* p) {
 
 int run(const Ctx& x, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_vgicp_params* prm,
         float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum,
-        uint64_t* out_count) {
+        uint64_t* out_count, const p2l::RobustArgs& rb) {
   GLOC_TRY(check_params(prm));
   GLOC_REQUIRE(tgt_ids && n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096] or null target ids", n);
   GLOC_REQUIRE(x.store, GLOC_ERR_INVALID, "unknown scan id %u", src_id);
@@ -119,11 +119,15 @@ int run(const Ctx& x, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const 
   const double gate2 = prm->max_corr_dist > 0.f ? (double)prm->max_corr_dist * (double)prm->max_corr_dist : 0.0;
   const float inv_res = 1.0f / prm->resolution;
   const float* src_nrm = src.nrm;
-  auto accum = [&](const Target* d_tgts, const gn6::State* states, float, bool skip_stopped, double* partials, uint32_t n_blk) {
-    hipLaunchKernelGGL(vgicp_accum_kernel, dim3(n_blk, g.n_jobs), dim3(gn6::ACC_THREADS), 0, q, g.src_pts, src_nrm, g.n_src, d_tgts,
-                       g.pose_f32, g.pose_stride, states, inv_res, prm->neighbors, gate2, a, skip_stopped, partials);
+  auto accum = [&](const Target* d_tgts, const gn6::State* states, float, bool skip_stopped, double* partials, uint32_t n_blk,
+                   const gn6::Scale2& sc) {
+    gn6::for_kind(rb.kind(), [&](auto kind) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(vgicp_accum_kernel<decltype(kind)::value>), dim3(n_blk, g.n_jobs), dim3(gn6::ACC_THREADS), 0, q,
+                         g.src_pts, src_nrm, g.n_src, d_tgts, g.pose_f32, g.pose_stride, states, inv_res, prm->neighbors, gate2, a,
+                         skip_stopped, partials, sc);
+    });
   };
-  return gn6::run(g, lp, ht, init_T, accum, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum, out_count);
+  return gn6::run(g, lp, ht, init_T, accum, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum, out_count, rb);
 }
 
 int voxels(const Ctx& x, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3, uint32_t* out_count,

@@ -24,7 +24,7 @@ int check_params(const gloc_vgicp_params* prm);
 // ONE evaluation at init_T of job 0 instead (gloc_reg_vgicp_system).  Returns after the results have been copied out.
 int run(const Ctx& x, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_vgicp_params* prm,
         float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum,
-        uint64_t* out_count);
+        uint64_t* out_count, const p2l::RobustArgs& rb = p2l::RobustArgs());
 int voxels(const Ctx& x, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3, uint32_t* out_count,
            double* out_mean3, double* out_nn6, size_t* n_voxels);
 

@@ -19,6 +19,11 @@
 //   neighbors  7   (0,0,0) (-1,0,0) (1,0,0) (0,-1,0) (0,1,0) (0,0,-1) (0,0,1)
 //   neighbors 27   dz, dy, dx from -1 to 1 each, dx fastest
 //
+// KIND (robust.hpp; 0: none, the plain entries' instantiation, whose arithmetic is what it was before there were kinds):
+// a pair's s2 = e^T S^-1 e is taken from the adjugate BEFORE the voxel's count rides on M -- (e^T adj e) / det -- and the
+// robust weight of the pass's scale then rides on M beside the count; sum w e^T M e stays unweighted by it (N s2) and the
+// weights' sum is one more loop-carried accumulator, slot 29.
+//
 // Registers: with more than one offset the 29 doubles ARE loop-carried (58 registers), unlike the one-pair kernels of
 // gn6_kernels.hpp; the loop over the offsets is kept rolled so that one pair's temporaries are live at a time.  The
 // compiler's figures are in DESIGN.md.  No floating-point atomics: a lane adds its pairs in offset order, the rest is
@@ -112,12 +117,14 @@ __device__ __forceinline__ void offset_of(uint32_t neighbors, uint32_t o, int* d
   }
 }
 
+template <int KIND>
 static __global__ __launch_bounds__(ACC_THREADS) void vgicp_accum_kernel(const f32x4* __restrict__ src_pts, const float* __restrict__ src_nrm,
                                                                          uint32_t n_src, const Target* __restrict__ tgts,
                                                                          const float* __restrict__ pose_f32, size_t pose_stride /* floats */,
                                                                          const State* __restrict__ states, float inv_res, uint32_t neighbors,
                                                                          double gate2 /* <= 0: off */, double a, bool skip_stopped,
-                                                                         double* __restrict__ partials /* [job][n_blk][NSLOT] */) {
+                                                                         double* __restrict__ partials /* [job][n_blk][NSLOT] */,
+                                                                         gn6::Scale2 sc) {
   __shared__ double red[ACC_THREADS / 64][NSLOT];
   const uint32_t job = blockIdx.y;
   if (skip_stopped && states[job].stopped) return;  // (uniform; the solve does not read a stopped job's partials)
@@ -149,6 +156,7 @@ static __global__ __launch_bounds__(ACC_THREADS) void vgicp_accum_kernel(const f
 #pragma unroll
       for (int r = 0; r < 3; ++r) m[r] = ((double)Tf[3 * r] * ns[0] + (double)Tf[3 * r + 1] * ns[1]) + (double)Tf[3 * r + 2] * ns[2];
       const double mm[6] = {m[0] * m[0], m[0] * m[1], m[0] * m[2], m[1] * m[1], m[1] * m[2], m[2] * m[2]};
+      const double c2 = KIND != GLOC_ROBUST_NONE ? gn6::scale2_of(sc, states[job]) : 0.0;
 #pragma nounroll
       for (uint32_t o = 0; o < neighbors; ++o) {
         int d[3];
@@ -178,7 +186,18 @@ static __global__ __launch_bounds__(ACC_THREADS) void vgicp_accum_kernel(const f
         const double syz = -a * (V.nn[4] + mm[4]), szz = 2.0 - a * (V.nn[5] + mm[5]);
         const double cxx = syy * szz - syz * syz, cxy = sxz * syz - sxy * szz, cxz = sxy * syz - sxz * syy;
         const double cyy = sxx * szz - sxz * sxz, cyz = sxy * sxz - sxx * syz, czz = sxx * syy - sxy * sxy;
-        const double inv = w / ((sxx * cxx + sxy * cxy) + sxz * cxz);  // the weight rides on M
+        double inv, s2 = 0.0;
+        if (KIND == GLOC_ROBUST_NONE) {
+          inv = w / ((sxx * cxx + sxy * cxy) + sxz * cxz);  // the weight rides on M
+        } else {
+          const double inv0 = 1.0 / ((sxx * cxx + sxy * cxy) + sxz * cxz);
+          const double ce[3] = {(cxx * E[0] + cxy * E[1]) + cxz * E[2], (cxy * E[0] + cyy * E[1]) + cyz * E[2],
+                                (cxz * E[0] + cyz * E[1]) + czz * E[2]};
+          s2 = ((E[0] * ce[0] + E[1] * ce[1]) + E[2] * ce[2]) * inv0;
+          const double wr = robust::weight<KIND>(s2, c2);
+          inv = (w * wr) * inv0;  // the count and the robust weight ride on M
+          v[gn6::WSLOT] += wr;
+        }
         const double M[3][3] = {{cxx * inv, cxy * inv, cxz * inv}, {cxy * inv, cyy * inv, cyz * inv}, {cxz * inv, cyz * inv, czz * inv}};
         double Me[3];
 #pragma unroll
@@ -205,7 +224,11 @@ static __global__ __launch_bounds__(ACC_THREADS) void vgicp_accum_kernel(const f
         v[20] += M[2][2];
         v[21] += gw[0]; v[22] += gw[1]; v[23] += gw[2];
         v[24] += Me[0]; v[25] += Me[1]; v[26] += Me[2];
-        v[27] += (E[0] * Me[0] + E[1] * Me[1]) + E[2] * Me[2];
+        if (KIND == GLOC_ROBUST_NONE) {
+          v[27] += (E[0] * Me[0] + E[1] * Me[1]) + E[2] * Me[2];
+        } else {
+          v[27] += w * s2;
+        }
         v[28] += 1.0;
       }
     }

@@ -676,6 +676,74 @@ int gloc_reg_vgicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_i
 int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3,
                           uint32_t* out_count, double* out_mean3, double* out_nn6, size_t* n_voxels);
 
+/* ---- robust weighting of the three Gauss-Newton refinements ---------------------------------------------- *
+ * Iteratively re-weighted least squares (an M-estimator per pair, as Open3D's RobustKernel and small_gicp's Huber and
+ * Cauchy factors) on point-to-plane, generalized and voxelized generalized ICP.  The gate max_corr_dist takes a pair
+ * in with full weight or leaves it out; a moved object, other traffic and the half of a scan that does not overlap the
+ * stored one all find a partner inside any gate wide enough to converge from a retrieval-grade guess.  Here every pair
+ * is weighted by its own residual, on a scale that may be annealed from a wide start (graduated non-convexity).
+ * Opt-in, through the _robust entries only: the plain entries do not change.  The executable contract is the float64
+ * restatement tests/robust_ref.py.
+ *
+ * The residual of a pair, squared, in fp64:
+ *   point-to-plane     s2 = r^2, r = n_j . (p - q_j): metres^2, so `scale` is in metres;
+ *   generalized ICP    s2 = e^T M e: dimensionless.  For two coplanar surfaces M is 1 / (2 plane_eps) along their normal,
+ *                      so s2 = e_n^2 / (2 plane_eps): a normal distance of d metres counts sqrt(s2) = 22.4 d at the default
+ *                      plane_eps = 1e-3, and `scale` is in those units;
+ *   voxelized          s2 = e^T M e of the (point, voxel) term, M = S^-1 BEFORE the voxel's point count N multiplies it.
+ * The weight, with c the scale of the pass and t = s2 / (c c):
+ *   HUBER          t <= 1 ? 1 : 1 / sqrt(t)          CAUCHY         1 / (1 + t)
+ *   TUKEY          t <= 1 ? (1 - t)^2 : 0            GEMAN_MCCLURE  1 / ((1 + t) (1 + t))
+ * What it multiplies: the pair's 27 contributions to H and g.  The squared-residual sum and the pair count stay what the
+ * plain entries make them -- rmse, the "fewer than 6 pairs" rule and the count keep their meaning -- and the sum of the
+ * weights is one more output.  A pair of weight 0 is still a pair: if every weight is 0, H is 0, the pivot rule makes
+ * the job degenerate (status 2) and the pose stays.  max_corr_dist is applied first and unchanged.
+ * The schedule:  c(0) = scale_start if one is set, else scale;  c(k + 1) = max(scale, c(k) anneal), in fp64 with the
+ * floats widened.  The update a job applies as its k-th (k = its `iters` before it) uses c(k).  The stop test (status 1)
+ * is honoured only on an update whose c(k) == scale: before that a small step means "this scale is exhausted", not
+ * "done".  The evaluation after the loop (rmse, the weights' sum) uses `scale`. */
+enum { GLOC_ROBUST_NONE = 0, GLOC_ROBUST_HUBER = 1, GLOC_ROBUST_CAUCHY = 2, GLOC_ROBUST_TUKEY = 3, GLOC_ROBUST_GEMAN_MCCLURE = 4 };
+typedef struct gloc_robust_params {
+  uint32_t kind;       /* NONE: the other three fields are ignored */
+  float scale;         /* c > 0, finite: where a residual stops counting fully (units above) */
+  float scale_start;   /* 0: no schedule; otherwise finite and >= scale */
+  float anneal;        /* with a schedule: in (0, 1), the factor per applied update */
+} gloc_robust_params;  /* 16 bytes */
+
+/* kind NONE and zeros. */
+void gloc_robust_default_params(gloc_robust_params* p);
+/* What the device uses, on the host: c(pass) (0 for kind NONE, which has no scale), and the weight of a squared residual
+ * s2 at c(pass) (1 for kind NONE).
+ * GLOC_ERR_INVALID: a null argument or a block the entries below refuse. */
+int gloc_robust_scale(const gloc_robust_params* prm, uint32_t pass, double* c);
+int gloc_robust_weight(const gloc_robust_params* prm, uint32_t pass, double s2, double* w);
+
+/* The plain entries' arguments with the robust block behind the method's own, and one more output: out_weight (may be
+ * NULL), per candidate the weights' sum over the pair count of the final evaluation, 0 where the count is 0.  With kind
+ * NONE every output equals the plain entry's bit for bit and out_weight is 1 where there are pairs.  GLOC_ERR_INVALID
+ * beyond the plain entries', looked at before the handle: a null robust block; kind > 4; with a kind other than NONE,
+ * scale <= 0 or not finite, scale_start negative, not finite or in (0, scale), anneal outside (0, 1) with a schedule. */
+int gloc_reg_p2l_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                                  const gloc_p2l_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse,
+                                  uint32_t* out_iters, int* out_status, float* out_weight);
+int gloc_reg_gicp_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                                   const gloc_gicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse,
+                                   uint32_t* out_iters, int* out_status, float* out_weight);
+int gloc_reg_vgicp_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                                    const gloc_vgicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse,
+                                    uint32_t* out_iters, int* out_status, float* out_weight);
+/* One evaluation at T16 with the weights of c(pass): the plain entries' outputs (the squared sum and the count
+ * unweighted) and out_wsum, the sum of the weights. */
+int gloc_reg_p2l_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_p2l_params* prm,
+                               const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6, double* out_sum_r2,
+                               uint64_t* out_count, double* out_wsum);
+int gloc_reg_gicp_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_gicp_params* prm,
+                                const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6, double* out_sum,
+                                uint64_t* out_count, double* out_wsum);
+int gloc_reg_vgicp_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16,
+                                 const gloc_vgicp_params* prm, const gloc_robust_params* robust, uint32_t pass, double* out_H36,
+                                 double* out_g6, double* out_sum, uint64_t* out_count, double* out_wsum);
+
 /* ---- FPFH feature-based global registration ------------------------------------------------------------- *
  * The 3-D answer to "where is this scan, from nothing": local shape descriptors (Fast Point Feature Histograms: Rusu,
  * Blodow & Beetz; pcl::FPFHEstimation in its k-nearest form), descriptor matching, and the RANSAC stage of

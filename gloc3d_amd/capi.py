@@ -280,6 +280,9 @@ _PROTOS = [
     ("gloc_reg_p2l_batch_ids_robust", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(P2lParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
     ("gloc_reg_gicp_batch_ids_robust", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(GicpParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
     ("gloc_reg_vgicp_batch_ids_robust", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(VgicpParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_p2l_pairs", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(P2lParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_gicp_pairs", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(GicpParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_vgicp_pairs", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(VgicpParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
     ("gloc_reg_p2l_system_robust", _i, [_vp, _u32, _u32, _vp, C.POINTER(P2lParams), C.POINTER(RobustParams), _u32, _vp, _vp, C.POINTER(C.c_double),
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     ("gloc_reg_gicp_system_robust", _i, [_vp, _u32, _u32, _vp, C.POINTER(GicpParams), C.POINTER(RobustParams), _u32, _vp, _vp, C.POINTER(C.c_double),
@@ -1332,6 +1335,35 @@ class Registrar(_Handle):
         check(lib().gloc_reg_vgicp_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
                                              C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
         return T, rmse, iters, status
+
+    def _pairs(self, fn, prm, src_ids, tgt_ids, init_T, robust):
+        """A pair-list entry (gloc_reg_<m>_pairs): row c is (src_ids[c], tgt_ids[c]); None in tgt_ids is "no target"."""
+        src = np.ascontiguousarray(np.atleast_1d(src_ids), np.uint32)
+        tgt = np.ascontiguousarray([NO_SCAN if t is None else t for t in np.atleast_1d(np.asarray(tgt_ids, dtype=object))], np.uint32)
+        n = src.shape[0]
+        if tgt.shape[0] != n:
+            raise ValueError("src_ids and tgt_ids differ in length")
+        it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
+        T = np.empty((n, 4, 4), np.float32)
+        rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
+        weight = None if robust is None else np.empty(n, np.float32)
+        check(fn(self._h, _np_ptr(src), _np_ptr(tgt), n, None if it is None else _np_ptr(it), C.byref(prm),
+                 None if robust is None else C.byref(robust), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status),
+                 None if weight is None else _np_ptr(weight)))
+        return (T, rmse, iters, status) if robust is None else (T, rmse, iters, status, weight)
+
+    def p2l_pairs(self, src_ids, tgt_ids, init_T=None, params=None, robust=None):
+        """Point-to-plane ICP of a list of (source, target) pairs in one call (gloc_reg_p2l_pairs): what p2l_batch returns,
+        row c that of p2l_batch(src_ids[c], [tgt_ids[c]]) bit for bit.  None in tgt_ids: no target (the row of an empty one)."""
+        return self._pairs(lib().gloc_reg_p2l_pairs, params or default_p2l_params(), src_ids, tgt_ids, init_T, robust)
+
+    def gicp_pairs(self, src_ids, tgt_ids, init_T=None, params=None, robust=None):
+        """Generalized ICP of a list of (source, target) pairs in one call (gloc_reg_gicp_pairs): as p2l_pairs."""
+        return self._pairs(lib().gloc_reg_gicp_pairs, params or default_gicp_params(), src_ids, tgt_ids, init_T, robust)
+
+    def vgicp_pairs(self, src_ids, tgt_ids, init_T=None, params=None, robust=None):
+        """Voxelized generalized ICP of a list of (source, target) pairs in one call (gloc_reg_vgicp_pairs): as p2l_pairs."""
+        return self._pairs(lib().gloc_reg_vgicp_pairs, params or default_vgicp_params(), src_ids, tgt_ids, init_T, robust)
 
     def vgicp_system(self, src_id, tgt_id, T=None, params=None, robust=None, robust_pass=0):
         """One evaluation of the voxelized generalized ICP normal equations at T: H [6, 6], g [6], the weighted sum of

@@ -6,8 +6,8 @@ namespace gloc {
 namespace gicp {
 
 int check_params(const gloc_gicp_params* prm);
-// As p2l::run, with the source's normals (the order of x.src_pts; zero = none) beside the targets'.
-int run(const p2l::Ctx& x, const float* src_nrm, const p2l::TargetView* tgts, const float* init_T, const gloc_gicp_params* prm,
+// As p2l::run, with the sources' normals (x.srcs[c].nrm, the order of its pts; zero = none) beside the targets'.
+int run(const p2l::Ctx& x, const p2l::TargetView* tgts, const float* init_T, const gloc_gicp_params* prm,
         float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum,
         uint64_t* out_count, const p2l::RobustArgs& rb = p2l::RobustArgs());
 

@@ -45,21 +45,23 @@ struct Target {  // of a job
 };
 
 template <int KIND>
-__global__ __launch_bounds__(ACC_THREADS) void gicp_accum_kernel(const f32x4* __restrict__ src_pts, const float* __restrict__ src_nrm,
-                                                                 uint32_t n_src, const Target* __restrict__ tgts,
+__global__ __launch_bounds__(ACC_THREADS) void gicp_accum_kernel(const gn6::Source* __restrict__ srcs, const Target* __restrict__ tgts,
                                                                  const float* __restrict__ pose_f32, size_t pose_stride /* floats */,
                                                                  const State* __restrict__ states, const uint32_t* __restrict__ corr,
                                                                  const float* __restrict__ d2in, size_t ld, float gate2, double a,
-                                                                 bool skip_stopped, double* __restrict__ partials /* [job][n_blk][NSLOT] */,
+                                                                 bool skip_stopped,
+                                                                 double* __restrict__ partials /* [srcs[job].row0 + block][NSLOT] */,
                                                                  gn6::Scale2 sc) {
   __shared__ double red[ACC_THREADS / 64][NSLOT];
   const uint32_t job = blockIdx.y;
+  const gn6::Source S = srcs[job];
+  if (blockIdx.x >= S.n_blk) return;                // (uniform: the grid is as wide as the batch's longest source)
   if (skip_stopped && states[job].stopped) return;  // (uniform; the solve does not read a stopped job's partials)
   const uint32_t i = blockIdx.x * ACC_THREADS + threadIdx.x;
   double v[NSLOT];
 #pragma unroll
   for (int k = 0; k < NSLOT; ++k) v[k] = 0.0;
-  if (i < n_src) {
+  if (i < S.n) {
     const Target T = tgts[job];
     const uint32_t j = corr[(size_t)job * ld + i];
     const float d2 = d2in[(size_t)job * ld + i];
@@ -68,14 +70,14 @@ __global__ __launch_bounds__(ACC_THREADS) void gicp_accum_kernel(const f32x4* __
       float Tf[12];
 #pragma unroll
       for (int k = 0; k < 12; ++k) Tf[k] = pose_f32[(size_t)job * pose_stride + k];
-      const f32x4 s = src_pts[i];
+      const f32x4 s = S.pts[i];
       const f32x4 q = T.pts[j];
       float px, py, pz;
       reg::xform(Tf, s.x, s.y, s.z, px, py, pz);
       const double P[3] = {(double)px, (double)py, (double)pz};
       const double E[3] = {P[0] - (double)q.x, P[1] - (double)q.y, P[2] - (double)q.z};
       const double B[3] = {(double)T.nrm[3 * (size_t)j], (double)T.nrm[3 * (size_t)j + 1], (double)T.nrm[3 * (size_t)j + 2]};
-      const double ns[3] = {(double)src_nrm[3 * (size_t)i], (double)src_nrm[3 * (size_t)i + 1], (double)src_nrm[3 * (size_t)i + 2]};
+      const double ns[3] = {(double)S.nrm[3 * (size_t)i], (double)S.nrm[3 * (size_t)i + 1], (double)S.nrm[3 * (size_t)i + 2]};
       double m[3];
 #pragma unroll
       for (int r = 0; r < 3; ++r) m[r] = ((double)Tf[3 * r] * ns[0] + (double)Tf[3 * r + 1] * ns[1]) + (double)Tf[3 * r + 2] * ns[2];
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(ACC_THREADS) void gicp_accum_kernel(const f32x4* __
       v[28] = 1.0;
     }
   }
-  gn6::reduce_store(v, red, partials + ((size_t)job * gridDim.x + blockIdx.x) * NSLOT);
+  gn6::reduce_store(v, red, partials + ((size_t)S.row0 + blockIdx.x) * NSLOT);
 }
 
 }  // namespace gicp

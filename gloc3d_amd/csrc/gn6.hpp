@@ -18,7 +18,7 @@ namespace gloc {
 namespace p2l {
 
 struct Ws {  // (one per handle, whichever refinement runs: the calls are synchronous)
-  DevBuf tgts, states, partials, done, exp, c2tab;
+  DevBuf tgts, srcs, states, partials, done, exp, c2tab;
   uint32_t* h_done = nullptr;  // pinned
   hipEvent_t ev = nullptr;
   ~Ws() {
@@ -52,9 +52,10 @@ struct Loop {  // what the refinements' parameter blocks have in common
 };
 
 // Refines every job from init_T ([n][16] or null: identity); any of the last four non-null: ONE evaluation at init_T of
-// job 0 instead.  `tgts`: the jobs' targets as the accumulate kernel takes them, copied to the device; accum(targets on
-// the device, states, gate^2, skip_stopped, partials, n_blk, the pass's Scale2) enqueues that kernel.  Returns after the
-// results have been copied out.
+// job 0 instead.  `tgts`: the jobs' targets as the accumulate kernel takes them, copied to the device beside the table of
+// the jobs' sources (gn6::Source, made here from x.srcs: every job's work-group count and its first row of the partials);
+// accum(targets and sources on the device, states, gate^2, skip_stopped, partials, the grid's width -- the largest
+// work-group count --, the pass's Scale2) enqueues that kernel.  Returns after the results have been copied out.
 //
 // rb (robust.hpp): with a kind other than NONE accum is also handed the pass's scale -- the table of c(k)^2 made here
 // with the host helper's own function, indexed by each job's update count, during the loop; scale^2 for the evaluation
@@ -72,7 +73,17 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
   const uint32_t n = x.n_jobs;
   const bool system = out_H36 || out_g6 || out_sum || out_count || rb.out_wsum;
   const bool weighted = rb.kind() != GLOC_ROBUST_NONE;
-  const uint32_t n_blk = std::max<uint32_t>(1, (x.n_src + ACC_THREADS - 1) / ACC_THREADS);
+  // a job's work-groups and rows depend on its own source alone: the partition a call on the job alone makes
+  std::vector<Source> hsrc(n);
+  uint64_t n_rows = 0;
+  uint32_t n_blk = 1;  // the grid's width
+  for (uint32_t c = 0; c < n; ++c) {
+    const p2l::SourceView& sv = x.srcs[c];
+    const uint32_t nb = (uint32_t)(((uint64_t)sv.n + ACC_THREADS - 1) / ACC_THREADS);
+    hsrc[c] = Source{sv.pts, sv.nrm, sv.n, nb, n_rows};
+    n_rows += nb;
+    n_blk = std::max(n_blk, nb);
+  }
   std::vector<State> hs(n);
   static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   for (uint32_t c = 0; c < n; ++c) {
@@ -86,12 +97,14 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
   }
   GLOC_TRY(w.tgts.ensure(sizeof(Target) * n, q));
   GLOC_TRY(w.states.ensure(sizeof(State) * n, q));
-  GLOC_TRY(w.partials.ensure(sizeof(double) * NSLOT * (size_t)n_blk * n, q));
+  GLOC_TRY(w.srcs.ensure(sizeof(Source) * n, q));
+  GLOC_TRY(w.partials.ensure(sizeof(double) * NSLOT * (size_t)std::max<uint64_t>(n_rows, 1), q));
   GLOC_TRY(w.done.ensure(16, q));
   GLOC_TRY(w.exp.ensure(sizeof(double) * NSUM * n, q));
   if (!w.h_done) GLOC_HIP(hipHostMalloc(reinterpret_cast<void**>(&w.h_done), 16, hipHostMallocDefault));
   if (!w.ev) GLOC_HIP(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
   GLOC_HIP(hipMemcpyAsync(w.tgts.p, tgts.data(), sizeof(Target) * n, hipMemcpyHostToDevice, q));
+  GLOC_HIP(hipMemcpyAsync(w.srcs.p, hsrc.data(), sizeof(Source) * n, hipMemcpyHostToDevice, q));
   GLOC_HIP(hipMemcpyAsync(w.states.p, hs.data(), sizeof(State) * n, hipMemcpyHostToDevice, q));
   GLOC_HIP(hipMemsetAsync(w.done.p, 0, 16, q));
   // the scales: c(k)^2 for k = 0 .. the last update index a job can have, cut where the schedule has settled
@@ -119,7 +132,7 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
       end_sc.fixed = (double)rb.prm->scale * (double)rb.prm->scale;
     }
   }
-  GLOC_HIP(hipStreamSynchronize(q));  // (tgts and hs are host vectors)
+  GLOC_HIP(hipStreamSynchronize(q));  // (tgts, hsrc and hs are host vectors)
   const float gate2 = lp.max_corr_dist > 0.f ? lp.max_corr_dist * lp.max_corr_dist : 0.f;
   bool warm = false;
   // search, accumulate, solve at the current poses; mode 1: evaluation only
@@ -128,13 +141,13 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
     warm = true;
     {
       ProfScope ps(*x.prof, lp.accum_name, q);
-      accum(w.tgts.template as<Target>(), w.states.template as<State>(), gate2, mode == 0, w.partials.template as<double>(), n_blk,
-            mode == 0 ? loop_sc : end_sc);
+      accum(w.tgts.template as<Target>(), w.srcs.template as<Source>(), w.states.template as<State>(), gate2, mode == 0,
+            w.partials.template as<double>(), n_blk, mode == 0 ? loop_sc : end_sc);
     }
     {
       ProfScope ps(*x.prof, lp.solve_name, q);
-      hipLaunchKernelGGL(solve_kernel, dim3(n), dim3(64), 0, q, w.partials.template as<double>(), n_blk, stop_from,
-                         w.states.template as<State>(), x.pose_f32, x.pose_stride, (double)lp.trans_eps, (double)lp.rot_eps, mode,
+      hipLaunchKernelGGL(solve_kernel, dim3(n), dim3(64), 0, q, w.partials.template as<double>(), w.srcs.template as<Source>(),
+                         stop_from, w.states.template as<State>(), x.pose_f32, x.pose_stride, (double)lp.trans_eps, (double)lp.rot_eps, mode,
                          w.done.template as<uint32_t>(), exp);
     }
     GLOC_HIP(hipGetLastError());

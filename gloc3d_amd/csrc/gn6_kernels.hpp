@@ -14,12 +14,19 @@
 // No floating-point atomics anywhere: a partial's slot is (job, work-group), the solve adds the slots in index order, so
 // a job's sums do not depend on the batch it runs in.
 //
+// Sources: every job has its own (Source) -- one scan repeated by the single-source entries, a scan per row by the pair
+// lists.  A job of n source slots is cut into ceil(n / ACC_THREADS) work-groups of consecutive slots whatever batch it is
+// in, and its partials are that many consecutive rows from row0 (a prefix sum of the counts): the solve adds exactly the
+// rows a call on the job alone adds, in the same order.  The accumulate grid is (the batch's largest count, jobs); a
+// work-group at or beyond its job's own count leaves at once.
+//
 // The kernel is static: p2l.hip and gicp.hip each carry their copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "lane_ops.hpp"
+#include "math3.hpp"  // f32x4
 #include "robust.hpp"
 
 namespace gloc {
@@ -42,6 +49,16 @@ struct State {
   int pad_;
   double wsum;  // of the last evaluation: the robust weights' sum (0 from a plain kernel)
 };
+
+// A job's source as the accumulate kernels take it, and where its partials are.
+struct Source {
+  const reg::f32x4* pts;  // the search order: x, y, z, bits(original index)
+  const float* nrm;       // normals in that order, packed; zero = none (null for point-to-plane, which reads none)
+  uint32_t n;
+  uint32_t n_blk;         // work-groups of ACC_THREADS slots: ceil(n / ACC_THREADS); 0: a job without a target
+  uint64_t row0;          // the job's first row of the partials: the sum of n_blk over the jobs before it
+};
+static_assert(sizeof(Source) == 32, "two to a 64-byte line");
 
 // The scale of a robust accumulate kernel's pass, squared: the table's entry at the job's update index (the last entry
 // from there on), or `fixed` without a table -- the evaluation after the loop and the system form.
@@ -90,7 +107,8 @@ __device__ __forceinline__ void reduce_store(double* v, double (*red)[NSLOT] /* 
 // mode 0: a pass (solve, update, stop test).  mode 1: evaluation only (sum_r2, count, rmse, wsum; `exp`, if given, gets
 // the job's 29 sums).  stop_from: the first update index at which the stop test counts (0: every update; a robust
 // schedule's first index at its final scale).
-static __global__ __launch_bounds__(64) void solve_kernel(const double* __restrict__ partials, uint32_t n_blk, uint32_t stop_from,
+static __global__ __launch_bounds__(64) void solve_kernel(const double* __restrict__ partials /* [sum of n_blk][NSLOT] */,
+                                                          const Source* __restrict__ srcs, uint32_t stop_from,
                                                           State* __restrict__ states,
                                                           float* __restrict__ pose_f32, size_t pose_stride, double trans_eps, double rot_eps,
                                                           int mode, uint32_t* __restrict__ done, double* __restrict__ exp) {
@@ -100,7 +118,8 @@ static __global__ __launch_bounds__(64) void solve_kernel(const double* __restri
   if (mode == 0 && st.stopped) return;
   const int lane = threadIdx.x;
   if (lane < NSLOT) {
-    const double* p = partials + (size_t)job * n_blk * NSLOT + lane;
+    const uint32_t n_blk = srcs[job].n_blk;
+    const double* p = partials + (size_t)srcs[job].row0 * NSLOT + lane;
     double s = 0.0;
     for (uint32_t b = 0; b < n_blk; ++b) s += p[(size_t)b * NSLOT];
     tot[lane] = s;

@@ -15,18 +15,24 @@ struct TargetView {  // a job's target as the search indexes it
   uint32_t n;
 };
 
+struct SourceView {  // a job's source in search order (idx.pts) with its normals in that order (null: none asked for)
+  const reg::f32x4* pts;
+  const float* nrm;
+  uint32_t n;  // 0: a job without a target -- no work-group, no pair, the degenerate row of an empty target
+};
+
 // The handle's view for one batch: its stream, profiler and workspace slot, and the batch reg.hip has set up for the
-// correspondence passes -- the source in search order, where job c's fp32 pose lives (what the search moves the source
-// by; written here after every update), where a pass leaves its matches, and the pass itself.
+// correspondence passes -- every job's source (the single-source entries repeat one), where job c's fp32 pose lives (what
+// the search moves the source by; written here after every update), where a pass leaves its matches, and the pass itself.
 struct Ctx {
   hipStream_t stream;
   Profiler* prof;
   Ws** ws;
-  const reg::f32x4* src_pts;
-  uint32_t n_src, n_jobs;
+  const SourceView* srcs;  // host [n_jobs]
+  uint32_t n_jobs;
   float* pose_f32;     // device: 12 floats (R row-major 9, t 3) per job ...
   size_t pose_stride;  // ... this many floats apart
-  const uint32_t* corr;  // device [job][ld]: sorted source slot -> position in the target's search order
+  const uint32_t* corr;  // device [job][ld], ld over the longest source: sorted source slot -> position in the target's search order
   const float* d2;
   size_t ld;
   int (*nn_pass)(void* self, bool warm);  // enqueues the exact 1-NN pass of every job at the current poses (null: no search)

@@ -33,20 +33,22 @@ struct Target {  // of a job
 };
 
 template <int KIND>
-__global__ __launch_bounds__(ACC_THREADS) void p2l_accum_kernel(const f32x4* __restrict__ src_pts, uint32_t n_src,
-                                                                const Target* __restrict__ tgts, const float* __restrict__ pose_f32,
-                                                                size_t pose_stride /* floats */, const State* __restrict__ states,
-                                                                const uint32_t* __restrict__ corr, const float* __restrict__ d2in, size_t ld,
-                                                                float gate2, bool skip_stopped, double* __restrict__ partials /* [job][n_blk][NSLOT] */,
+__global__ __launch_bounds__(ACC_THREADS) void p2l_accum_kernel(const gn6::Source* __restrict__ srcs, const Target* __restrict__ tgts,
+                                                                const float* __restrict__ pose_f32, size_t pose_stride /* floats */,
+                                                                const State* __restrict__ states, const uint32_t* __restrict__ corr,
+                                                                const float* __restrict__ d2in, size_t ld, float gate2, bool skip_stopped,
+                                                                double* __restrict__ partials /* [srcs[job].row0 + block][NSLOT] */,
                                                                 gn6::Scale2 sc) {
   __shared__ double red[ACC_THREADS / 64][NSLOT];
   const uint32_t job = blockIdx.y;
+  const gn6::Source S = srcs[job];
+  if (blockIdx.x >= S.n_blk) return;                // (uniform: the grid is as wide as the batch's longest source)
   if (skip_stopped && states[job].stopped) return;  // (uniform; the solve does not read a stopped job's partials)
   const uint32_t i = blockIdx.x * ACC_THREADS + threadIdx.x;
   double v[NSLOT];
 #pragma unroll
   for (int k = 0; k < NSLOT; ++k) v[k] = 0.0;
-  if (i < n_src) {
+  if (i < S.n) {
     const Target T = tgts[job];
     const uint32_t j = corr[(size_t)job * ld + i];
     const float d2 = d2in[(size_t)job * ld + i];
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(ACC_THREADS) void p2l_accum_kernel(const f32x4* __r
         float Tf[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) Tf[k] = pose_f32[(size_t)job * pose_stride + k];
-        const f32x4 s = src_pts[i];
+        const f32x4 s = S.pts[i];
         const f32x4 q = T.pts[j];
         float px, py, pz;
         reg::xform(Tf, s.x, s.y, s.z, px, py, pz);
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(ACC_THREADS) void p2l_accum_kernel(const f32x4* __r
       }
     }
   }
-  gn6::reduce_store(v, red, partials + ((size_t)job * gridDim.x + blockIdx.x) * NSLOT);
+  gn6::reduce_store(v, red, partials + ((size_t)S.row0 + blockIdx.x) * NSLOT);
 }
 
 }  // namespace p2l

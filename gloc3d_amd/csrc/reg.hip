@@ -834,12 +834,16 @@ struct TempScans {
   }
 };
 
-// Point-to-plane or generalized ICP refinement of one source against n targets (p2l.hip, gicp.hip): a searching batch
-// (open_batch) -- job table, fp32 poses in the CandState array the search reads, corr / d2 -- without a split plan (it is
-// solve_kernel that makes one), and `refine` (p2l::run or gicp::run behind their arguments) drives the passes
-// through launch_nn.  Synchronous: the scans are pinned for the call.  Targets without normals get them with normal_k, and
-// with src_normals so does the source; `refine` is handed the source's (null without src_normals): DevScan::nrm is in the
-// order of idx.pts whatever that order is (curve or kd: scan_store.hpp), the order of the slots corr is indexed by.
+// Point-to-plane or generalized ICP refinement (p2l.hip, gicp.hip) of a list of (source, target) jobs: a searching batch
+// (open_batch) over the longest source -- job table, fp32 poses in the CandState array the search reads, corr / d2 as
+// [job][ld(longest source)] -- without a split plan (it is solve_kernel that makes one), and `refine` (p2l::run or
+// gicp::run behind their arguments) drives the passes through launch_nn.  Synchronous: the scans are pinned for the call.
+// `pairs` false: ONE source, src_ids[0], against n targets (the single-source entries); true: row c is (src_ids[c],
+// tgt_ids[c]), 0xFFFFFFFF for "no target" -- such a row has no source group to search and no source slot to sum, and comes
+// out as the row of an empty target -- and the ids are checked before anything is enqueued (store_check_pairs).
+// Targets without normals get them with normal_k, and with src_normals so does every distinct source; `refine` is handed
+// every job's source (its normals null without src_normals): DevScan::nrm is in the order of idx.pts whatever that order is
+// (curve or kd: scan_store.hpp), the order of the slots corr is indexed by.
 struct P2lPass {
   gloc_reg* h;
   BatchDims bd;
@@ -850,40 +854,68 @@ struct P2lPass {
   }
 };
 
+constexpr uint32_t NO_SCAN = 0xFFFFFFFFu;
+
 template <class Refine>
-int run_refine(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, uint32_t normal_k,
-               bool src_normals, Refine&& refine) {
+int run_refine(gloc_reg* h, const uint32_t* src_ids, bool pairs, const uint32_t* tgt_ids, size_t n, const float* init_T,
+               uint32_t normal_k, bool src_normals, Refine&& refine) {
   GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
-  GLOC_REQUIRE(h->store, GLOC_ERR_INVALID, "unknown scan id %u", src_id);
+  GLOC_REQUIRE(h->store, GLOC_ERR_INVALID, "unknown scan id %u", src_ids[0]);
   gloc_scan_store* st = h->store;
   hipStream_t s = h->stream;
   const int cs = h->nn_src_per_lane;
-  std::vector<uint32_t> ids(1 + n);
-  std::vector<int> css(1 + n, 0);
-  ids[0] = src_id;
-  css[0] = cs;
-  std::copy(tgt_ids, tgt_ids + n, ids.begin() + 1);
-  GLOC_TRY(store_ensure_normals(st, tgt_ids, n, normal_k));  // (an unknown source id without src_normals: refused by pin())
-  if (src_normals) GLOC_TRY(store_ensure_normals(st, &src_id, 1, normal_k));
+  if (pairs) GLOC_TRY(store_check_pairs(st, src_ids, tgt_ids, n));
+  // the scans of the call: every distinct source (with its launch order), then the target of every job that has one
+  std::vector<uint32_t> ids, job_src;
+  distinct_in_order(src_ids, pairs ? n : 1, &ids, &job_src);
+  job_src.resize(n, 0u);
+  const size_t n_srcs = ids.size();
+  std::vector<int> css(n_srcs, cs);
+  std::vector<uint32_t> job_scan(n, NO_SCAN);  // where job c's target is among the pinned scans
+  for (size_t c = 0; c < n; ++c) {
+    if (pairs && tgt_ids[c] == NO_SCAN) continue;
+    job_scan[c] = (uint32_t)ids.size();
+    ids.push_back(tgt_ids[c]);
+    css.push_back(0);
+  }
+  // (an unknown source id without src_normals: refused by pin())
+  if (ids.size() > n_srcs) GLOC_TRY(store_ensure_normals(st, ids.data() + n_srcs, ids.size() - n_srcs, normal_k));
+  if (src_normals) GLOC_TRY(store_ensure_normals(st, ids.data(), n_srcs, normal_k));
   ScopedPins pins(st, s);
   GLOC_TRY(pins.pin(ids.data(), css.data(), ids.size()));
   const std::vector<DevScan>& scans = pins.scans;
-  const DevScan& src = scans[0];
-  GLOC_REQUIRE(src.n >= 1 && src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
-  GLOC_REQUIRE(!src_normals || src.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", src_id);
+  size_t max_src = 0;
+  for (size_t u = 0; u < n_srcs; ++u) {
+    const DevScan& src = scans[u];
+    GLOC_REQUIRE(src.n >= 1 && src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
+    GLOC_REQUIRE(!src_normals || src.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", ids[u]);
+    max_src = std::max<size_t>(max_src, src.n);
+  }
   const uint32_t n_jobs = (uint32_t)n;
-  const uint32_t ng = src_groups(src.n, cs);
   std::vector<gloc::p2l::TargetView> tv(n);
+  std::vector<gloc::p2l::SourceView> sv(n);
   for (uint32_t c = 0; c < n_jobs; ++c) {
-    const DevScan& t = scans[1 + c];
+    const DevScan& src = scans[job_src[c]];
+    if (job_scan[c] == NO_SCAN) {
+      tv[c] = gloc::p2l::TargetView{nullptr, nullptr, 0u};
+      sv[c] = gloc::p2l::SourceView{src.idx.pts, src_normals ? src.nrm : nullptr, 0u};
+      continue;
+    }
+    const DevScan& t = scans[job_scan[c]];
     GLOC_REQUIRE(t.n == 0 || t.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", tgt_ids[c]);
     tv[c] = gloc::p2l::TargetView{t.idx.pts, t.nrm, (uint32_t)t.n};
+    sv[c] = gloc::p2l::SourceView{src.idx.pts, src_normals ? src.nrm : nullptr, (uint32_t)src.n};
   }
   Batch b;
-  GLOC_TRY(open_batch(h, BatchSpec::searching(n_jobs, src.n, ng), &b, [&](Job* jd, CandState* cst) {
+  GLOC_TRY(open_batch(h, BatchSpec::searching(n_jobs, max_src, src_groups(max_src, cs)), &b, [&](Job* jd, CandState* cst) {
     for (uint32_t c = 0; c < n_jobs; ++c) {
-      const DevScan& t = scans[1 + c];
-      jd[c] = Job{src.idx.pts, src.order, src.idx.inv, t.xyz, t.idx, (uint32_t)src.n, ng, c, 0u};
+      const DevScan& src = scans[job_src[c]];
+      if (job_scan[c] == NO_SCAN) {
+        jd[c] = Job{src.idx.pts, src.order, src.idx.inv, nullptr, ScanIndexDev{}, 0u, 0u, c, 0u};
+      } else {
+        const DevScan& t = scans[job_scan[c]];
+        jd[c] = Job{src.idx.pts, src.order, src.idx.inv, t.xyz, t.idx, (uint32_t)src.n, src_groups(src.n, cs), c, 0u};
+      }
       init_state(cst[c], init_T ? init_T + 16 * (size_t)c : nullptr);
     }
   }));
@@ -894,8 +926,7 @@ int run_refine(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, 
   x.stream = s;
   x.prof = &h->prof;
   x.ws = &h->p2l;
-  x.src_pts = src.idx.pts;
-  x.n_src = (uint32_t)src.n;
+  x.srcs = sv.data();
   x.n_jobs = n_jobs;
   x.pose_f32 = reinterpret_cast<float*>(h->states.as<char>() + offsetof(CandState, Tf));
   x.pose_stride = sizeof(CandState) / sizeof(float);
@@ -904,28 +935,24 @@ int run_refine(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, 
   x.ld = bd.ld;
   x.nn_pass = &P2lPass::run;
   x.self = &pass;
-  return refine(x, src_normals ? src.nrm : nullptr, tv.data());
+  return refine(x, tv.data());
 }
 
-int run_p2l(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_p2l_params* prm,
-            float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6,
-            double* out_sum_r2, uint64_t* out_count, const gloc::p2l::RobustArgs& rb = gloc::p2l::RobustArgs()) {
+int run_p2l(gloc_reg* h, const uint32_t* src_ids, bool pairs, const uint32_t* tgt_ids, size_t n, const float* init_T,
+            const gloc_p2l_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36,
+            double* out_g6, double* out_sum_r2, uint64_t* out_count, const gloc::p2l::RobustArgs& rb = gloc::p2l::RobustArgs()) {
   GLOC_TRY(gloc::p2l::check_params(prm));
-  return run_refine(h, src_id, tgt_ids, n, init_T, prm->normal_k, false,
-                    [&](const gloc::p2l::Ctx& x, const float*, const gloc::p2l::TargetView* tv) {
-                      return gloc::p2l::run(x, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum_r2, out_count,
-                                            rb);
-                    });
+  return run_refine(h, src_ids, pairs, tgt_ids, n, init_T, prm->normal_k, false, [&](const gloc::p2l::Ctx& x, const gloc::p2l::TargetView* tv) {
+    return gloc::p2l::run(x, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum_r2, out_count, rb);
+  });
 }
 
-int run_gicp(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const float* init_T, const gloc_gicp_params* prm,
-             float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum,
-             uint64_t* out_count, const gloc::p2l::RobustArgs& rb = gloc::p2l::RobustArgs()) {
-  return run_refine(h, src_id, tgt_ids, n, init_T, prm->normal_k, true,
-                    [&](const gloc::p2l::Ctx& x, const float* src_nrm, const gloc::p2l::TargetView* tv) {
-                      return gloc::gicp::run(x, src_nrm, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum,
-                                             out_count, rb);
-                    });
+int run_gicp(gloc_reg* h, const uint32_t* src_ids, bool pairs, const uint32_t* tgt_ids, size_t n, const float* init_T,
+             const gloc_gicp_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36,
+             double* out_g6, double* out_sum, uint64_t* out_count, const gloc::p2l::RobustArgs& rb = gloc::p2l::RobustArgs()) {
+  return run_refine(h, src_ids, pairs, tgt_ids, n, init_T, prm->normal_k, true, [&](const gloc::p2l::Ctx& x, const gloc::p2l::TargetView* tv) {
+    return gloc::gicp::run(x, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum, out_count, rb);
+  });
 }
 
 // FPFH feature-based global registration (fpfh.hip): the descriptor matches of the source against every target, forward and
@@ -1771,7 +1798,7 @@ int gloc_reg_p2l_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tg
   GLOC_REQUIRE(h && out_T && tgt_scan_ids && prm, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return run_p2l(h, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+  return run_p2l(h, &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
                  nullptr);
 }
 
@@ -1780,7 +1807,7 @@ int gloc_reg_p2l_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id,
   GLOC_REQUIRE(h && prm && out_H36 && out_g6 && out_sum_r2 && out_count, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return run_p2l(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum_r2, out_count);
+  return run_p2l(h, &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum_r2, out_count);
 }
 
 // (the parameters are looked at before the handle: a bad block is refused whatever it is handed with)
@@ -1790,7 +1817,7 @@ int gloc_reg_gicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* t
   GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return run_gicp(h, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+  return run_gicp(h, &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
                   nullptr);
 }
 
@@ -1800,7 +1827,7 @@ int gloc_reg_gicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id
   GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return run_gicp(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum, out_count);
+  return run_gicp(h, &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum, out_count);
 }
 
 // Voxelized generalized ICP (vgicp.hip): no 1-NN search, so none of this file's batch set-up -- the call builds its
@@ -1811,7 +1838,7 @@ int gloc_reg_vgicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* 
   GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return gloc::vgicp::run(vgicp_ctx(h), src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
+  return gloc::vgicp::run(vgicp_ctx(h), &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
                           nullptr, nullptr);
 }
 
@@ -1821,7 +1848,7 @@ int gloc_reg_vgicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_i
   GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count, GLOC_ERR_INVALID, "null argument");
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
-  return gloc::vgicp::run(vgicp_ctx(h), src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
+  return gloc::vgicp::run(vgicp_ctx(h), &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
                           out_count);
 }
 
@@ -1838,7 +1865,7 @@ int gloc_reg_p2l_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint3
   gloc::p2l::RobustArgs rb;
   rb.prm = robust;
   rb.out_weight = out_weight;
-  return run_p2l(h, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+  return run_p2l(h, &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
                  nullptr, rb);
 }
 
@@ -1854,7 +1881,7 @@ int gloc_reg_p2l_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_s
   rb.prm = robust;
   rb.pass = pass;
   rb.out_wsum = out_wsum;
-  return run_p2l(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum_r2, out_count,
+  return run_p2l(h, &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum_r2, out_count,
                  rb);
 }
 
@@ -1869,7 +1896,7 @@ int gloc_reg_gicp_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint
   gloc::p2l::RobustArgs rb;
   rb.prm = robust;
   rb.out_weight = out_weight;
-  return run_gicp(h, src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+  return run_gicp(h, &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
                   nullptr, rb);
 }
 
@@ -1885,7 +1912,7 @@ int gloc_reg_gicp_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_
   rb.prm = robust;
   rb.pass = pass;
   rb.out_wsum = out_wsum;
-  return run_gicp(h, src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum, out_count, rb);
+  return run_gicp(h, &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum, out_count, rb);
 }
 
 int gloc_reg_vgicp_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
@@ -1899,7 +1926,7 @@ int gloc_reg_vgicp_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uin
   gloc::p2l::RobustArgs rb;
   rb.prm = robust;
   rb.out_weight = out_weight;
-  return gloc::vgicp::run(vgicp_ctx(h), src_scan_id, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
+  return gloc::vgicp::run(vgicp_ctx(h), &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
                           nullptr, nullptr, rb);
 }
 
@@ -1915,8 +1942,59 @@ int gloc_reg_vgicp_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt
   rb.prm = robust;
   rb.pass = pass;
   rb.out_wsum = out_wsum;
-  return gloc::vgicp::run(vgicp_ctx(h), src_scan_id, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
+  return gloc::vgicp::run(vgicp_ctx(h), &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
                           out_count, rb);
+}
+
+// The pair-list entries: row c is (src_scan_ids[c], tgt_scan_ids[c]) -- run_refine's and vgicp::run's list form, every row
+// the single-source entry's row.  pairs_head is what they refuse behind the method's own block, in this order: the robust
+// block (null: the plain step), the arrays, n, the handle, a batch in flight.
+static int pairs_head(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const gloc_robust_params* robust,
+                      const float* out_T) {
+  if (robust) GLOC_TRY(gloc::robust::check_params(robust));
+  GLOC_REQUIRE(src_scan_ids && tgt_scan_ids, GLOC_ERR_INVALID, "null scan ids");
+  GLOC_REQUIRE(out_T, GLOC_ERR_INVALID, "out_T is null");
+  GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return GLOC_OK;
+}
+
+int gloc_reg_p2l_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                       const gloc_p2l_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse, uint32_t* out_iters,
+                       int* out_status, float* out_weight) {
+  GLOC_TRY(gloc::p2l::check_params(prm));
+  GLOC_TRY(pairs_head(h, src_scan_ids, tgt_scan_ids, n, robust, out_T));
+  gloc::p2l::RobustArgs rb;
+  rb.prm = robust;
+  rb.out_weight = robust ? out_weight : nullptr;  // (the plain step has no weights to report)
+  return run_p2l(h, src_scan_ids, true, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+                 nullptr, rb);
+}
+
+int gloc_reg_gicp_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                        const gloc_gicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse, uint32_t* out_iters,
+                        int* out_status, float* out_weight) {
+  GLOC_TRY(gloc::gicp::check_params(prm));
+  GLOC_TRY(pairs_head(h, src_scan_ids, tgt_scan_ids, n, robust, out_T));
+  gloc::p2l::RobustArgs rb;
+  rb.prm = robust;
+  rb.out_weight = robust ? out_weight : nullptr;  // (the plain step has no weights to report)
+  return run_gicp(h, src_scan_ids, true, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
+                  nullptr, rb);
+}
+
+int gloc_reg_vgicp_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                         const gloc_vgicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse, uint32_t* out_iters,
+                         int* out_status, float* out_weight) {
+  GLOC_TRY(gloc::vgicp::check_params(prm));
+  GLOC_TRY(pairs_head(h, src_scan_ids, tgt_scan_ids, n, robust, out_T));
+  gloc::p2l::RobustArgs rb;
+  rb.prm = robust;
+  rb.out_weight = robust ? out_weight : nullptr;  // (the plain step has no weights to report)
+  return gloc::vgicp::run(vgicp_ctx(h), src_scan_ids, true, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr,
+                          nullptr, nullptr, nullptr, rb);
 }
 
 int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3,

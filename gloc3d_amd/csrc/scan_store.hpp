@@ -201,5 +201,21 @@ inline void distinct_in_order(const uint32_t* ids, size_t n, std::vector<uint32_
   }
 }
 
+// What a list of (source, target) pairs is refused for before anything is enqueued: an id the store does not know (a
+// target of 0xFFFFFFFF is "no target", not an id) and a source that is empty or too large.  Looks each distinct id up once.
+inline int store_check_pairs(gloc_scan_store* st, const uint32_t* src_ids, const uint32_t* tgt_ids, size_t n) {
+  std::vector<uint32_t> seen_src, seen_tgt, at;
+  distinct_in_order(src_ids, n, &seen_src, &at);
+  distinct_in_order(tgt_ids, n, &seen_tgt, &at);
+  DevScan s;
+  for (const uint32_t id : seen_src) {
+    GLOC_TRY(store_get(st, id, 0, &s));
+    GLOC_REQUIRE(s.n >= 1 && s.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan %u is empty or too large", id);
+  }
+  for (const uint32_t id : seen_tgt)
+    if (id != 0xFFFFFFFFu) GLOC_TRY(store_get(st, id, 0, &s));
+  return GLOC_OK;
+}
+
 }  // namespace reg
 }  // namespace gloc

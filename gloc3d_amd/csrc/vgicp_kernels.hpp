@@ -118,26 +118,27 @@ __device__ __forceinline__ void offset_of(uint32_t neighbors, uint32_t o, int* d
 }
 
 template <int KIND>
-static __global__ __launch_bounds__(ACC_THREADS) void vgicp_accum_kernel(const f32x4* __restrict__ src_pts, const float* __restrict__ src_nrm,
-                                                                         uint32_t n_src, const Target* __restrict__ tgts,
+static __global__ __launch_bounds__(ACC_THREADS) void vgicp_accum_kernel(const gn6::Source* __restrict__ srcs, const Target* __restrict__ tgts,
                                                                          const float* __restrict__ pose_f32, size_t pose_stride /* floats */,
                                                                          const State* __restrict__ states, float inv_res, uint32_t neighbors,
                                                                          double gate2 /* <= 0: off */, double a, bool skip_stopped,
-                                                                         double* __restrict__ partials /* [job][n_blk][NSLOT] */,
+                                                                         double* __restrict__ partials /* [srcs[job].row0 + block][NSLOT] */,
                                                                          gn6::Scale2 sc) {
   __shared__ double red[ACC_THREADS / 64][NSLOT];
   const uint32_t job = blockIdx.y;
+  const gn6::Source S = srcs[job];
+  if (blockIdx.x >= S.n_blk) return;                // (uniform: the grid is as wide as the batch's longest source)
   if (skip_stopped && states[job].stopped) return;  // (uniform; the solve does not read a stopped job's partials)
   const uint32_t i = blockIdx.x * ACC_THREADS + threadIdx.x;
   double v[NSLOT];
 #pragma unroll
   for (int k = 0; k < NSLOT; ++k) v[k] = 0.0;
-  if (i < n_src) {
+  if (i < S.n) {
     const Target T = tgts[job];
     float Tf[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) Tf[k] = pose_f32[(size_t)job * pose_stride + k];
-    const f32x4 s = src_pts[i];
+    const f32x4 s = S.pts[i];
     float pf[3];
     reg::xform(Tf, s.x, s.y, s.z, pf[0], pf[1], pf[2]);
     // the voxel of p: cell_keys_kernel's rule (a NaN or inf p fails the comparison; so does |k| >= 2^20)
@@ -151,7 +152,7 @@ static __global__ __launch_bounds__(ACC_THREADS) void vgicp_accum_kernel(const f
     }
     if (ok) {
       const double P[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
-      const double ns[3] = {(double)src_nrm[3 * (size_t)i], (double)src_nrm[3 * (size_t)i + 1], (double)src_nrm[3 * (size_t)i + 2]};
+      const double ns[3] = {(double)S.nrm[3 * (size_t)i], (double)S.nrm[3 * (size_t)i + 1], (double)S.nrm[3 * (size_t)i + 2]};
       double m[3];
 #pragma unroll
       for (int r = 0; r < 3; ++r) m[r] = ((double)Tf[3 * r] * ns[0] + (double)Tf[3 * r + 1] * ns[1]) + (double)Tf[3 * r + 2] * ns[2];
@@ -233,7 +234,7 @@ static __global__ __launch_bounds__(ACC_THREADS) void vgicp_accum_kernel(const f
       }
     }
   }
-  gn6::reduce_store(v, red, partials + ((size_t)job * gridDim.x + blockIdx.x) * NSLOT);
+  gn6::reduce_store(v, red, partials + ((size_t)S.row0 + blockIdx.x) * NSLOT);
 }
 
 }  // namespace vgicp

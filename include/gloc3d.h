@@ -744,6 +744,43 @@ int gloc_reg_vgicp_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt
                                  const gloc_vgicp_params* prm, const gloc_robust_params* robust, uint32_t pass, double* out_H36,
                                  double* out_g6, double* out_sum, uint64_t* out_count, double* out_wsum);
 
+/* ---- pair lists: many (source, target) pairs through one of the three refinements in ONE call ------------- *
+ * The entries above take one source against n targets; a stream of queries, the loop-closure edges of a pose graph or a
+ * multi-way registration hand over a LIST of pairs.  Row c is (src_scan_ids[c], tgt_scan_ids[c]) from init_T + 16 c
+ * (init_T NULL: the identity), and every launch of the call -- the 1-NN pass, the accumulate kernel, the solve -- covers
+ * all rows: one batch set-up, one launch sequence, one read-back.
+ *
+ * Row equality.  Row c is the result of the single-source entry for (src_scan_ids[c], &tgt_scan_ids[c], 1, init_T + 16 c):
+ * gloc_reg_<m>_batch_ids with robust NULL, gloc_reg_<m>_batch_ids_robust otherwise.  Every output is equal BIT FOR BIT,
+ * out_iters and out_status included.  robust NULL is the plain step, and out_weight is then left alone; a block of kind
+ * NONE gives the same rows and out_weight 1 where there are pairs, as the _robust entries do.
+ * Independence.  A row does not depend on the list it is in, on its position there or on how often its scans appear
+ * elsewhere in the list, as sources, as targets or as both: a job is cut into work-groups of 256 consecutive source
+ * slots, its sums are added in that order, and both depend on its own source alone.  A scan against itself is a legal
+ * pair.  A target may or may not carry a target index: the same bits.  (A SOURCE that carries one is kept in kd order,
+ * and its rows are those of the single-source entries on that scan as it is kept: the same pairs summed in another order.)
+ * Absent target.  tgt_scan_ids[c] == UINT32_MAX is "no target", as in gloc_reg_batch_multi: the row is exactly that of an
+ * empty target scan -- the guess, 0 iterations, status 2, rmse 0, weight 0.
+ * Normals that scans lack are built first with normal_k, as the single-source entries do: the targets', and for
+ * generalized and voxelized ICP every distinct source's.  A voxelized call builds one voxel map per distinct target.
+ * Memory: the correspondences are kept as [n][the longest source of the list], so the call's workspace grows as n times
+ * the LONGEST source, not as the sum of the sources; the partial sums are one row per work-group the list really has.
+ *
+ * The parameter blocks are checked before the handle: the method's own, then -- where it is not NULL -- the robust one.
+ * GLOC_ERR_INVALID, before any device work and with the outputs untouched: a null src_scan_ids, tgt_scan_ids or out_T;
+ * n outside [1, 4096]; an id the store does not know; a source, anywhere in the list, that is empty or too large.
+ * GLOC_ERR_STATE: a batch in flight on the handle.  The call is synchronous and the scans are pinned for it.
+ * out_rmse, out_iters, out_status and out_weight may be NULL. */
+int gloc_reg_p2l_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                       const gloc_p2l_params* prm, const gloc_robust_params* robust /* NULL: the plain step */, float* out_T,
+                       float* out_rmse, uint32_t* out_iters, int* out_status, float* out_weight);
+int gloc_reg_gicp_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                        const gloc_gicp_params* prm, const gloc_robust_params* robust /* NULL: the plain step */, float* out_T,
+                        float* out_rmse, uint32_t* out_iters, int* out_status, float* out_weight);
+int gloc_reg_vgicp_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
+                         const gloc_vgicp_params* prm, const gloc_robust_params* robust /* NULL: the plain step */, float* out_T,
+                         float* out_rmse, uint32_t* out_iters, int* out_status, float* out_weight);
+
 /* ---- FPFH feature-based global registration ------------------------------------------------------------- *
  * The 3-D answer to "where is this scan, from nothing": local shape descriptors (Fast Point Feature Histograms: Rusu,
  * Blodow & Beetz; pcl::FPFHEstimation in its k-nearest form), descriptor matching, and the RANSAC stage of

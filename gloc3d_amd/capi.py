@@ -160,6 +160,11 @@ class ScParams(C.Structure):
                 ("min_common_columns", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class M2dpParams(C.Structure):
+    _fields_ = [("n_azimuth", C.c_uint32), ("n_elevation", C.c_uint32), ("n_rings", C.c_uint32), ("n_sectors", C.c_uint32),
+                ("max_range", C.c_float), ("min_points", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class GroundParams(C.Structure):
     _fields_ = [("near_range2", C.c_float), ("knn", C.c_uint32), ("plane_thresh", C.c_float),
                 ("ransac_iters", C.c_uint32), ("ransac_conf", C.c_float), ("reserved_", C.c_uint32),
@@ -409,6 +414,20 @@ _PROTOS = [
     ("gloc_sc_set_profile", _i, [_vp, _i]),
     ("gloc_sc_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
     ("gloc_sc_profile_reset", _i, [_vp]),
+    ("gloc_m2dp_default_params", _i, [C.POINTER(M2dpParams)]),
+    ("gloc_m2dp_dim", _i, [C.POINTER(M2dpParams), C.POINTER(_sz)]),
+    ("gloc_m2dp_create", _i, [_i, C.POINTER(M2dpParams), C.POINTER(_vp)]),
+    ("gloc_m2dp_destroy", _i, [_vp]),
+    ("gloc_m2dp_set_stream", _i, [_vp, _vp]),
+    ("gloc_m2dp_synchronize", _i, [_vp]),
+    ("gloc_m2dp_describe", _i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    ("gloc_m2dp_describe_store_scans", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gloc_m2dp_describe_store_scans_device", _i, [_vp, _vp, _vp, _sz, _vp]),
+    ("gloc_m2dp_signature_svd", _i, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gloc_m2dp_frame_to_seed", _i, [_vp, _vp, _vp]),
+    ("gloc_m2dp_set_profile", _i, [_vp, _i]),
+    ("gloc_m2dp_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
+    ("gloc_m2dp_profile_reset", _i, [_vp]),
     ("gloc_ground_default_params", _i, [_vp]),
     ("gloc_ground_create", _i, [_i, C.POINTER(_vp)]),
     ("gloc_ground_destroy", _i, [_vp]),
@@ -1994,6 +2013,79 @@ class ScanContext(_Handle):
 
     def shift_to_yaw(self, shift):
         return sc_shift_to_yaw(self.params, shift)
+
+
+def default_m2dp_params(**over):
+    p = M2dpParams()
+    check(lib().gloc_m2dp_default_params(C.byref(p)))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def m2dp_dim(params):
+    n = C.c_size_t()
+    check(lib().gloc_m2dp_dim(C.byref(params), C.byref(n)))
+    return n.value
+
+
+def m2dp_frame_to_seed(frame_q, frame_db):
+    """The 4 x 4 float32 pose query -> place of two M2DP frames [12] (gloc_m2dp_frame_to_seed; host only)."""
+    fq, fd = (np.ascontiguousarray(f, np.float64).reshape(12) for f in (frame_q, frame_db))
+    T = np.empty((4, 4), np.float32)
+    check(lib().gloc_m2dp_frame_to_seed(_np_ptr(fq), _np_ptr(fd), _np_ptr(T)))
+    return T
+
+
+class M2dp(_Handle):
+    """M2DP place descriptors (He, Wang & Zhang, IROS 2016): plain L2 vectors for KnnIndex, built from host or resident
+    scans together with the PCA frame they are built in (gloc_m2dp_* of include/gloc3d.h)."""
+
+    _C = "m2dp"
+    set_stream, synchronize = _set_stream, _synchronize
+    set_profile, profile, profile_reset = _set_profile, _profile, _profile_reset
+
+    def __init__(self, device=0, params=None):
+        self._h = C.c_void_p()
+        self.params = params or default_m2dp_params()
+        check(lib().gloc_m2dp_create(device, C.byref(self.params), C.byref(self._h)))
+        self.n_planes = int(self.params.n_azimuth * self.params.n_elevation)
+        self.n_bins = int(self.params.n_rings * self.params.n_sectors)
+        self.dim = self.n_planes + self.n_bins
+
+    def _outs(self, n, counts):
+        return (np.empty((n, self.dim), np.float32), np.empty((n, 12), np.float64),
+                np.empty((n, self.n_planes, self.n_bins), np.uint32) if counts else None)
+
+    def describe(self, pts, counts=False):
+        """(descriptor [dim], frame [12][, counts [planes, bins]]) of one host scan [n, 3..16]."""
+        pts = np.ascontiguousarray(pts, np.float32)
+        d, f, c = self._outs(1, counts)
+        check(lib().gloc_m2dp_describe(self._h, _np_ptr(pts), pts.shape[0], pts.shape[1], _np_ptr(d), _np_ptr(f),
+                                       _np_ptr(c) if counts else None))
+        return (d[0], f[0], c[0]) if counts else (d[0], f[0])
+
+    def describe_store_scans(self, store, scan_ids, counts=False):
+        """(descriptors [n, dim], frames [n, 12][, counts [n, planes, bins]]) of resident scans, one launch sequence."""
+        ids = np.ascontiguousarray(scan_ids, np.uint32).reshape(-1)
+        d, f, c = self._outs(ids.shape[0], counts)
+        check(lib().gloc_m2dp_describe_store_scans(self._h, store._h, _np_ptr(ids), ids.shape[0], _np_ptr(d), _np_ptr(f),
+                                                   _np_ptr(c) if counts else None))
+        return (d, f, c) if counts else (d, f)
+
+    def describe_store_scans_device(self, store, scan_ids, out_ptr):
+        """The rows [n, dim] float32 into device memory at out_ptr, enqueued on the handle's stream."""
+        ids = np.ascontiguousarray(scan_ids, np.uint32).reshape(-1)
+        check(lib().gloc_m2dp_describe_store_scans_device(self._h, store._h, _np_ptr(ids), ids.shape[0], C.c_void_p(out_ptr)))
+
+    def signature_svd(self, counts, n_points):
+        """(descriptors [n, dim], sigma [n, 2]) of given count matrices [n, planes, bins] (the SVD kernel alone)."""
+        c = np.ascontiguousarray(counts, np.uint32).reshape(-1, self.n_planes, self.n_bins)
+        n = np.ascontiguousarray(n_points, np.uint32).reshape(-1)
+        assert n.shape[0] == c.shape[0]
+        d, s = np.empty((c.shape[0], self.dim), np.float32), np.empty((c.shape[0], 2), np.float64)
+        check(lib().gloc_m2dp_signature_svd(self._h, _np_ptr(c), _np_ptr(n), c.shape[0], _np_ptr(d), _np_ptr(s)))
+        return d, s
 
 
 def default_ground_params(**over):

@@ -1374,6 +1374,76 @@ int gloc_sc_set_profile(gloc_sc* h, int enable);
 int gloc_sc_profile(gloc_sc* h, const char* kernel, double* total_ms, uint64_t* launches);
 int gloc_sc_profile_reset(gloc_sc* h);
 
+/* ============================ M2DP place descriptor ========================================= *
+ * NO COUNTERPART IN THE REFERENCE, whose descriptors come from trained networks (gloc_vgg_*, gloc_pillar_*): this is
+ * the training-free descriptor of He, Wang & Zhang, "M2DP: a novel 3D point cloud descriptor and its application in
+ * loop closure detection", IROS 2016 -- a plain vector of dim = p q + l t floats (192 at the defaults), so that scan ->
+ * descriptor -> gloc_knn_* -> registration runs on what the repository holds, at any database size the kNN handles.
+ * tests/m2dp_ref.py restates the contract in numpy.
+ *
+ * M1 points: a point is used iff its three coordinates are finite and (x x + y y) + z z < max_range^2 in un-fused fp32.
+ *    Fewer than min_points used points: "no descriptor" -- the zero row, the identity frame with centroid 0, counts 0.
+ * M2 frame, fp64 from the fp32 inputs: c = mean; C = sum (p - c)(p - c)^T / n about c (two passes); eigenpairs by the
+ *    cyclic Jacobi of the normals, sorted l1 >= l2 >= l3 with ties to the lower column; for a = 1, 2: e_a is negated iff
+ *    sum ((p - c) . e_a)^3 < 0; e3 = e1 x e2; R = [e1 e2 e3] as columns.  The frame is R row-major followed by c: 12
+ *    doubles.  With this sign rule the frame of a scan turns with the scan.  No floating-point atomics: the summation
+ *    tree is fixed, two runs agree bit for bit and a scan in a batch equals the scan alone.
+ * M3 signature: y = R^T (p - c); r = max |p - c| over the used points.  Plane a q + b has theta = -pi/2 + a pi / p,
+ *    phi = b (pi/2) / q and the in-plane unit pair u = (-sin theta, cos theta, 0), v = (-sin phi cos theta,
+ *    -sin phi sin theta, cos phi); alpha = y . u, beta = y . v, rho = hypot(alpha, beta);
+ *    ring = min(floor(sqrt(rho / r) l), l - 1), sector = min(floor((atan2(beta, alpha) mod 2 pi) / 2 pi t), t - 1);
+ *    rho = 0 gives bin 0, r = 0 puts everything into bin 0.  counts[plane][ring t + sector] is a u32 count.  The device
+ *    decides ring and sector by fp64 comparisons against tabulated (k / l)^4 and border directions; a (point, plane) whose
+ *    fractional coordinate is within 1e-12 of a border may fall on either side.
+ * M4 descriptor: A = counts / n; u1, v1 = its first left and right singular vectors, both negated iff sum u1 < 0
+ *    (A >= 0: the first pair can be taken non-negative); the descriptor is fp32([u1, v1]).  fp64 power iteration on
+ *    A A^T, run until the vector moves by less than 2^-46 (at most 20 000 steps: sigma2 / sigma1 up to ~0.9996).
+ * M5 seed (host): R_db R_q^T and t = c_db - R_db R_q^T c_q as a row-major fp32 4 x 4, query -> place.  The rotation is
+ *    the rotation between the two scans at any yaw; the centroid of a ring scan sits at the sensor, so the translation
+ *    carries little. */
+typedef struct gloc_m2dp gloc_m2dp;
+
+typedef struct gloc_m2dp_params {
+  uint32_t n_azimuth;   /* p: 4  (>= 1, p q <= 64) */
+  uint32_t n_elevation; /* q: 16 (>= 1, p q <= 64) */
+  uint32_t n_rings;     /* l: 8  (>= 1, l t <= 128) */
+  uint32_t n_sectors;   /* t: 16 (>= 2, l t <= 128) */
+  float max_range;      /* 80 m, finite and positive */
+  uint32_t min_points;  /* 16 (>= 4) */
+  uint32_t reserved_;   /* must be 0 */
+} gloc_m2dp_params;
+
+int gloc_m2dp_default_params(gloc_m2dp_params* p);
+/* dim = p q + l t of a valid block.  Host only. */
+int gloc_m2dp_dim(const gloc_m2dp_params* params, size_t* dim);
+/* The parameters are fixed for the handle's life; they are checked before the device is (GLOC_ERR_INVALID). */
+int gloc_m2dp_create(int device, const gloc_m2dp_params* params, gloc_m2dp** out);
+int gloc_m2dp_destroy(gloc_m2dp* h);
+int gloc_m2dp_set_stream(gloc_m2dp* h, void* hip_stream);
+int gloc_m2dp_synchronize(gloc_m2dp* h);
+/* One host scan (x y z first in every stride_floats floats) -> out_desc [dim], out_frame12 [12] and out_counts
+ * [p q][l t] (the test hook of M3); the last two may be NULL. */
+int gloc_m2dp_describe(gloc_m2dp* h, const float* xyz, size_t n, size_t stride_floats, float* out_desc,
+                       double* out_frame12, uint32_t* out_counts);
+/* n (<= 4096) scans resident in a store on the same device: one launch sequence whose launch count does not depend on n,
+ * the points stay on the device.  The original-order points are read: nothing depends on a target index. */
+int gloc_m2dp_describe_store_scans(gloc_m2dp* h, gloc_scan_store* store, const uint32_t* scan_ids, size_t n,
+                                   float* out_desc, double* out_frame12, uint32_t* out_counts);
+/* The same with the rows left in device memory (d_out_desc [n][dim]), enqueued on the handle's stream: ready for
+ * gloc_knn_add_device / gloc_knn_search_device on that stream without a host round trip. */
+int gloc_m2dp_describe_store_scans_device(gloc_m2dp* h, gloc_scan_store* store, const uint32_t* scan_ids, size_t n,
+                                          float* d_out_desc);
+/* M4 alone on given counts [n_sig][p q][l t] with n_points [n_sig]: out_desc [n_sig][dim] and, unless NULL, out_sigma2
+ * [n_sig][2] = sigma1, sigma2 of counts / n_points.  The test hook of the SVD kernel. */
+int gloc_m2dp_signature_svd(gloc_m2dp* h, const uint32_t* counts, const uint32_t* n_points, size_t n_sig,
+                            float* out_desc, double* out_sigma2);
+/* M5.  Host only. */
+int gloc_m2dp_frame_to_seed(const double* frame_q, const double* frame_db, float* T16);
+int gloc_m2dp_set_profile(gloc_m2dp* h, int enable);
+/* kernel families: "m2dp_frame", "m2dp_project", "m2dp_svd" */
+int gloc_m2dp_profile(gloc_m2dp* h, const char* kernel, double* total_ms, uint64_t* launches);
+int gloc_m2dp_profile_reset(gloc_m2dp* h);
+
 /* ============================ ground pre-alignment ("next" row N3) ========================= *
  * Replaces GroundEstimator::EsitmateGroundAndTransform (registration/ground_estimator.cpp:196-228),
  * the optional 4th-argument mode of global_localization (registration/global_localization.cpp:431-436,

@@ -910,6 +910,28 @@ class ScanStore(_Handle):
         check(f(self._h, int(scan_id), _np_ptr(perm), _np_ptr(keys), _np_ptr(kpos), _np_ptr(order2), C.byref(kd)))
         return dict(perm=perm, keys=keys, kpos=kpos, order2=order2, kd=bool(kd.value))
 
+    def debug_boxes(self, scan_id, cs=2):
+        """Test aid: the rest of the scan's index as the search sees it now -- dict(lo, hi: the header's box as
+        order-preserving integers [3]; ox, oy, oz, inv_cell: the key grid (float32); box_lo, box_hi [nchunks, 4]: the chunk
+        boxes' centres and negated half extents / 64; sb2 [n_pad / 32, 3, 4]: the paired sub-block boxes as interleaved;
+        sup_lo, sup_hi [nsup, 4]; pad [n_pad - n, 4]: the padding points; order: the launch order for cs sources per lane).
+        An empty scan has a header and empty arrays."""
+        f = lib().gloc_scan_store_debug_boxes
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_uint32, C.c_int] + [C.c_void_p] * 9
+        n = self.points(scan_id)
+        nch = (n + 127) // 128
+        n_pad, nsup, group = nch * 128, (nch + 63) // 64, 64 * int(cs)
+        hb, hg = np.empty(6, np.uint32), np.empty(4, np.float32)
+        box_lo, box_hi = np.empty((nch, 4), np.float32), np.empty((nch, 4), np.float32)
+        sb2 = np.empty((n_pad // 32, 3, 4), np.float32)
+        sup_lo, sup_hi = np.empty((nsup, 4), np.float32), np.empty((nsup, 4), np.float32)
+        pad = np.empty((n_pad - n, 4), np.float32)
+        order = np.empty((n + group - 1) // group if group else 0, np.uint32)
+        check(f(self._h, int(scan_id), int(cs), *[_np_ptr(a) for a in (hb, hg, box_lo, box_hi, sb2, sup_lo, sup_hi, pad, order)]))
+        return dict(lo=hb[:3].copy(), hi=hb[3:].copy(), ox=hg[0], oy=hg[1], oz=hg[2], inv_cell=hg[3], box_lo=box_lo,
+                    box_hi=box_hi, sb2=sb2, sup_lo=sup_lo, sup_hi=sup_hi, pad=pad, order=order)
+
     def build_target_index_batch(self, scan_ids):
         ids = np.ascontiguousarray(scan_ids, np.uint32).reshape(-1)
         check(lib().gloc_scan_store_build_target_index_batch(self._h, _np_ptr(ids), ids.shape[0]))

@@ -70,5 +70,12 @@ __host__ __device__ __forceinline__ float ord2f(uint32_t o) {
   return __builtin_bit_cast(float, u);
 }
 
+// A non-finite coordinate (the reference's readers pass NaN and +-inf records through) takes no part in any bounding box
+// of the index: an infinite corner would turn centre and half extent into inf and inf - inf, and a NaN with its sign bit
+// set orders below every number.  An axis left without any finite coordinate gets the empty box of the sub-blocks.
+__host__ __device__ __forceinline__ bool finite_coord(float f) {
+  return (__builtin_bit_cast(uint32_t, f) & 0x7F800000u) != 0x7F800000u;
+}
+
 }  // namespace reg
 }  // namespace gloc

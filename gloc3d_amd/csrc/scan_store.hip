@@ -61,6 +61,7 @@ __global__ __launch_bounds__(256) void pack_bbox_kernel(const ScanBuild* __restr
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       xyz[(size_t)i * 3 + a] = v[a];
+      if (!finite_coord(v[a])) continue;  // (kept as a point, no part of the box: scan_index.hpp)
       const uint32_t o = f2ord(v[a]);
       lo[a] = o < lo[a] ? o : lo[a];
       hi[a] = o > hi[a] ? o : hi[a];
@@ -123,8 +124,10 @@ __global__ __launch_bounds__(64) void header_finish_kernel(const ScanBuild* __re
     hdr->inv_cell = 4.f;
     return;
   }
-  const float mn0 = ord2f(lo[0]), mn1 = ord2f(lo[1]), mn2 = ord2f(lo[2]);
-  const float e0 = ord2f(hi[0]) - mn0, e1 = ord2f(hi[1]) - mn1, e2 = ord2f(hi[2]) - mn2;
+  // (an axis without any finite coordinate: origin 0, no extent)
+  const bool some0 = lo[0] <= hi[0], some1 = lo[1] <= hi[1], some2 = lo[2] <= hi[2];
+  const float mn0 = some0 ? ord2f(lo[0]) : 0.f, mn1 = some1 ? ord2f(lo[1]) : 0.f, mn2 = some2 ? ord2f(lo[2]) : 0.f;
+  const float e0 = some0 ? ord2f(hi[0]) - mn0 : 0.f, e1 = some1 ? ord2f(hi[1]) - mn1 : 0.f, e2 = some2 ? ord2f(hi[2]) - mn2 : 0.f;
   const float ext = fmaxf(fmaxf(e0, e1), e2);
   const float cell = fmaxf(0.25f, ext / 1023.0f);
   hdr->ox = mn0;
@@ -162,6 +165,17 @@ __global__ void gather_sorted_kernel(const ScanBuild* __restrict__ sbs, const ui
   sb.keys[s] = skeys[sb.key_off + s];
 }
 
+// a point into a running box (mn from 3.4e38, mx from -3.4e38), finite coordinates only
+__device__ __forceinline__ void box_add(float mn[3], float mx[3], const f32x4& p) {
+  const float v[3] = {p.x, p.y, p.z};
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    if (finite_coord(v[a])) {
+      mn[a] = fminf(mn[a], v[a]);
+      mx[a] = fmaxf(mx[a], v[a]);
+    }
+}
+
 // one wave per chunk
 __global__ __launch_bounds__(64) void chunk_boxes_kernel(const ScanBuild* __restrict__ sbs) {
   const ScanBuild& sb = sbs[blockIdx.y];
@@ -172,12 +186,7 @@ __global__ __launch_bounds__(64) void chunk_boxes_kernel(const ScanBuild* __rest
   float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
   for (uint32_t t = lane; t < CH; t += 64) {
     const uint32_t j = c * CH + t;
-    if (j < n) {
-      const f32x4 p = pts[j];
-      mn[0] = fminf(mn[0], p.x); mx[0] = fmaxf(mx[0], p.x);
-      mn[1] = fminf(mn[1], p.y); mx[1] = fmaxf(mx[1], p.y);
-      mn[2] = fminf(mn[2], p.z); mx[2] = fmaxf(mx[2], p.z);
-    }
+    if (j < n) box_add(mn, mx, pts[j]);
   }
   for (int o = 32; o > 0; o >>= 1)
     for (int a = 0; a < 3; ++a) {
@@ -191,6 +200,11 @@ __global__ __launch_bounds__(64) void chunk_boxes_kernel(const ScanBuild* __rest
     // whatever the rounding of c.
     float cc[3], nh[3];
     for (int a = 0; a < 3; ++a) {
+      if (mn[a] > mx[a]) {  // no finite coordinate on this axis: the empty box of the sub-blocks
+        cc[a] = 0.f;
+        nh[a] = 1.0e30f;
+        continue;
+      }
       const float c_ = 0.5f * mn[a] + 0.5f * mx[a];
       const float he = fmaxf(c_ - mn[a], mx[a] - c_) * 1.0000005f + 1.0e-30f;  // (each difference within 2^-24 of exact)
       cc[a] = c_;
@@ -212,6 +226,7 @@ __global__ __launch_bounds__(64) void super_boxes_kernel(const ScanBuild* __rest
     const f32x4 a = sb.lo[c], b = sb.hi[c];
     const float cc[3] = {a.x, a.y, a.z}, he[3] = {-b.x * SB2_RANGE, -b.y * SB2_RANGE, -b.z * SB2_RANGE};
     for (int k = 0; k < 3; ++k) {
+      if (he[k] < 0.f) continue;  // (the chunk's empty axis: no part of the union)
       const float slack = 2.0e-7f * (fabsf(cc[k]) + he[k]);
       mn[k] = (cc[k] - he[k]) - slack;
       mx[k] = (cc[k] + he[k]) + slack;
@@ -243,12 +258,7 @@ __global__ void subblock_boxes_kernel(const ScanBuild* __restrict__ sbs) {
     }
     for (uint32_t t = 0; t < SB; ++t) {
       const uint32_t j = (2 * b + h) * SB + t;
-      if (j < n) {
-        const f32x4 p = pts[j];
-        mn[h][0] = fminf(mn[h][0], p.x); mx[h][0] = fmaxf(mx[h][0], p.x);
-        mn[h][1] = fminf(mn[h][1], p.y); mx[h][1] = fmaxf(mx[h][1], p.y);
-        mn[h][2] = fminf(mn[h][2], p.z); mx[h][2] = fmaxf(mx[h][2], p.z);
-      }
+      if (j < n) box_add(mn[h], mx[h], pts[j]);
     }
   }
   // Stored as CENTRE and NEGATED HALF EXTENT / 64 (scan_index.hpp: SB2_*), two sub-blocks interleaved for packed fp32:
@@ -289,12 +299,7 @@ __global__ __launch_bounds__(256) void group_extent_kernel(const ScanBuild* __re
   const f32x4* __restrict__ pts = sb.pts;
   const uint32_t n = sb.n, group = sb.group;
   float lo[3] = {3.4e38f, 3.4e38f, 3.4e38f}, hi[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-  for (uint32_t i = g * group + lane; i < (g + 1) * group && i < n; i += 64) {
-    const f32x4 p = pts[i];
-    lo[0] = fminf(lo[0], p.x); hi[0] = fmaxf(hi[0], p.x);
-    lo[1] = fminf(lo[1], p.y); hi[1] = fmaxf(hi[1], p.y);
-    lo[2] = fminf(lo[2], p.z); hi[2] = fmaxf(hi[2], p.z);
-  }
+  for (uint32_t i = g * group + lane; i < (g + 1) * group && i < n; i += 64) box_add(lo, hi, pts[i]);
   for (int o = 32; o > 0; o >>= 1)
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -302,7 +307,9 @@ __global__ __launch_bounds__(256) void group_extent_kernel(const ScanBuild* __re
       hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o));
     }
   if (lane == 0) {
-    const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+    // (an axis without any finite coordinate has no extent)
+    const float dx = lo[0] <= hi[0] ? hi[0] - lo[0] : 0.f, dy = lo[1] <= hi[1] ? hi[1] - lo[1] : 0.f,
+                dz = lo[2] <= hi[2] ? hi[2] - lo[2] : 0.f;
     keys[sb.grp_off + g] = ~f2ord(dx * dx + dy * dy + dz * dz);
     ids[sb.grp_off + g] = g;
   }
@@ -388,11 +395,13 @@ __global__ __launch_bounds__(256) void kd_node_bbox_kernel(const ScanKd* __restr
     const uint32_t i1 = i0 + 16u < n ? i0 + 16u : n;
     for (uint32_t i = i0; i < i1; ++i) {
       const f32x4 v = p[i];
-      const uint32_t o[3] = {f2ord(v.x), f2ord(v.y), f2ord(v.z)};
+      const float f[3] = {v.x, v.y, v.z};
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
-        lo[a] = o[a] < lo[a] ? o[a] : lo[a];
-        hi[a] = o[a] > hi[a] ? o[a] : hi[a];
+        if (!finite_coord(f[a])) continue;  // (no part of the node's box: scan_index.hpp)
+        const uint32_t o = f2ord(f[a]);
+        lo[a] = o < lo[a] ? o : lo[a];
+        hi[a] = o > hi[a] ? o : hi[a];
       }
     }
   }
@@ -408,7 +417,7 @@ __global__ __launch_bounds__(256) void kd_node_bbox_kernel(const ScanKd* __restr
     first = (b & ~63u) * 16u;
     if ((threadIdx.x & 63) != 0) return;
   }
-  if (lo[0] > hi[0]) return;  // no point in this block / wave
+  if (lo[0] > hi[0] && lo[1] > hi[1] && lo[2] > hi[2]) return;  // no finite coordinate in this block / wave
   uint32_t* o = box + k.box_off + 6 * (size_t)(first >> shift);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -431,7 +440,9 @@ __global__ void kd_keys_kernel(const ScanKd* __restrict__ ks, uint32_t level, co
   const uint32_t shift = 4 + k.levels - level;
   const uint32_t node = i >> shift;
   const uint32_t* b = box + k.box_off + 6 * (size_t)node;
-  const float ex = ord2f(b[3]) - ord2f(b[0]), ey = ord2f(b[4]) - ord2f(b[1]), ez = ord2f(b[5]) - ord2f(b[2]);
+  // (an axis on which the node has no finite coordinate is never the widest)
+  const float ex = b[0] <= b[3] ? ord2f(b[3]) - ord2f(b[0]) : -1.f, ey = b[1] <= b[4] ? ord2f(b[4]) - ord2f(b[1]) : -1.f,
+              ez = b[2] <= b[5] ? ord2f(b[5]) - ord2f(b[2]) : -1.f;
   int axis = 0;  // the widest axis; ties -> the lower axis
   float e = ex;
   if (ey > e) { axis = 1; e = ey; }
@@ -1269,6 +1280,54 @@ int gloc_scan_store_debug_index(gloc_scan_store* st, uint32_t scan_id, uint32_t*
   }
   GLOC_HIP(hipStreamSynchronize(q));
   return GLOC_OK;
+}
+
+// Developer / test aid (not part of include/gloc3d.h): the rest of the index, as the search would see it now (curve or
+// kd order).  hdr_box: the header's lo[3], hi[3] (order-preserving integers); hdr_grid: ox, oy, oz, inv_cell; box_lo /
+// box_hi: the chunk boxes' centres and negated half extents / 64, 4 floats per chunk; sb2: the paired sub-block boxes,
+// 12 floats per pair, all n_pad / 32 pairs; sup_lo / sup_hi: 4 floats per super-chunk; pad_pts: pts[n : n_pad], 4 floats
+// each; order: the launch order for cs (1, 2 or 4) sources per lane, ceil(n / (64 cs)) entries, built on demand.  Any
+// output may be null.  An empty scan has a header and nothing else.
+int gloc_scan_store_debug_boxes(gloc_scan_store* st, uint32_t scan_id, int cs, uint32_t* hdr_box, float* hdr_grid,
+                                float* box_lo, float* box_hi, float* sb2, float* sup_lo, float* sup_hi, float* pad_pts,
+                                uint32_t* order) {
+  GLOC_REQUIRE(st, GLOC_ERR_INVALID, "null store");
+  GLOC_REQUIRE(!order || cs == 1 || cs == 2 || cs == 4, GLOC_ERR_INVALID, "sources per lane must be 1, 2 or 4 (got %d)", cs);
+  GLOC_HIP(hipSetDevice(st->device));
+  std::lock_guard<std::mutex> lk(st->mu);
+  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
+  DevScan& s = st->scans[scan_id];
+  hipStream_t q = st->stream;
+  if (hdr_box || hdr_grid) {
+    ScanHeader h;
+    GLOC_HIP(hipMemcpyAsync(&h, s.idx.hdr, sizeof(ScanHeader), hipMemcpyDeviceToHost, q));
+    GLOC_HIP(hipStreamSynchronize(q));
+    for (int a = 0; a < 3 && hdr_box; ++a) {
+      hdr_box[a] = h.lo[a];
+      hdr_box[3 + a] = h.hi[a];
+    }
+    if (hdr_grid) {
+      hdr_grid[0] = h.ox;
+      hdr_grid[1] = h.oy;
+      hdr_grid[2] = h.oz;
+      hdr_grid[3] = h.inv_cell;
+    }
+  }
+  if (!s.n) return GLOC_OK;
+  const size_t nch = s.idx.nchunks, n_pad = nch * CH, f4 = sizeof(f32x4);
+  if (box_lo) GLOC_HIP(hipMemcpyAsync(box_lo, s.idx.box_lo, f4 * nch, hipMemcpyDeviceToHost, q));
+  if (box_hi) GLOC_HIP(hipMemcpyAsync(box_hi, s.idx.box_hi, f4 * nch, hipMemcpyDeviceToHost, q));
+  if (sb2) GLOC_HIP(hipMemcpyAsync(sb2, s.idx.sb2, f4 * 3 * (n_pad / (2 * SB)), hipMemcpyDeviceToHost, q));
+  if (sup_lo) GLOC_HIP(hipMemcpyAsync(sup_lo, s.idx.sup_lo, f4 * s.idx.nsup, hipMemcpyDeviceToHost, q));
+  if (sup_hi) GLOC_HIP(hipMemcpyAsync(sup_hi, s.idx.sup_hi, f4 * s.idx.nsup, hipMemcpyDeviceToHost, q));
+  if (pad_pts && n_pad > s.n) GLOC_HIP(hipMemcpyAsync(pad_pts, s.idx.pts + s.n, f4 * (n_pad - s.n), hipMemcpyDeviceToHost, q));
+  int rc = GLOC_OK;
+  if (order && (rc = store_build_order(st, s, cs)) == GLOC_OK) {
+    const size_t group = 64 * (size_t)cs;
+    GLOC_HIP(hipMemcpyAsync(order, s.order_of(cs), sizeof(uint32_t) * ((s.n + group - 1) / group), hipMemcpyDeviceToHost, q));
+  }
+  GLOC_HIP(hipStreamSynchronize(q));  // (also after a failed order: the copies above write the caller's buffers)
+  return rc;
 }
 
 int gloc_scan_store_download(gloc_scan_store* st, uint32_t scan_id, float* out_xyz, size_t capacity_points) {

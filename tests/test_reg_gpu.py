@@ -3,6 +3,7 @@ nanoflann golden; RANSAC/ICP against the repo's CPU restatement -- parity unpinn
 import numpy as np
 import pytest
 
+import scan_index_ref as index_ref
 from util import bits, load_nn3_case, load_nn3_fullsize
 
 pytestmark = pytest.mark.gpu
@@ -190,6 +191,46 @@ def test_nn_with_nan_points_in_source_and_target(reg, oracle_mod, scans):
     r = reg.batch(src, [tgt], params=c.default_reg_params(ransac_iters=64, icp_iters=3))
     first = _LATTICE.setdefault("nan", (r["inliers"].copy(), r["T"].copy()))
     assert (first[0] == r["inliers"]).all() and np.isfinite(r["T"]).all() and r["inliers"][0] > 1000
+
+
+def test_nn_with_infinite_points_in_source_and_target(reg, oracle_mod):
+    """Targets with one non-finite coordinate (the scans of test_scan_index_gpu.py: one chunk, several chunks, two super
+    boxes; a +inf, a -inf, a sign-bit-set NaN; a far cluster that shares its chunk with the infinite point), sources with
+    +-inf rows: every finite source gets the oracle's neighbour among the wholly finite targets, bit for bit -- sources
+    beside the far cluster included, whose neighbour lies in the infinite point's chunk."""
+    rng = np.random.default_rng(31)
+    for name, tgt in index_ref.nonfinite_clouds():
+        side = 40.0 if name == "v" else 10.0
+        src = rng.uniform(-side / 2 - 1, side / 2 + 1, (500, 3)).astype(np.float32)
+        src[40:60] = index_ref.FAR + rng.uniform(-3, 3, (20, 3)).astype(np.float32)
+        bad_s = np.array([3, 100, 257, 499])
+        src[3, 0], src[100, 2], src[257], src[499, 1] = np.inf, -np.inf, np.inf, -np.inf
+        fin_s = np.ones(len(src), bool)
+        fin_s[bad_s] = False
+        fin_t = np.isfinite(tgt).all(1)
+        idx, d2 = reg.nn(src, tgt)
+        oi, od = oracle_mod.nn3(src[fin_s], tgt[fin_t])
+        back = np.flatnonzero(fin_t)          # positions in tgt of the finite targets
+        assert (idx[fin_s] == back[oi]).all() and (bits(d2[fin_s]) == bits(od)).all(), name
+
+
+@pytest.mark.parametrize("cs", [1, 2, 4])
+@pytest.mark.parametrize("ns,nt", index_ref.GROUP_SIZES)   # (63, 15) ... (257, 8193): test_scan_index_ref_cpu.py checks the list
+def test_nn_at_index_boundaries(reg, capi, oracle_mod, ns, nt, cs):
+    """Source groups of 64 * cs points and targets of one sub-block, pair, chunk and super box, each one short, full and
+    one over, under every sources-per-lane setting."""
+    from gloc3d_amd import synth
+    rng = np.random.default_rng(ns * 11 + nt)
+    src = rng.uniform(-50, 50, (ns, 3)).astype(np.float32)
+    tgt = rng.uniform(-50, 50, (nt, 3)).astype(np.float32)
+    T = synth.se3(12.0, (1.0, -2.0, 0.3)).astype(np.float32)
+    reg.set_option(capi.REG_OPT_NN_SRC_PER_LANE, cs)
+    try:
+        idx, d2 = reg.nn(src, tgt, T)
+    finally:
+        reg.set_option(capi.REG_OPT_NN_SRC_PER_LANE, 2)      # (the handle is the module's: back to the default)
+    oi, od = oracle_mod.nn3(oracle_mod.transform_points(T, src), tgt)
+    assert (idx == oi).all() and (bits(d2) == bits(od)).all()
 
 
 def test_nn_full_size_properties(reg, scans):

@@ -1216,79 +1216,57 @@ class Registrar(_Handle):
                                            C.byref(prm), _np_ptr(T), _np_ptr(prob), _np_ptr(iters), _np_ptr(conv)))
         return T, prob, iters, conv.astype(bool)
 
+    def _refine_batch(self, method, prm, src_id, tgt_ids, init_T, robust):
+        """A single-source entry of a Gauss-Newton refinement: gloc_reg_<method>_batch_ids, or its _robust form with the robust
+        block behind the method's own and the weights behind the other outputs."""
+        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
+        n = ids.shape[0]
+        it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
+        out = [np.empty((n, 4, 4), np.float32), np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)]
+        blocks = [C.byref(prm)]
+        if robust is not None:
+            out.append(np.empty(n, np.float32))
+            blocks.append(C.byref(robust))
+        fn = getattr(lib(), "gloc_reg_%s_batch_ids%s" % (method, "" if robust is None else "_robust"))
+        check(fn(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it), *blocks, *[_np_ptr(o) for o in out]))
+        return tuple(out)
+
+    def _refine_system(self, method, prm, src_id, tgt_id, T, robust, robust_pass):
+        """One evaluation of a refinement's normal equations: gloc_reg_<method>_system, or its _robust form with the robust
+        block and the pass behind the method's own block and the weights' sum behind the other outputs."""
+        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
+        H, g, s, c, ws = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64(), C.c_double()
+        head = (self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm))
+        if robust is not None:
+            check(getattr(lib(), "gloc_reg_%s_system_robust" % method)(*head, C.byref(robust), int(robust_pass), _np_ptr(H), _np_ptr(g),
+                                                                       C.byref(s), C.byref(c), C.byref(ws)))
+            return H, g, s.value, c.value, ws.value
+        check(getattr(lib(), "gloc_reg_%s_system" % method)(*head, _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
+        return H, g, s.value, c.value
+
     def p2l_batch(self, src_id, tgt_ids, init_T=None, params=None, robust=None):
         """Point-to-plane ICP of scan src_id against each of tgt_ids (gloc_reg_p2l_batch_ids): returns T [n, 4, 4] float32,
         rmse [n] float32 (point-to-plane, at the final pose), iterations [n], status [n] (0 cap, 1 converged, 2 degenerate).
         robust: a RobustParams -- every pair weighted by its residual (gloc_reg_p2l_batch_ids_robust); then also weight [n]
         float32, the mean weight of the final evaluation."""
-        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
-        n = ids.shape[0]
-        prm = params or default_p2l_params()
-        it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
-        T = np.empty((n, 4, 4), np.float32)
-        rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
-        if robust is not None:
-            weight = np.empty(n, np.float32)
-            check(lib().gloc_reg_p2l_batch_ids_robust(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
-                                                      C.byref(prm), C.byref(robust), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters),
-                                                      _np_ptr(status), _np_ptr(weight)))
-            return T, rmse, iters, status, weight
-        check(lib().gloc_reg_p2l_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
-                                           C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
-        return T, rmse, iters, status
+        return self._refine_batch("p2l", params or default_p2l_params(), src_id, tgt_ids, init_T, robust)
 
     def p2l_system(self, src_id, tgt_id, T=None, params=None, robust=None, robust_pass=0):
         """One evaluation of the point-to-plane normal equations at T: H [6, 6], g [6], sum r^2, pairs used.  robust: as
         p2l_batch, weighted at c(robust_pass) (gloc_reg_p2l_system_robust); then also the weights' sum."""
-        prm = params or default_p2l_params()
-        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
-        H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
-        if robust is not None:
-            ws = C.c_double()
-            check(lib().gloc_reg_p2l_system_robust(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
-                                                   C.byref(robust), int(robust_pass), _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c),
-                                                   C.byref(ws)))
-            return H, g, s.value, c.value, ws.value
-        check(lib().gloc_reg_p2l_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
-                                        _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
-        return H, g, s.value, c.value
+        return self._refine_system("p2l", params or default_p2l_params(), src_id, tgt_id, T, robust, robust_pass)
 
     def gicp_batch(self, src_id, tgt_ids, init_T=None, params=None, robust=None):
         """Generalized ICP of scan src_id against each of tgt_ids (gloc_reg_gicp_batch_ids): returns T [n, 4, 4] float32,
         rmse [n] float32 (sqrt of the mean e^T M e at the final pose), iterations [n], status [n] (0 cap, 1 converged,
         2 degenerate).  robust: a RobustParams (gloc_reg_gicp_batch_ids_robust); then also weight [n] float32, the mean
         weight of the final evaluation."""
-        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
-        n = ids.shape[0]
-        prm = params or default_gicp_params()
-        it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
-        T = np.empty((n, 4, 4), np.float32)
-        rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
-        if robust is not None:
-            weight = np.empty(n, np.float32)
-            check(lib().gloc_reg_gicp_batch_ids_robust(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
-                                                       C.byref(prm), C.byref(robust), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters),
-                                                       _np_ptr(status), _np_ptr(weight)))
-            return T, rmse, iters, status, weight
-        check(lib().gloc_reg_gicp_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
-                                            C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
-        return T, rmse, iters, status
+        return self._refine_batch("gicp", params or default_gicp_params(), src_id, tgt_ids, init_T, robust)
 
     def gicp_system(self, src_id, tgt_id, T=None, params=None, robust=None, robust_pass=0):
         """One evaluation of the generalized ICP normal equations at T: H [6, 6], g [6], sum e^T M e, pairs used.  robust: as
         gicp_batch, weighted at c(robust_pass) (gloc_reg_gicp_system_robust); then also the weights' sum."""
-        prm = params or default_gicp_params()
-        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
-        H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
-        if robust is not None:
-            ws = C.c_double()
-            check(lib().gloc_reg_gicp_system_robust(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
-                                                    C.byref(robust), int(robust_pass), _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c),
-                                                    C.byref(ws)))
-            return H, g, s.value, c.value, ws.value
-        check(lib().gloc_reg_gicp_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
-                                         _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
-        return H, g, s.value, c.value
+        return self._refine_system("gicp", params or default_gicp_params(), src_id, tgt_id, T, robust, robust_pass)
 
     def fpfh_match(self, src_feat, tgt_feat, mutual=True):
         """Nearest feature of every source row among the target rows (gloc_reg_fpfh_match): idx [n_src] uint32
@@ -1361,21 +1339,7 @@ class Registrar(_Handle):
         T [n, 4, 4] float32, rmse [n] float32 (sqrt of the weighted e^T M e per pair at the final pose), iterations [n],
         status [n] (0 cap, 1 converged, 2 degenerate).  robust: a RobustParams (gloc_reg_vgicp_batch_ids_robust); then also
         weight [n] float32, the mean weight of the final evaluation."""
-        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
-        n = ids.shape[0]
-        prm = params or default_vgicp_params()
-        it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
-        T = np.empty((n, 4, 4), np.float32)
-        rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
-        if robust is not None:
-            weight = np.empty(n, np.float32)
-            check(lib().gloc_reg_vgicp_batch_ids_robust(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
-                                                        C.byref(prm), C.byref(robust), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters),
-                                                        _np_ptr(status), _np_ptr(weight)))
-            return T, rmse, iters, status, weight
-        check(lib().gloc_reg_vgicp_batch_ids(self._h, int(src_id), _np_ptr(ids), n, None if it is None else _np_ptr(it),
-                                             C.byref(prm), _np_ptr(T), _np_ptr(rmse), _np_ptr(iters), _np_ptr(status)))
-        return T, rmse, iters, status
+        return self._refine_batch("vgicp", params or default_vgicp_params(), src_id, tgt_ids, init_T, robust)
 
     def _pairs(self, fn, prm, src_ids, tgt_ids, init_T, robust):
         """A pair-list entry (gloc_reg_<m>_pairs): row c is (src_ids[c], tgt_ids[c]); None in tgt_ids is "no target"."""
@@ -1410,18 +1374,7 @@ class Registrar(_Handle):
         """One evaluation of the voxelized generalized ICP normal equations at T: H [6, 6], g [6], the weighted sum of
         e^T M e, pairs used.  robust: as vgicp_batch, weighted at c(robust_pass) (gloc_reg_vgicp_system_robust); then also
         the weights' sum."""
-        prm = params or default_vgicp_params()
-        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
-        H, g, s, c = np.empty((6, 6), np.float64), np.empty(6, np.float64), C.c_double(), C.c_uint64()
-        if robust is not None:
-            ws = C.c_double()
-            check(lib().gloc_reg_vgicp_system_robust(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
-                                                     C.byref(robust), int(robust_pass), _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c),
-                                                     C.byref(ws)))
-            return H, g, s.value, c.value, ws.value
-        check(lib().gloc_reg_vgicp_system(self._h, int(src_id), int(tgt_id), None if t is None else _np_ptr(t), C.byref(prm),
-                                          _np_ptr(H), _np_ptr(g), C.byref(s), C.byref(c)))
-        return H, g, s.value, c.value
+        return self._refine_system("vgicp", params or default_vgicp_params(), src_id, tgt_id, T, robust, robust_pass)
 
     def vgicp_voxels(self, scan_id, params=None):
         """The voxels of a scan, sorted by key: dict(key3 [m, 3] int32, count [m], mean [m, 3], nn6 [m, 6] = the mean of the

@@ -23,22 +23,18 @@ int check_params(const gloc_gicp_params* p) {
   return GLOC_OK;
 }
 
-int run(const p2l::Ctx& x, const p2l::TargetView* tgts, const float* init_T, const gloc_gicp_params* prm,
-        float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum,
-        uint64_t* out_count, const p2l::RobustArgs& rb) {
-  std::vector<Target> ht(x.n_jobs);
-  for (uint32_t c = 0; c < x.n_jobs; ++c) ht[c] = Target{tgts[c].pts, tgts[c].nrm, tgts[c].n, 0u};
+int run(const p2l::Ctx& x, const Target* tgts, const gn6::Call& call, const gloc_gicp_params* prm) {
   const gn6::Loop lp{prm->max_iters, prm->max_corr_dist, prm->trans_eps, prm->rot_eps, "gicp_accum", "gicp_solve"};
   const double a = 1.0 - (double)prm->plane_eps;
   auto accum = [&](const Target* d_tgts, const gn6::Source* d_srcs, const State* states, float gate2, bool skip_stopped, double* partials,
                    uint32_t n_blk, const gn6::Scale2& sc) {
-    gn6::for_kind(rb.kind(), [&](auto kind) {
+    gn6::for_kind(call.kind(), [&](auto kind) {
       hipLaunchKernelGGL(HIP_KERNEL_NAME(gicp_accum_kernel<decltype(kind)::value>), dim3(n_blk, x.n_jobs), dim3(ACC_THREADS), 0, x.stream,
                          d_srcs, d_tgts, x.pose_f32, x.pose_stride, states, x.corr, x.d2, x.ld, gate2, a, skip_stopped,
                          partials, sc);
     });
   };
-  return gn6::run(x, lp, ht, init_T, accum, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum, out_count, rb);
+  return gn6::run(x, lp, tgts, call, accum);
 }
 
 }  // namespace gicp

@@ -37,12 +37,7 @@ using gn6::ACC_THREADS;
 using gn6::NSLOT;
 using gn6::NSUM;
 using gn6::State;
-
-struct Target {  // of a job
-  const f32x4* pts;  // the search order: x, y, z, bits(original index)
-  const float* nrm;  // normals in that order, packed; zero = none
-  uint32_t n, pad_;
-};
+using gn6::Target;
 
 template <int KIND>
 __global__ __launch_bounds__(ACC_THREADS) void gicp_accum_kernel(const gn6::Source* __restrict__ srcs, const Target* __restrict__ tgts,

@@ -1,6 +1,8 @@
 // gn6.hpp -- the host side the Gauss-Newton refinements share (p2l.hip, gicp.hip, vgicp.hip): the handle's workspace and the
 // loop of passes.  A pass is three enqueues: the registration's exact 1-NN search (none for the voxelized refinement,
-// whose Ctx::nn_pass is null), the refinement's own accumulate kernel, the solve kernel of gn6_kernels.hpp.
+// whose Ctx::nn_pass is null), the refinement's own accumulate kernel, the solve kernel of gn6_kernels.hpp.  What is asked
+// for -- the guesses, a batch or ONE evaluation of the system, the outputs, the robust block -- arrives as the gn6::Call
+// (p2l.hpp) the C entry filled.
 //
 // Synchronisation between passes: none.  Whether a job has stopped is a flag on the device that the accumulate and solve
 // kernels of later passes read.  With both eps off a job can only stop early by being degenerate, so all max_iters passes
@@ -51,19 +53,20 @@ struct Loop {  // what the refinements' parameter blocks have in common
   const char *accum_name, *solve_name;  // in the handle's profile
 };
 
-// Refines every job from init_T ([n][16] or null: identity); any of the last four non-null: ONE evaluation at init_T of
-// job 0 instead.  `tgts`: the jobs' targets as the accumulate kernel takes them, copied to the device beside the table of
-// the jobs' sources (gn6::Source, made here from x.srcs: every job's work-group count and its first row of the partials);
-// accum(targets and sources on the device, states, gate^2, skip_stopped, partials, the grid's width -- the largest
-// work-group count --, the pass's Scale2) enqueues that kernel.  Returns after the results have been copied out.
+// Refines every job of `call` from its init_T, or with call.system evaluates job 0 ONCE at it.  `tgts` [x.n_jobs]: the
+// jobs' targets as the accumulate kernel takes them, copied to the device beside the table of the jobs' sources
+// (gn6::Source, made here from x.srcs: every job's work-group count and its first row of the partials); accum(targets and
+// sources on the device, states, gate^2, skip_stopped, partials, the grid's width -- the largest work-group count --, the
+// pass's Scale2) enqueues that kernel.  Returns after the results have been copied out.
 //
-// rb (robust.hpp): with a kind other than NONE accum is also handed the pass's scale -- the table of c(k)^2 made here
-// with the host helper's own function, indexed by each job's update count, during the loop; scale^2 for the evaluation
-// after it; c(pass)^2 for the system form -- and the solve kernel the first update index at which the stop test counts.
+// call.robust (robust.hpp): with a kind other than NONE accum is also handed the pass's scale -- the table of c(k)^2 made
+// here with the host helper's own function, indexed by each job's update count, during the loop; scale^2 for the
+// evaluation after it; c(call.pass)^2 for the system form -- and the solve kernel the first update index at which the
+// stop test counts.
 template <class Target, class Accum>
-int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, const float* init_T, Accum&& accum, float* out_T,
-        float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count,
-        const p2l::RobustArgs& rb = p2l::RobustArgs()) {
+int run(const p2l::Ctx& x, const Loop& lp, const Target* tgts, const Call& call, Accum&& accum) {
+  const float* init_T = call.init_T;
+  const gloc_robust_params* rb = call.robust;
   if (!*x.ws) {
     *x.ws = new (std::nothrow) p2l::Ws;
     GLOC_REQUIRE(*x.ws, GLOC_ERR_NOMEM, "host allocation failed");
@@ -71,8 +74,7 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
   p2l::Ws& w = **x.ws;
   const hipStream_t q = x.stream;
   const uint32_t n = x.n_jobs;
-  const bool system = out_H36 || out_g6 || out_sum || out_count || rb.out_wsum;
-  const bool weighted = rb.kind() != GLOC_ROBUST_NONE;
+  const bool weighted = call.kind() != GLOC_ROBUST_NONE;
   // a job's work-groups and rows depend on its own source alone: the partition a call on the job alone makes
   std::vector<Source> hsrc(n);
   uint64_t n_rows = 0;
@@ -103,7 +105,7 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
   GLOC_TRY(w.exp.ensure(sizeof(double) * NSUM * n, q));
   if (!w.h_done) GLOC_HIP(hipHostMalloc(reinterpret_cast<void**>(&w.h_done), 16, hipHostMallocDefault));
   if (!w.ev) GLOC_HIP(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
-  GLOC_HIP(hipMemcpyAsync(w.tgts.p, tgts.data(), sizeof(Target) * n, hipMemcpyHostToDevice, q));
+  GLOC_HIP(hipMemcpyAsync(w.tgts.p, tgts, sizeof(Target) * n, hipMemcpyHostToDevice, q));
   GLOC_HIP(hipMemcpyAsync(w.srcs.p, hsrc.data(), sizeof(Source) * n, hipMemcpyHostToDevice, q));
   GLOC_HIP(hipMemcpyAsync(w.states.p, hs.data(), sizeof(State) * n, hipMemcpyHostToDevice, q));
   GLOC_HIP(hipMemsetAsync(w.done.p, 0, 16, q));
@@ -112,15 +114,15 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
   uint32_t stop_from = 0;
   Scale2 loop_sc{nullptr, 0, 0.0}, end_sc{nullptr, 0, 0.0};
   if (weighted) {
-    if (system) {
-      const double c = robust::scale_at(rb.prm, rb.pass);
+    if (call.system) {
+      const double c = robust::scale_at(rb, call.pass);
       end_sc.fixed = c * c;
     } else {
       stop_from = 0xFFFFFFFFu;  // (a schedule that has not settled by the last update: no update's stop test counts)
-      double c = robust::scale_first(rb.prm);
-      for (uint32_t k = 0; k < lp.max_iters; ++k, c = robust::scale_next(rb.prm, c)) {
+      double c = robust::scale_first(rb);
+      for (uint32_t k = 0; k < lp.max_iters; ++k, c = robust::scale_next(rb, c)) {
         c2.push_back(c * c);
-        if (c == (double)rb.prm->scale) {
+        if (c == (double)rb->scale) {
           stop_from = k;
           break;
         }
@@ -129,10 +131,10 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
       GLOC_TRY(w.c2tab.ensure(sizeof(double) * n_tab, q));
       GLOC_HIP(hipMemcpyAsync(w.c2tab.p, c2.data(), sizeof(double) * n_tab, hipMemcpyHostToDevice, q));
       loop_sc = Scale2{w.c2tab.template as<double>(), n_tab, 0.0};
-      end_sc.fixed = (double)rb.prm->scale * (double)rb.prm->scale;
+      end_sc.fixed = (double)rb->scale * (double)rb->scale;
     }
   }
-  GLOC_HIP(hipStreamSynchronize(q));  // (tgts, hsrc and hs are host vectors)
+  GLOC_HIP(hipStreamSynchronize(q));  // (tgts, hsrc and hs are host memory)
   const float gate2 = lp.max_corr_dist > 0.f ? lp.max_corr_dist * lp.max_corr_dist : 0.f;
   bool warm = false;
   // search, accumulate, solve at the current poses; mode 1: evaluation only
@@ -153,21 +155,21 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
     GLOC_HIP(hipGetLastError());
     return GLOC_OK;
   };
-  if (system) {
+  if (call.system) {
     GLOC_TRY(pass(1, w.exp.template as<double>()));
     double s[NSUM];
     GLOC_HIP(hipMemcpyAsync(s, w.exp.p, sizeof(double) * NSUM, hipMemcpyDeviceToHost, q));
     GLOC_HIP(hipMemcpyAsync(hs.data(), w.states.p, sizeof(State), hipMemcpyDeviceToHost, q));
     GLOC_HIP(hipStreamSynchronize(q));
-    if (out_H36) {
+    if (call.out_H36) {
       int e = 0;
       for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b, ++e) out_H36[6 * a + b] = out_H36[6 * b + a] = s[e];
+        for (int b = a; b < 6; ++b, ++e) call.out_H36[6 * a + b] = call.out_H36[6 * b + a] = s[e];
     }
-    if (out_g6) std::copy(s + 21, s + 27, out_g6);
-    if (out_sum) *out_sum = s[27];
-    if (out_count) *out_count = (uint64_t)s[28];
-    if (rb.out_wsum) *rb.out_wsum = weighted ? hs[0].wsum : s[28];  // (kind NONE: every pair's weight is 1)
+    if (call.out_g6) std::copy(s + 21, s + 27, call.out_g6);
+    if (call.out_sum) *call.out_sum = s[27];
+    if (call.out_count) *call.out_count = (uint64_t)s[28];
+    if (call.out_wsum) *call.out_wsum = weighted ? hs[0].wsum : s[28];  // (kind NONE: every pair's weight is 1)
     return GLOC_OK;
   }
   const bool can_converge = lp.trans_eps > 0.f && lp.rot_eps > 0.f;
@@ -185,18 +187,18 @@ int run(const p2l::Ctx& x, const Loop& lp, const std::vector<Target>& tgts, cons
   GLOC_HIP(hipStreamSynchronize(q));
   for (uint32_t c = 0; c < n; ++c) {
     const State& s = hs[c];
-    if (out_T) {
-      float* T = out_T + 16 * (size_t)c;
+    if (call.out_T) {
+      float* T = call.out_T + 16 * (size_t)c;
       for (int i = 0; i < 3; ++i) {
         for (int j = 0; j < 3; ++j) T[4 * i + j] = (float)s.Td[3 * i + j];
         T[4 * i + 3] = (float)s.Td[9 + i];
       }
       T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
     }
-    if (out_rmse) out_rmse[c] = (float)s.rmse;
-    if (out_iters) out_iters[c] = s.iters;
-    if (out_status) out_status[c] = s.status;
-    if (rb.out_weight) rb.out_weight[c] = s.count == 0 ? 0.f : weighted ? (float)(s.wsum / (double)s.count) : 1.f;
+    if (call.out_rmse) call.out_rmse[c] = (float)s.rmse;
+    if (call.out_iters) call.out_iters[c] = s.iters;
+    if (call.out_status) call.out_status[c] = s.status;
+    if (call.out_weight) call.out_weight[c] = s.count == 0 ? 0.f : weighted ? (float)(s.wsum / (double)s.count) : 1.f;
   }
   return GLOC_OK;
 }

@@ -27,6 +27,7 @@
 
 #include "lane_ops.hpp"
 #include "math3.hpp"  // f32x4
+#include "p2l.hpp"    // gn6::Target: declared where reg.hip, which fills the table, sees it
 #include "robust.hpp"
 
 namespace gloc {

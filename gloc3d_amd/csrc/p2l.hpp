@@ -1,19 +1,56 @@
-// p2l.hpp -- what reg.hip (which owns the registration handle and the 1-NN passes) calls of p2l.hip.
+// p2l.hpp -- what the Gauss-Newton refinements (p2l.hip, gicp.hip, vgicp.hip) share on the host with reg.hip, which owns
+// the registration handle and the 1-NN passes: the description of a call (gn6::Call), the handle's view for one batch
+// (Ctx) and the entry points of p2l.hip.
 #pragma once
 #include "common.hpp"
 #include "math3.hpp"
 
 namespace gloc {
+namespace gn6 {
+
+// A job's target as the point-based accumulate kernels take it (p2l_kernels.hpp, gicp_kernels.hpp): the scan as the search
+// indexes it.  reg.hip fills the table; n = 0 (and null pointers): a job without a target.
+struct Target {
+  const reg::f32x4* pts;  // the search order: x, y, z, bits(original index)
+  const float* nrm;       // normals in that order, packed; zero = none
+  uint32_t n, pad_;
+};
+
+// One call of a refinement entry, whatever its cost function: the jobs, where the results go and the robust half.  A C
+// entry of reg.hip fills one; everything below it -- refine_entry, run_p2l / run_gicp, run_refine, vgicp::run, p2l::run,
+// gicp::run, gn6::run -- takes it beside the method's own parameter block.
+struct Call {
+  // the jobs: the ONE source src_ids[0] against n targets, or with `pairs` row c is (src_ids[c], tgt_ids[c]), 0xFFFFFFFF in
+  // tgt_ids for "no target"; init_T [n][16] or null: identity
+  const uint32_t* src_ids = nullptr;
+  bool pairs = false;
+  const uint32_t* tgt_ids = nullptr;
+  size_t n = 0;
+  const float* init_T = nullptr;
+  // false: every job is refined and the batch outputs [n] are written (out_T is asked for, the others may be null);
+  // true: ONE evaluation at init_T of job 0 into the system outputs (all asked for; out_wsum by a robust entry)
+  bool system = false;
+  float *out_T = nullptr, *out_rmse = nullptr;
+  uint32_t* out_iters = nullptr;
+  int* out_status = nullptr;
+  float* out_weight = nullptr;  // the weights' sum over the count of the final evaluation
+  double *out_H36 = nullptr, *out_g6 = nullptr, *out_sum = nullptr;
+  uint64_t* out_count = nullptr;
+  double* out_wsum = nullptr;
+  // the robust half (robust.hpp; include/gloc3d.h): null or of kind NONE: the plain kernels.  need_robust: the entry is a
+  // _robust one, which refuses a null block; pass: the update the system form evaluates at
+  const gloc_robust_params* robust = nullptr;
+  bool need_robust = false;
+  uint32_t pass = 0;
+  uint32_t kind() const { return robust ? robust->kind : (uint32_t)GLOC_ROBUST_NONE; }
+};
+
+}  // namespace gn6
+
 namespace p2l {
 
 struct Ws;  // a handle's workspace for point-to-plane and generalized ICP (gn6.hpp; created on first use)
 void ws_free(Ws* w);
-
-struct TargetView {  // a job's target as the search indexes it
-  const reg::f32x4* pts;
-  const float* nrm;
-  uint32_t n;
-};
 
 struct SourceView {  // a job's source in search order (idx.pts) with its normals in that order (null: none asked for)
   const reg::f32x4* pts;
@@ -39,22 +76,10 @@ struct Ctx {
   void* self;
 };
 
-// The robust half of a call (the _robust entries; include/gloc3d.h): the block, the pass the system form evaluates at and
-// the outputs the plain entries do not have.  prm null or of kind NONE: the plain kernels.
-struct RobustArgs {
-  const gloc_robust_params* prm = nullptr;
-  uint32_t pass = 0;
-  float* out_weight = nullptr;  // [n]: the weights' sum over the count of the final evaluation
-  double* out_wsum = nullptr;   // system form
-  uint32_t kind() const { return prm ? prm->kind : (uint32_t)GLOC_ROBUST_NONE; }
-};
-
 int check_params(const gloc_p2l_params* prm);
-// Refines every job from init_T ([n][16] or null: identity).  system36/g6/sum_r2/count non-null: ONE evaluation at init_T
-// of job 0 instead (gloc_reg_p2l_system).  Returns after the results have been copied out.
-int run(const Ctx& x, const TargetView* tgts, const float* init_T, const gloc_p2l_params* prm, float* out_T, float* out_rmse,
-        uint32_t* out_iters, int* out_status, double* out_H36, double* out_g6, double* out_sum_r2, uint64_t* out_count,
-        const RobustArgs& rb = RobustArgs());
+// Refines every job of c, or evaluates job 0 once (c.system); tgts [x.n_jobs]: the jobs' targets as the search indexes
+// them.  Returns after the results have been copied out.
+int run(const Ctx& x, const gn6::Target* tgts, const gn6::Call& c, const gloc_p2l_params* prm);
 
 }  // namespace p2l
 }  // namespace gloc

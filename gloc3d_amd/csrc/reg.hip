@@ -834,16 +834,16 @@ struct TempScans {
   }
 };
 
-// Point-to-plane or generalized ICP refinement (p2l.hip, gicp.hip) of a list of (source, target) jobs: a searching batch
-// (open_batch) over the longest source -- job table, fp32 poses in the CandState array the search reads, corr / d2 as
-// [job][ld(longest source)] -- without a split plan (it is solve_kernel that makes one), and `refine` (p2l::run or
-// gicp::run behind their arguments) drives the passes through launch_nn.  Synchronous: the scans are pinned for the call.
-// `pairs` false: ONE source, src_ids[0], against n targets (the single-source entries); true: row c is (src_ids[c],
-// tgt_ids[c]), 0xFFFFFFFF for "no target" -- such a row has no source group to search and no source slot to sum, and comes
-// out as the row of an empty target -- and the ids are checked before anything is enqueued (store_check_pairs).
-// Targets without normals get them with normal_k, and with src_normals so does every distinct source; `refine` is handed
-// every job's source (its normals null without src_normals): DevScan::nrm is in the order of idx.pts whatever that order is
-// (curve or kd: scan_store.hpp), the order of the slots corr is indexed by.
+// Point-to-plane or generalized ICP refinement (p2l.hip, gicp.hip) of the jobs of a call (gn6::Call: one source against n
+// targets, or a list of (source, target) pairs): the scans of the call resolved and pinned (CallScans, scan_store.hpp,
+// shared with vgicp::run: ids checked before anything is enqueued, targets without normals given them with normal_k and
+// with src_normals so is every distinct source), then a searching batch (open_batch) over the longest source -- job table,
+// fp32 poses in the CandState array the search reads, corr / d2 as [job][ld(longest source)] -- without a split plan (it is
+// solve_kernel that makes one), and `refine` (p2l::run or gicp::run with the method's block) drives the passes through
+// launch_nn.  Synchronous: the scans stay pinned for the call.  A row without a target has no source group to search and
+// no source slot to sum, and comes out as the row of an empty target.  `refine` is handed every job's target as the
+// search indexes it, and through the Ctx its source (normals null without src_normals): DevScan::nrm is in the order of
+// idx.pts whatever that order is (curve or kd: scan_store.hpp), the order of the slots corr is indexed by.
 struct P2lPass {
   gloc_reg* h;
   BatchDims bd;
@@ -854,69 +854,28 @@ struct P2lPass {
   }
 };
 
-constexpr uint32_t NO_SCAN = 0xFFFFFFFFu;
-
 template <class Refine>
-int run_refine(gloc_reg* h, const uint32_t* src_ids, bool pairs, const uint32_t* tgt_ids, size_t n, const float* init_T,
-               uint32_t normal_k, bool src_normals, Refine&& refine) {
-  GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
-  GLOC_REQUIRE(h->store, GLOC_ERR_INVALID, "unknown scan id %u", src_ids[0]);
-  gloc_scan_store* st = h->store;
+int run_refine(gloc_reg* h, const gloc::gn6::Call& call, uint32_t normal_k, bool src_normals, Refine&& refine) {
   hipStream_t s = h->stream;
   const int cs = h->nn_src_per_lane;
-  if (pairs) GLOC_TRY(store_check_pairs(st, src_ids, tgt_ids, n));
-  // the scans of the call: every distinct source (with its launch order), then the target of every job that has one
-  std::vector<uint32_t> ids, job_src;
-  distinct_in_order(src_ids, pairs ? n : 1, &ids, &job_src);
-  job_src.resize(n, 0u);
-  const size_t n_srcs = ids.size();
-  std::vector<int> css(n_srcs, cs);
-  std::vector<uint32_t> job_scan(n, NO_SCAN);  // where job c's target is among the pinned scans
-  for (size_t c = 0; c < n; ++c) {
-    if (pairs && tgt_ids[c] == NO_SCAN) continue;
-    job_scan[c] = (uint32_t)ids.size();
-    ids.push_back(tgt_ids[c]);
-    css.push_back(0);
-  }
-  // (an unknown source id without src_normals: refused by pin())
-  if (ids.size() > n_srcs) GLOC_TRY(store_ensure_normals(st, ids.data() + n_srcs, ids.size() - n_srcs, normal_k));
-  if (src_normals) GLOC_TRY(store_ensure_normals(st, ids.data(), n_srcs, normal_k));
-  ScopedPins pins(st, s);
-  GLOC_TRY(pins.pin(ids.data(), css.data(), ids.size()));
-  const std::vector<DevScan>& scans = pins.scans;
+  CallScans rs(h->store, s);
+  GLOC_TRY(rs.resolve(call, normal_k, src_normals, cs));
+  const uint32_t n_jobs = (uint32_t)call.n;
   size_t max_src = 0;
-  for (size_t u = 0; u < n_srcs; ++u) {
-    const DevScan& src = scans[u];
-    GLOC_REQUIRE(src.n >= 1 && src.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
-    GLOC_REQUIRE(!src_normals || src.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", ids[u]);
-    max_src = std::max<size_t>(max_src, src.n);
-  }
-  const uint32_t n_jobs = (uint32_t)n;
-  std::vector<gloc::p2l::TargetView> tv(n);
-  std::vector<gloc::p2l::SourceView> sv(n);
-  for (uint32_t c = 0; c < n_jobs; ++c) {
-    const DevScan& src = scans[job_src[c]];
-    if (job_scan[c] == NO_SCAN) {
-      tv[c] = gloc::p2l::TargetView{nullptr, nullptr, 0u};
-      sv[c] = gloc::p2l::SourceView{src.idx.pts, src_normals ? src.nrm : nullptr, 0u};
-      continue;
-    }
-    const DevScan& t = scans[job_scan[c]];
-    GLOC_REQUIRE(t.n == 0 || t.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", tgt_ids[c]);
-    tv[c] = gloc::p2l::TargetView{t.idx.pts, t.nrm, (uint32_t)t.n};
-    sv[c] = gloc::p2l::SourceView{src.idx.pts, src_normals ? src.nrm : nullptr, (uint32_t)src.n};
-  }
+  for (size_t u = 0; u < rs.n_srcs; ++u) max_src = std::max<size_t>(max_src, rs.pins.scans[u].n);
+  std::vector<gloc::gn6::Target> tv(n_jobs, gloc::gn6::Target{nullptr, nullptr, 0u, 0u});
+  for (uint32_t c = 0; c < n_jobs; ++c)
+    if (const DevScan* t = rs.tgt(c)) tv[c] = gloc::gn6::Target{t->idx.pts, t->nrm, (uint32_t)t->n, 0u};
   Batch b;
   GLOC_TRY(open_batch(h, BatchSpec::searching(n_jobs, max_src, src_groups(max_src, cs)), &b, [&](Job* jd, CandState* cst) {
     for (uint32_t c = 0; c < n_jobs; ++c) {
-      const DevScan& src = scans[job_src[c]];
-      if (job_scan[c] == NO_SCAN) {
-        jd[c] = Job{src.idx.pts, src.order, src.idx.inv, nullptr, ScanIndexDev{}, 0u, 0u, c, 0u};
+      const DevScan& src = rs.src(c);
+      if (const DevScan* t = rs.tgt(c)) {
+        jd[c] = Job{src.idx.pts, src.order, src.idx.inv, t->xyz, t->idx, (uint32_t)src.n, src_groups(src.n, cs), c, 0u};
       } else {
-        const DevScan& t = scans[job_scan[c]];
-        jd[c] = Job{src.idx.pts, src.order, src.idx.inv, t.xyz, t.idx, (uint32_t)src.n, src_groups(src.n, cs), c, 0u};
+        jd[c] = Job{src.idx.pts, src.order, src.idx.inv, nullptr, ScanIndexDev{}, 0u, 0u, c, 0u};
       }
-      init_state(cst[c], init_T ? init_T + 16 * (size_t)c : nullptr);
+      init_state(cst[c], call.init_T ? call.init_T + 16 * (size_t)c : nullptr);
     }
   }));
   const BatchDims& bd = b.bd;
@@ -926,7 +885,7 @@ int run_refine(gloc_reg* h, const uint32_t* src_ids, bool pairs, const uint32_t*
   x.stream = s;
   x.prof = &h->prof;
   x.ws = &h->p2l;
-  x.srcs = sv.data();
+  x.srcs = rs.srcs.data();
   x.n_jobs = n_jobs;
   x.pose_f32 = reinterpret_cast<float*>(h->states.as<char>() + offsetof(CandState, Tf));
   x.pose_stride = sizeof(CandState) / sizeof(float);
@@ -938,21 +897,14 @@ int run_refine(gloc_reg* h, const uint32_t* src_ids, bool pairs, const uint32_t*
   return refine(x, tv.data());
 }
 
-int run_p2l(gloc_reg* h, const uint32_t* src_ids, bool pairs, const uint32_t* tgt_ids, size_t n, const float* init_T,
-            const gloc_p2l_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36,
-            double* out_g6, double* out_sum_r2, uint64_t* out_count, const gloc::p2l::RobustArgs& rb = gloc::p2l::RobustArgs()) {
-  GLOC_TRY(gloc::p2l::check_params(prm));
-  return run_refine(h, src_ids, pairs, tgt_ids, n, init_T, prm->normal_k, false, [&](const gloc::p2l::Ctx& x, const gloc::p2l::TargetView* tv) {
-    return gloc::p2l::run(x, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum_r2, out_count, rb);
-  });
+int run_p2l(gloc_reg* h, const gloc::gn6::Call& call, const gloc_p2l_params* prm) {
+  return run_refine(h, call, prm->normal_k, false,
+                    [&](const gloc::p2l::Ctx& x, const gloc::gn6::Target* tv) { return gloc::p2l::run(x, tv, call, prm); });
 }
 
-int run_gicp(gloc_reg* h, const uint32_t* src_ids, bool pairs, const uint32_t* tgt_ids, size_t n, const float* init_T,
-             const gloc_gicp_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36,
-             double* out_g6, double* out_sum, uint64_t* out_count, const gloc::p2l::RobustArgs& rb = gloc::p2l::RobustArgs()) {
-  return run_refine(h, src_ids, pairs, tgt_ids, n, init_T, prm->normal_k, true, [&](const gloc::p2l::Ctx& x, const gloc::p2l::TargetView* tv) {
-    return gloc::gicp::run(x, tv, init_T, prm, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum, out_count, rb);
-  });
+int run_gicp(gloc_reg* h, const gloc::gn6::Call& call, const gloc_gicp_params* prm) {
+  return run_refine(h, call, prm->normal_k, true,
+                    [&](const gloc::p2l::Ctx& x, const gloc::gn6::Target* tv) { return gloc::gicp::run(x, tv, call, prm); });
 }
 
 // FPFH feature-based global registration (fpfh.hip): the descriptor matches of the source against every target, forward and
@@ -1207,6 +1159,74 @@ int run_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const 
 
 gloc::ndt::Ctx ndt_ctx(gloc_reg* h) { return gloc::ndt::Ctx{h->store, h->stream, &h->prof, &h->ndt}; }
 gloc::vgicp::Ctx vgicp_ctx(gloc_reg* h) { return gloc::vgicp::Ctx{h->store, h->stream, &h->prof, &h->vgicp, &h->p2l}; }
+
+// Voxelized generalized ICP (vgicp.hip): no 1-NN search, so none of this file's batch set-up -- the call builds its
+// targets' voxel maps and runs the shared loop of passes on the handle's stream.
+int run_vgicp(gloc_reg* h, const gloc::gn6::Call& call, const gloc_vgicp_params* prm) { return gloc::vgicp::run(vgicp_ctx(h), call, prm); }
+
+// The two shapes of a Gauss-Newton refinement call (gn6::Call, p2l.hpp) as the C entries fill them; an entry with a robust
+// block sets the robust half behind it.
+gloc::gn6::Call batch_call(const uint32_t* src_ids, bool pairs, const uint32_t* tgt_ids, size_t n, const float* init_T, float* out_T,
+                           float* out_rmse, uint32_t* out_iters, int* out_status) {
+  gloc::gn6::Call c;
+  c.src_ids = src_ids;
+  c.pairs = pairs;
+  c.tgt_ids = tgt_ids;
+  c.n = n;
+  c.init_T = init_T;
+  c.out_T = out_T;
+  c.out_rmse = out_rmse;
+  c.out_iters = out_iters;
+  c.out_status = out_status;
+  return c;
+}
+
+gloc::gn6::Call system_call(const uint32_t* src_id, const uint32_t* tgt_id, const float* T16, double* out_H36, double* out_g6, double* out_sum,
+                            uint64_t* out_count) {
+  gloc::gn6::Call c;
+  c.src_ids = src_id;
+  c.tgt_ids = tgt_id;
+  c.n = 1;
+  c.init_T = T16;
+  c.system = true;
+  c.out_H36 = out_H36;
+  c.out_g6 = out_g6;
+  c.out_sum = out_sum;
+  c.out_count = out_count;
+  return c;
+}
+
+gloc::gn6::Call robust_call(gloc::gn6::Call c, const gloc_robust_params* robust, uint32_t pass, float* out_weight, double* out_wsum) {
+  c.robust = robust;
+  c.need_robust = true;
+  c.pass = pass;
+  c.out_weight = out_weight;
+  c.out_wsum = out_wsum;
+  return c;
+}
+
+// What every entry of the three refinements does with its call, and the ONE order of its refusals: the method's own
+// block, the robust block (a null one only where the entry has to have one), the arrays and n, the handle, a batch in
+// flight -- and then the method's run.
+template <class Params>
+int refine_entry(gloc_reg* h, const gloc::gn6::Call& c, const Params* prm, int (*check)(const Params*),
+                 int (*run)(gloc_reg*, const gloc::gn6::Call&, const Params*)) {
+  GLOC_TRY(check(prm));
+  if (c.robust || c.need_robust) GLOC_TRY(gloc::robust::check_params(c.robust));
+  if (c.system) {
+    GLOC_REQUIRE(c.out_H36 && c.out_g6 && c.out_sum && c.out_count && (c.out_wsum || !c.need_robust), GLOC_ERR_INVALID, "null argument");
+  } else if (c.pairs) {
+    GLOC_REQUIRE(c.src_ids && c.tgt_ids, GLOC_ERR_INVALID, "null scan ids");
+    GLOC_REQUIRE(c.out_T, GLOC_ERR_INVALID, "out_T is null");
+  } else {
+    GLOC_REQUIRE(c.out_T && c.tgt_ids, GLOC_ERR_INVALID, "null argument");
+  }
+  GLOC_REQUIRE(c.n >= 1 && c.n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", c.n);
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run(h, c, prm);
+}
 
 }  // namespace
 
@@ -1793,208 +1813,113 @@ int gloc_reg_ndt_cells(gloc_reg* h, uint32_t scan_id, const gloc_ndt_params* prm
   return gloc::ndt::cells(ndt_ctx(h), scan_id, prm, capacity, out_key3, out_count, out_mean3, out_icov9, n_cells);
 }
 
+// The entries of the three Gauss-Newton refinements: each fills its call (batch_call / system_call, the robust half behind
+// it) and hands it with the method's block to refine_entry.
 int gloc_reg_p2l_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
                            const gloc_p2l_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status) {
-  GLOC_REQUIRE(h && out_T && tgt_scan_ids && prm, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  return run_p2l(h, &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
-                 nullptr);
+  return refine_entry(h, batch_call(&src_scan_id, false, tgt_scan_ids, n, init_T, out_T, out_rmse, out_iters, out_status), prm,
+                      gloc::p2l::check_params, run_p2l);
 }
 
 int gloc_reg_p2l_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_p2l_params* prm,
                         double* out_H36, double* out_g6, double* out_sum_r2, uint64_t* out_count) {
-  GLOC_REQUIRE(h && prm && out_H36 && out_g6 && out_sum_r2 && out_count, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  return run_p2l(h, &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum_r2, out_count);
+  return refine_entry(h, system_call(&src_scan_id, &tgt_scan_id, T16, out_H36, out_g6, out_sum_r2, out_count), prm,
+                      gloc::p2l::check_params, run_p2l);
 }
 
-// (the parameters are looked at before the handle: a bad block is refused whatever it is handed with)
 int gloc_reg_gicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
                             const gloc_gicp_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status) {
-  GLOC_TRY(gloc::gicp::check_params(prm));
-  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  return run_gicp(h, &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
-                  nullptr);
+  return refine_entry(h, batch_call(&src_scan_id, false, tgt_scan_ids, n, init_T, out_T, out_rmse, out_iters, out_status), prm,
+                      gloc::gicp::check_params, run_gicp);
 }
 
 int gloc_reg_gicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_gicp_params* prm,
                          double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count) {
-  GLOC_TRY(gloc::gicp::check_params(prm));
-  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  return run_gicp(h, &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum, out_count);
+  return refine_entry(h, system_call(&src_scan_id, &tgt_scan_id, T16, out_H36, out_g6, out_sum, out_count), prm,
+                      gloc::gicp::check_params, run_gicp);
 }
 
-// Voxelized generalized ICP (vgicp.hip): no 1-NN search, so none of this file's batch set-up -- the call builds its
-// targets' voxel maps and runs the shared loop of passes on the handle's stream.
 int gloc_reg_vgicp_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
                              const gloc_vgicp_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status) {
-  GLOC_TRY(gloc::vgicp::check_params(prm));
-  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  return gloc::vgicp::run(vgicp_ctx(h), &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
-                          nullptr, nullptr);
+  return refine_entry(h, batch_call(&src_scan_id, false, tgt_scan_ids, n, init_T, out_T, out_rmse, out_iters, out_status), prm,
+                      gloc::vgicp::check_params, run_vgicp);
 }
 
 int gloc_reg_vgicp_system(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_vgicp_params* prm,
                           double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count) {
-  GLOC_TRY(gloc::vgicp::check_params(prm));
-  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  return gloc::vgicp::run(vgicp_ctx(h), &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
-                          out_count);
+  return refine_entry(h, system_call(&src_scan_id, &tgt_scan_id, T16, out_H36, out_g6, out_sum, out_count), prm,
+                      gloc::vgicp::check_params, run_vgicp);
 }
 
-// The robust entries (robust.hpp): the plain ones' calls with the robust half of the arguments behind them.  Both blocks
-// are looked at before the handle.
 int gloc_reg_p2l_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
                                   const gloc_p2l_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse,
                                   uint32_t* out_iters, int* out_status, float* out_weight) {
-  GLOC_TRY(gloc::p2l::check_params(prm));
-  GLOC_TRY(gloc::robust::check_params(robust));
-  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  gloc::p2l::RobustArgs rb;
-  rb.prm = robust;
-  rb.out_weight = out_weight;
-  return run_p2l(h, &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
-                 nullptr, rb);
+  const gloc::gn6::Call c = batch_call(&src_scan_id, false, tgt_scan_ids, n, init_T, out_T, out_rmse, out_iters, out_status);
+  return refine_entry(h, robust_call(c, robust, 0, out_weight, nullptr), prm, gloc::p2l::check_params, run_p2l);
 }
 
 int gloc_reg_p2l_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_p2l_params* prm,
                                const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6, double* out_sum_r2,
                                uint64_t* out_count, double* out_wsum) {
-  GLOC_TRY(gloc::p2l::check_params(prm));
-  GLOC_TRY(gloc::robust::check_params(robust));
-  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum_r2 && out_count && out_wsum, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  gloc::p2l::RobustArgs rb;
-  rb.prm = robust;
-  rb.pass = pass;
-  rb.out_wsum = out_wsum;
-  return run_p2l(h, &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum_r2, out_count,
-                 rb);
+  const gloc::gn6::Call c = system_call(&src_scan_id, &tgt_scan_id, T16, out_H36, out_g6, out_sum_r2, out_count);
+  return refine_entry(h, robust_call(c, robust, pass, nullptr, out_wsum), prm, gloc::p2l::check_params, run_p2l);
 }
 
 int gloc_reg_gicp_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
                                    const gloc_gicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse,
                                    uint32_t* out_iters, int* out_status, float* out_weight) {
-  GLOC_TRY(gloc::gicp::check_params(prm));
-  GLOC_TRY(gloc::robust::check_params(robust));
-  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  gloc::p2l::RobustArgs rb;
-  rb.prm = robust;
-  rb.out_weight = out_weight;
-  return run_gicp(h, &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
-                  nullptr, rb);
+  const gloc::gn6::Call c = batch_call(&src_scan_id, false, tgt_scan_ids, n, init_T, out_T, out_rmse, out_iters, out_status);
+  return refine_entry(h, robust_call(c, robust, 0, out_weight, nullptr), prm, gloc::gicp::check_params, run_gicp);
 }
 
 int gloc_reg_gicp_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16, const gloc_gicp_params* prm,
                                 const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6, double* out_sum,
                                 uint64_t* out_count, double* out_wsum) {
-  GLOC_TRY(gloc::gicp::check_params(prm));
-  GLOC_TRY(gloc::robust::check_params(robust));
-  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count && out_wsum, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  gloc::p2l::RobustArgs rb;
-  rb.prm = robust;
-  rb.pass = pass;
-  rb.out_wsum = out_wsum;
-  return run_gicp(h, &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum, out_count, rb);
+  const gloc::gn6::Call c = system_call(&src_scan_id, &tgt_scan_id, T16, out_H36, out_g6, out_sum, out_count);
+  return refine_entry(h, robust_call(c, robust, pass, nullptr, out_wsum), prm, gloc::gicp::check_params, run_gicp);
 }
 
 int gloc_reg_vgicp_batch_ids_robust(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
                                     const gloc_vgicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse,
                                     uint32_t* out_iters, int* out_status, float* out_weight) {
-  GLOC_TRY(gloc::vgicp::check_params(prm));
-  GLOC_TRY(gloc::robust::check_params(robust));
-  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  gloc::p2l::RobustArgs rb;
-  rb.prm = robust;
-  rb.out_weight = out_weight;
-  return gloc::vgicp::run(vgicp_ctx(h), &src_scan_id, false, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr,
-                          nullptr, nullptr, rb);
+  const gloc::gn6::Call c = batch_call(&src_scan_id, false, tgt_scan_ids, n, init_T, out_T, out_rmse, out_iters, out_status);
+  return refine_entry(h, robust_call(c, robust, 0, out_weight, nullptr), prm, gloc::vgicp::check_params, run_vgicp);
 }
 
 int gloc_reg_vgicp_system_robust(gloc_reg* h, uint32_t src_scan_id, uint32_t tgt_scan_id, const float* T16,
                                  const gloc_vgicp_params* prm, const gloc_robust_params* robust, uint32_t pass, double* out_H36,
                                  double* out_g6, double* out_sum, uint64_t* out_count, double* out_wsum) {
-  GLOC_TRY(gloc::vgicp::check_params(prm));
-  GLOC_TRY(gloc::robust::check_params(robust));
-  GLOC_REQUIRE(h && out_H36 && out_g6 && out_sum && out_count && out_wsum, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  gloc::p2l::RobustArgs rb;
-  rb.prm = robust;
-  rb.pass = pass;
-  rb.out_wsum = out_wsum;
-  return gloc::vgicp::run(vgicp_ctx(h), &src_scan_id, false, &tgt_scan_id, 1, T16, prm, nullptr, nullptr, nullptr, nullptr, out_H36, out_g6, out_sum,
-                          out_count, rb);
+  const gloc::gn6::Call c = system_call(&src_scan_id, &tgt_scan_id, T16, out_H36, out_g6, out_sum, out_count);
+  return refine_entry(h, robust_call(c, robust, pass, nullptr, out_wsum), prm, gloc::vgicp::check_params, run_vgicp);
 }
 
-// The pair-list entries: row c is (src_scan_ids[c], tgt_scan_ids[c]) -- run_refine's and vgicp::run's list form, every row
-// the single-source entry's row.  pairs_head is what they refuse behind the method's own block, in this order: the robust
-// block (null: the plain step), the arrays, n, the handle, a batch in flight.
-static int pairs_head(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const gloc_robust_params* robust,
-                      const float* out_T) {
-  if (robust) GLOC_TRY(gloc::robust::check_params(robust));
-  GLOC_REQUIRE(src_scan_ids && tgt_scan_ids, GLOC_ERR_INVALID, "null scan ids");
-  GLOC_REQUIRE(out_T, GLOC_ERR_INVALID, "out_T is null");
-  GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
-  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null argument");
-  GLOC_NOT_PENDING(h);
-  GLOC_HIP(hipSetDevice(h->device));
-  return GLOC_OK;
-}
-
+// The pair-list entries: row c is (src_scan_ids[c], tgt_scan_ids[c]), every row the single-source entry's row.  The robust
+// block may be null (the plain step, which has no weights to report).
 int gloc_reg_p2l_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
                        const gloc_p2l_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse, uint32_t* out_iters,
                        int* out_status, float* out_weight) {
-  GLOC_TRY(gloc::p2l::check_params(prm));
-  GLOC_TRY(pairs_head(h, src_scan_ids, tgt_scan_ids, n, robust, out_T));
-  gloc::p2l::RobustArgs rb;
-  rb.prm = robust;
-  rb.out_weight = robust ? out_weight : nullptr;  // (the plain step has no weights to report)
-  return run_p2l(h, src_scan_ids, true, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
-                 nullptr, rb);
+  gloc::gn6::Call c = batch_call(src_scan_ids, true, tgt_scan_ids, n, init_T, out_T, out_rmse, out_iters, out_status);
+  c.robust = robust;
+  c.out_weight = robust ? out_weight : nullptr;
+  return refine_entry(h, c, prm, gloc::p2l::check_params, run_p2l);
 }
 
 int gloc_reg_gicp_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
                         const gloc_gicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse, uint32_t* out_iters,
                         int* out_status, float* out_weight) {
-  GLOC_TRY(gloc::gicp::check_params(prm));
-  GLOC_TRY(pairs_head(h, src_scan_ids, tgt_scan_ids, n, robust, out_T));
-  gloc::p2l::RobustArgs rb;
-  rb.prm = robust;
-  rb.out_weight = robust ? out_weight : nullptr;  // (the plain step has no weights to report)
-  return run_gicp(h, src_scan_ids, true, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr, nullptr, nullptr,
-                  nullptr, rb);
+  gloc::gn6::Call c = batch_call(src_scan_ids, true, tgt_scan_ids, n, init_T, out_T, out_rmse, out_iters, out_status);
+  c.robust = robust;
+  c.out_weight = robust ? out_weight : nullptr;
+  return refine_entry(h, c, prm, gloc::gicp::check_params, run_gicp);
 }
 
 int gloc_reg_vgicp_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* init_T,
                          const gloc_vgicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse, uint32_t* out_iters,
                          int* out_status, float* out_weight) {
-  GLOC_TRY(gloc::vgicp::check_params(prm));
-  GLOC_TRY(pairs_head(h, src_scan_ids, tgt_scan_ids, n, robust, out_T));
-  gloc::p2l::RobustArgs rb;
-  rb.prm = robust;
-  rb.out_weight = robust ? out_weight : nullptr;  // (the plain step has no weights to report)
-  return gloc::vgicp::run(vgicp_ctx(h), src_scan_ids, true, tgt_scan_ids, n, init_T, prm, out_T, out_rmse, out_iters, out_status, nullptr,
-                          nullptr, nullptr, nullptr, rb);
+  gloc::gn6::Call c = batch_call(src_scan_ids, true, tgt_scan_ids, n, init_T, out_T, out_rmse, out_iters, out_status);
+  c.robust = robust;
+  c.out_weight = robust ? out_weight : nullptr;
+  return refine_entry(h, c, prm, gloc::vgicp::check_params, run_vgicp);
 }
 
 int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3,

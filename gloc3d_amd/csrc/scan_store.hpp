@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "ground_normals.hpp"
+#include "p2l.hpp"  // gn6::Call, p2l::SourceView: what CallScans resolves
 #include "scan_index.hpp"
 
 // A scan resident in HBM: original-order xyz plus its search index (Hilbert-sorted copy with the
@@ -216,6 +217,55 @@ inline int store_check_pairs(gloc_scan_store* st, const uint32_t* src_ids, const
     if (id != 0xFFFFFFFFu) GLOC_TRY(store_get(st, id, 0, &s));
   return GLOC_OK;
 }
+
+constexpr uint32_t NO_SCAN = 0xFFFFFFFFu;  // "no target" in a pair list
+
+// The scans of a refinement call (gn6::Call), resolved once for reg.hip's run_refine and vgicp::run: the ids checked
+// before anything is enqueued (a pair list: store_check_pairs), every distinct source and then every distinct target
+// pinned for as long as this lives, targets -- and with src_normals sources -- without normals given them from normal_k
+// neighbours, and every job's source as the accumulate kernels take it.  cs: the sources' launch order (0: nothing searches).
+struct CallScans {
+  ScopedPins pins;                         // .scans: the distinct sources, then the distinct targets
+  size_t n_srcs = 0;
+  std::vector<uint32_t> job_src, job_tgt;  // [n]: which of each job c reads; job_tgt NO_SCAN: a row without a target
+  std::vector<p2l::SourceView> srcs;       // [n]; n = 0 in such a row: no work-group, no pair
+  CallScans(gloc_scan_store* st, hipStream_t q) : pins(st, q) {}
+  const DevScan& src(size_t c) const { return pins.scans[job_src[c]]; }
+  const DevScan* tgt(size_t c) const { return job_tgt[c] == NO_SCAN ? nullptr : &pins.scans[n_srcs + job_tgt[c]]; }
+  int resolve(const gn6::Call& c, uint32_t normal_k, bool src_normals, int cs) {
+    gloc_scan_store* st = pins.st;
+    GLOC_REQUIRE(st, GLOC_ERR_INVALID, "unknown scan id %u", c.src_ids[0]);
+    if (c.pairs) GLOC_TRY(store_check_pairs(st, c.src_ids, c.tgt_ids, c.n));
+    std::vector<uint32_t> ids, have, uniq, have_tgt;
+    distinct_in_order(c.src_ids, c.pairs ? c.n : 1, &ids, &job_src);
+    job_src.resize(c.n, 0u);
+    n_srcs = ids.size();
+    for (size_t j = 0; j < c.n; ++j)
+      if (!c.pairs || c.tgt_ids[j] != NO_SCAN) have.push_back(c.tgt_ids[j]);
+    distinct_in_order(have.data(), have.size(), &uniq, &have_tgt);
+    job_tgt.assign(c.n, NO_SCAN);
+    for (size_t j = 0, k = 0; j < c.n; ++j)
+      if (!c.pairs || c.tgt_ids[j] != NO_SCAN) job_tgt[j] = have_tgt[k++];
+    ids.insert(ids.end(), uniq.begin(), uniq.end());
+    // (an unknown source id without src_normals: refused by pin())
+    const size_t first = src_normals ? 0 : n_srcs;
+    GLOC_TRY(store_ensure_normals(st, ids.data() + first, ids.size() - first, normal_k));
+    std::vector<int> css(ids.size(), 0);
+    std::fill(css.begin(), css.begin() + n_srcs, cs);
+    GLOC_TRY(pins.pin(ids.data(), css.data(), ids.size()));
+    const std::vector<DevScan>& scans = pins.scans;
+    for (size_t u = 0; u < scans.size(); ++u) {
+      const DevScan& s = scans[u];
+      if (u < n_srcs) GLOC_REQUIRE(s.n >= 1 && s.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
+      const bool read = u < n_srcs ? src_normals : s.n > 0;  // are its normals read (an empty target has none)
+      GLOC_REQUIRE(!read || s.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", ids[u]);
+    }
+    srcs.resize(c.n);
+    for (size_t j = 0; j < c.n; ++j)
+      srcs[j] = p2l::SourceView{src(j).idx.pts, src_normals ? src(j).nrm : nullptr, job_tgt[j] == NO_SCAN ? 0u : (uint32_t)src(j).n};
+    return GLOC_OK;
+  }
+};
 
 }  // namespace reg
 }  // namespace gloc

@@ -58,67 +58,34 @@ int check_params(const gloc_vgicp_params* p) {
   return GLOC_OK;
 }
 
-int run(const Ctx& x, const uint32_t* src_ids, bool pairs, const uint32_t* tgt_ids, size_t n, const float* init_T,
-        const gloc_vgicp_params* prm, float* out_T, float* out_rmse, uint32_t* out_iters, int* out_status, double* out_H36,
-        double* out_g6, double* out_sum, uint64_t* out_count, const p2l::RobustArgs& rb) {
-  GLOC_TRY(check_params(prm));
-  GLOC_REQUIRE(src_ids && tgt_ids && n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096] or null scan ids", n);
-  GLOC_REQUIRE(x.store, GLOC_ERR_INVALID, "unknown scan id %u", src_ids[0]);
-  if (pairs) GLOC_TRY(reg::store_check_pairs(x.store, src_ids, tgt_ids, n));
+int run(const Ctx& x, const gn6::Call& c, const gloc_vgicp_params* prm) {
+  const hipStream_t q = x.stream;
+  const size_t n = c.n;
+  // every distinct source, then every distinct target -- one voxel map each; no launch order: nothing here searches
+  reg::CallScans rs(x.store, q);
+  GLOC_TRY(rs.resolve(c, prm->normal_k, true, 0));
   GLOC_TRY(ensure_ws(x.ws));
   Ws& w = **x.ws;
-  const hipStream_t q = x.stream;
-  constexpr uint32_t NO_SCAN = 0xFFFFFFFFu;
-  // the scans of the call: every distinct source, then every distinct target -- one voxel map each; a row of a pair list
-  // without a target has none
-  std::vector<uint32_t> ids, job_src, have, uniq, have_tgt;
-  reg::distinct_in_order(src_ids, pairs ? n : 1, &ids, &job_src);
-  job_src.resize(n, 0u);
-  const size_t n_srcs = ids.size();
-  for (size_t c = 0; c < n; ++c)
-    if (!pairs || tgt_ids[c] != NO_SCAN) have.push_back(tgt_ids[c]);
-  reg::distinct_in_order(have.data(), have.size(), &uniq, &have_tgt);
-  std::vector<uint32_t> job_tgt(n, NO_SCAN);
-  for (size_t c = 0, k = 0; c < n; ++c)
-    if (!pairs || tgt_ids[c] != NO_SCAN) job_tgt[c] = have_tgt[k++];
-  ids.insert(ids.end(), uniq.begin(), uniq.end());
-  GLOC_TRY(reg::store_ensure_normals(x.store, ids.data(), ids.size(), prm->normal_k));
-  reg::ScopedPins pins(x.store, q);
-  GLOC_TRY(pins.pin(ids.data(), nullptr, ids.size()));  // (no launch order: nothing here searches)
-  const std::vector<DevScan>& scans = pins.scans;
-  for (size_t u = 0; u < n_srcs; ++u) {
-    GLOC_REQUIRE(scans[u].n >= 1 && scans[u].n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
-    GLOC_REQUIRE(scans[u].nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", ids[u]);
-  }
-  for (size_t t = n_srcs; t < scans.size(); ++t)
-    GLOC_REQUIRE(scans[t].n == 0 || scans[t].nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", ids[t]);
   voxmap::Maps tm;
-  if (!uniq.empty()) {
+  if (rs.pins.scans.size() > rs.n_srcs) {
     ProfScope ps(*x.prof, "vgicp_voxels", q);
-    std::vector<DevScan> tg(scans.begin() + n_srcs, scans.end());
+    std::vector<DevScan> tg(rs.pins.scans.begin() + rs.n_srcs, rs.pins.scans.end());
     GLOC_TRY(target_voxels(q, w, tg, prm, &tm));
   }
   // the fp32 poses the accumulate kernel reads and the solve kernel writes after every update
   static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::vector<float> pose(12 * n);
-  std::vector<Target> ht(n);
-  std::vector<p2l::SourceView> sv(n);
-  for (size_t c = 0; c < n; ++c) {
-    const float* T = init_T ? init_T + 16 * c : I16;
+  std::vector<Target> ht(n, Target{nullptr, nullptr, nullptr, 0u, 0u});  // (a row without a target: no table to probe)
+  for (size_t j = 0; j < n; ++j) {
+    const float* T = c.init_T ? c.init_T + 16 * j : I16;
     for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) pose[12 * c + 3 * i + j] = T[4 * i + j];
-      pose[12 * c + 9 + i] = T[4 * i + 3];
+      for (int k = 0; k < 3; ++k) pose[12 * j + 3 * i + k] = T[4 * i + k];
+      pose[12 * j + 9 + i] = T[4 * i + 3];
     }
-    const DevScan& src = scans[job_src[c]];
-    const uint32_t t = job_tgt[c];
-    if (t == NO_SCAN) {  // no table to probe: no source slot, no work-group
-      ht[c] = Target{nullptr, nullptr, nullptr, 0u, 0u};
-      sv[c] = p2l::SourceView{src.idx.pts, src.nrm, 0u};
-      continue;
-    }
-    ht[c] = Target{reinterpret_cast<const unsigned long long*>(w.map.hkey.p) + tm.toff[t], w.map.hval.as<uint32_t>() + tm.toff[t],
-                   w.map.cells.as<Voxel>(), tm.tmask[t], 0u};
-    sv[c] = p2l::SourceView{src.idx.pts, src.nrm, (uint32_t)src.n};
+    const uint32_t t = rs.job_tgt[j];
+    if (t != reg::NO_SCAN)
+      ht[j] = Target{reinterpret_cast<const unsigned long long*>(w.map.hkey.p) + tm.toff[t], w.map.hval.as<uint32_t>() + tm.toff[t],
+                     w.map.cells.as<Voxel>(), tm.tmask[t], 0u};
   }
   GLOC_TRY(w.pose.ensure(sizeof(float) * 12 * n, q));
   GLOC_HIP(hipMemcpyAsync(w.pose.p, pose.data(), sizeof(float) * 12 * n, hipMemcpyHostToDevice, q));
@@ -127,7 +94,7 @@ int run(const Ctx& x, const uint32_t* src_ids, bool pairs, const uint32_t* tgt_i
   g.stream = q;
   g.prof = x.prof;
   g.ws = x.gn;
-  g.srcs = sv.data();
+  g.srcs = rs.srcs.data();
   g.n_jobs = (uint32_t)n;
   g.pose_f32 = w.pose.as<float>();
   g.pose_stride = 12;
@@ -138,12 +105,12 @@ int run(const Ctx& x, const uint32_t* src_ids, bool pairs, const uint32_t* tgt_i
   const float inv_res = 1.0f / prm->resolution;
   auto accum = [&](const Target* d_tgts, const gn6::Source* d_srcs, const gn6::State* states, float, bool skip_stopped, double* partials,
                    uint32_t n_blk, const gn6::Scale2& sc) {
-    gn6::for_kind(rb.kind(), [&](auto kind) {
+    gn6::for_kind(c.kind(), [&](auto kind) {
       hipLaunchKernelGGL(HIP_KERNEL_NAME(vgicp_accum_kernel<decltype(kind)::value>), dim3(n_blk, g.n_jobs), dim3(gn6::ACC_THREADS), 0, q,
                          d_srcs, d_tgts, g.pose_f32, g.pose_stride, states, inv_res, prm->neighbors, gate2, a, skip_stopped, partials, sc);
     });
   };
-  return gn6::run(g, lp, ht, init_T, accum, out_T, out_rmse, out_iters, out_status, out_H36, out_g6, out_sum, out_count, rb);
+  return gn6::run(g, lp, ht.data(), c, accum);
 }
 
 int voxels(const Ctx& x, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3, uint32_t* out_count,

@@ -1,13 +1,15 @@
-"""The outputs of the single-source entries of the three Gauss-Newton refinements (gloc_reg_{p2l,gicp,vgicp}_batch_ids,
-_system and their _robust forms) as raw bits: one file, to be compared byte for byte between two builds of the library on
-one machine -- the check that a change under those entries moved nothing.
+"""The outputs of the entries of the three Gauss-Newton refinements (gloc_reg_{p2l,gicp,vgicp}_batch_ids, _system, their
+_robust forms and _pairs) as raw bits: one file, to be compared byte for byte between two builds of the library on one
+machine -- the check that a change under those entries moved nothing.
 
     GLOC3D_LIB_PATH=<a build's libgloc3d.so> python tools/gn_bits_dump.py --out FILE
 
 What is run: every case of tests/gn_cases.py CASES (its own method, plain and with a robust block; the generalized ICP cases'
 scans and guesses through the voxelized refinement as well), the batches of gn_cases.MIXED as ONE call each (plain and
-robust), every case of tests/robust_cases.py CASES, and the system form of each case at its guess.  The file is a line per
-call: a label, then the hex of every output array.  The last line printed is the file's SHA-256."""
+robust), every case of tests/robust_cases.py CASES, and the system form of each case at its guess.  Through the pair-list
+entries: the list of tests/pairs_cases.py under both of its blocks, and a short list of two sources, a repeated target and
+a row without a target, each method plain and robust.  The file is a line per call: a label, then the hex of every output
+array.  The last line printed is the file's SHA-256."""
 import argparse
 import hashlib
 import os
@@ -25,6 +27,7 @@ def main():
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     import gn_cases as GC
+    import pairs_cases as PC
     import robust_cases as RC
     import robust_ref as RR
     from gloc3d_amd import capi
@@ -79,6 +82,19 @@ def main():
                                                       params=prm(case["method"], RC.params(case)),
                                                       robust=capi.default_robust_params(**case["robust"]))
         put("robust_" + case["name"], out)
+    # the pair-list entries: the ragged list of pairs_cases, then two sources, a repeated target and a row without one
+    short = [("a2", "a0"), ("a3", "a0"), ("a2", None), ("a3", "a1")]
+    short_init = np.stack([(GC.truth(s, t or "a0") @ GC._se3(0.5 + 0.25 * j, (0.05, -0.02 * j, 0.01))).astype(np.float32)
+                           for j, (s, t) in enumerate(short)])
+    lists = [(b, [(q["src"], q["tgt"]) for q in PC.pairs(b)], PC.guesses(PC.pairs(b)), b) for b in PC.BLOCKS] + [("short", short, short_init, "P1")]
+    for method in PC.METHODS:
+        for label, names, init, block in lists:
+            for rb in (None, PC.robust(method)):
+                out = getattr(reg, method + "_pairs")([sid(s) for s, _ in names], [None if t is None else sid(t) for _, t in names],
+                                                      init_T=np.ascontiguousarray(init, np.float32),
+                                                      params=getattr(capi, "default_%s_params" % method)(**PC.params(method, block)),
+                                                      robust=None if rb is None else capi.default_robust_params(**rb))
+                put("pairs_%s %s %s" % (label, method, "plain" if rb is None else RR.NAMES[rb["kind"]]), out)
     reg.close()
     store.close()
     blob = ("\n".join(lines) + "\n").encode()

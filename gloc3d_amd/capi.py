@@ -932,6 +932,19 @@ class ScanStore(_Handle):
         return dict(lo=hb[:3].copy(), hi=hb[3:].copy(), ox=hg[0], oy=hg[1], oz=hg[2], inv_cell=hg[3], box_lo=box_lo,
                     box_hi=box_hi, sb2=sb2, sup_lo=sup_lo, sup_hi=sup_hi, pad=pad, order=order)
 
+    def debug_kd_table(self, scan_id):
+        """Test aid: the split planes of a target index -- dict(rounds: record levels on a path, split [records, 7]
+        float32, axes [records] uint32: 2 bits per node in heap order); rounds = 0 and empty arrays without a table."""
+        f = lib().gloc_scan_store_debug_kd_table
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
+        rounds, n_rec = C.c_uint32(), C.c_size_t()
+        check(f(self._h, int(scan_id), C.byref(rounds), C.byref(n_rec), None, 0))
+        rec = np.empty((n_rec.value, 8), np.uint32)
+        if n_rec.value:
+            check(f(self._h, int(scan_id), C.byref(rounds), C.byref(n_rec), _np_ptr(rec), rec.shape[0]))
+        return dict(rounds=int(rounds.value), split=rec[:, :7].copy().view(np.float32), axes=rec[:, 7].copy())
+
     def build_target_index_batch(self, scan_ids):
         ids = np.ascontiguousarray(scan_ids, np.uint32).reshape(-1)
         check(lib().gloc_scan_store_build_target_index_batch(self._h, _np_ptr(ids), ids.shape[0]))

@@ -358,6 +358,25 @@ struct NnPos {
   uint32_t role = 0, pass = 0, job = 0;  // chained launch only: 0 a search wave; 1 + r: reducer r of `job`; 1 + NN_CHAIN_RED: its planner
 };
 
+// One record of a target's split planes (KdRecord, scan_index.hpp; a: split values 0 - 3, b: 4 - 6 and the axes) against
+// the point (x, y, z): which of the record's eight children holds it.  Three levels, right iff coordinate > split; the
+// axes of a wave's lanes differ, so everything is a select.  (A function of VALUES: written with the caller's arrays in
+// place, the selects became selects between addresses and the arrays a table in scratch memory.)
+__device__ __forceinline__ float kd_coord(uint32_t axis, float x, float y, float z) {
+  const float c01 = (axis & 1u) != 0u ? y : x;
+  return (axis & 2u) != 0u ? z : c01;
+}
+__device__ __forceinline__ uint32_t kd_record_child(f32x4 a, f32x4 b, float x, float y, float z) {
+  const uint32_t ax = __float_as_uint(b.w);
+  const bool g0 = kd_coord(ax, x, y, z) > a.x;
+  const float s1 = g0 ? a.z : a.y;
+  const bool g1 = kd_coord(ax >> (g0 ? 4 : 2), x, y, z) > s1;
+  const float s2l = g1 ? b.x : a.w, s2r = g1 ? b.z : b.y;
+  const uint32_t h2 = (g0 ? 2u : 0u) + (g1 ? 1u : 0u);  // heap node 3 + h2
+  const bool g2 = kd_coord(ax >> (6u + 2u * h2), x, y, z) > (g0 ? s2r : s2l);
+  return h2 * 2u + (g2 ? 1u : 0u);
+}
+
 template <int CS, bool PAIRS, bool SPLIT = false /* with the plan for heavy groups (NnSplit; sp.hx > 0) */,
           bool WARM = false, bool HEAVY = false /* the second launch of a cold pass: the groups its waves gave up (NnHeavy) */,
           bool CHAIN = false /* a pass of the chained launch (NnChain): what other waves of the SAME launch wrote or will read goes past the caches */>
@@ -481,6 +500,7 @@ __device__ __forceinline__ void nn_compact_body(
   struct IndexView {
     GPTR(f32x4) pts; GPTR(f32x4) box_lo; GPTR(f32x4) box_hi; GPTR(f32x4) sb2;
     GPTR(uint32_t) keys; GPTR(uint32_t) kpos; GPTR(uint32_t) inv; GPTR(ScanHeader) hdr;
+    GPTR(KdRecord) kdt; uint32_t kd_rounds;
     uint32_t n, nchunks;
     GPTR(f32x4) sup_lo; GPTR(f32x4) sup_hi;
     uint32_t nsup;
@@ -491,7 +511,7 @@ __device__ __forceinline__ void nn_compact_body(
   const ScanIndexDev ixg = J.tgt;
   const IndexView ix{(GPTR(f32x4))ixg.pts, (GPTR(f32x4))ixg.box_lo, (GPTR(f32x4))ixg.box_hi,
                      (GPTR(f32x4))ixg.sb2, (GPTR(uint32_t))ixg.keys, (GPTR(uint32_t))ixg.kpos,
-                     (GPTR(uint32_t))ixg.inv, (GPTR(ScanHeader))ixg.hdr, ixg.n, ixg.nchunks,
+                     (GPTR(uint32_t))ixg.inv, (GPTR(ScanHeader))ixg.hdr, (GPTR(KdRecord))ixg.kdt, ixg.kd_rounds, ixg.n, ixg.nchunks,
                      (GPTR(f32x4))ixg.sup_lo, (GPTR(f32x4))ixg.sup_hi, ixg.nsup,
                      (CPTR(f32x4))ixg.box_lo, (CPTR(f32x4))ixg.box_hi};
   GPTR(f32x4) src4 = (GPTR(f32x4))J.src_pts;
@@ -578,6 +598,83 @@ __device__ __forceinline__ void nn_compact_body(
       tie0[s] = (uint8_t)(((uint32_t)k >> 31) & 1u);
     }
   } else if constexpr (!WARM) {  // (a warm pass: a point that found no neighbour -- a NaN -- searches without a bound)
+   if (ix.kdt != nullptr) {  // (uniform: a target index with its split planes)
+    // POINT LOCATION in the target's kd tree (KdRecord, scan_index.hpp): one 32-byte record per three levels -- five
+    // dependent loads at 124 k points, where the key search below takes eleven behind a Hilbert key -- down to the
+    // 16-point leaf whose cell holds the source.  Any path stays inside the table and ends in a leaf with a real point,
+    // whatever the source (a NaN goes left everywhere).  The lane's CS sources descend together.
+    bool cold[CS];
+    uint32_t node[CS];
+#pragma unroll
+    for (int s = 0; s < CS; ++s) {
+      cold[s] = !(pj[s] < ix.n);
+      node[s] = 0;
+    }
+    const uint32_t R = ix.kd_rounds;
+    uint32_t first = 0;
+    for (uint32_t r = 0; r < R; ++r) {
+      f32x4 ra[CS], rb[CS];
+#pragma unroll
+      for (int s = 0; s < CS; ++s) {
+        GPTR(f32x4) rp = (GPTR(f32x4))(ix.kdt + (first + node[s]));
+        ra[s] = rp[0];
+        rb[s] = rp[1];
+      }
+#pragma unroll
+      for (int s = 0; s < CS; ++s) node[s] = node[s] * 8u + kd_record_child(ra[s], rb[s], px[s], py[s], pz[s]);
+      first += kd_level_records(ix.n, R, r);
+    }
+    // The bound: the distance to GLOC_NN_LEAF_POINTS of the leaf's 16 points -- one of each quarter (4: points 0, 5, 9, 13),
+    // all of them (16) or the first alone (1).  Measured, cold launch of 500 jobs on one box: 16 points 3.23 - 3.26 ms, 4 points
+    // 3.10 - 3.12 (the CPU model has the nearest of 4 no tighter than the curve's five neighbours at p90 / p99 and the nearest
+    // of 16 at half of it; the 24 further gathers and their arithmetic cost a cold wave more than the looser bounds do).
+    // Distances FUSED as the evaluation rounds compute them (the same expression: a round over this sub-block finds the same
+    // value in the same quarter).  At most 8 points of each source are in flight at a time, the groups kept apart: 32 loads
+    // at once are 96 registers, a wave fewer per SIMD (measured: 4.1 ms).
+#ifndef GLOC_NN_LEAF_POINTS
+#define GLOC_NN_LEAF_POINTS 4
+#endif
+    constexpr int LP = GLOC_NN_LEAF_POINTS, LG = LP < 8 ? LP : 8;
+    static_assert(LP == 1 || LP == 4 || LP == 16, "1, 4 or 16 points of the leaf");
+    // the i-th point looked at: the leaf's first point is always a real one (the last leaf of a scan may hold no other)
+    auto leaf_at = [](int i) { return LP == 16 ? i : (LP == 4 && i ? 4 * i + 1 : 0); };
+    typedef float f32x3 __attribute__((ext_vector_type(3)));  // (x, y, z of a point: three registers, not four)
+    float mq[CS][4];
+#pragma unroll
+    for (int s = 0; s < CS; ++s)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) mq[s][q] = 3.402823466e+38f;
+#pragma unroll
+    for (int i0 = 0; i0 < LP; i0 += LG) {
+      if (i0) __builtin_amdgcn_sched_barrier(0);
+      f32x3 t[CS][LG];
+#pragma unroll
+      for (int s = 0; s < CS; ++s)
+#pragma unroll
+        for (int u = 0; u < LG; ++u) t[s][u] = *(GPTR(f32x3))(ix.pts + ((size_t)node[s] * SB + leaf_at(i0 + u)));
+#pragma unroll
+      for (int s = 0; s < CS; ++s)
+#pragma unroll
+        for (int u = 0; u < LG; u += 2) {  // (two points per packed instruction; a NaN or the +inf of the padding is never the minimum)
+          const int v = u + 1 < LG ? u + 1 : u;
+          const f32x2 dx = f32x2{px[s], px[s]} - f32x2{t[s][u].x, t[s][v].x}, dy = f32x2{py[s], py[s]} - f32x2{t[s][u].y, t[s][v].y},
+                      dz = f32x2{pz[s], pz[s]} - f32x2{t[s][u].z, t[s][v].z};
+          const f32x2 d2 = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
+          mq[s][leaf_at(i0 + u) / 4] = fminf(mq[s][leaf_at(i0 + u) / 4], d2.x);
+          mq[s][leaf_at(i0 + v) / 4] = fminf(mq[s][leaf_at(i0 + v) / 4], d2.y);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < CS; ++s) {
+      const float m = fminf(fminf(fminf(mq[s][0], mq[s][1]), mq[s][2]), mq[s][3]);
+      // the first quarter at the minimum, without a branch: the count of leading quarters above it
+      const uint32_t n0 = mq[s][0] != m ? 1u : 0u, n1 = n0 & (mq[s][1] != m ? 1u : 0u), n2 = n1 & (mq[s][2] != m ? 1u : 0u);
+      const bool take = cold[s] && m < best[s];  // (no finite distance -- a non-finite source: no bound)
+      best[s] = take ? m : best[s];
+      b0s[s] = take ? node[s] * 4u + (n0 + n1 + n2) : b0s[s];
+    }
+   } else {
+    // (a target without a kd table -- a scan in curve order, a query scan as a target: the curve neighbours)
     // lower_bound over the sorted keys, (KP + 1)-way: KP independent probes per round trip.  The binary search took 17
     // dependent trips at 124 k keys (46 % of a cold wave's time, traced); nine-way (8 probes, 7 trips, 56 loads) made the
     // memory pipe the limit (every lane its own addresses: 40 %); five-way is 8 trips of 4.  The lane's CS sources search
@@ -674,6 +771,7 @@ __device__ __forceinline__ void nn_compact_body(
         }
       }
     }
+   }
   }
 #pragma unroll
   for (int s = 0; s < CS; ++s) {
@@ -1032,7 +1130,10 @@ __device__ __forceinline__ void nn_compact_body(
   // unserved source's, then the next's ...): the bounds the sweep then starts from are those of a warm pass.  The sweep
   // skips them (they are done: bounds only tighten).  Same result: every chunk that can hold a nearer-or-equal point is
   // still visited, once, with bounds that are upper bounds.
-  constexpr int NSEED = 4;
+#ifndef GLOC_NN_SEEDS
+#define GLOC_NN_SEEDS 4
+#endif
+  constexpr int NSEED = GLOC_NN_SEEDS;
   uint32_t seed_c[NSEED];
 #pragma unroll
   for (int k = 0; k < NSEED; ++k) seed_c[k] = 0xFFFFFFFFu;

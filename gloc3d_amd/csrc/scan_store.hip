@@ -357,8 +357,21 @@ struct ScanKd {
   uint32_t n, n_pad, levels;
   uint32_t off;      // slice of the concatenated working arrays
   uint32_t box_off;  // slice of the node boxes (6 words per node)
-  uint32_t pad_;
+  uint32_t kdt_records;
+  KdRecord* kdt;     // the split planes (scan_index.hpp), kdt_records of them
 };
+
+// the widest axis of a node's box; ties -> the lower axis (an axis on which the node has no finite coordinate is never
+// the widest)
+__device__ __forceinline__ int kd_widest_axis(const uint32_t* b) {
+  const float ex = b[0] <= b[3] ? ord2f(b[3]) - ord2f(b[0]) : -1.f, ey = b[1] <= b[4] ? ord2f(b[4]) - ord2f(b[1]) : -1.f,
+              ez = b[2] <= b[5] ? ord2f(b[5]) - ord2f(b[2]) : -1.f;
+  int axis = 0;
+  float e = ex;
+  if (ey > e) { axis = 1; e = ey; }
+  if (ez > e) axis = 2;
+  return axis;
+}
 
 __global__ void kd_load_kernel(const ScanKd* __restrict__ ks, f32x4* __restrict__ p, uint32_t* __restrict__ h) {
   const ScanKd& k = ks[blockIdx.y];
@@ -440,13 +453,7 @@ __global__ void kd_keys_kernel(const ScanKd* __restrict__ ks, uint32_t level, co
   const uint32_t shift = 4 + k.levels - level;
   const uint32_t node = i >> shift;
   const uint32_t* b = box + k.box_off + 6 * (size_t)node;
-  // (an axis on which the node has no finite coordinate is never the widest)
-  const float ex = b[0] <= b[3] ? ord2f(b[3]) - ord2f(b[0]) : -1.f, ey = b[1] <= b[4] ? ord2f(b[4]) - ord2f(b[1]) : -1.f,
-              ez = b[2] <= b[5] ? ord2f(b[5]) - ord2f(b[2]) : -1.f;
-  int axis = 0;  // the widest axis; ties -> the lower axis
-  float e = ex;
-  if (ey > e) { axis = 1; e = ey; }
-  if (ez > e) axis = 2;
+  const int axis = kd_widest_axis(b);
   const f32x4 v = p_all[k.off + i];
   const float c = axis == 0 ? v.x : (axis == 1 ? v.y : v.z);
   keys[k.off + i] = ((unsigned long long)node << 32) | f2ord(c);
@@ -461,6 +468,45 @@ __global__ void kd_gather_kernel(const ScanKd* __restrict__ ks, const f32x4* __r
   const uint32_t s = perm[k.off + j];
   p_out[k.off + j] = p_in[k.off + s];
   h_out[k.off + j] = h_in[k.off + s];
+}
+
+// ---- the split planes (KdRecord, scan_index.hpp) ----
+// every record starts as seven planes that nothing exceeds (+inf: the node's right half holds no real point)
+__global__ void kd_table_init_kernel(const ScanKd* __restrict__ ks) {
+  const ScanKd& k = ks[blockIdx.y];
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= k.kdt_records) return;
+  KdRecord r;
+#pragma unroll
+  for (int h = 0; h < 7; ++h) r.split[h] = __builtin_inff();
+  r.axes = 0u;
+  k.kdt[t] = r;
+}
+
+// Behind the sort of level `level` (p_all: its output): one thread per node with real points in its right half records
+// the node's axis and the largest coordinate of its left half -- the point at the middle position minus one -- a NaN as
+// the infinity of its sign (where f2ord sorted it).
+__global__ void kd_planes_kernel(const ScanKd* __restrict__ ks, uint32_t level, const f32x4* __restrict__ p_all,
+                                 const uint32_t* __restrict__ box) {
+  const ScanKd& k = ks[blockIdx.y];
+  const uint32_t nd = blockIdx.x * blockDim.x + threadIdx.x;
+  if (level >= k.levels || nd >= (1u << level)) return;
+  const uint32_t size = (16u << k.levels) >> level;
+  const uint32_t mid = nd * size + size / 2;
+  if (mid >= k.n) return;
+  const int axis = kd_widest_axis(box + k.box_off + 6 * (size_t)nd);
+  const f32x4 v = p_all[k.off + mid - 1];
+  float c = axis == 0 ? v.x : (axis == 1 ? v.y : v.z);
+  if (c != c) c = (__float_as_uint(c) & 0x80000000u) ? -__builtin_inff() : __builtin_inff();
+  const uint32_t R = (k.levels + 2) / 3;
+  const uint32_t lam = level + 3 * R - k.levels;  // the level in the tree of 3 R levels
+  const uint32_t r = lam / 3, j = lam % 3;
+  uint32_t first = 0;
+  for (uint32_t q = 0; q < r; ++q) first += kd_level_records(k.n, R, q);
+  const uint32_t h = (1u << j) - 1u + (nd & ((1u << j) - 1u));
+  KdRecord* rec = k.kdt + first + (nd >> j);
+  rec->split[h] = c;
+  atomicOr(&rec->axes, (uint32_t)axis << (2 * h));
 }
 
 // the re-sorted points back into the scan: pts (kd order, padded), inv (original index -> kd position), kpos
@@ -482,7 +528,7 @@ __global__ void kd_finish_kernel(const ScanKd* __restrict__ ks, const f32x4* __r
 namespace {
 
 struct Layout {
-  size_t bytes, n1, np, c1, b1, u1, g1;
+  size_t bytes, n1, np, c1, b1, u1, g1, kdt_off;
 };
 Layout layout_for(size_t n) {
   Layout L;
@@ -495,9 +541,12 @@ Layout layout_for(size_t n) {
   L.b1 = L.c1 * (CH / SB / 2) * 3;  // float4 per scan of the paired sub-block boxes
   L.u1 = std::max<size_t>(nsup, 1);
   L.g1 = (L.n1 + 63) / 64;
-  // header | pts4 | box_lo | box_hi | sb2 | sup_lo | sup_hi | xyz | keys | inv | order (cs = 1 | 2 | 4) | kpos
-  L.bytes = sizeof(ScanHeader) + sizeof(f32x4) * (L.np + 2 * L.c1 + L.b1 + 2 * L.u1) +
-            sizeof(float) * 3 * L.n1 + sizeof(uint32_t) * (3 * L.n1 + 2 * L.g1 + 2);
+  // header | pts4 | box_lo | box_hi | sb2 | sup_lo | sup_hi | xyz | keys | inv | order (cs = 1 | 2 | 4) | kpos | kdt
+  // (kdt: the split planes of a target index, 32-byte records at the next multiple of 32 bytes -- 32 / 7 bytes per
+  // sub-block and an eighth of that per record level above the last: 40 KB for a scan of 124 k points)
+  L.kdt_off = (sizeof(ScanHeader) + sizeof(f32x4) * (L.np + 2 * L.c1 + L.b1 + 2 * L.u1) + sizeof(float) * 3 * L.n1 +
+               sizeof(uint32_t) * (3 * L.n1 + 2 * L.g1 + 2) + 31) & ~(size_t)31;
+  L.bytes = L.kdt_off + sizeof(KdRecord) * kd_table_records(n);
   return L;
 }
 
@@ -676,6 +725,7 @@ int store_make_scans(gloc_scan_store* st, size_t count, const float* const* pts,
     s.order_g1 = L.g1;
     s.order = nullptr;
     s.kpos_mem = s.order_base + 2 * L.g1 + 2;
+    s.kdt_mem = reinterpret_cast<KdRecord*>(static_cast<char*>(s.block) + L.kdt_off);
     s.idx = ScanIndexDev{p4, lo, hi, sb2, nullptr, keys, inv, hdr, ulo, uhi, (uint32_t)n[i], (uint32_t)nch,
                          (uint32_t)nsup, 0u};
     out[i] = s;
@@ -784,7 +834,7 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
     std::vector<DevScan*> todo;
     std::vector<segsort::Seg> segs;
     size_t total = 0, box_words = 0, total_grp = 0;
-    uint32_t max_n = 0, max_np = 0, max_levels = 0, max_nch = 0, max_npairs = 0, max_nsup = 0;
+    uint32_t max_n = 0, max_np = 0, max_levels = 0, max_nch = 0, max_npairs = 0, max_nsup = 0, max_records = 0;
     size_t b = a;
     for (; b < count; ++b) {
       DevScan& s = *scans[b];
@@ -806,6 +856,9 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
       k.levels = L;
       k.off = (uint32_t)total;
       k.box_off = (uint32_t)box_words;
+      k.kdt = s.kdt_mem;
+      k.kdt_records = (uint32_t)kd_table_records(s.n);
+      max_records = std::max(max_records, k.kdt_records);
       ScanBuild sb = build_desc(s, lay);
       sb.group = 128;
       sb.n_groups = (uint32_t)((s.n + 127) / 128);
@@ -866,6 +919,7 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
         GLOC_TRY(gloc::fpfh::reorder_rows(q, todo[i]->idx.pts, n, todo[i]->fpfh, fpfh_keep[i].as<float>(), gloc::fpfh::FEAT_DIM, false));
       }
     hipLaunchKernelGGL(kd_load_kernel, gpt, dim3(256), 0, q, d_k, pp[0], hh[0]);
+    hipLaunchKernelGGL(kd_table_init_kernel, dim3((max_records + 255) / 256, cnt), dim3(256), 0, q, d_k);
     int cur = 0;
     static_assert(SB == 16, "the node size arithmetic assumes 16-point leaves");
     for (uint32_t l = 0; l < max_levels; ++l) {
@@ -876,6 +930,7 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
                                                                 max_n, 0, (int)(32 + l), st->sort_hist.as<uint32_t>());
       hipLaunchKernelGGL(kd_gather_kernel, gpt, dim3(256), 0, q, d_k, pp[cur], hh[cur], vv[r], pp[cur ^ 1], hh[cur ^ 1]);
       cur ^= 1;
+      hipLaunchKernelGGL(kd_planes_kernel, dim3(((1u << l) + 255) / 256, cnt), dim3(256), 0, q, d_k, l, pp[cur], st->kd_box.as<uint32_t>());
     }
     // write back and rebuild what depends on the order: inv, kpos, all boxes, the launch orders
     hipLaunchKernelGGL(kd_finish_kernel, dim3((max_np + 255) / 256, cnt), dim3(256), 0, q, d_k, pp[cur], hh[cur]);
@@ -893,6 +948,8 @@ int store_build_target_indices(gloc_scan_store* st, DevScan* const* scans, size_
     // and the launch orders, which listed groups of the old order, are rebuilt on demand.
     for (DevScan* s : todo) {
       s->idx.kpos = s->kpos_mem;
+      s->idx.kdt = s->kdt_mem;
+      s->idx.kd_rounds = kd_rounds_for(s->n);
       s->kd = true;
       s->order_built = 0;
     }
@@ -1279,6 +1336,26 @@ int gloc_scan_store_debug_index(gloc_scan_store* st, uint32_t scan_id, uint32_t*
     GLOC_HIP(hipMemcpyAsync(order2, s.order_of(2), sizeof(uint32_t) * ((s.n + 127) / 128), hipMemcpyDeviceToHost, q));
   }
   GLOC_HIP(hipStreamSynchronize(q));
+  return GLOC_OK;
+}
+
+// Developer / test aid (not part of include/gloc3d.h): the split planes of a target index (scan_index.hpp) -- *rounds
+// record levels, *n_records records of 8 words each, copied to `records` when it holds them (capacity_records; null:
+// the counts only).  A scan without a table (not in kd order, or at most one sub-block) reports 0 and 0.
+int gloc_scan_store_debug_kd_table(gloc_scan_store* st, uint32_t scan_id, uint32_t* rounds, size_t* n_records, void* records,
+                                   size_t capacity_records) {
+  GLOC_REQUIRE(st && rounds && n_records, GLOC_ERR_INVALID, "null argument");
+  GLOC_HIP(hipSetDevice(st->device));
+  std::lock_guard<std::mutex> lk(st->mu);
+  GLOC_REQUIRE(scan_id < st->scans.size() && st->scans[scan_id].live, GLOC_ERR_INVALID, "unknown scan id %u", scan_id);
+  const DevScan& s = st->scans[scan_id];
+  *rounds = s.idx.kdt ? s.idx.kd_rounds : 0u;
+  *n_records = s.idx.kdt ? kd_table_records(s.n) : 0;
+  if (!records || !*n_records) return GLOC_OK;
+  GLOC_REQUIRE(capacity_records >= *n_records, GLOC_ERR_INVALID, "buffer holds %zu records, the table has %zu", capacity_records,
+               *n_records);
+  GLOC_HIP(hipMemcpyAsync(records, s.idx.kdt, sizeof(KdRecord) * *n_records, hipMemcpyDeviceToHost, st->stream));
+  GLOC_HIP(hipStreamSynchronize(st->stream));
   return GLOC_OK;
 }
 

@@ -30,6 +30,7 @@ struct DevScan {
   uint32_t* order = nullptr;
   unsigned order_built = 0;  // bit (cs) set: order_of(cs) is valid
   uint32_t* kpos_mem = nullptr;  // room for the target index's curve position -> kd position table
+  gloc::reg::KdRecord* kdt_mem = nullptr;  // ... and for its split planes (scan_index.hpp): kd_table_records(n) records
   size_t order_g1 = 0;       // groups at cs = 1
   uint32_t* order_of(int cs) const {
     return order_base + (cs == 1 ? 0 : cs == 2 ? order_g1 : order_g1 + (order_g1 + 1) / 2);

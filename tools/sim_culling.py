@@ -11,7 +11,10 @@ found that the target's ORDER, not the kernel, was the thing to change (DESIGN.m
 items by 27-46 % on same-place, 4 m-apart and different-world pairs.
 
     python tools/sim_culling.py                      (about two minutes)
-    python tools/sim_culling.py --real SCAN.bin      only the curve-order / kd-order comparison, on a real KITTI scan
+    python tools/sim_culling.py --cold-bounds        only the cold pass's starting bounds: the five curve neighbours against
+                                                     the kd leaf (1 / 4 / 16 of its points) on three pairs (20 s;
+                                                     profiles/kd_cold_bounds_model.txt)
+    python tools/sim_culling.py --real SCAN.bin     only the curve-order / kd-order comparison, on a real KITTI scan
                                                      (x y z i float32): its even points as the target, its odd points
                                                      moved by a small pose + 2 cm noise as the source.  On the
                                                      reference's sample scan (s2s_libtorch/000000.bin, 124 668 points;
@@ -92,6 +95,98 @@ def _kd_order_simple(P):
         rec(ids[part[:half]],lo); rec(ids[part[half:]],lo+half)
     rec(np.arange(n),0)
     return out
+
+# ---- --cold-bounds: where does a COLD wave's starting bound come from? ----------------------------------------------
+# Two sources of a first upper bound per source point, on targets sorted exactly as the store sorts them (P = 16 * 2^L
+# positions, every node split at its middle position along the widest axis of its real points, positions >= n at +inf):
+#   curve   the best of the five neighbours of the point's Hilbert key among the target's sorted keys (1024^3 grid)
+#   kd leaf the point is located in the target's kd tree by its split planes (left half's maximum: right iff q > split);
+#           the bound is the distance to 1 / 4 / 16 points of the 16-point leaf
+# and what the cold wave then does with them: the seed chunks (up to NSEED, the chunks of the first unserved sources'
+# bounds) first, then the sweep in chunk order, bounds tightening chunk by chunk -- processed chunks, evaluated items
+# and the share of waves that reach the give-up threshold.
+def store_kd_order(P):
+    n=len(P); L=0
+    while (16<<L)<n: L+=1
+    order=np.arange(n); planes=[]
+    for l in range(L):
+        size=(16<<L)>>l; half=size//2; ax_l=np.zeros(1<<l,np.int64); sp_l=np.full(1<<l,np.inf)
+        for nd in range(1<<l):
+            a=nd*size
+            if a>=n: break
+            b=min(a+size,n); ids=order[a:b]; pts=P[ids]
+            ax=int(np.argmax(pts.max(0)-pts.min(0))); ax_l[nd]=ax
+            ids=ids[np.argsort(pts[:,ax],kind='stable')]; order[a:b]=ids
+            if a+half<n: sp_l[nd]=P[ids[half-1],ax]
+        planes.append((ax_l,sp_l))
+    return order,planes,L
+def kd_locate(Q, planes):
+    node=np.zeros(len(Q),np.int64)
+    for ax_l,sp_l in planes:
+        q=Q[np.arange(len(Q)),ax_l[node]]
+        node=2*node+(q>sp_l[node])
+    return node   # the leaf = sub-block index
+def cold_bounds(Ssorted, Tgt, tag, nseed=4, thresh=32, leaf_pts=(1,4,16)):
+    n=len(Tgt)
+    o,planes,L=store_kd_order(Tgt); Tk=Tgt[o]
+    npad=((n+127)//128)*128
+    Tp=np.concatenate([Tk,np.full((npad-n,3),1e18)])
+    clo,chi=boxes(Tk,128); slo,shi=boxes(Tk,16)
+    dtrue,_=cKDTree(Tgt).query(Ssorted)
+    # curve: keys of the target on its own grid, kpos = kd position of the i-th key
+    mn=Tgt.min(0); cell=(Tgt.max(0)-mn).max()/1024.0
+    kt=hilbert_keys(np.clip(np.floor((Tk-mn)/cell),0,1023).astype(np.uint64),10)
+    kpos=np.argsort(kt,kind='stable'); ks=kt[kpos]
+    kq=hilbert_keys(np.clip(np.floor((Ssorted-mn)/cell),0,1023).astype(np.uint64),10)
+    lo=np.searchsorted(ks,kq,side='left')
+    nb=np.clip(lo[:,None]+np.arange(-2,3)[None],0,n-1); pj=kpos[nb]
+    dc=np.linalg.norm(Tk[pj]-Ssorted[:,None],axis=2); jc=dc.argmin(1)
+    bounds={"curve 5":(dc.min(1),pj[np.arange(len(pj)),jc])}
+    leaf=kd_locate(Ssorted,planes)
+    for m in leaf_pts:
+        sel={1:[0],4:[0,5,9,13],16:list(range(16))}[m]   # the points the kernel looks at
+        pos=leaf[:,None]*16+np.array(sel)[None]
+        dl=np.linalg.norm(Tp[pos]-Ssorted[:,None],axis=2); jl=dl.argmin(1)
+        bounds[f"kd leaf {m}"]=(dl.min(1),pos[np.arange(len(pos)),jl])
+    print(f"== {tag}: {len(Ssorted)} sources, target {n} points, {L} levels")
+    for name,(bd,bp) in bounds.items():
+        r=bd/np.maximum(dtrue,1e-9)
+        q=np.percentile(r,[50,90,99,99.9])
+        proc=[];items=[];gave=0;nw=0
+        for wv in range(0,len(Ssorted)//128,8):
+            S=Ssorted[wv*128:(wv+1)*128]; b=bd[wv*128:(wv+1)*128].copy(); sc=bp[wv*128:(wv+1)*128]//128
+            def visit(c, b):
+                lbc=lb2(S,clo[c:c+1],chi[c:c+1])[:,0]
+                if not (lbc<=b*b).any(): return 0,0
+                it=(lb2(S,slo[c*8:c*8+8],shi[c*8:c*8+8])<=(b*b)[:,None]).sum()
+                dd=np.sqrt(((Tp[c*128:(c+1)*128][None]-S[:,None])**2).sum(-1)).min(1)
+                np.minimum(b,dd,out=b)
+                return 1,it
+            npr=0;nit=0;seeds=[];pend=np.ones(128,bool)
+            for k in range(nseed):
+                if not pend.any(): break
+                c=sc[np.argmax(pend)]; seeds.append(c); pend&=sc!=c
+                a,i=visit(c,b); npr+=a; nit+=i
+            wl,wh=S.min(0),S.max(0)
+            e=np.maximum(np.maximum(clo-wh, wl-chi),0); lbw=(e*e).sum(-1)
+            for c in np.nonzero(lbw<=b.max()**2)[0]:
+                if c in seeds or lbw[c]>b.max()**2: continue
+                a,i=visit(c,b); npr+=a; nit+=i
+            proc.append(npr); items.append(nit); gave+=npr>=thresh; nw+=1
+        print(f"  {name:10s} bound / true distance p50 {q[0]:.2f} p90 {q[1]:.2f} p99 {q[2]:.1f} p99.9 {q[3]:.1f} | per cold wave: processed chunks "
+              f"{np.mean(proc):.1f} (p99 {np.percentile(proc,99):.0f}) items {np.mean(items):.0f} | waves at >= {thresh} chunks {100.0*gave/nw:.1f} %")
+if len(sys.argv) > 1 and sys.argv[1] == "--cold-bounds":
+    w2=synth.make_world(2002)
+    N=synth.lidar_scan(w2,synth.se3(7.0,(1.5,-0.7,0)),seed=5001)[:,:3].astype(np.float64)
+    T4=synth.se3(2.0,(4.0,0.8,0.0))
+    C=synth.lidar_scan(w,T4,seed=1003)[:,:3].astype(np.float64)
+    Cw=C@T4[:3,:3].T+T4[:3,3]
+    # a cold pass runs at the pose the coarse matcher hands over: 0.3 m / 1 deg off (E is the mid-ICP error above)
+    Ec=synth.se3(1.0,(0.3,-0.2,0.02))
+    cold_bounds(sort_scan(Bw@Ec[:3,:3].T+Ec[:3,3],0.25,10), A, "same place")
+    cold_bounds(sort_scan(Cw@Ec[:3,:3].T+Ec[:3,3],0.25,10), A, "4 m apart")
+    cold_bounds(sort_scan(Bm,0.25,10), N, "different world")
+    sys.exit(0)
 
 if len(sys.argv) > 2 and sys.argv[1] == "--real":
     R=np.fromfile(sys.argv[2],np.float32).reshape(-1,4)[:,:3].astype(np.float64)

@@ -1,6 +1,8 @@
 // common.hip -- error reporting, device selection, device buffers, HIP-event profiler.
 #include "common.hpp"
 
+#include <algorithm>
+
 namespace gloc {
 
 char* err_buf() {
@@ -76,45 +78,69 @@ hipEvent_t Profiler::get_event() {
   return e;
 }
 
-void Profiler::begin(const char* name, hipStream_t s) {
+void Profiler::begin(const char* name, hipStream_t s, bool joined) {
   Family& f = fam[name];
-  Span sp{get_event(), get_event()};
-  (void)hipEventRecord(sp.a, s);
+  Span sp;
+  if (joined && tail && tail_s == s) {
+    sp.a = tail;  // (recorded already, by the scope that ended here)
+  } else {
+    sp.a = get_event();
+    (void)hipEventRecord(sp.a, s);
+  }
+  sp.b = get_event();
+  tail = nullptr;  // (work follows: the next scope joins this one's end, not its start)
   f.open.push_back(sp);
 }
 
-void Profiler::end(const char* name, hipStream_t s) {
+void Profiler::end(const char* name, hipStream_t s, const char* also) {
   Family& f = fam[name];
   if (f.open.empty()) return;
-  (void)hipEventRecord(f.open.back().b, s);
+  const Span sp = f.open.back();
+  (void)hipEventRecord(sp.b, s);
+  tail = sp.b;
+  tail_s = s;
   f.launches++;
+  if (also) {
+    Family& g = fam[also];
+    g.open.push_back(sp);
+    g.launches++;
+  }
   // bound the number of live events: fold when many are open
   size_t live = 0;
   for (auto& kv : fam) live += kv.second.open.size();
   if (live > 8192) (void)collect(s);
 }
 
-int Profiler::collect(hipStream_t s) {
-  GLOC_HIP(hipStreamSynchronize(s));
+// The events of the open spans back into the pool, each ONCE (joined scopes and second families share events), and no
+// span open any more; the tail goes with them.
+void Profiler::release_open() {
+  const size_t first = pool.size();
   for (auto& kv : fam) {
     for (Span& sp : kv.second.open) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) kv.second.total_ms += ms;
       pool.push_back(sp.a);
       pool.push_back(sp.b);
     }
     kv.second.open.clear();
   }
+  std::sort(pool.begin() + first, pool.end());
+  pool.erase(std::unique(pool.begin() + first, pool.end()), pool.end());
+  tail = nullptr;
+}
+
+int Profiler::collect(hipStream_t s) {
+  GLOC_HIP(hipStreamSynchronize(s));
+  for (auto& kv : fam)
+    for (Span& sp : kv.second.open) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) kv.second.total_ms += ms;
+    }
+  release_open();
   return GLOC_OK;
 }
 
 void Profiler::reset() {
+  release_open();
   for (auto& kv : fam) {
-    for (Span& sp : kv.second.open) {
-      pool.push_back(sp.a);
-      pool.push_back(sp.b);
-    }
-    kv.second.open.clear();
     kv.second.total_ms = 0;
     kv.second.launches = 0;
   }

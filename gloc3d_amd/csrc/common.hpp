@@ -88,23 +88,32 @@ struct Profiler {
   };
   std::map<std::string, Family> fam;
   std::vector<hipEvent_t> pool;
+  // The event the last end() recorded and its stream.  A scope that begins where that one ended -- `joined`: the caller
+  // has enqueued NOTHING on the stream in between -- takes it as its start instead of recording another: one event, not
+  // two, between two dependent kernels.  The idle gap between the kernels then counts for the later family.
+  hipEvent_t tail = nullptr;
+  hipStream_t tail_s = nullptr;
   hipEvent_t get_event();
-  void begin(const char* name, hipStream_t s);
-  void end(const char* name, hipStream_t s);
+  void begin(const char* name, hipStream_t s, bool joined = false);
+  // also: a second family that counts the same span (the same two events, no record of its own)
+  void end(const char* name, hipStream_t s, const char* also = nullptr);
   int collect(hipStream_t s);  // sync + fold open spans into totals
+  void release_open();
   void reset();
   void destroy();
 };
 
 struct ProfScope {
+  enum Join { Apart, Joined };  // Joined: nothing was enqueued on the stream since the scope before this one ended
   Profiler& p;
   const char* name;
   hipStream_t s;
-  ProfScope(Profiler& p_, const char* n, hipStream_t s_) : p(p_), name(n), s(s_) {
-    if (p.enabled) p.begin(name, s);
+  const char* also;
+  ProfScope(Profiler& p_, const char* n, hipStream_t s_, Join j = Apart, const char* also_ = nullptr) : p(p_), name(n), s(s_), also(also_) {
+    if (p.enabled) p.begin(name, s, j == Joined);
   }
   ~ProfScope() {
-    if (p.enabled) p.end(name, s);
+    if (p.enabled) p.end(name, s, also);
   }
 };
 

@@ -1494,6 +1494,14 @@ __global__ __launch_bounds__(64 * NN_WPB) void nn_compact_kernel(NN_COMPACT_PARA
   nn_compact_body<CS, PAIRS, SPLIT, WARM>(NnPos{blockIdx.z, blockIdx.x, blockIdx.y}, NN_COMPACT_ARGS);
 }
 
+// The cold pass of a batch without a split plan at two sources per lane -- a large batch's first launch -- held to the
+// register budget of six waves per SIMD like the warm kernels: left alone the compiler takes 83-85 registers, five waves,
+// and the sixth is what covers the prologue's dependent kd loads, the seed chunks and the pair stores.
+template <bool PAIRS>
+__global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 6))) void nn_compact_cold_kernel(NN_COMPACT_PARAMS) {
+  nn_compact_body<2, PAIRS, false, false>(NnPos{blockIdx.z, blockIdx.x, blockIdx.y}, NN_COMPACT_ARGS);
+}
+
 // The second launch of a cold pass: the groups its waves gave up, NN_HEAVY_PARTS waves each (NnHeavy).
 template <int CS, bool PAIRS>
 __global__ __launch_bounds__(64) void nn_compact_heavy_kernel(NN_COMPACT_PARAMS) {

@@ -287,7 +287,10 @@ void launch_compact(const NnArgs& a, dim3 grid, const uint32_t* prev_corr, bool 
 // query alone runs pass after pass -- is a kernel of its own at two sources per lane (nn_compact_split_warm_kernel).
 template <int CS, bool PAIRS, bool WARM>
 void launch_pass(const NnArgs& a, dim3 grid, const uint32_t* prev_corr, NnHeavy hv) {
-  if (!a.v.split.hx) launch_compact<nn_compact_kernel<CS, PAIRS, false, WARM>>(a, grid, prev_corr, PAIRS, hv);
+  if (!a.v.split.hx) {
+    if constexpr (CS == 2 && !WARM) launch_compact<nn_compact_cold_kernel<PAIRS>>(a, grid, prev_corr, PAIRS, hv);  // (six waves per SIMD)
+    else launch_compact<nn_compact_kernel<CS, PAIRS, false, WARM>>(a, grid, prev_corr, PAIRS, hv);
+  }
   else if constexpr (CS == 2 && !PAIRS && WARM) launch_compact<nn_compact_split_warm_kernel<2>>(a, grid, prev_corr, PAIRS, hv);
   else launch_compact<nn_compact_kernel<CS, PAIRS, true, WARM>>(a, grid, prev_corr, PAIRS, hv);
 }
@@ -303,12 +306,12 @@ void launch_kind(const NnArgs& a, dim3 grid, const uint32_t* prev_corr, NnHeavy 
 // S1 for every job of the batch.  warm: corr holds the previous pass's result.  want_pairs: write the (moved
 // source, matched target) pairs INSTEAD of the moments (the RANSAC stage refits from the pairs: accum_kernel<1>).  The culled search leaves the wave partials of the
 // fp64 moments in h->partials (per source group); the exhaustive one needs accum_kernel<0> afterwards.
-int launch_nn(gloc_reg* h, const BatchDims& bd, const WsView& v, bool warm, bool want_pairs, float gate2) {
-  ProfScope ps(h->prof, "nn", v.s);
+// join: the pass follows a profiled scope with nothing enqueued in between (a warm pass behind its solve).
+int launch_nn(gloc_reg* h, const BatchDims& bd, const WsView& v, bool warm, bool want_pairs, float gate2, ProfScope::Join join = ProfScope::Apart) {
   // (the first pass of a batch -- no previous correspondence, or the pass that writes the pairs -- is another
-  // instantiation and ~1.6 x a warm pass: also counted in its own family, so that "nn" - "nn_cold" is the warm passes alone)
-  Profiler no_prof;
-  ProfScope ps_cold((want_pairs || !warm) ? h->prof : no_prof, "nn_cold", v.s);
+  // instantiation and ~1.6 x a warm pass: also counted in its own family, on the same two events, so that "nn" - "nn_cold"
+  // is the warm passes alone)
+  ProfScope ps(h->prof, "nn", v.s, join, (want_pairs || !warm) ? "nn_cold" : nullptr);
   h->nn_launches++;
   if (h->nn_mode == 1) {
     dim3 grid((bd.max_src + 256 * NN_S - 1) / (256 * NN_S), v.n_jobs);
@@ -542,15 +545,15 @@ uint32_t score_hpb(uint32_t len) { return len <= 16 ? 16u : (len <= 64 ? 64u : 2
 // The refit on the winning hypothesis' inliers among the pairs, behind the scan that chose it.
 int enqueue_refit(gloc_reg* h, const BatchDims& bd, const WsView& v, float thr2, uint32_t nblocks) {
   const uint32_t n_jobs = v.n_jobs;
-  {
-    ProfScope ps(h->prof, "accum", v.s);
+  {  // (both callers come straight from their last ransac_score scope)
+    ProfScope ps(h->prof, "accum", v.s, ProfScope::Joined);
     hipLaunchKernelGGL(accum_kernel<1>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, v.s, v.jobs, v.states, v.corr, v.d2, v.pairs, bd.ld, thr2,
                        v.partials, bd.n_part);
     GLOC_HIP(hipGetLastError());
   }
   {
-    ProfScope ps(h->prof, "solve", v.s);
-    hipLaunchKernelGGL(solve_kernel<1>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(SOLVE_THREADS), 0, v.s, v.partials, bd.n_part, false, v.jobs,
+    ProfScope ps(h->prof, "solve", v.s, ProfScope::Joined);
+    hipLaunchKernelGGL(solve_kernel<1>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(v.split.hx ? SOLVE_THREADS : SOLVE_THREADS_LIGHT), 0, v.s, v.partials, bd.n_part, false, v.jobs,
                        v.states, v.split, n_jobs);
     GLOC_HIP(hipGetLastError());
   }
@@ -590,12 +593,12 @@ int enqueue_ransac(gloc_reg* h, const BatchDims& bd, const RansacRule& r, const 
     const uint32_t h0 = bounds[ph], h1 = bounds[ph + 1], len = h1 - h0;
     const CandState* st = ph ? v.states : (const CandState*)nullptr;
     {
-      ProfScope ps(h->prof, "ransac_hyp", s);
+      ProfScope ps(h->prof, "ransac_hyp", s, ph ? ProfScope::Joined : ProfScope::Apart);  // (behind the phase before; the first behind the fills)
       hipLaunchKernelGGL(ransac_hyp_kernel, dim3((len + 127) / 128, n_jobs), dim3(128), 0, s, v.pairs, bd.ld,
                          v.jobs, r.seed, H, h0, h1, st, v.Rt, v.valid);
       GLOC_HIP(hipGetLastError());
     }
-    ProfScope ps(h->prof, "ransac_score", s);
+    ProfScope ps(h->prof, "ransac_score", s, ProfScope::Joined);
     const uint32_t hpb = score_hpb(len);
     const unsigned NP = 8;
     if (!adaptive && ph > 0 && len >= 512 && cchunks >= NP) {
@@ -650,18 +653,20 @@ int enqueue_pipeline(gloc_reg* h, const BatchDims& bd, const gloc_reg_params* pr
       GLOC_TRY(launch_nn_chain(h, bd, v, prm->icp_iters - it, gate2));
       break;
     }
-    GLOC_TRY(launch_nn(h, bd, v, have_corr, false, gate2));
+    // (profiled scopes end to end: this pass behind the refit's or the previous pass's solve -- a batch's first launch
+    // apart, behind the preamble's copies and fills -- and the solve behind its pass)
+    GLOC_TRY(launch_nn(h, bd, v, have_corr, false, gate2, have_corr ? ProfScope::Joined : ProfScope::Apart));
     have_corr = true;
     if (!culled) {
-      ProfScope ps(h->prof, "accum", s);
+      ProfScope ps(h->prof, "accum", s, ProfScope::Joined);
       hipLaunchKernelGGL(accum_kernel<0>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, s, v.jobs,
                          v.states, v.corr, v.d2,
                          (const f32x4*)nullptr, bd.ld, gate2, v.partials, bd.n_part);
       GLOC_HIP(hipGetLastError());
     }
     {
-      ProfScope ps(h->prof, "solve", s);
-      hipLaunchKernelGGL(solve_kernel<0>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(SOLVE_THREADS), 0, s, v.partials,
+      ProfScope ps(h->prof, "solve", s, ProfScope::Joined);
+      hipLaunchKernelGGL(solve_kernel<0>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(v.split.hx ? SOLVE_THREADS : SOLVE_THREADS_LIGHT), 0, s, v.partials,
                          bd.n_part, culled, v.jobs, v.states, v.split, n_jobs);
       GLOC_HIP(hipGetLastError());
     }

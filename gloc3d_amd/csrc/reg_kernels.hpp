@@ -794,6 +794,14 @@ constexpr int WAVE_PARTIAL_FLOATS = 21;  // the culled search's partial: 17 fp32
 constexpr int SOLVE_R = 56;  // (56 x 18 moments = 1008 threads)
 constexpr int SOLVE_THREADS = 1024;
 static_assert(SOLVE_R * ACC_NV <= SOLVE_THREADS, "a thread per (stride class, moment)");
+// The work-group of a launch WITHOUT the planner (a large batch: no helper slots).  The kernel's 124 registers let ONE
+// work-group of 1024 threads into a CU -- four waves on each SIMD -- and the next only when the last lane of the one
+// before has finished its Kabsch: 500 jobs ran as two rounds on 256 CUs.  Four of these fit a CU, so every job of such
+// a batch is resident at once and the one-lane Kabsch of a job runs beside the others' reductions.  The sums do not
+// change: each wave makes the rows of four of the 16 "waves" in turn (solve_kernel), the same additions in the same order.
+// (512 threads -- two work-groups a CU, 512 at once -- measured 0.02 ms per step of 500 jobs faster; a batch of 513 is back to two rounds)
+constexpr int SOLVE_THREADS_LIGHT = 256;
+static_assert(SOLVE_THREADS_LIGHT % 64 == 0 && SOLVE_THREADS % SOLVE_THREADS_LIGHT == 0 && SOLVE_THREADS_LIGHT >= 64, "whole waves, whole turns");
 
 // memory that every XCD sees without a cache write-back or invalidate: relaxed device-scope atomics (loads and stores
 // that go past the XCD's own L2) -- what the chained passes (NnChain, nn_compact.hpp) hand from one wave to another
@@ -1032,6 +1040,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const double* __re
     return;
   }
   const int cand = blockIdx.x;
+  const int nthr = (int)blockDim.x;  // SOLVE_THREADS, or SOLVE_THREADS_LIGHT where no plan is made
   const uint32_t cnt = per_group ? jobs[cand].n_groups
                                  : (jobs[cand].n_src + ACC_PER_BLOCK - 1) / ACC_PER_BLOCK;
   if (per_group) {
@@ -1040,39 +1049,45 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const double* __re
     // fp64.  A thread takes whole partials (one each at 124 k points: 969 waves), the work-group sums them in a
     // fixed order: xor butterfly inside the wave, the 16 waves in order.
     static_assert(SOLVE_THREADS / 64 <= SOLVE_R, "a row of sub[][] per wave");
+    // The sums are those of SOLVE_THREADS threads whatever the work-group's size: row rw of sub[][] is "wave rw of
+    // 1024 threads" -- the partials rw * 64 + lane, + 1024, ... in that order, then the butterfly -- and a wave of a
+    // smaller work-group (SOLVE_THREADS_LIGHT) makes several rows one after the other, each from zero.
     const float* base = reinterpret_cast<const float*>(partials + (size_t)cand * n_part * ACC_NV);
-    double v[ACC_NV];
+    const int lane = tid & 63, n_waves = nthr >> 6;
+    for (int rw = __builtin_amdgcn_readfirstlane(tid >> 6); rw < SOLVE_THREADS / 64; rw += n_waves) {
+      double v[ACC_NV];
 #pragma unroll
-    for (int k = 0; k < ACC_NV; ++k) v[k] = 0.0;
-    for (uint32_t g = (uint32_t)tid; g < cnt; g += SOLVE_THREADS) {
-      typedef float f32x2_ __attribute__((ext_vector_type(2)));
-      const f32x2_* f2 = reinterpret_cast<const f32x2_*>(base + (size_t)g * (2 * ACC_NV));  // (a slot is 136 B: 8-byte aligned)
-      float f[WAVE_PARTIAL_FLOATS + 1];
+      for (int k = 0; k < ACC_NV; ++k) v[k] = 0.0;
+      for (uint32_t g = (uint32_t)(rw * 64 + lane); g < cnt; g += SOLVE_THREADS) {
+        typedef float f32x2_ __attribute__((ext_vector_type(2)));
+        const f32x2_* f2 = reinterpret_cast<const f32x2_*>(base + (size_t)g * (2 * ACC_NV));  // (a slot is 136 B: 8-byte aligned)
+        float f[WAVE_PARTIAL_FLOATS + 1];
 #pragma unroll
-      for (int i = 0; i < (WAVE_PARTIAL_FLOATS + 1) / 2; ++i) {
-        const f32x2_ t = f2[i];
-        f[2 * i] = t.x;
-        f[2 * i + 1] = t.y;
+        for (int i = 0; i < (WAVE_PARTIAL_FLOATS + 1) / 2; ++i) {
+          const f32x2_ t = f2[i];
+          f[2 * i] = t.x;
+          f[2 * i + 1] = t.y;
+        }
+        add_wave_partial(f, v);
       }
-      add_wave_partial(f, v);
-    }
 #pragma unroll
-    for (int k = 0; k < ACC_NV; ++k) {  // (DPP / permlane exchanges: the LDS crossbar's __shfl_xor made this 8 us of chain)
-      double x = v[k];
-      x += xor_lane<32>(x);
-      x += xor_lane<16>(x);
-      x += xor_lane<8>(x);
-      x += xor_lane<4>(x);
-      x += xor_lane<2>(x);
-      x += xor_lane<1>(x);
-      v[k] = x;
-    }
-    if ((tid & 63) == 0) {
+      for (int k = 0; k < ACC_NV; ++k) {  // (DPP / permlane exchanges: the LDS crossbar's __shfl_xor made this 8 us of chain)
+        double x = v[k];
+        x += xor_lane<32>(x);
+        x += xor_lane<16>(x);
+        x += xor_lane<8>(x);
+        x += xor_lane<4>(x);
+        x += xor_lane<2>(x);
+        x += xor_lane<1>(x);
+        v[k] = x;
+      }
+      if (lane == 0) {
 #pragma unroll
-      for (int k = 0; k < ACC_NV; ++k) sub[tid >> 6][k] = v[k];
+        for (int k = 0; k < ACC_NV; ++k) sub[rw][k] = v[k];
+      }
     }
-  } else if (tid < SOLVE_R * ACC_NV) {
-    const int k = tid % ACC_NV, r = tid / ACC_NV;
+  } else for (int t = tid; t < SOLVE_R * ACC_NV; t += nthr) {
+    const int k = t % ACC_NV, r = t / ACC_NV;
     double acc = 0.0;
     uint32_t b = (uint32_t)r;
     const double* pp = partials + (size_t)cand * n_part * ACC_NV + k;

@@ -422,7 +422,10 @@ int gloc_reg_ransac_hypotheses(gloc_reg* h, const float* src_xyz, const float* t
                                uint32_t* out_valid, uint32_t* out_inliers, float inlier_thresh);
 
 /* HIP-event time per kernel family ("nn", "ransac_hyp", "ransac_score", "accum", "solve",
- * "transform"), as gloc_knn_profile. */
+ * "transform"), as gloc_knn_profile.  "nn_cold" is the part of "nn" that a batch's first, cold, pass took: the same
+ * span counted a second time, so "nn" - "nn_cold" is the warm passes alone.  Where one family's launches follow
+ * another's with nothing enqueued in between (a pass and its solve, the RANSAC phases, the refit), the two spans
+ * share ONE event: the idle gap between the two kernels belongs to the later family, launch counts are unaffected. */
 int gloc_reg_profile(gloc_reg* h, const char* kernel, double* total_ms, uint64_t* launches);
 int gloc_reg_profile_reset(gloc_reg* h);
 /* With profiling on: (source, target) pairs evaluated by the culled 1-NN kernel and the number of

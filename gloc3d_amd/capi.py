@@ -103,6 +103,13 @@ class FpfhGraphParams(C.Structure):
                 ("theta_num", C.c_uint32), ("theta_den", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class FgrParams(C.Structure):
+    _fields_ = [("normal_k", C.c_uint32), ("feature_k", C.c_uint32), ("mutual", C.c_uint32), ("tuple_tries", C.c_uint32),
+                ("max_tuples", C.c_uint32), ("tuple_scale", C.c_float), ("max_iters", C.c_uint32), ("anneal_every", C.c_uint32),
+                ("anneal_div", C.c_float), ("max_corr_dist", C.c_float), ("inlier_thresh", C.c_float), ("min_inlier_ratio", C.c_float),
+                ("seed", C.c_uint64)]
+
+
 class FpfhRadiusParams(C.Structure):
     _fields_ = [("normal_radius", C.c_float), ("normal_max_nn", C.c_uint32), ("normal_min_nn", C.c_uint32),
                 ("feature_radius", C.c_float), ("feature_max_nn", C.c_uint32), ("reserved_", C.c_uint32)]
@@ -320,6 +327,12 @@ _PROTOS = [
                                            _vp, _vp, _vp, _vp]),
     ("gloc_reg_fpfh_graph_batch_ids_keypoints", _i, [_vp, _u32, _vp, _sz, C.POINTER(FpfhGraphParams), C.POINTER(FpfhRadiusParams),
                                                  C.POINTER(IssParams), _vp, _vp, _vp, _vp]),
+    ("gloc_fgr_default_params", None, [C.POINTER(FgrParams)]),
+    ("gloc_reg_fpfh_fgr_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FgrParams), _vp, _vp, _vp, _vp]),
+    ("gloc_reg_fpfh_fgr_batch_ids_radius", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FgrParams), C.POINTER(FpfhRadiusParams), _vp, _vp, _vp, _vp]),
+    ("gloc_reg_fpfh_fgr_batch_ids_keypoints", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FgrParams), C.POINTER(FpfhRadiusParams),
+                                               C.POINTER(IssParams), _vp, _vp, _vp, _vp]),
+    ("gloc_reg_fgr_pairs", _i, [_vp, _vp, _vp, _sz, _u32, C.POINTER(FgrParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
@@ -800,6 +813,17 @@ def default_fpfh_graph_params(**over):
     64 seeds, 0.6 m compatibility and inlier thresholds, theta = 1 / 2), then `over`."""
     p = FpfhGraphParams()
     lib().gloc_fpfh_graph_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
+def default_fgr_params(**over):
+    """gloc_fgr_params as gloc_fgr_default_params leaves them (normal_k = 10, feature_k = 16, mutual matches, 10 000 tuple
+    tries of which the first 1000 passing at scale 0.9 are kept, 64 updates, mu divided by 1.4 every 4, 0.6 m match distance
+    and inlier threshold, seed 1234), then `over`."""
+    p = FgrParams()
+    lib().gloc_fgr_default_params(C.byref(p))
     for k_, v in over.items():
         setattr(p, k_, v)
     return p
@@ -1327,6 +1351,34 @@ class Registrar(_Handle):
         ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
         prm = params or default_fpfh_graph_params()
         return self._fpfh_jobs("gloc_reg_fpfh_graph_batch_ids", src_id, ids, [C.byref(prm)], support, keypoints)
+
+    def fpfh_fgr_batch(self, src_id, tgt_ids, params=None, support=None, keypoints=None, stream_ids=None):
+        """Feature-based global registration by Fast Global Registration (gloc_reg_fpfh_fgr_batch_ids): the matches of
+        fpfh_batch, the pose from one graduated-non-convexity optimisation over them instead of RANSAC.  Returns dict(T [n, 4,
+        4] float32 source -> target, inliers [n], n_pairs [n], ok [n] bool); T is a start for a refinement, as fpfh_batch's.
+        support, keypoints, stream_ids: as fpfh_batch's (the _radius and _keypoints entries)."""
+        ids = np.ascontiguousarray(np.atleast_1d(tgt_ids), np.uint32)
+        prm = params or default_fgr_params()
+        sid = None if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32).reshape(ids.shape[0])
+        return self._fpfh_jobs("gloc_reg_fpfh_fgr_batch_ids", src_id, ids, [None if sid is None else _np_ptr(sid), C.byref(prm)], support, keypoints)
+
+    def fgr_pairs(self, P, Q, params=None, stream_id=0):
+        """Fast Global Registration of a pair list P, Q [m, 3] (gloc_reg_fgr_pairs): dict(mult [m] uint32, n_tuples, d2,
+        system [27] float64 (H's upper triangle, then g, of the last update formed), T [4, 4] float32, inliers, status (0: all
+        updates ran, 2: degenerate), ok)."""
+        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        Q = np.ascontiguousarray(Q, np.float32).reshape(-1, 3)
+        m = P.shape[0]
+        assert Q.shape[0] == m
+        prm = params or default_fgr_params()
+        mult, system = np.empty(max(m, 1), np.uint32), np.empty(27, np.float64)
+        T = np.empty((4, 4), np.float32)
+        nt, inl, d2, status, ok = C.c_uint32(), C.c_uint32(), C.c_double(), C.c_int(), C.c_int()
+        check(lib().gloc_reg_fgr_pairs(self._h, _np_ptr(P) if m else None, _np_ptr(Q) if m else None, m, int(stream_id), C.byref(prm),
+                                       _np_ptr(mult), C.byref(nt), C.byref(d2), _np_ptr(system), _np_ptr(T), C.byref(inl), C.byref(status),
+                                       C.byref(ok)))
+        return dict(mult=mult[:m], n_tuples=nt.value, d2=d2.value, system=system, T=T, inliers=inl.value, status=status.value,
+                    ok=bool(ok.value))
 
     def pair_graph(self, P, Q, params=None):
         """The correspondence graph of a pair list P, Q [m, 3] (gloc_reg_pair_graph): dict(degree [m] uint32, score [m] uint64,

@@ -5,7 +5,9 @@
 //
 //   reduce_store    the 29 sums of a pass (21 entries of the upper triangle of H, 6 of g, the squared residual, the count):
 //                   a reduce-scatter over the wave, the work-group's waves in LDS, one partial per work-group
-//   solve_kernel    one wave per job: the partials summed in index order, 6 x 6 Cholesky, Rodrigues, T <- T_k T,
+//   chol_rodrigues  the update itself, fp64: 6 x 6 Cholesky with the pivot rule, xi = -H^-1 g, Rodrigues, exp(xi) T (also
+//                   what the one-launch GNC of fgr_kernels.hpp runs once per update)
+//   solve_kernel    one wave per job: the partials summed in index order, chol_rodrigues, T <- T_k T,
 //                   the stop test and the freeze flag -- all fp64
 //
 // Registers: a lane has ONE point, so its 29 fp64 values are products, not loop-carried accumulators; they are live only
@@ -105,6 +107,88 @@ __device__ __forceinline__ void reduce_store(double* v, double (*red)[NSLOT] /* 
   }
 }
 
+// The update of a pose from a 6 x 6 system, as both the refinements' solve_kernel below and the one-launch GNC of the Fast
+// Global Registration (fgr_kernels.hpp) run it: tot is H's upper triangle (21, row-major) and g (6); Cholesky row by row
+// with the pivot rule, xi = -H^-1 g (rotation first), Rodrigues, Tn = exp(xi) Td.  false: a degenerate system (Tn, xi and
+// th_out are then not written).  th_out: |xi's rotation part|.
+__device__ inline bool chol_rodrigues(const double* tot /* [27] */, const double* Td /* [12] */, double* Tn /* [12] */, double* xi /* [6] */,
+                                      double* th_out) {
+  double L[6][6];
+  double dmax = 0.0;
+  {
+    int e = 0;
+    #pragma unroll
+    for (int a = 0; a < 6; ++a)
+      #pragma unroll
+      for (int b = a; b < 6; ++b) {
+        L[a][b] = tot[e];
+        L[b][a] = tot[e];
+        ++e;
+      }
+    #pragma unroll
+    for (int a = 0; a < 6; ++a) dmax = L[a][a] > dmax ? L[a][a] : dmax;
+  }
+  bool ok = true;
+  // Cholesky, row by row (lower triangle in place): a pivot at or below 1e-12 of the largest diagonal entry is degenerate
+  #pragma unroll
+  for (int jj = 0; jj < 6 && ok; ++jj) {
+    double d = L[jj][jj];
+    #pragma unroll
+    for (int k = 0; k < jj; ++k) d -= L[jj][k] * L[jj][k];
+    if (!(d > 1e-12 * dmax)) {
+      ok = false;
+      break;
+    }
+    const double dj = sqrt(d);
+    L[jj][jj] = dj;
+    #pragma unroll
+    for (int i = jj + 1; i < 6; ++i) {
+      double s = L[i][jj];
+      #pragma unroll
+      for (int k = 0; k < jj; ++k) s -= L[i][k] * L[jj][k];
+      L[i][jj] = s / dj;
+    }
+  }
+  if (!ok) return false;
+  double y[6];
+  #pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = -tot[21 + i];
+    #pragma unroll
+    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+    y[i] = s / L[i][i];
+  }
+  #pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i];
+    #pragma unroll
+    for (int k = i + 1; k < 6; ++k) s -= L[k][i] * xi[k];
+    xi[i] = s / L[i][i];
+  }
+  // Rodrigues: R = I + (sin th / th) K + ((1 - cos th) / th^2) K^2, K = [w]x
+  const double wx = xi[0], wy = xi[1], wz = xi[2];
+  const double th2 = (wx * wx + wy * wy) + wz * wz, th = sqrt(th2);
+  *th_out = th;
+  double A = 1.0, B = 0.5;
+  if (th > 0.0) {
+    A = sin(th) / th;
+    const double sh = sin(0.5 * th);
+    B = 2.0 * (sh * sh) / th2;  // (1 - cos th) / th^2 without the cancellation
+  }
+  const double K[9] = {0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0};
+  double Rk[9];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const double k2 = (K[3 * a + 0] * K[0 + b] + K[3 * a + 1] * K[3 + b]) + K[3 * a + 2] * K[6 + b];
+      Rk[3 * a + b] = ((a == b ? 1.0 : 0.0) + A * K[3 * a + b]) + B * k2;
+    }
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) Tn[3 * a + b] = (Rk[3 * a + 0] * Td[0 + b] + Rk[3 * a + 1] * Td[3 + b]) + Rk[3 * a + 2] * Td[6 + b];
+    Tn[9 + a] = ((Rk[3 * a + 0] * Td[9] + Rk[3 * a + 1] * Td[10]) + Rk[3 * a + 2] * Td[11]) + xi[3 + a];
+  }
+  return true;
+}
+
 // mode 0: a pass (solve, update, stop test).  mode 1: evaluation only (sum_r2, count, rmse, wsum; `exp`, if given, gets
 // the job's 29 sums).  stop_from: the first update index at which the stop test counts (0: every update; a robust
 // schedule's first index at its final scale).
@@ -139,70 +223,10 @@ static __global__ __launch_bounds__(64) void solve_kernel(const double* __restri
     st.stopped = 1;
     atomicAdd(done, 1u);
   };
-  double L[6][6];
-  double dmax = 0.0;
-  {
-    int e = 0;
-    for (int a = 0; a < 6; ++a)
-      for (int b = a; b < 6; ++b) {
-        L[a][b] = tot[e];
-        L[b][a] = tot[e];
-        ++e;
-      }
-    for (int a = 0; a < 6; ++a) dmax = L[a][a] > dmax ? L[a][a] : dmax;
-  }
-  bool ok = cnt >= 6.0;
-  // Cholesky, row by row (lower triangle in place): a pivot at or below 1e-12 of the largest diagonal entry is degenerate
-  for (int jj = 0; jj < 6 && ok; ++jj) {
-    double d = L[jj][jj];
-    for (int k = 0; k < jj; ++k) d -= L[jj][k] * L[jj][k];
-    if (!(d > 1e-12 * dmax)) {
-      ok = false;
-      break;
-    }
-    const double dj = sqrt(d);
-    L[jj][jj] = dj;
-    for (int i = jj + 1; i < 6; ++i) {
-      double s = L[i][jj];
-      for (int k = 0; k < jj; ++k) s -= L[i][k] * L[jj][k];
-      L[i][jj] = s / dj;
-    }
-  }
-  if (!ok) {
+  double Tn[12], xi[6], th;
+  if (!(cnt >= 6.0) || !chol_rodrigues(tot, st.Td, Tn, xi, &th)) {
     stop(2);
     return;
-  }
-  double y[6], xi[6];
-  for (int i = 0; i < 6; ++i) {
-    double s = -tot[21 + i];
-    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
-    y[i] = s / L[i][i];
-  }
-  for (int i = 5; i >= 0; --i) {
-    double s = y[i];
-    for (int k = i + 1; k < 6; ++k) s -= L[k][i] * xi[k];
-    xi[i] = s / L[i][i];
-  }
-  // Rodrigues: R = I + (sin th / th) K + ((1 - cos th) / th^2) K^2, K = [w]x
-  const double wx = xi[0], wy = xi[1], wz = xi[2];
-  const double th2 = (wx * wx + wy * wy) + wz * wz, th = sqrt(th2);
-  double A = 1.0, B = 0.5;
-  if (th > 0.0) {
-    A = sin(th) / th;
-    const double sh = sin(0.5 * th);
-    B = 2.0 * (sh * sh) / th2;  // (1 - cos th) / th^2 without the cancellation
-  }
-  const double K[9] = {0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0};
-  double Rk[9];
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) {
-      const double k2 = (K[3 * a + 0] * K[0 + b] + K[3 * a + 1] * K[3 + b]) + K[3 * a + 2] * K[6 + b];
-      Rk[3 * a + b] = ((a == b ? 1.0 : 0.0) + A * K[3 * a + b]) + B * k2;
-    }
-  double Tn[12];
-  for (int a = 0; a < 3; ++a) {
-    for (int b = 0; b < 3; ++b) Tn[3 * a + b] = (Rk[3 * a + 0] * st.Td[0 + b] + Rk[3 * a + 1] * st.Td[3 + b]) + Rk[3 * a + 2] * st.Td[6 + b];
-    Tn[9 + a] = ((Rk[3 * a + 0] * st.Td[9] + Rk[3 * a + 1] * st.Td[10]) + Rk[3 * a + 2] * st.Td[11]) + xi[3 + a];
   }
   for (int k = 0; k < 12; ++k) {
     st.Td[k] = Tn[k];

@@ -9,6 +9,7 @@
 
 #include "common.hpp"
 
+#include "fgr.hpp"
 #include "fpfh.hpp"
 #include "ndt.hpp"
 #include "nn_compact.hpp"
@@ -95,6 +96,7 @@ struct gloc_reg : Handle {
   gloc::fpfh::Ws* fpfh = nullptr;    // the feature matcher's keys and tables (fpfh.hip), made on first use
   gloc::pairgraph::Ws* pgraph = nullptr;  // the correspondence graph's bit matrices and seed rows (pairgraph.hip), made on first use
   size_t pgraph_budget = 0;          // bytes of them in flight at a time (GLOC_REG_OPT_PAIRGRAPH_BUDGET; 0: pairgraph::BUDGET_BYTES)
+  gloc::fgr::Ws* fgr = nullptr;      // Fast Global Registration's pass bits, multiplicities and results (fgr.hip), made on first use
   ~gloc_reg() {  // (the handle's work has been waited for: destroy_handle)
     if (pending.active && pending.store) store_pin(pending.store, pending.pinned.data(), pending.pinned.size(), -1);
     if (store) store->attached--;
@@ -104,6 +106,7 @@ struct gloc_reg : Handle {
     gloc::vgicp::ws_free(vgicp);
     gloc::fpfh::ws_free(fpfh);
     gloc::pairgraph::ws_free(pgraph);
+    gloc::fgr::ws_free(fgr);
     if (done_ev) (void)hipEventDestroy(done_ev);
     if (pin) (void)hipHostFree(pin);
   }
@@ -929,10 +932,11 @@ struct FpfhFront {
   bool adaptive;
   float min_inlier_ratio;
   const gloc_iss_params* iss = nullptr;  // match the scans' keypoints of these parameters alone (I4); null: every point
+  bool ok_from_state = false;            // the stage leaves a verdict of its own in the state's ok, which ok also asks for (R4)
 };
 
 // stage(bd, v, nblocks, m_max): the launches from the pairs in v.pairs (M of job c in jobs[c].n_src; none above m_max) to
-// the pose in the states -- enqueue_ransac (F4) or enqueue_graph (G1 - G4).
+// the pose in the states -- enqueue_ransac (F4), enqueue_graph (G1 - G4) or enqueue_fgr (R1 - R4).
 template <class Stage>
 int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const uint32_t* stream_ids, const FpfhFront* prm,
                    float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok, Stage&& stage) {
@@ -1035,6 +1039,7 @@ int run_fpfh_pairs(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t
     const uint32_t M = counts[c];
     bool found, ok;
     pair_verdict(cs, M, prm->min_inlier_ratio, &found, &ok);
+    if (prm->ok_from_state) ok = ok && cs.ok != 0;
     pose_to_T16(cs, out_T + 16 * (size_t)c);
     if (out_n_pairs) out_n_pairs[c] = M;
     if (out_inliers) out_inliers[c] = found ? cs.best_inl : 0u;
@@ -1159,6 +1164,96 @@ int run_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const 
   if (out_inliers) *out_inliers = found ? cs.best_inl : 0u;
   if (out_winner_rank) *out_winner_rank = found ? cs.best_h : 0xFFFFFFFFu;
   if (out_ok) *out_ok = ok;
+  return GLOC_OK;
+}
+
+// Fast Global Registration (fgr.hip): R1 - R4 on the pairs in v.pairs.  The stage has its own job table (the list's length
+// and the sample stream, taken from the batch's on the device) and its own results, which fgr_state_kernel turns into
+// what the shared part reads from the states: the fp32 pose, best_h = 0 once an update has completed (else none: the
+// identity and 0 inliers), the inliers, and ok = (status 0).
+__global__ void fgr_jobs_kernel(const Job* __restrict__ jobs, uint32_t n_jobs, gloc::fgr::JobIn* __restrict__ out) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < n_jobs) out[c] = gloc::fgr::JobIn{jobs[c].n_src, jobs[c].cand_id};
+}
+
+__global__ void fgr_state_kernel(const gloc::fgr::Result* __restrict__ res, uint32_t n_jobs, CandState* __restrict__ states) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_jobs) return;
+  const gloc::fgr::Result& r = res[c];
+  CandState& st = states[c];
+  if (r.updates) {
+    for (int k = 0; k < 12; ++k) {
+      st.Td[k] = r.Td[k];
+      st.Tf[k] = r.Tf[k];
+    }
+    st.best_h = 0u;
+    st.best_inl = r.inliers;
+  }
+  st.ok = r.status == 0 ? 1 : 0;
+}
+
+int enqueue_fgr(gloc_reg* h, const BatchDims& bd, const gloc_fgr_params* prm, const WsView& v, uint32_t m_max) {
+  const uint32_t n_jobs = v.n_jobs;
+  hipStream_t s = v.s;
+  GLOC_TRY(ensure_ws(&h->fgr));
+  gloc::fgr::Ws& w = *h->fgr;
+  GLOC_TRY(w.jobs.ensure(sizeof(gloc::fgr::JobIn) * n_jobs, s));
+  hipLaunchKernelGGL(fgr_jobs_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, s, v.jobs, n_jobs, w.jobs.as<gloc::fgr::JobIn>());
+  GLOC_HIP(hipGetLastError());
+  GLOC_TRY(gloc::fgr::enqueue(s, h->prof, w, gloc::fgr::Batch{v.pairs, bd.ld, n_jobs, m_max}, *prm));
+  hipLaunchKernelGGL(fgr_state_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, s, w.results.as<gloc::fgr::Result>(), n_jobs, v.states);
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int run_fpfh_fgr(gloc_reg* h, uint32_t src_id, const uint32_t* tgt_ids, size_t n, const uint32_t* stream_ids, const gloc_fgr_params* prm,
+                 const Support& normal, const Support& feature, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok,
+                 const gloc_iss_params* iss = nullptr) {
+  const FpfhFront f{normal, feature, prm->mutual, 1u, true, prm->min_inlier_ratio, iss, true};
+  return run_fpfh_pairs(h, src_id, tgt_ids, n, stream_ids, &f, out_T, out_inliers, out_n_pairs, out_ok,
+                        [&](const BatchDims& bd, const WsView& v, uint32_t, uint32_t m_max) { return enqueue_fgr(h, bd, prm, v, m_max); });
+}
+
+// gloc_reg_fgr_pairs: one job on a host list, every diagnostic brought down.
+int run_fgr_pairs(gloc_reg* h, const float* P, const float* Q, size_t m, uint32_t stream_id, const gloc_fgr_params* prm, uint32_t* out_mult,
+                  uint32_t* out_n_tuples, double* out_d2, double* out_system, float* out_T, uint32_t* out_inliers, int* out_status,
+                  int* out_ok) {
+  const uint32_t M = (uint32_t)m;
+  memcpy(out_T, I16, sizeof(I16));
+  if (out_n_tuples) *out_n_tuples = 0;
+  if (out_d2) *out_d2 = 0.0;
+  if (out_system) std::fill(out_system, out_system + gloc::fgr::NSYS, 0.0);
+  if (out_inliers) *out_inliers = 0;
+  if (out_status) *out_status = 2;
+  if (out_ok) *out_ok = 0;
+  if (out_mult) std::fill(out_mult, out_mult + m, 0u);
+  if (M == 0) return GLOC_OK;
+  hipStream_t s = h->stream;
+  Batch b;
+  GLOC_TRY(open_batch(h, BatchSpec::on_pairs(1, M, 1, false), &b, [&](Job* jd, CandState* cst) {
+    jd[0] = Job{nullptr, nullptr, nullptr, nullptr, ScanIndexDev{}, M, 0u, stream_id, 0u};
+    init_state(cst[0], nullptr, 1);
+  }));
+  const WsView& v = b.v;
+  const std::vector<float> hp = pack_pairs(P, Q, nullptr, m, b.bd.ld);
+  GLOC_HIP(hipMemcpyAsync(v.pairs, hp.data(), sizeof(float) * hp.size(), hipMemcpyHostToDevice, s));
+  GLOC_TRY(enqueue_fgr(h, b.bd, prm, v, M));
+  const gloc::fgr::Ws& w = *h->fgr;
+  gloc::fgr::Result res;
+  GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState), hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipMemcpyAsync(&res, w.results.p, sizeof(res), hipMemcpyDeviceToHost, s));
+  if (out_mult) GLOC_HIP(hipMemcpyAsync(out_mult, w.mult.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, s));
+  GLOC_HIP(hipStreamSynchronize(s));  // (hp, too, is done with)
+  const CandState& cs = h->h_states[0];
+  bool found, ok;
+  pair_verdict(cs, M, prm->min_inlier_ratio, &found, &ok);
+  pose_to_T16(cs, out_T);
+  if (out_n_tuples) *out_n_tuples = res.n_tuples;
+  if (out_d2) *out_d2 = res.d2;
+  if (out_system) std::copy(res.system, res.system + gloc::fgr::NSYS, out_system);
+  if (out_inliers) *out_inliers = found ? cs.best_inl : 0u;
+  if (out_status) *out_status = res.status;
+  if (out_ok) *out_ok = ok && cs.ok != 0;
   return GLOC_OK;
 }
 
@@ -2021,6 +2116,55 @@ int gloc_reg_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, c
   GLOC_HIP(hipSetDevice(h->device));
   return run_pair_graph(h, P, Q, m, prm, out_degree, out_score, out_seeds, out_set_sizes, out_seed_inliers, out_T, out_inliers,
                         out_winner_rank, out_ok);
+}
+
+int gloc_reg_fpfh_fgr_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
+                                const gloc_fgr_params* prm, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+  GLOC_TRY(gloc::fgr::check_params(prm));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_fpfh_fgr(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, Support::nearest(prm->normal_k), Support::nearest(prm->feature_k),
+                      out_T, out_inliers, out_n_pairs, out_ok);
+}
+
+int gloc_reg_fpfh_fgr_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
+                                       const gloc_fgr_params* prm, const gloc_fpfh_radius_params* support, float* out_T,
+                                       uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok) {
+  GLOC_TRY(gloc::fgr::check_params(prm));
+  GLOC_TRY(gloc::fpfh::check_radius_params(support));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_fpfh_fgr(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, Support::normals_of(*support), Support::features_of(*support), out_T,
+                      out_inliers, out_n_pairs, out_ok);
+}
+
+// (support == NULL: the k-mode features of prm)
+int gloc_reg_fpfh_fgr_batch_ids_keypoints(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n,
+                                          const uint32_t* stream_ids, const gloc_fgr_params* prm, const gloc_fpfh_radius_params* support,
+                                          const gloc_iss_params* iss, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs,
+                                          int* out_ok) {
+  GLOC_TRY(gloc::fgr::check_params(prm));
+  if (support) GLOC_TRY(gloc::fpfh::check_radius_params(support));
+  GLOC_TRY(check_iss_params(iss));
+  GLOC_REQUIRE(h && out_T && tgt_scan_ids, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_fpfh_fgr(h, src_scan_id, tgt_scan_ids, n, stream_ids, prm, support ? Support::normals_of(*support) : Support::nearest(prm->normal_k),
+                      support ? Support::features_of(*support) : Support::nearest(prm->feature_k), out_T, out_inliers, out_n_pairs, out_ok,
+                      iss);
+}
+
+int gloc_reg_fgr_pairs(gloc_reg* h, const float* P, const float* Q, size_t m, uint32_t stream_id, const gloc_fgr_params* prm,
+                       uint32_t* out_mult, uint32_t* out_n_tuples, double* out_d2, double* out_system, float* out_T,
+                       uint32_t* out_inliers, int* out_status, int* out_ok) {
+  GLOC_TRY(gloc::fgr::check_params(prm));
+  GLOC_REQUIRE(h && out_T && ((P && Q) || m == 0), GLOC_ERR_INVALID, "null argument");
+  GLOC_REQUIRE(m < (1ull << 31), GLOC_ERR_INVALID, "too many pairs");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return run_fgr_pairs(h, P, Q, m, stream_id, prm, out_mult, out_n_tuples, out_d2, out_system, out_T, out_inliers, out_status, out_ok);
 }
 
 int gloc_reg_fpfh_match(gloc_reg* h, const float* src_feat, size_t n_src, const float* tgt_feat, size_t n_tgt, uint32_t mutual,

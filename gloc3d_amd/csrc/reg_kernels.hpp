@@ -17,6 +17,7 @@
 
 #include "math3.hpp"          // f32x4, xform, dist2, jacobi_eig3, cross3, mulhi_idx, NN_FAR
 #include "lane_ops.hpp"
+#include "ransac_sample.hpp"  // the keyed 3-point sample
 #include "scan_index.hpp"     // ScanIndexDev, CH, SB
 #include "synth_kernels.hpp"  // mix64 / rng_key / rng_draw
 
@@ -380,14 +381,8 @@ __global__ void ransac_hyp_kernel(const f32x4* __restrict__ pairs, size_t ld,
   const uint32_t n = jobs[cand].n_src;
   if (n < 3) return;
   const uint32_t* __restrict__ inv = jobs[cand].src_inv;
-  const uint64_t key = synth::rng_key(seed, ((uint64_t)jobs[cand].cand_id << 32) | (uint64_t)h);
-  uint64_t ctr = 0;
-  uint32_t s0 = mulhi_idx(synth::rng_draw(key, ctr++), n), s1 = s0, s2 = s0;
-  for (int tries = 0; tries < 16 && s1 == s0; ++tries) s1 = mulhi_idx(synth::rng_draw(key, ctr++), n);
-  for (int tries = 0; tries < 16 && (s2 == s0 || s2 == s1); ++tries)
-    s2 = mulhi_idx(synth::rng_draw(key, ctr++), n);
-  if (s0 == s1 || s0 == s2 || s1 == s2) return;
-  const uint32_t sidx[3] = {s0, s1, s2};
+  uint32_t sidx[3];
+  if (!ransac_sample(seed, jobs[cand].cand_id, h, n, sidx)) return;
   double p[3][3], q[3][3];
   for (int k = 0; k < 3; ++k) {
     const uint32_t slot = inv ? inv[sidx[k]] : sidx[k];

@@ -1027,6 +1027,78 @@ int gloc_reg_fpfh_graph_batch_ids_keypoints(gloc_reg* h, uint32_t src_scan_id, c
                                             const gloc_iss_params* iss, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs,
                                             int* out_ok);
 
+/* ---- Fast Global Registration on the FPFH matches -------------------------------------------------------------- *
+ * A third way from F3's match list to a pose, beside F4 and G1 - G4: Fast Global Registration (Zhou, Park, Koltun, ECCV
+ * 2016; pcl and Open3D carry it beside their RANSAC routes).  A tuple test thins the matches, then ONE graduated-non-convexity
+ * optimisation runs over the fixed correspondences with the Geman-McClure line process, its scale mu annealed from the
+ * clouds' extent down to the match distance.  No hypotheses are drawn or scored and no neighbour is searched for behind
+ * the matcher.  The executable contract is tests/fgr_ref.py.
+ *
+ * The list is F4's: the kept pairs in ascending source index, M long; P_i the source point, Q_i the target point, fp32.
+ * R1  Tuple test (tuple_tries > 0).  For h = 0 .. tuple_tries - 1, (a, b, c) is F4's sample of (seed, stream id, h) over
+ *     [0, M); a sample with two equal members is skipped.  For the edges (a, b), (b, c), (c, a), in fp64 from the fp32
+ *     inputs: lp = sqrt((dx dx + dy dy) + dz dz) over P, lq likewise over Q.  The tuple passes iff every edge has
+ *     s lp < lq and s lq < lp, s = tuple_scale widened to fp64: a non-finite coordinate or a zero-length edge fails
+ *     without a special case.  The kept tuples are the first max_tuples passing ones in ascending h; mult_i is the number
+ *     of times pair i occurs in them, n_tuples their count.  tuple_tries = 0: mult_i = 1 for every pair with six finite
+ *     coordinates, else 0, and n_tuples = 0.
+ * R2  Scale.  A = {i : mult_i > 0}, in ascending position.  c_P = sum mult_i P_i / sum mult_i over A in fp64, c_Q
+ *     likewise; D^2 = max over A of max(|P_i - c_P|^2, |Q_i - c_Q|^2) (0 for an empty A); delta = max_corr_dist widened to
+ *     fp64; mu_0 = max(D^2, delta^2).  Going into update k > 0 with k mod anneal_every = 0: mu <- max(mu / anneal_div,
+ *     delta^2), one fp64 division per step, applied in sequence.
+ * R3  Updates k = 0 .. max_iters - 1 from the identity, all fp64.  For i in A: x = R p_i + t, r = x - q_i,
+ *     s2 = (r_x^2 + r_y^2) + r_z^2, l_i = the Geman-McClure weight of the robust block at (s2, mu_k), that is
+ *     1 / (1 + s2 / mu_k)^2; J_i = [-[x]x | I], rotation first; H = sum mult_i l_i J^T J, g = sum mult_i l_i J^T r.  The
+ *     solve is the Gauss-Newton refinements': degenerate with fewer than 3 members in A or a Cholesky pivot at or below
+ *     1e-12 of the largest diagonal entry, else xi = -H^-1 g and T <- exp(xi) T by the same Rodrigues form.  A degenerate
+ *     update leaves the pose of the update before it, sets status 2 and ends the loop; otherwise all max_iters updates run
+ *     and status is 0.  There is no stop test.
+ * R4  Verdict.  The pose is rounded to fp32; its inliers are counted over all M pairs as F4 counts them (fp32, un-fused,
+ *     < inlier_thresh^2); there is no refit.  ok iff status = 0 and inliers >= max(3, ceil(min_inlier_ratio M)), the
+ *     product in fp64.  M < 3, a test with no kept tuple, and any other degenerate first update: the identity, status 2,
+ *     ok = 0, 0 inliers.  For M < 3 nothing is looked at: every mult_i is 0 whatever tuple_tries is, D^2 and the system are 0. */
+typedef struct gloc_fgr_params {
+  uint32_t normal_k, feature_k, mutual;  /* as gloc_fpfh_params: 10, 16, 1 */
+  uint32_t tuple_tries;    /* default 10000; 0: no tuple test; <= 2^20 */
+  uint32_t max_tuples;     /* default 1000; 1 .. 2^20 */
+  float tuple_scale;       /* default 0.9; (0, 1] */
+  uint32_t max_iters;      /* default 64; 1 .. 1024 */
+  uint32_t anneal_every;   /* default 4; >= 1 */
+  float anneal_div;        /* default 1.4; > 1, finite */
+  float max_corr_dist;     /* default 0.6 m; > 0, finite */
+  float inlier_thresh;     /* default 0.6 m; > 0 */
+  float min_inlier_ratio;  /* default 0 */
+  uint64_t seed;           /* default 1234; offset 48 */
+} gloc_fgr_params;         /* 56 bytes */
+
+void gloc_fgr_default_params(gloc_fgr_params* p);
+
+/* Locate scan src_scan_id in each of the n targets (F3, then R1 - R4), shaped like gloc_reg_fpfh_batch_ids: out_T [n][16]
+ * source -> target, out_inliers, out_n_pairs (M), out_ok (each may be NULL but out_T); stream_ids: the sample stream of
+ * each job (NULL: 0 .. n - 1).  Job c equals its single call with stream_ids[c] bit for bit; the result does not depend
+ * on whether a scan carries a target index.  The parameter block is checked before the handle.  GLOC_ERR_INVALID: null
+ * arguments, an unknown id, n outside [1, 4096], a parameter outside its range (the message names the field);
+ * GLOC_ERR_STATE: a batch in flight on the handle. */
+int gloc_reg_fpfh_fgr_batch_ids(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
+                                const gloc_fgr_params* prm, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok);
+/* ... with features of a radius support, and on the keypoints of `iss` alone (support == NULL there: the k-mode features
+ * of prm): as the graph stage's two entries, argument for argument, plus stream_ids. */
+int gloc_reg_fpfh_fgr_batch_ids_radius(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n, const uint32_t* stream_ids,
+                                       const gloc_fgr_params* prm, const gloc_fpfh_radius_params* support, float* out_T,
+                                       uint32_t* out_inliers, uint32_t* out_n_pairs, int* out_ok);
+int gloc_reg_fpfh_fgr_batch_ids_keypoints(gloc_reg* h, uint32_t src_scan_id, const uint32_t* tgt_scan_ids, size_t n,
+                                          const uint32_t* stream_ids, const gloc_fgr_params* prm, const gloc_fpfh_radius_params* support,
+                                          const gloc_iss_params* iss, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs,
+                                          int* out_ok);
+
+/* R1 - R4 on a host pair list (a building block and diagnostic): P, Q [m][3].  Every output but out_T may be NULL:
+ * out_mult [m], out_n_tuples, out_d2 (D^2), out_system [27] (H's upper triangle, row-major, 21, then g, 6, of the last
+ * update that was formed; zeros for m < 3), out_T [16], out_inliers, out_status (0 or 2), out_ok.  normal_k, feature_k
+ * and mutual are checked and not used. */
+int gloc_reg_fgr_pairs(gloc_reg* h, const float* P, const float* Q, size_t m, uint32_t stream_id, const gloc_fgr_params* prm,
+                       uint32_t* out_mult, uint32_t* out_n_tuples, double* out_d2, double* out_system, float* out_T,
+                       uint32_t* out_inliers, int* out_status, int* out_ok);
+
 /* ============================ NetVLAD-FC pooling head ("next" row N2) ===================== *
  * Replaces NetVLAD.forward of the reference (model/netvlad_fc.py:73-109, built without gating at
  * main.py:594) -- the tail of the TorchScript module RpyPCLoopDetector::get_place_feature runs

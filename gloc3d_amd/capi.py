@@ -110,6 +110,10 @@ class FgrParams(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class EvalParams(C.Structure):
+    _fields_ = [("max_corr_dist", C.c_float), ("reserved_", C.c_uint32)]
+
+
 class FpfhRadiusParams(C.Structure):
     _fields_ = [("normal_radius", C.c_float), ("normal_max_nn", C.c_uint32), ("normal_min_nn", C.c_uint32),
                 ("feature_radius", C.c_float), ("feature_max_nn", C.c_uint32), ("reserved_", C.c_uint32)]
@@ -333,6 +337,11 @@ _PROTOS = [
     ("gloc_reg_fpfh_fgr_batch_ids_keypoints", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FgrParams), C.POINTER(FpfhRadiusParams),
                                                C.POINTER(IssParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_fgr_pairs", _i, [_vp, _vp, _vp, _sz, _u32, C.POINTER(FgrParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_p2l_pairs_system", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(P2lParams), C.POINTER(RobustParams), _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_gicp_pairs_system", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(GicpParams), C.POINTER(RobustParams), _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_vgicp_pairs_system", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(VgicpParams), C.POINTER(RobustParams), _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_eval_default_params", None, [C.POINTER(EvalParams)]),
+    ("gloc_reg_evaluate_pairs", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(EvalParams), _vp, _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_derivatives", _i, [_vp, _u32, _u32, _vp, C.POINTER(NdtParams), _vp, _vp, _vp]),
     ("gloc_reg_ndt_cells", _i, [_vp, _u32, C.POINTER(NdtParams), _sz, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
@@ -824,6 +833,15 @@ def default_fgr_params(**over):
     and inlier threshold, seed 1234), then `over`."""
     p = FgrParams()
     lib().gloc_fgr_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
+def default_eval_params(**over):
+    """gloc_eval_params as gloc_eval_default_params leaves them (0.6 m correspondence distance), then `over`."""
+    p = EvalParams()
+    lib().gloc_eval_default_params(C.byref(p))
     for k_, v in over.items():
         setattr(p, k_, v)
     return p
@@ -1408,11 +1426,8 @@ class Registrar(_Handle):
 
     def _pairs(self, fn, prm, src_ids, tgt_ids, init_T, robust):
         """A pair-list entry (gloc_reg_<m>_pairs): row c is (src_ids[c], tgt_ids[c]); None in tgt_ids is "no target"."""
-        src = np.ascontiguousarray(np.atleast_1d(src_ids), np.uint32)
-        tgt = np.ascontiguousarray([NO_SCAN if t is None else t for t in np.atleast_1d(np.asarray(tgt_ids, dtype=object))], np.uint32)
+        src, tgt = self._pair_ids(src_ids, tgt_ids)
         n = src.shape[0]
-        if tgt.shape[0] != n:
-            raise ValueError("src_ids and tgt_ids differ in length")
         it = None if init_T is None else np.ascontiguousarray(init_T, np.float32).reshape(n, 16)
         T = np.empty((n, 4, 4), np.float32)
         rmse, iters, status = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty(n, np.int32)
@@ -1434,6 +1449,70 @@ class Registrar(_Handle):
     def vgicp_pairs(self, src_ids, tgt_ids, init_T=None, params=None, robust=None):
         """Voxelized generalized ICP of a list of (source, target) pairs in one call (gloc_reg_vgicp_pairs): as p2l_pairs."""
         return self._pairs(lib().gloc_reg_vgicp_pairs, params or default_vgicp_params(), src_ids, tgt_ids, init_T, robust)
+
+    @staticmethod
+    def _pair_ids(src_ids, tgt_ids):
+        """The id arrays of a pair list: None in tgt_ids is "no target"."""
+        src = np.ascontiguousarray(np.atleast_1d(src_ids), np.uint32)
+        tgt = np.ascontiguousarray([NO_SCAN if t is None else t for t in np.atleast_1d(np.asarray(tgt_ids, dtype=object))], np.uint32)
+        if tgt.shape[0] != src.shape[0]:
+            raise ValueError("src_ids and tgt_ids differ in length")
+        return src, tgt
+
+    def _pairs_system(self, fn, prm, src_ids, tgt_ids, T, robust, robust_pass):
+        """The system form of a pair list (gloc_reg_<m>_pairs_system): row c is <m>_system(src_ids[c], tgt_ids[c], T[c]) bit
+        for bit.  Returns H [n, 6, 6], g [n, 6], sum [n], count [n] uint64, and with a robust block the weights' sums [n]."""
+        src, tgt = self._pair_ids(src_ids, tgt_ids)
+        n = src.shape[0]
+        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(n, 16)
+        H, g, s, c = np.empty((n, 6, 6), np.float64), np.empty((n, 6), np.float64), np.empty(n, np.float64), np.empty(n, np.uint64)
+        ws = None if robust is None else np.empty(n, np.float64)
+        check(fn(self._h, _np_ptr(src), _np_ptr(tgt), n, None if t is None else _np_ptr(t), C.byref(prm),
+                 None if robust is None else C.byref(robust), int(robust_pass), _np_ptr(H), _np_ptr(g), _np_ptr(s), _np_ptr(c),
+                 None if ws is None else _np_ptr(ws)))
+        return (H, g, s, c) if robust is None else (H, g, s, c, ws)
+
+    def p2l_pairs_system(self, src_ids, tgt_ids, T=None, params=None, robust=None, robust_pass=0):
+        """The point-to-plane normal equations of a list of (source, target, pose) rows in one call
+        (gloc_reg_p2l_pairs_system): what p2l_system returns, stacked.  None in tgt_ids: no target (a zero row)."""
+        return self._pairs_system(lib().gloc_reg_p2l_pairs_system, params or default_p2l_params(), src_ids, tgt_ids, T, robust, robust_pass)
+
+    def gicp_pairs_system(self, src_ids, tgt_ids, T=None, params=None, robust=None, robust_pass=0):
+        """The generalized ICP normal equations of a list of rows in one call (gloc_reg_gicp_pairs_system): as p2l_pairs_system."""
+        return self._pairs_system(lib().gloc_reg_gicp_pairs_system, params or default_gicp_params(), src_ids, tgt_ids, T, robust, robust_pass)
+
+    def vgicp_pairs_system(self, src_ids, tgt_ids, T=None, params=None, robust=None, robust_pass=0):
+        """The voxelized generalized ICP normal equations of a list of rows in one call (gloc_reg_vgicp_pairs_system): as
+        p2l_pairs_system."""
+        return self._pairs_system(lib().gloc_reg_vgicp_pairs_system, params or default_vgicp_params(), src_ids, tgt_ids, T, robust, robust_pass)
+
+    def evaluate_pairs(self, src_ids, tgt_ids, T=None, params=None, symmetric=False):
+        """The point-to-point evaluation of a list of (source, target, pose) rows in one call (gloc_reg_evaluate_pairs):
+        dict(fitness [n] float32 = counted pairs / source points, rmse [n] float32 over the counted pairs, count [n] uint32,
+        info [n, 6, 6] float64 = sum J^T J with J = [-[p]x, I], g [n, 6] = sum J^T e).  A pair counts within
+        params.max_corr_dist (0.6 m).  None in tgt_ids: no target (a zero row).
+        symmetric: the reversed rows (tgt, src, T^-1 -- inverted in float64, rounded to fp32) are evaluated in the same call;
+        adds fitness_rev, rmse_rev, count_rev and overlap = min(fitness, fitness_rev).  Every target then has to be a scan."""
+        prm = params or default_eval_params()
+        src, tgt = self._pair_ids(src_ids, tgt_ids)
+        n = src.shape[0]
+        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(n, 16)
+        if symmetric:
+            if (tgt == NO_SCAN).any():
+                raise ValueError("symmetric evaluation needs a target in every row")
+            if t is not None:
+                inv = np.linalg.inv(t.reshape(n, 4, 4).astype(np.float64)).astype(np.float32).reshape(n, 16)
+                t = np.ascontiguousarray(np.concatenate([t, inv]))
+            src, tgt = np.concatenate([src, tgt]), np.concatenate([tgt, src])
+        m = src.shape[0]
+        fit, rmse, cnt = np.empty(m, np.float32), np.empty(m, np.float32), np.empty(m, np.uint32)
+        info, g = np.empty((m, 6, 6), np.float64), np.empty((m, 6), np.float64)
+        check(lib().gloc_reg_evaluate_pairs(self._h, _np_ptr(src), _np_ptr(tgt), m, None if t is None else _np_ptr(t), C.byref(prm),
+                                            _np_ptr(fit), _np_ptr(rmse), _np_ptr(cnt), _np_ptr(info), _np_ptr(g)))
+        out = dict(fitness=fit[:n], rmse=rmse[:n], count=cnt[:n], info=info[:n], g=g[:n])
+        if symmetric:
+            out.update(fitness_rev=fit[n:], rmse_rev=rmse[n:], count_rev=cnt[n:], overlap=np.minimum(fit[:n], fit[n:]))
+        return out
 
     def vgicp_system(self, src_id, tgt_id, T=None, params=None, robust=None, robust_pass=0):
         """One evaluation of the voxelized generalized ICP normal equations at T: H [6, 6], g [6], the weighted sum of

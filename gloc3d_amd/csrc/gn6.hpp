@@ -53,7 +53,8 @@ struct Loop {  // what the refinements' parameter blocks have in common
   const char *accum_name, *solve_name;  // in the handle's profile
 };
 
-// Refines every job of `call` from its init_T, or with call.system evaluates job 0 ONCE at it.  `tgts` [x.n_jobs]: the
+// Refines every job of `call` from its init_T, or with call.system evaluates every job ONCE at it (the single-pair entries
+// have one).  `tgts` [x.n_jobs]: the
 // jobs' targets as the accumulate kernel takes them, copied to the device beside the table of the jobs' sources
 // (gn6::Source, made here from x.srcs: every job's work-group count and its first row of the partials); accum(targets and
 // sources on the device, states, gate^2, skip_stopped, partials, the grid's width -- the largest work-group count --, the
@@ -156,20 +157,25 @@ int run(const p2l::Ctx& x, const Loop& lp, const Target* tgts, const Call& call,
     return GLOC_OK;
   };
   if (call.system) {
+    // (a single-pair entry: n = 1; a list: every job evaluated by the one pass, the sums of all of them in one copy)
     GLOC_TRY(pass(1, w.exp.template as<double>()));
-    double s[NSUM];
-    GLOC_HIP(hipMemcpyAsync(s, w.exp.p, sizeof(double) * NSUM, hipMemcpyDeviceToHost, q));
-    GLOC_HIP(hipMemcpyAsync(hs.data(), w.states.p, sizeof(State), hipMemcpyDeviceToHost, q));
+    std::vector<double> sums((size_t)NSUM * n);
+    GLOC_HIP(hipMemcpyAsync(sums.data(), w.exp.p, sizeof(double) * NSUM * n, hipMemcpyDeviceToHost, q));
+    GLOC_HIP(hipMemcpyAsync(hs.data(), w.states.p, sizeof(State) * n, hipMemcpyDeviceToHost, q));
     GLOC_HIP(hipStreamSynchronize(q));
-    if (call.out_H36) {
-      int e = 0;
-      for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b, ++e) call.out_H36[6 * a + b] = call.out_H36[6 * b + a] = s[e];
+    for (uint32_t c = 0; c < n; ++c) {
+      const double* s = sums.data() + (size_t)NSUM * c;
+      if (call.out_H36) {
+        double* H = call.out_H36 + 36 * (size_t)c;
+        int e = 0;
+        for (int a = 0; a < 6; ++a)
+          for (int b = a; b < 6; ++b, ++e) H[6 * a + b] = H[6 * b + a] = s[e];
+      }
+      if (call.out_g6) std::copy(s + 21, s + 27, call.out_g6 + 6 * (size_t)c);
+      if (call.out_sum) call.out_sum[c] = s[27];
+      if (call.out_count) call.out_count[c] = (uint64_t)s[28];
+      if (call.out_wsum) call.out_wsum[c] = weighted ? hs[c].wsum : s[28];  // (kind NONE: every pair's weight is 1)
     }
-    if (call.out_g6) std::copy(s + 21, s + 27, call.out_g6);
-    if (call.out_sum) *call.out_sum = s[27];
-    if (call.out_count) *call.out_count = (uint64_t)s[28];
-    if (call.out_wsum) *call.out_wsum = weighted ? hs[0].wsum : s[28];  // (kind NONE: every pair's weight is 1)
     return GLOC_OK;
   }
   const bool can_converge = lp.trans_eps > 0.f && lp.rot_eps > 0.f;

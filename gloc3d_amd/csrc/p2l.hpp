@@ -28,7 +28,8 @@ struct Call {
   size_t n = 0;
   const float* init_T = nullptr;
   // false: every job is refined and the batch outputs [n] are written (out_T is asked for, the others may be null);
-  // true: ONE evaluation at init_T of job 0 into the system outputs (all asked for; out_wsum by a robust entry)
+  // true: ONE evaluation of every job at its init_T into the system outputs, [n] rows each (all asked for; out_wsum by a
+  // robust entry): n = 1 from the single-pair entries, a list with `pairs`
   bool system = false;
   float *out_T = nullptr, *out_rmse = nullptr;
   uint32_t* out_iters = nullptr;
@@ -77,7 +78,7 @@ struct Ctx {
 };
 
 int check_params(const gloc_p2l_params* prm);
-// Refines every job of c, or evaluates job 0 once (c.system); tgts [x.n_jobs]: the jobs' targets as the search indexes
+// Refines every job of c, or evaluates every job once (c.system); tgts [x.n_jobs]: the jobs' targets as the search indexes
 // them.  Returns after the results have been copied out.
 int run(const Ctx& x, const gn6::Target* tgts, const gn6::Call& c, const gloc_p2l_params* prm);
 

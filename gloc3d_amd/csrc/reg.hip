@@ -9,6 +9,7 @@
 
 #include "common.hpp"
 
+#include "eval.hpp"
 #include "fgr.hpp"
 #include "fpfh.hpp"
 #include "ndt.hpp"
@@ -915,6 +916,13 @@ int run_gicp(gloc_reg* h, const gloc::gn6::Call& call, const gloc_gicp_params* p
                     [&](const gloc::p2l::Ctx& x, const gloc::gn6::Target* tv) { return gloc::gicp::run(x, tv, call, prm); });
 }
 
+// The point-to-point evaluation of a pair list (eval.hip): run_refine's batch without any scan's normals (normal_k 0), the
+// ONE cold pass the system form of the loop makes, and the rows' figures from its sums.
+int run_eval(gloc_reg* h, const gloc::gn6::Call& call, const gloc_eval_params* prm, const gloc::eval::Out& out) {
+  return run_refine(h, call, 0, false,
+                    [&](const gloc::p2l::Ctx& x, const gloc::gn6::Target* tv) { return gloc::eval::run(x, tv, call.init_T, prm, out); });
+}
+
 // FPFH feature-based global registration (fpfh.hip): the descriptor matches of the source against every target, forward and
 // -- mutual -- backward in ONE launch, compacted per job into the pairs layout, and enqueue_ransac on them from the
 // identity.  The Job of such a batch carries what the RANSAC kernels read: the pair count as n_src (written on the device
@@ -1296,6 +1304,18 @@ gloc::gn6::Call system_call(const uint32_t* src_id, const uint32_t* tgt_id, cons
   return c;
 }
 
+// The system form over a pair list: every row evaluated once at init_T + 16 c.  robust null: the plain step.
+gloc::gn6::Call pairs_system_call(const uint32_t* src_ids, const uint32_t* tgt_ids, size_t n, const float* T, const gloc_robust_params* robust,
+                                  uint32_t pass, double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count, double* out_wsum) {
+  gloc::gn6::Call c = system_call(src_ids, tgt_ids, T, out_H36, out_g6, out_sum, out_count);
+  c.pairs = true;
+  c.n = n;
+  c.robust = robust;
+  c.pass = pass;
+  c.out_wsum = out_wsum;
+  return c;
+}
+
 gloc::gn6::Call robust_call(gloc::gn6::Call c, const gloc_robust_params* robust, uint32_t pass, float* out_weight, double* out_wsum) {
   c.robust = robust;
   c.need_robust = true;
@@ -1314,6 +1334,7 @@ int refine_entry(gloc_reg* h, const gloc::gn6::Call& c, const Params* prm, int (
   GLOC_TRY(check(prm));
   if (c.robust || c.need_robust) GLOC_TRY(gloc::robust::check_params(c.robust));
   if (c.system) {
+    GLOC_REQUIRE(!c.pairs || (c.src_ids && c.tgt_ids), GLOC_ERR_INVALID, "null scan ids");
     GLOC_REQUIRE(c.out_H36 && c.out_g6 && c.out_sum && c.out_count && (c.out_wsum || !c.need_robust), GLOC_ERR_INVALID, "null argument");
   } else if (c.pairs) {
     GLOC_REQUIRE(c.src_ids && c.tgt_ids, GLOC_ERR_INVALID, "null scan ids");
@@ -2020,6 +2041,50 @@ int gloc_reg_vgicp_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32
   c.robust = robust;
   c.out_weight = robust ? out_weight : nullptr;
   return refine_entry(h, c, prm, gloc::vgicp::check_params, run_vgicp);
+}
+
+// The system form of the pair lists: row c is the single-pair _system (robust NULL) or _system_robust entry's result.
+int gloc_reg_p2l_pairs_system(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* T,
+                              const gloc_p2l_params* prm, const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6,
+                              double* out_sum, uint64_t* out_count, double* out_wsum) {
+  return refine_entry(h, pairs_system_call(src_scan_ids, tgt_scan_ids, n, T, robust, pass, out_H36, out_g6, out_sum, out_count, out_wsum), prm,
+                      gloc::p2l::check_params, run_p2l);
+}
+
+int gloc_reg_gicp_pairs_system(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* T,
+                               const gloc_gicp_params* prm, const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6,
+                               double* out_sum, uint64_t* out_count, double* out_wsum) {
+  return refine_entry(h, pairs_system_call(src_scan_ids, tgt_scan_ids, n, T, robust, pass, out_H36, out_g6, out_sum, out_count, out_wsum), prm,
+                      gloc::gicp::check_params, run_gicp);
+}
+
+int gloc_reg_vgicp_pairs_system(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* T,
+                                const gloc_vgicp_params* prm, const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6,
+                                double* out_sum, uint64_t* out_count, double* out_wsum) {
+  return refine_entry(h, pairs_system_call(src_scan_ids, tgt_scan_ids, n, T, robust, pass, out_H36, out_g6, out_sum, out_count, out_wsum), prm,
+                      gloc::vgicp::check_params, run_vgicp);
+}
+
+// The point-to-point evaluation of a pair list (include/gloc3d.h: V1 - V6).  The block, the arrays and n, the handle, a
+// batch in flight -- the order of refine_entry.
+int gloc_reg_evaluate_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* T,
+                            const gloc_eval_params* prm, float* out_fitness, float* out_rmse, uint32_t* out_count, double* out_info36,
+                            double* out_g6) {
+  GLOC_TRY(gloc::eval::check_params(prm));
+  GLOC_REQUIRE(src_scan_ids && tgt_scan_ids, GLOC_ERR_INVALID, "null scan ids");
+  GLOC_REQUIRE(out_fitness || out_rmse || out_count || out_info36 || out_g6, GLOC_ERR_INVALID, "every output is null");
+  GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  gloc::gn6::Call c;
+  c.src_ids = src_scan_ids;
+  c.pairs = true;
+  c.tgt_ids = tgt_scan_ids;
+  c.n = n;
+  c.init_T = T;
+  c.system = true;
+  return run_eval(h, c, prm, gloc::eval::Out{out_fitness, out_rmse, out_count, out_info36, out_g6});
 }
 
 int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params* prm, size_t capacity, int32_t* out_key3,

@@ -225,6 +225,7 @@ constexpr uint32_t NO_SCAN = 0xFFFFFFFFu;  // "no target" in a pair list
 // before anything is enqueued (a pair list: store_check_pairs), every distinct source and then every distinct target
 // pinned for as long as this lives, targets -- and with src_normals sources -- without normals given them from normal_k
 // neighbours, and every job's source as the accumulate kernels take it.  cs: the sources' launch order (0: nothing searches).
+// normal_k 0: a call that reads no normals (the point-to-point evaluation, eval.hip) -- none is built, none is asked for.
 struct CallScans {
   ScopedPins pins;                         // .scans: the distinct sources, then the distinct targets
   size_t n_srcs = 0;
@@ -250,7 +251,7 @@ struct CallScans {
     ids.insert(ids.end(), uniq.begin(), uniq.end());
     // (an unknown source id without src_normals: refused by pin())
     const size_t first = src_normals ? 0 : n_srcs;
-    GLOC_TRY(store_ensure_normals(st, ids.data() + first, ids.size() - first, normal_k));
+    if (normal_k) GLOC_TRY(store_ensure_normals(st, ids.data() + first, ids.size() - first, normal_k));
     std::vector<int> css(ids.size(), 0);
     std::fill(css.begin(), css.begin() + n_srcs, cs);
     GLOC_TRY(pins.pin(ids.data(), css.data(), ids.size()));
@@ -258,7 +259,7 @@ struct CallScans {
     for (size_t u = 0; u < scans.size(); ++u) {
       const DevScan& s = scans[u];
       if (u < n_srcs) GLOC_REQUIRE(s.n >= 1 && s.n < (1ull << 31), GLOC_ERR_INVALID, "the source scan is empty or too large");
-      const bool read = u < n_srcs ? src_normals : s.n > 0;  // are its normals read (an empty target has none)
+      const bool read = normal_k && (u < n_srcs ? src_normals : s.n > 0);  // are its normals read (an empty target has none)
       GLOC_REQUIRE(!read || s.nrm, GLOC_ERR_STATE, "scan %u lost its normals during the call", ids[u]);
     }
     srcs.resize(c.n);

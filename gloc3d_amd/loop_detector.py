@@ -200,6 +200,19 @@ class RpyPCLoopDetector:
         r = capi.reg_select_first_ok(res["ok"].astype(np.int32))
         return r, (res["T"][r] if r >= 0 else np.eye(4, dtype=np.float32)), res
 
+    def evaluate(self, q_scan, db_indices, T, max_corr_dist=None):
+        """The point-to-point evaluation of the query scan against the places db_indices at the poses T [n, 4, 4]
+        (query -> db, from whichever registration made them): Registrar.evaluate_pairs' dict -- fitness, rmse, count,
+        info [n, 6, 6], g.  max_corr_dist: the distance within which a pair counts (None: the default, 0.6 m).  It reports
+        figures and accepts nothing."""
+        ids = [self._target_id(int(i)) for i in db_indices]
+        prm = capi.default_eval_params() if max_corr_dist is None else capi.default_eval_params(max_corr_dist=float(max_corr_dist))
+        qid = self._reg.scan_upload(np.ascontiguousarray(q_scan, np.float32))
+        try:
+            return self._reg.evaluate_pairs([qid] * len(ids), ids, T=T, params=prm)
+        finally:
+            self._reg.scan_release(qid)
+
 
 def recognition_recalls(queried_idx, gt_pos, k_values=(1, 5, 10, 20)):
     """recall@N with the reference's first-hit semantics (global_localization.cpp:221-268,

@@ -784,6 +784,70 @@ int gloc_reg_vgicp_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32
                          const gloc_vgicp_params* prm, const gloc_robust_params* robust /* NULL: the plain step */, float* out_T,
                          float* out_rmse, uint32_t* out_iters, int* out_status, float* out_weight);
 
+/* The system form of a pair list: steps 1 - 6 (1 - 4 for point-to-plane) ONCE per row at T + 16 c (T NULL: the identity),
+ * every row in the one launch sequence -- one cold 1-NN pass (none for the voxelized form), one accumulate launch, one
+ * read-back of all n rows.  Outputs per row: H (6 x 6 row-major, symmetric), g, the squared-residual sum, the number of
+ * pairs and, where out_wsum is not NULL, the sum of the weights (the count with robust NULL).
+ * Row c equals BIT FOR BIT the single-pair call on (src_scan_ids[c], tgt_scan_ids[c], T + 16 c): gloc_reg_<m>_system with
+ * robust NULL, gloc_reg_<m>_system_robust with the same `pass` otherwise (pass is ignored with robust NULL).  A row whose
+ * target is UINT32_MAX is the row of an empty target scan: all zeros.  Normals built on demand, one voxel map per distinct
+ * target, the limit on n and the refusals are those of gloc_reg_<m>_pairs, with out_H36, out_g6, out_sum and out_count in
+ * the place of out_T: none of them may be NULL. */
+int gloc_reg_p2l_pairs_system(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* T,
+                              const gloc_p2l_params* prm, const gloc_robust_params* robust /* NULL: plain */, uint32_t pass,
+                              double* out_H36 /* [n][36] */, double* out_g6 /* [n][6] */, double* out_sum /* [n] */,
+                              uint64_t* out_count /* [n] */, double* out_wsum /* [n], may be NULL */);
+int gloc_reg_gicp_pairs_system(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* T,
+                               const gloc_gicp_params* prm, const gloc_robust_params* robust /* NULL: plain */, uint32_t pass,
+                               double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count, double* out_wsum);
+int gloc_reg_vgicp_pairs_system(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n, const float* T,
+                                const gloc_vgicp_params* prm, const gloc_robust_params* robust /* NULL: plain */, uint32_t pass,
+                                double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count, double* out_wsum);
+
+/* ---- evaluation of registered pairs: overlap, RMSE and the 6 x 6 information matrix ---------------------- *
+ * Every way of bringing a scan into a place's frame reports a quality figure of its own -- an RMS nearest-neighbour
+ * distance, a plane residual, a Mahalanobis residual, an inlier count over descriptor matches -- and none compares two
+ * poses of the same pair that came from two methods.  This entry evaluates a LIST of (source, target, pose) rows with the
+ * method-independent point-to-point figures (Open3D's evaluate_registration and GetInformationMatrixFromPointClouds, PCL's
+ * getFitnessScore, small_gicp's H): what a pose-graph back end needs per edge -- an overlap figure to keep or drop it, an
+ * information matrix to weight it.  It reports numbers and decides nothing: no `ok`, no gate.  The executable contract is
+ * the float64 restatement tests/eval_ref.py; parity with Open3D is unpinned (V4).
+ *
+ * Row c is (src_scan_ids[c], tgt_scan_ids[c]) at T + 16 c (row-major, source -> target; T NULL: the identity).  One row:
+ *   V1. every source point s: p = R s + t in fp32 (the pose as given, the ICP's operation order: step 1 of the refinements);
+ *   V2. j = the exact 1-NN of p in the target, d2 the search's fp32 squared distance (the ICP's search: same bits, same tie
+ *       rule as every other entry);
+ *   V3. the pair counts iff d2 is finite and d2 <= max_corr_dist x max_corr_dist, the product formed in fp32;
+ *   V4. in fp64 from the fp32 values: e = p - q_j and, for T <- exp(xi) T with xi = (w, v), rotation first, J = [-[p]x , I]
+ *       (generalized ICP's step 6):  info += J^T J, g += J^T e, sum += (ex ex + ey ey) + ez ez, count += 1.  Open3D builds J
+ *       from the TARGET point q_j instead; at a registered pose the two differ by the residual;
+ *   V5. fitness = (float)((double)count / (double)n_src), n_src the source scan's point count, rows with non-finite
+ *       coordinates included (they are in no pair); rmse = (float)sqrt(sum / count), 0 when count = 0; info is symmetric,
+ *       filled from its upper triangle as gloc_reg_<m>_system fills H;
+ *   V6. independence and row equality as for gloc_reg_<m>_pairs: a job is cut into work-groups of 256 consecutive source
+ *       slots and its partial sums are added in index order, so a row's bits do not depend on the list, on its position
+ *       there or on whether the target carries a target index.  tgt_scan_ids[c] == UINT32_MAX or an empty target: count 0,
+ *       fitness 0, rmse 0, info and g all zero.  A scan against itself is legal.
+ * The reverse direction (target -> source, for a symmetric overlap) is another row: (tgt, src, T^-1).
+ * Cost: ONE cold pass of the registration's exact 1-NN search over all rows, one accumulate launch, one read-back.
+ *
+ * The parameter block is checked before the handle.  GLOC_ERR_INVALID, before any device work and with the outputs
+ * untouched: a null prm; max_corr_dist <= 0, NaN or infinite; null id arrays; all five outputs NULL (any four may be);
+ * n outside [1, 4096]; an id the store does not know; a source that is empty or too large.  GLOC_ERR_STATE: a batch in
+ * flight on the handle.  The call is synchronous and the scans are pinned for it. */
+typedef struct gloc_eval_params {
+  float max_corr_dist; /* 0.6 m = 3 x 0.2 m (registration/loop_detector.cpp:257, the library's inlier_thresh); must be > 0
+                          and finite */
+  uint32_t reserved_;
+} gloc_eval_params;    /* 8 bytes */
+
+void gloc_eval_default_params(gloc_eval_params* p);
+
+int gloc_reg_evaluate_pairs(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* tgt_scan_ids, size_t n,
+                            const float* T /* [n][16] source -> target, NULL: identity */, const gloc_eval_params* prm,
+                            float* out_fitness, float* out_rmse, uint32_t* out_count,
+                            double* out_info36 /* [n][36] row-major, symmetric */, double* out_g6 /* [n][6] */);
+
 /* ---- FPFH feature-based global registration ------------------------------------------------------------- *
  * The 3-D answer to "where is this scan, from nothing": local shape descriptors (Fast Point Feature Histograms: Rusu,
  * Blodow & Beetz; pcl::FPFHEstimation in its k-nearest form), descriptor matching, and the RANSAC stage of

@@ -84,6 +84,15 @@ class VgicpParams(C.Structure):
                 ("min_points", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class VmapParams(C.Structure):
+    _fields_ = [("resolution", C.c_float), ("capacity", C.c_uint32), ("normal_k", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class VmapInfo(C.Structure):
+    _fields_ = [("n_voxels", C.c_uint32), ("capacity", C.c_uint32), ("n_inserts", C.c_uint32), ("resolution", C.c_float),
+                ("n_points", C.c_uint64)]
+
+
 class RobustParams(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("scale", C.c_float), ("scale_start", C.c_float), ("anneal", C.c_float)]
 
@@ -340,6 +349,15 @@ _PROTOS = [
     ("gloc_reg_p2l_pairs_system", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(P2lParams), C.POINTER(RobustParams), _u32, _vp, _vp, _vp, _vp, _vp]),
     ("gloc_reg_gicp_pairs_system", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(GicpParams), C.POINTER(RobustParams), _u32, _vp, _vp, _vp, _vp, _vp]),
     ("gloc_reg_vgicp_pairs_system", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(VgicpParams), C.POINTER(RobustParams), _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_vmap_default_params", None, [C.POINTER(VmapParams)]),
+    ("gloc_reg_vmap_create", _i, [_vp, C.POINTER(VmapParams), C.POINTER(_u32)]),
+    ("gloc_reg_vmap_destroy", _i, [_vp, _u32]),
+    ("gloc_reg_vmap_insert", _i, [_vp, _u32, _vp, _sz, _vp]),
+    ("gloc_reg_vmap_prune", _i, [_vp, _u32, _vp, C.c_float, _u32, C.POINTER(_u32)]),
+    ("gloc_reg_vmap_info", _i, [_vp, _u32, C.POINTER(VmapInfo)]),
+    ("gloc_reg_vmap_voxels", _i, [_vp, _u32, _sz, _vp, _vp, _vp, _vp, _vp, C.POINTER(_sz)]),
+    ("gloc_reg_vgicp_vmap", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(VgicpParams), C.POINTER(RobustParams), _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_reg_vgicp_vmap_system", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(VgicpParams), C.POINTER(RobustParams), _u32, _vp, _vp, _vp, _vp, _vp]),
     ("gloc_eval_default_params", None, [C.POINTER(EvalParams)]),
     ("gloc_reg_evaluate_pairs", _i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(EvalParams), _vp, _vp, _vp, _vp, _vp]),
     ("gloc_reg_ndt_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(NdtParams), _vp, _vp, _vp, _vp]),
@@ -779,6 +797,15 @@ def default_vgicp_params(**over):
     one point and more), then `over`."""
     p = VgicpParams()
     lib().gloc_vgicp_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
+def default_vmap_params(**over):
+    """gloc_vmap_params as gloc_vmap_default_params leaves them (1 m voxels, 2^18 of them, normal_k 10), then `over`."""
+    p = VmapParams()
+    lib().gloc_vmap_default_params(C.byref(p))
     for k_, v in over.items():
         setattr(p, k_, v)
     return p
@@ -1533,6 +1560,62 @@ class Registrar(_Handle):
             check(lib().gloc_reg_vgicp_voxels(self._h, int(scan_id), C.byref(prm), k, _np_ptr(key), _np_ptr(cnt), _np_ptr(mean),
                                               _np_ptr(nn6), C.byref(m)))
         return dict(key3=key, count=cnt, mean=mean, nn6=nn6)
+
+    # ---- resident voxel maps (include/gloc3d.h: M1 - M8) ----
+    def vmap_create(self, params=None):
+        """A resident voxel map owned by this handle (gloc_reg_vmap_create): its id."""
+        prm = params or default_vmap_params()
+        mid = C.c_uint32()
+        check(lib().gloc_reg_vmap_create(self._h, C.byref(prm), C.byref(mid)))
+        return mid.value
+
+    def vmap_destroy(self, map_id):
+        check(lib().gloc_reg_vmap_destroy(self._h, int(map_id)))
+
+    def vmap_insert(self, map_id, scan_ids, T=None):
+        """Merges the scans into the map in order, scan i under T[i] (scan -> map, [n, 4, 4]); T None: as they are
+        (gloc_reg_vmap_insert).  GlocError with code 3 (GLOC_ERR_NOMEM) at the first scan that does not fit."""
+        ids = np.ascontiguousarray(np.atleast_1d(scan_ids), np.uint32)
+        n = ids.shape[0]
+        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(n, 16)
+        check(lib().gloc_reg_vmap_insert(self._h, int(map_id), _np_ptr(ids), n, None if t is None else _np_ptr(t)))
+
+    def vmap_prune(self, map_id, center=None, max_dist=0.0, max_age=0):
+        """Removes the voxels farther than max_dist from center (None: rule off) or older than max_age inserts (0: off)
+        (gloc_reg_vmap_prune): how many went."""
+        c = None if center is None else np.ascontiguousarray(center, np.float32).reshape(3)
+        removed = C.c_uint32()
+        check(lib().gloc_reg_vmap_prune(self._h, int(map_id), None if c is None else _np_ptr(c), float(max_dist), int(max_age),
+                                        C.byref(removed)))
+        return removed.value
+
+    def vmap_info(self, map_id):
+        """dict(n_voxels, capacity, n_inserts, resolution, n_points) (gloc_reg_vmap_info)."""
+        o = VmapInfo()
+        check(lib().gloc_reg_vmap_info(self._h, int(map_id), C.byref(o)))
+        return dict(n_voxels=o.n_voxels, capacity=o.capacity, n_inserts=o.n_inserts, resolution=o.resolution, n_points=o.n_points)
+
+    def vmap_voxels(self, map_id):
+        """The map's voxels, sorted by key: vgicp_voxels' dict and stamp [m] uint32, the insert that last touched each."""
+        m = C.c_size_t()
+        check(lib().gloc_reg_vmap_voxels(self._h, int(map_id), 0, None, None, None, None, None, C.byref(m)))
+        k = m.value
+        key, cnt, stamp = np.empty((k, 3), np.int32), np.empty(k, np.uint32), np.empty(k, np.uint32)
+        mean, nn6 = np.empty((k, 3), np.float64), np.empty((k, 6), np.float64)
+        if k:
+            check(lib().gloc_reg_vmap_voxels(self._h, int(map_id), k, _np_ptr(key), _np_ptr(cnt), _np_ptr(mean), _np_ptr(nn6),
+                                             _np_ptr(stamp), C.byref(m)))
+        return dict(key3=key, count=cnt, mean=mean, nn6=nn6, stamp=stamp)
+
+    def vgicp_vmap(self, src_ids, map_ids, init_T=None, params=None, robust=None):
+        """Voxelized generalized ICP of a list of (source scan, resident map) rows in one call (gloc_reg_vgicp_vmap): what
+        vgicp_pairs returns.  None in map_ids: no target.  params.resolution must be the maps', params.min_points 1."""
+        return self._pairs(lib().gloc_reg_vgicp_vmap, params or default_vgicp_params(), src_ids, map_ids, init_T, robust)
+
+    def vgicp_vmap_system(self, src_ids, map_ids, T=None, params=None, robust=None, robust_pass=0):
+        """The normal equations of a list of (source scan, resident map, pose) rows (gloc_reg_vgicp_vmap_system): what
+        vgicp_pairs_system returns."""
+        return self._pairs_system(lib().gloc_reg_vgicp_vmap_system, params or default_vgicp_params(), src_ids, map_ids, T, robust, robust_pass)
 
     def ndt_derivatives(self, src_id, tgt_id, p6, params=None):
         """score, gradient [6], Hessian [6, 6] of the filtered source against the target's cells at p6."""

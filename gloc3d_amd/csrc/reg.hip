@@ -21,6 +21,7 @@
 #include "robust.hpp"
 #include "scan_store.hpp"
 #include "vgicp.hpp"
+#include "vmap.hpp"
 
 using namespace gloc;
 using namespace gloc::reg;
@@ -94,6 +95,7 @@ struct gloc_reg : Handle {
   gloc::ndt::Ws* ndt = nullptr;  // NDT workspace (ndt.hip), made on first use
   gloc::p2l::Ws* p2l = nullptr;  // point-to-plane / generalized ICP workspace (gn6.hpp), made on first use
   gloc::vgicp::Ws* vgicp = nullptr;  // voxelized generalized ICP's voxel maps (vgicp.hip), made on first use
+  gloc::vmap::Set* vmaps = nullptr;  // the resident voxel maps this handle owns (vmap.hip): they go with it
   gloc::fpfh::Ws* fpfh = nullptr;    // the feature matcher's keys and tables (fpfh.hip), made on first use
   gloc::pairgraph::Ws* pgraph = nullptr;  // the correspondence graph's bit matrices and seed rows (pairgraph.hip), made on first use
   size_t pgraph_budget = 0;          // bytes of them in flight at a time (GLOC_REG_OPT_PAIRGRAPH_BUDGET; 0: pairgraph::BUDGET_BYTES)
@@ -105,6 +107,7 @@ struct gloc_reg : Handle {
     gloc::ndt::ws_free(ndt);
     gloc::p2l::ws_free(p2l);
     gloc::vgicp::ws_free(vgicp);
+    gloc::vmap::set_free(vmaps);
     gloc::fpfh::ws_free(fpfh);
     gloc::pairgraph::ws_free(pgraph);
     gloc::fgr::ws_free(fgr);
@@ -1272,6 +1275,22 @@ gloc::vgicp::Ctx vgicp_ctx(gloc_reg* h) { return gloc::vgicp::Ctx{h->store, h->s
 // targets' voxel maps and runs the shared loop of passes on the handle's stream.
 int run_vgicp(gloc_reg* h, const gloc::gn6::Call& call, const gloc_vgicp_params* prm) { return gloc::vgicp::run(vgicp_ctx(h), call, prm); }
 
+// ... and against the handle's resident voxel maps (vmap.hip): call.tgt_ids are map ids, no map is built.
+gloc::vmap::Ctx vmap_ctx(gloc_reg* h) { return gloc::vmap::Ctx{h->store, h->stream, &h->prof, &h->vmaps}; }
+int run_vgicp_vmap(gloc_reg* h, const gloc::gn6::Call& call, const gloc_vgicp_params* prm) {
+  return gloc::vmap::refine(vmap_ctx(h), vgicp_ctx(h), call, prm);
+}
+
+// What the map entries that are no refinement start with: the handle, a batch in flight, the map's id -- before any
+// device work.
+int vmap_entry(gloc_reg* h, uint32_t map_id) {
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_TRY(gloc::vmap::check_id(vmap_ctx(h), map_id));
+  GLOC_HIP(hipSetDevice(h->device));
+  return GLOC_OK;
+}
+
 // The two shapes of a Gauss-Newton refinement call (gn6::Call, p2l.hpp) as the C entries fill them; an entry with a robust
 // block sets the robust half behind it.
 gloc::gn6::Call batch_call(const uint32_t* src_ids, bool pairs, const uint32_t* tgt_ids, size_t n, const float* init_T, float* out_T,
@@ -2094,6 +2113,64 @@ int gloc_reg_vgicp_voxels(gloc_reg* h, uint32_t scan_id, const gloc_vgicp_params
   GLOC_NOT_PENDING(h);
   GLOC_HIP(hipSetDevice(h->device));
   return gloc::vgicp::voxels(vgicp_ctx(h), scan_id, prm, capacity, out_key3, out_count, out_mean3, out_nn6, n_voxels);
+}
+
+// Resident voxel maps (include/gloc3d.h: M1 - M8; vmap.hip).  The parameters and the arguments, the handle, a batch in
+// flight, the map's id -- the order of refine_entry -- and all of it before any device work.
+int gloc_reg_vmap_create(gloc_reg* h, const gloc_vmap_params* prm, uint32_t* out_map_id) {
+  GLOC_TRY(gloc::vmap::check_params(prm));
+  GLOC_REQUIRE(h && out_map_id, GLOC_ERR_INVALID, "null argument");
+  GLOC_NOT_PENDING(h);
+  GLOC_HIP(hipSetDevice(h->device));
+  return gloc::vmap::create(vmap_ctx(h), prm, out_map_id);
+}
+
+int gloc_reg_vmap_destroy(gloc_reg* h, uint32_t map_id) {
+  GLOC_TRY(vmap_entry(h, map_id));
+  return gloc::vmap::destroy(vmap_ctx(h), map_id);
+}
+
+int gloc_reg_vmap_insert(gloc_reg* h, uint32_t map_id, const uint32_t* scan_ids, size_t n, const float* T) {
+  GLOC_REQUIRE(scan_ids, GLOC_ERR_INVALID, "null scan ids");
+  GLOC_REQUIRE(n >= 1 && n <= 4096, GLOC_ERR_INVALID, "n = %zu outside [1, 4096]", n);
+  GLOC_TRY(vmap_entry(h, map_id));
+  return gloc::vmap::insert(vmap_ctx(h), map_id, scan_ids, n, T);
+}
+
+int gloc_reg_vmap_prune(gloc_reg* h, uint32_t map_id, const float* center3, float max_dist, uint32_t max_age, uint32_t* out_removed) {
+  GLOC_REQUIRE(!center3 || (max_dist >= 0.f && max_dist <= 3.0e38f), GLOC_ERR_INVALID, "max_dist = %g must be >= 0 and finite", (double)max_dist);
+  GLOC_TRY(vmap_entry(h, map_id));
+  return gloc::vmap::prune(vmap_ctx(h), map_id, center3, max_dist, max_age, out_removed);
+}
+
+int gloc_reg_vmap_info(gloc_reg* h, uint32_t map_id, gloc_vmap_info* out) {
+  GLOC_REQUIRE(out, GLOC_ERR_INVALID, "null argument");
+  GLOC_TRY(vmap_entry(h, map_id));
+  return gloc::vmap::info(vmap_ctx(h), map_id, out);
+}
+
+int gloc_reg_vmap_voxels(gloc_reg* h, uint32_t map_id, size_t capacity, int32_t* out_key3, uint32_t* out_count, double* out_mean3,
+                         double* out_nn6, uint32_t* out_stamp, size_t* n_voxels) {
+  GLOC_REQUIRE(n_voxels, GLOC_ERR_INVALID, "null argument");
+  GLOC_TRY(vmap_entry(h, map_id));
+  return gloc::vmap::voxels(vmap_ctx(h), map_id, capacity, out_key3, out_count, out_mean3, out_nn6, out_stamp, n_voxels);
+}
+
+// The pair-list entries with maps for targets: row c is (src_scan_ids[c], map_ids[c]).
+int gloc_reg_vgicp_vmap(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* map_ids, size_t n, const float* init_T,
+                        const gloc_vgicp_params* prm, const gloc_robust_params* robust, float* out_T, float* out_rmse, uint32_t* out_iters,
+                        int* out_status, float* out_weight) {
+  gloc::gn6::Call c = batch_call(src_scan_ids, true, map_ids, n, init_T, out_T, out_rmse, out_iters, out_status);
+  c.robust = robust;
+  c.out_weight = robust ? out_weight : nullptr;
+  return refine_entry(h, c, prm, gloc::vgicp::check_params, run_vgicp_vmap);
+}
+
+int gloc_reg_vgicp_vmap_system(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* map_ids, size_t n, const float* T,
+                               const gloc_vgicp_params* prm, const gloc_robust_params* robust, uint32_t pass, double* out_H36, double* out_g6,
+                               double* out_sum, uint64_t* out_count, double* out_wsum) {
+  return refine_entry(h, pairs_system_call(src_scan_ids, map_ids, n, T, robust, pass, out_H36, out_g6, out_sum, out_count, out_wsum), prm,
+                      gloc::vgicp::check_params, run_vgicp_vmap);
 }
 
 // (the parameters are looked at before the handle, as generalized ICP's are)

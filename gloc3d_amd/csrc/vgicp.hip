@@ -7,6 +7,9 @@
 // segmented sort, flag scan, one thread per voxel, open-addressing hash tables -- and then runs gn6.hpp's loop of passes
 // WITHOUT a search: a pass is the accumulate kernel, which probes the tables, and the shared solve kernel.  Nothing of
 // the 1-NN search's batch (job table, corr, d2, launch order) is set up, and a target needs no target index.
+//
+// run() also takes its targets as views into resident voxel maps (vmap.hip), which outlive the call: then it builds nothing
+// and resolves the sources alone; the poses, the loop and the kernels are the same.
 #include <algorithm>
 #include <vector>
 
@@ -58,12 +61,16 @@ int check_params(const gloc_vgicp_params* p) {
   return GLOC_OK;
 }
 
-int run(const Ctx& x, const gn6::Call& c, const gloc_vgicp_params* prm) {
+int run(const Ctx& x, const gn6::Call& c, const gloc_vgicp_params* prm, const Target* resident) {
   const hipStream_t q = x.stream;
   const size_t n = c.n;
-  // every distinct source, then every distinct target -- one voxel map each; no launch order: nothing here searches
+  // every distinct source, then every distinct target -- one voxel map each; no launch order: nothing here searches.
+  // Against resident maps the call's targets are no scans: the sources alone are resolved, as those of rows without a target
   reg::CallScans rs(x.store, q);
-  GLOC_TRY(rs.resolve(c, prm->normal_k, true, 0));
+  const std::vector<uint32_t> no_scans(resident ? n : 0, reg::NO_SCAN);
+  gn6::Call cs = c;
+  if (resident) cs.tgt_ids = no_scans.data();
+  GLOC_TRY(rs.resolve(cs, prm->normal_k, true, 0));
   GLOC_TRY(ensure_ws(x.ws));
   Ws& w = **x.ws;
   voxmap::Maps tm;
@@ -86,6 +93,10 @@ int run(const Ctx& x, const gn6::Call& c, const gloc_vgicp_params* prm) {
     if (t != reg::NO_SCAN)
       ht[j] = Target{reinterpret_cast<const unsigned long long*>(w.map.hkey.p) + tm.toff[t], w.map.hval.as<uint32_t>() + tm.toff[t],
                      w.map.cells.as<Voxel>(), tm.tmask[t], 0u};
+    if (resident && resident[j].hkey) {  // (resolved as a row without a target: its source is summed after all)
+      ht[j] = resident[j];
+      rs.srcs[j].n = (uint32_t)rs.src(j).n;
+    }
   }
   GLOC_TRY(w.pose.ensure(sizeof(float) * 12 * n, q));
   GLOC_HIP(hipMemcpyAsync(w.pose.p, pose.data(), sizeof(float) * 12 * n, hipMemcpyHostToDevice, q));

@@ -804,6 +804,83 @@ int gloc_reg_vgicp_pairs_system(gloc_reg* h, const uint32_t* src_scan_ids, const
                                 const gloc_vgicp_params* prm, const gloc_robust_params* robust /* NULL: plain */, uint32_t pass,
                                 double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count, double* out_wsum);
 
+/* ---- resident voxel maps: insert scans, prune, voxelized generalized ICP against them ---------------------- *
+ * The voxelized refinement above builds the voxels of its targets in every call.  A resident map is those voxel
+ * statistics -- count, mean, mean normal outer product -- as a target that lives across calls: it is owned by a
+ * registration handle, scans of the handle's store are merged into it under poses, voxels leave it by distance and age,
+ * and gloc_reg_vgicp_vmap refines against it without building anything (small_gicp's IncrementalVoxelMap, fast_gicp's
+ * voxel maps and KISS-ICP's local map are maps of this kind).  Scan-to-map tracking after a global fix and LiDAR odometry
+ * are its use; a submap (gloc_scan_store_add_submap) is a different object, a scan of one point per voxel.
+ *   M1. A map has a resolution (fp32, > 0), a capacity in voxels (1 .. 2^24) and normal_k.  Its frame is whatever frame
+ *       the caller's poses map into.  There is no min_points: every voxel with at least one point is a voxel.  Everything
+ *       is allocated at creation and never moves: the voxel array [capacity], beside it per voxel the running sums (3 + 6
+ *       doubles) and a stamp, and ONE open-addressing table of the smallest power of two >= 2 x capacity slots (at least
+ *       16).  The table is never more than half full, so every probe ends at an empty slot; there are no tombstones:
+ *       removal rebuilds the table (M5).
+ *   M2. Insert of scan s under pose T (scan -> map, 16 fp32 row-major).  The scan's normals are built first with normal_k,
+ *       by the rule of gloc_scan_store_build_normals, if it has none.  With T given every point, in upload order, is moved
+ *       as p = R s + t in fp32 in the refinements' operation order (step 3 of the voxelized refinement), and m = R n is
+ *       formed in fp64 from the fp32 values as ((R0 n0 + R1 n1) + R2 n2), the accumulate kernel's expression.  With T NULL
+ *       point and normal are taken as they are, without arithmetic.  The voxel of p is found by step 2 (floorf(p * inv),
+ *       |k| < 2^20); a non-finite or out-of-range p is in no voxel.
+ *   M3. Per voxel the insert contributes n, s1 = sum (p - corner) and s2 = sum m m^T (six entries): fp64 sums in upload
+ *       order, corner = k x resolution -- the sums of step 2.  A voxel new to the map takes the contribution as it is; a
+ *       voxel already there gets N += n, S1 += s1, S2 += s2, one fp64 add per component per insert, in insert order.  Then
+ *       mean = corner + S1 / N, Nbar = S2 / N, count = N, and the voxel's stamp becomes the map's insert counter after this
+ *       insert (1-based).  So after exactly one insert with T NULL into an empty map the voxels equal
+ *       gloc_reg_vgicp_voxels of that scan (same resolution, min_points 1) bit for bit.
+ *   M4. An insert that would take the map above its capacity is refused with GLOC_ERR_NOMEM and the map is left exactly as
+ *       it was: the new keys are counted against the table before anything is written.  gloc_reg_vmap_insert takes a list
+ *       and is its single inserts in order: the first scan that does not fit is refused, the ones before it stay.
+ *   M5. Prune removes a voxel if a rule is set and holds -- distance, center3 not NULL: |mean - c|^2 > max_dist^2 in fp64
+ *       from the widened fp32 values; age, max_age > 0: n_inserts - stamp > max_age.  The survivors' values and stamps are
+ *       untouched; the voxel array is compacted and the table rebuilt from them.  Pruning to empty is legal.
+ *   M6. Export: the voxels sorted by (kx, ky, kz), as gloc_reg_vgicp_voxels lists them, and their stamps.  The count is
+ *       returned even where the buffers are too small (GLOC_ERR_INVALID then), as by that entry.
+ *   M7. gloc_reg_vgicp_vmap and _system are steps 3 - 10 of the voxelized refinement with the map's voxels in place of
+ *       step 2's, through the same accumulate and solve kernels, robust as in gloc_reg_vgicp_pairs[_system].
+ *       prm->resolution must equal the map's bit for bit and prm->min_points must be 1 (GLOC_ERR_INVALID); plane_eps,
+ *       neighbors, the gate, max_iters and both eps are the call's.  Rows are equal to their single calls and independent
+ *       of each other, as the pair lists' are.  Against a map that holds exactly one scan inserted with T NULL every
+ *       output equals gloc_reg_vgicp_pairs / _pairs_system on (source, that scan) bit for bit.  A map id of 0xFFFFFFFF,
+ *       or an empty map, gives the row of an empty target.
+ *   M8. All calls are synchronous.  GLOC_ERR_STATE with a batch in flight on the handle; GLOC_ERR_INVALID, before any
+ *       device work and with the outputs untouched, for an unknown or destroyed map id, null arguments or bad parameters.
+ *       A map owes nothing to a scan once its insert has returned: the scan may be released.  Destroying the handle frees
+ *       its maps.  Ids are not reused on a handle. */
+typedef struct gloc_vmap_params {
+  float resolution;    /* 1.0 m: the voxels' edge; must be > 0 */
+  uint32_t capacity;   /* 1 << 18 voxels; 1 .. 2^24 */
+  uint32_t normal_k;   /* 10: inserted scans without normals get them built with this k; 3 .. 16 */
+  uint32_t reserved_;
+} gloc_vmap_params;    /* 16 bytes */
+
+typedef struct gloc_vmap_info {
+  uint32_t n_voxels, capacity;
+  uint32_t n_inserts;  /* scans inserted so far: what the stamps count in */
+  float resolution;
+  uint64_t n_points;   /* the sum of the voxels' counts */
+} gloc_vmap_info;      /* 24 bytes */
+
+void gloc_vmap_default_params(gloc_vmap_params* p);
+int gloc_reg_vmap_create(gloc_reg* h, const gloc_vmap_params* prm, uint32_t* out_map_id);
+int gloc_reg_vmap_destroy(gloc_reg* h, uint32_t map_id);
+/* T [n][16] or NULL: M2's "as they are".  GLOC_ERR_NOMEM: M4. */
+int gloc_reg_vmap_insert(gloc_reg* h, uint32_t map_id, const uint32_t* scan_ids, size_t n, const float* T);
+/* center3 NULL: the distance rule is off; max_age 0: the age rule is off.  out_removed may be NULL. */
+int gloc_reg_vmap_prune(gloc_reg* h, uint32_t map_id, const float* center3, float max_dist, uint32_t max_age, uint32_t* out_removed);
+int gloc_reg_vmap_info(gloc_reg* h, uint32_t map_id, gloc_vmap_info* out);
+/* M6.  n_voxels: how many there are (the arrays may be NULL to ask). */
+int gloc_reg_vmap_voxels(gloc_reg* h, uint32_t map_id, size_t capacity, int32_t* out_key3, uint32_t* out_count, double* out_mean3,
+                         double* out_nn6, uint32_t* out_stamp, size_t* n_voxels);
+/* M7: row c is (src_scan_ids[c], map_ids[c]); arguments and outputs as gloc_reg_vgicp_pairs / _pairs_system. */
+int gloc_reg_vgicp_vmap(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* map_ids, size_t n, const float* init_T,
+                        const gloc_vgicp_params* prm, const gloc_robust_params* robust /* NULL: the plain step */, float* out_T,
+                        float* out_rmse, uint32_t* out_iters, int* out_status, float* out_weight);
+int gloc_reg_vgicp_vmap_system(gloc_reg* h, const uint32_t* src_scan_ids, const uint32_t* map_ids, size_t n, const float* T,
+                               const gloc_vgicp_params* prm, const gloc_robust_params* robust /* NULL: plain */, uint32_t pass,
+                               double* out_H36, double* out_g6, double* out_sum, uint64_t* out_count, double* out_wsum);
+
 /* ---- evaluation of registered pairs: overlap, RMSE and the 6 x 6 information matrix ---------------------- *
  * Every way of bringing a scan into a place's frame reports a quality figure of its own -- an RMS nearest-neighbour
  * distance, a plane residual, a Mahalanobis residual, an inlier count over descriptor matches -- and none compares two

@@ -111,6 +111,56 @@ void Profiler::end(const char* name, hipStream_t s, const char* also) {
   if (live > 8192) (void)collect(s);
 }
 
+int Profiler::open_stamps(int device, unsigned long long* d_words, uint32_t cap) {
+  if (ms_per_tick == 0) {
+    int khz = 0;
+    GLOC_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device));
+    GLOC_REQUIRE(khz > 0, GLOC_ERR_HIP, "the device reports no wall clock rate");
+    ms_per_tick = 1.0 / (double)khz;
+  }
+  slots.clear();  // (a batch that was closed and never folded is dropped)
+  h_stamps = nullptr;
+  d_stamps = d_words;
+  stamp_cap = cap;
+  tail = nullptr;
+  stamping = true;
+  return GLOC_OK;
+}
+
+unsigned long long* Profiler::next_stamp(const char* name, const char* also) {
+  slots.push_back(Slot{name, also});
+  return slots.size() < stamp_cap ? d_stamps + (slots.size() - 1) : nullptr;  // (the last word is the closing stamp's)
+}
+
+unsigned long long* Profiler::close_stamps(const unsigned long long* h_words) {
+  stamping = false;
+  h_stamps = h_words;
+  return d_stamps + std::min<size_t>(slots.size(), stamp_cap - 1);
+}
+
+// Scope k lasted from its stamp to the next one there is (a scope that launched nothing left its word zero, and one
+// past the array has none: counted, no time of its own).
+void Profiler::fold_stamps() {
+  if (!h_stamps) return;
+  const size_t n = std::min<size_t>(slots.size(), stamp_cap - 1);
+  for (size_t k = 0; k < slots.size(); ++k) {
+    double ms = 0;
+    if (k < n && h_stamps[k]) {
+      size_t e = k + 1;
+      while (e < n && !h_stamps[e]) ++e;
+      if (h_stamps[e] > h_stamps[k]) ms = (double)(h_stamps[e] - h_stamps[k]) * ms_per_tick;
+    }
+    for (const char* name : {slots[k].name, slots[k].also}) {
+      if (!name) continue;
+      Family& f = fam[name];
+      f.total_ms += ms;
+      f.launches++;
+    }
+  }
+  slots.clear();
+  h_stamps = nullptr;
+}
+
 // The events of the open spans back into the pool, each ONCE (joined scopes and second families share events), and no
 // span open any more; the tail goes with them.
 void Profiler::release_open() {
@@ -129,6 +179,7 @@ void Profiler::release_open() {
 
 int Profiler::collect(hipStream_t s) {
   GLOC_HIP(hipStreamSynchronize(s));
+  fold_stamps();
   for (auto& kv : fam)
     for (Span& sp : kv.second.open) {
       float ms = 0.f;

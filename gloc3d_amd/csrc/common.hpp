@@ -1,5 +1,5 @@
 // common.hpp -- shared host-side plumbing for the gloc3d C ABI (error reporting, HIP checks,
-// per-kernel HIP-event profiler, device buffers).  gfx950 only; no CPU fallback anywhere.
+// per-kernel profiler on HIP events or device stamps, device buffers).  gfx950 only; no CPU fallback anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,7 +75,8 @@ struct DevBuf {
 static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value,
               "a DevBuf has one owner: two copies would free the same memory");
 
-// HIP-event profiler: brackets kernel launches of one family and sums elapsed time lazily.
+// Profiler: brackets kernel launches of one family with HIP events and sums elapsed time lazily -- or, for a batch whose
+// kernels stamp the device clock themselves, takes the times from those stamps (below).
 struct Profiler {
   bool enabled = false;
   struct Span {
@@ -93,6 +94,26 @@ struct Profiler {
   // two, between two dependent kernels.  The idle gap between the kernels then counts for the later family.
   hipEvent_t tail = nullptr;
   hipStream_t tail_s = nullptr;
+  // A device-stamped batch (the registration batch, reg.hip): no event between its kernels.  Every scope of it takes a
+  // slot of a device array of 64-bit words -- the caller's, zero when the batch starts -- and the first work-group of the
+  // scope's first kernel leaves the device's constant-rate clock there (stamp_launch, reg_kernels.hpp).  Kernels of one
+  // stream run back to back, so scope k lasted stamp(k + 1) - stamp(k): the idle time and the runtime's fills and copies
+  // behind a scope's kernels count for that scope, and the last scope ends at the stamp of a trivial kernel the caller
+  // launches behind it (close_stamps).  The caller brings the words down with the batch's results and folds them.
+  struct Slot {
+    const char *name, *also;
+  };
+  bool stamping = false;          // between open_stamps and close_stamps: ProfScope hands out slots, records nothing
+  unsigned long long* d_stamps = nullptr;
+  uint32_t stamp_cap = 0;
+  std::vector<Slot> slots;        // of the batch being enqueued, or enqueued last and not folded yet
+  double ms_per_tick = 0;         // of the device clock (hipDeviceAttributeWallClockRate)
+  int open_stamps(int device, unsigned long long* d_words, uint32_t cap);  // (the batch before has been folded)
+  unsigned long long* next_stamp(const char* name, const char* also);      // null: no slot left (the batch's owner makes that an error)
+  // the slot of the closing stamp; h_words: where the caller's copy leaves the slots' words and that one, on the host
+  unsigned long long* close_stamps(const unsigned long long* h_words);
+  void fold_stamps();  // once that copy has been waited for: the scopes into their families (no batch to fold: nothing)
+  const unsigned long long* h_stamps = nullptr;  // set: a closed batch waits to be folded
   hipEvent_t get_event();
   void begin(const char* name, hipStream_t s, bool joined = false);
   // also: a second family that counts the same span (the same two events, no record of its own)
@@ -109,11 +130,13 @@ struct ProfScope {
   const char* name;
   hipStream_t s;
   const char* also;
+  unsigned long long* stamp = nullptr;  // in a device-stamped batch: the scope's slot, for its first kernel
   ProfScope(Profiler& p_, const char* n, hipStream_t s_, Join j = Apart, const char* also_ = nullptr) : p(p_), name(n), s(s_), also(also_) {
-    if (p.enabled) p.begin(name, s, j == Joined);
+    if (p.stamping) stamp = p.next_stamp(name, also);
+    else if (p.enabled) p.begin(name, s, j == Joined);
   }
   ~ProfScope() {
-    if (p.enabled) p.end(name, s, also);
+    if (!p.stamping && p.enabled) p.end(name, s, also);
   }
 };
 

@@ -1409,7 +1409,9 @@ __device__ __forceinline__ void nn_compact_body(
     if (!valid[s]) continue;
     const size_t o = (size_t)job * ld + wave_base + s * 64 + lane;
     st_u32<CHAIN>(corr + o, bpos[s]);  // (chained: written through -- the group's next pass may run on another XCD)
-    st_f32<CHAIN>(d2out + o, best[s]);
+    // (a warm moments pass launched on its own is told when nobody reads its distances -- the moments carry their sum:
+    // d2out null, a wave-uniform test)
+    if (!(WARM && !PAIRS && !CHAIN) || d2out != nullptr) st_f32<CHAIN>(d2out + o, best[s]);
     f32x4 q = {NN_FAR, NN_FAR, NN_FAR, 0.f};  // no correspondence (empty target): never an inlier
     if (bpos[s] != 0xFFFFFFFFu) {
       q = ix.pts[bpos[s]];  // just loaded above: an L1 hit
@@ -1486,11 +1488,13 @@ __device__ __forceinline__ void nn_compact_body(
   const Job *__restrict__ jobs, uint32_t n_jobs, uint32_t job_group, uint32_t n_wg, uint32_t subs,                     \
       const CandState *__restrict__ states, const uint32_t *prev_corr, uint32_t *corr, float *__restrict__ d2out,      \
       f32x4 *__restrict__ pairs, double *__restrict__ partials, uint32_t n_part, size_t ld, float gate2, NnSplit sp,   \
-      NnHeavy hv, unsigned long long *__restrict__ stat_pairs
+      NnHeavy hv, unsigned long long *__restrict__ stat_pairs,                                                         \
+      unsigned long long *__restrict__ stamp /* a profiled batch: the launch's slot (stamp_launch), else null */
 #define NN_COMPACT_ARGS jobs, n_jobs, job_group, n_wg, subs, states, prev_corr, corr, d2out, pairs, partials, n_part, ld, gate2, sp, hv, stat_pairs
 
 template <int CS, bool PAIRS, bool SPLIT = false, bool WARM = false>
 __global__ __launch_bounds__(64 * NN_WPB) void nn_compact_kernel(NN_COMPACT_PARAMS) {
+  stamp_launch(stamp);
   nn_compact_body<CS, PAIRS, SPLIT, WARM>(NnPos{blockIdx.z, blockIdx.x, blockIdx.y}, NN_COMPACT_ARGS);
 }
 
@@ -1499,12 +1503,14 @@ __global__ __launch_bounds__(64 * NN_WPB) void nn_compact_kernel(NN_COMPACT_PARA
 // and the sixth is what covers the prologue's dependent kd loads, the seed chunks and the pair stores.
 template <bool PAIRS>
 __global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 6))) void nn_compact_cold_kernel(NN_COMPACT_PARAMS) {
+  stamp_launch(stamp);
   nn_compact_body<2, PAIRS, false, false>(NnPos{blockIdx.z, blockIdx.x, blockIdx.y}, NN_COMPACT_ARGS);
 }
 
 // The second launch of a cold pass: the groups its waves gave up, NN_HEAVY_PARTS waves each (NnHeavy).
 template <int CS, bool PAIRS>
 __global__ __launch_bounds__(64) void nn_compact_heavy_kernel(NN_COMPACT_PARAMS) {
+  (void)stamp;  // (the second launch of its scope: never stamped)
   nn_compact_body<CS, PAIRS, true, false, true>(NnPos{0u, 0u, 0u}, NN_COMPACT_ARGS);
 }
 
@@ -1513,6 +1519,7 @@ __global__ __launch_bounds__(64) void nn_compact_heavy_kernel(NN_COMPACT_PARAMS)
 // kernel fits by itself.
 template <int CS>
 __global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 6))) void nn_compact_split_warm_kernel(NN_COMPACT_PARAMS) {
+  stamp_launch(stamp);
   nn_compact_body<CS, false, true, true>(NnPos{blockIdx.z, blockIdx.x, blockIdx.y}, NN_COMPACT_ARGS);
 }
 
@@ -1523,6 +1530,7 @@ __global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 
 template <int CS>
 __global__ __launch_bounds__(64 * NN_WPB) __attribute__((amdgpu_waves_per_eu(6, 6))) void nn_chain_kernel(NN_COMPACT_PARAMS, NnChain ch) {
   static_assert(NN_WPB == 1, "a work-group is a wave: the roles and the arrival counts are per wave");
+  (void)stamp;  // (a profiled batch is never chained)
   const uint32_t b = blockIdx.x;
   const uint32_t pass = b / ch.pass_size, r1 = b - pass * ch.pass_size;
   const uint32_t grp = r1 / ch.grp_size, r2 = r1 - grp * ch.grp_size;

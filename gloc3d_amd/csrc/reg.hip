@@ -33,7 +33,7 @@ struct gloc_reg : Handle {
   gloc_scan_store* own_store = nullptr;
   DevBuf jobs, states;           // Job[], CandState[]
   DevBuf corr, d2, pairs;        // [job][ld]
-  DevBuf Rt, valid, inliers;     // RANSAC hypotheses
+  DevBuf Rt, valid;              // RANSAC hypotheses; valid: [job][hyp] valid, [job][hyp] inliers behind it (one fill clears both)
   DevBuf alive;                  // all-hypotheses RANSAC: [job][H] list of the hypotheses still in the race + [job] counts
   DevBuf partials;               // [job][n_part][ACC_NV] fp64
   DevBuf export_idx, export_d2;  // gloc_reg_nn: results in the caller's index space
@@ -42,7 +42,7 @@ struct gloc_reg : Handle {
   // wait for the stream, i.e. for the batch BEFORE this one when handles share a stream
   void* pin = nullptr;
   size_t pin_cap = 0;
-  CandState* h_states = nullptr;  // [n_jobs], inside pin
+  CandState* h_states = nullptr;  // [n_jobs], inside pin; a profiled batch's stamps behind them (up and down with the states)
   Job* h_jobs = nullptr;          // [n_jobs], inside pin
   // a batch between gloc_reg_batch_multi_begin and _end
   struct Pending {
@@ -280,14 +280,16 @@ struct NnArgs {
   uint32_t jg, n_wg, subs;  // the launch order (launch_order)
   float gate2;
   unsigned long long* stat_pairs;  // profiling only, else null
+  unsigned long long* stamp;       // a profiled batch: the slot of the scope this launch opens (ProfScope), else null
+  bool keep_d2 = true;             // false: a warm moments pass whose distances nobody reads leaves d2 as it is
 };
 
 // One launch of an instance of the culled search; `chain`: the chained launch's NnChain.
 template <auto KERNEL, typename... Chain>
 void launch_compact(const NnArgs& a, dim3 grid, const uint32_t* prev_corr, bool pairs, NnHeavy hv, Chain... chain) {
   hipLaunchKernelGGL(KERNEL, grid, dim3(64 * NN_WPB), 0, a.v.s, a.v.jobs, a.v.n_jobs, a.jg, a.n_wg, a.subs, a.v.states, prev_corr,
-                     a.v.corr, a.v.d2, a.v.pairs, pairs ? (double*)nullptr : a.v.partials, a.bd.n_part, a.bd.ld, a.gate2, a.v.split, hv,
-                     a.stat_pairs, chain...);
+                     a.v.corr, a.keep_d2 ? a.v.d2 : (float*)nullptr, a.v.pairs, pairs ? (double*)nullptr : a.v.partials, a.bd.n_part, a.bd.ld, a.gate2, a.v.split, hv,
+                     a.stat_pairs, a.stamp, chain...);
 }
 
 // The instance of a pass: sources per lane x pass kind x the split plan.  The warm moments pass with the plan -- what one
@@ -314,16 +316,20 @@ void launch_kind(const NnArgs& a, dim3 grid, const uint32_t* prev_corr, NnHeavy 
 // source, matched target) pairs INSTEAD of the moments (the RANSAC stage refits from the pairs: accum_kernel<1>).  The culled search leaves the wave partials of the
 // fp64 moments in h->partials (per source group); the exhaustive one needs accum_kernel<0> afterwards.
 // join: the pass follows a profiled scope with nothing enqueued in between (a warm pass behind its solve).
-int launch_nn(gloc_reg* h, const BatchDims& bd, const WsView& v, bool warm, bool want_pairs, float gate2, ProfScope::Join join = ProfScope::Apart) {
+// keep_d2 = false: a warm moments pass of the culled search that another pass follows -- nothing reads its distances (the
+// exhaustive mode's accum_kernel<0>, gloc_reg_debug_corr and the refinements read those of the pass before them) and it
+// does not write them.
+int launch_nn(gloc_reg* h, const BatchDims& bd, const WsView& v, bool warm, bool want_pairs, float gate2, ProfScope::Join join = ProfScope::Apart,
+              bool keep_d2 = true) {
   // (the first pass of a batch -- no previous correspondence, or the pass that writes the pairs -- is another
-  // instantiation and ~1.6 x a warm pass: also counted in its own family, on the same two events, so that "nn" - "nn_cold"
+  // instantiation and ~1.6 x a warm pass: also counted in its own family, on the same span, so that "nn" - "nn_cold"
   // is the warm passes alone)
   ProfScope ps(h->prof, "nn", v.s, join, (want_pairs || !warm) ? "nn_cold" : nullptr);
   h->nn_launches++;
   if (h->nn_mode == 1) {
     dim3 grid((bd.max_src + 256 * NN_S - 1) / (256 * NN_S), v.n_jobs);
     hipLaunchKernelGGL(nn_kernel, grid, dim3(256), 0, v.s, v.jobs, v.states,
-                       v.corr, v.d2, bd.ld);
+                       v.corr, v.d2, bd.ld, ps.stamp);
     if (want_pairs)
       hipLaunchKernelGGL(gather_pairs_kernel, dim3((bd.max_src + 255) / 256, v.n_jobs), dim3(256), 0, v.s,
                          v.jobs, v.states, v.corr, bd.ld,
@@ -349,7 +355,8 @@ int launch_nn(gloc_reg* h, const BatchDims& bd, const WsView& v, bool warm, bool
                  "the culled search's grid: %u work-groups per job slot (scans above ~8 M points) or %u job groups exceed 65535", n_wg,
                  (n_slots + jg - 1) / jg);
     if (grid) {
-      const NnArgs a{v, bd, jg, n_wg, subs, gate2, h->prof.enabled ? h->counters.as<unsigned long long>() : nullptr};
+      NnArgs a{v, bd, jg, n_wg, subs, gate2, h->prof.enabled ? h->counters.as<unsigned long long>() : nullptr, ps.stamp,
+               keep_d2 || !warm || want_pairs};
       const dim3 g3(jg, n_wg, (n_slots + jg - 1) / jg);
       const uint32_t* prev_corr = warm ? v.corr : nullptr;
       if (cs == 1) launch_kind<1>(a, g3, prev_corr, hv, want_pairs, warm);
@@ -357,6 +364,7 @@ int launch_nn(gloc_reg* h, const BatchDims& bd, const WsView& v, bool warm, bool
       else launch_kind<4>(a, g3, prev_corr, hv, want_pairs, warm);
       if (hv.cap) {  // the groups the cold pass's waves gave up: NN_HEAVY_PARTS waves each (the list's length stays on the device)
         const dim3 gh(hv.cap * NN_HEAVY_PARTS);
+        a.stamp = nullptr;  // (the scope's second launch: its time is the scope's)
         if (want_pairs) launch_compact<nn_compact_heavy_kernel<2, true>>(a, gh, nullptr, true, hv);
         else launch_compact<nn_compact_heavy_kernel<2, false>>(a, gh, nullptr, false, hv);
       }
@@ -416,15 +424,16 @@ int launch_nn_chain(gloc_reg* h, const BatchDims& bd, const WsView& v, uint32_t 
   h->nn_launches += n_pass;
   h->chain_launches++;
   h->chain_in_batch = true;
-  const NnArgs a{v, bd, jg, n_wg, subs, gate2, nullptr};
+  const NnArgs a{v, bd, jg, n_wg, subs, gate2, nullptr, nullptr};
   launch_compact<nn_chain_kernel<2>>(a, dim3(ch.pass_size * n_pass), v.corr, false, NnHeavy{}, ch);
   GLOC_HIP(hipGetLastError());
   GLOC_HIP(hipMemcpyAsync(h->h_chain_err, ch.err, 4, hipMemcpyDeviceToHost, v.s));
   return GLOC_OK;
 }
 
-int ensure_pinned(gloc_reg* h, uint32_t n_jobs) {
-  const size_t need = (sizeof(CandState) + sizeof(Job)) * (size_t)n_jobs + 64;
+int ensure_pinned(gloc_reg* h, uint32_t n_jobs, uint32_t n_stamps) {
+  static_assert(sizeof(CandState) % 8 == 0 && sizeof(Job) % 4 == 0, "the stamps behind the states are 64-bit words, the jobs behind them 32-bit");
+  const size_t need = (sizeof(CandState) + sizeof(Job)) * (size_t)n_jobs + 8 * (size_t)n_stamps + 64;
   if (need > h->pin_cap) {
     if (h->pin) (void)hipHostFree(h->pin);
     h->pin = nullptr;
@@ -434,7 +443,7 @@ int ensure_pinned(gloc_reg* h, uint32_t n_jobs) {
     h->pin_cap = cap;
   }
   h->h_states = reinterpret_cast<CandState*>(h->pin);
-  h->h_jobs = reinterpret_cast<Job*>(h->h_states + n_jobs);
+  h->h_jobs = reinterpret_cast<Job*>(reinterpret_cast<unsigned long long*>(h->h_states + n_jobs) + n_stamps);
   h->h_chain_err = reinterpret_cast<uint32_t*>(h->h_jobs + n_jobs);
   return GLOC_OK;
 }
@@ -449,12 +458,13 @@ struct BatchSpec {
   bool alive;            // ... and ransac_alive_kernel's lists
   uint32_t split_hx;     // helper slots per job of the split plan (split_helpers; 0: none) ...
   uint32_t warm_passes;  // ... and the passes behind its first that could run chained (batch_chains)
+  uint32_t stamps = 0;   // a profiled registration batch: the words of its time line (Profiler::open_stamps), behind the states
   // a batch that searches (and no more: RANSAC and the split plan are added by enqueue_jobs) / a batch on pairs alone
   static BatchSpec searching(uint32_t n_jobs, size_t max_src, uint32_t max_groups) {
-    return BatchSpec{n_jobs, (uint32_t)max_src, max_groups, true, false, 0, false, 0u, 0u};
+    return BatchSpec{n_jobs, (uint32_t)max_src, max_groups, true, false, 0, false, 0u, 0u, 0u};
   }
   static BatchSpec on_pairs(uint32_t n_jobs, size_t max_src, size_t hyp, bool alive) {
-    return BatchSpec{n_jobs, (uint32_t)max_src, 0u, false, true, hyp, alive, 0u, 0u};
+    return BatchSpec{n_jobs, (uint32_t)max_src, 0u, false, true, hyp, alive, 0u, 0u, 0u};
   }
 };
 
@@ -484,15 +494,20 @@ int open_batch(gloc_reg* h, const BatchSpec& sp, Batch* out, Fill&& fill) {
   bd.n_part = (std::max<uint32_t>(std::max(bd.max_groups, b.nblocks), 1) + 31u) & ~31u;  // (a job's row of a [job][n_part] table: whole 128-byte lines)
   bd.ld = ((size_t)bd.max_src + 127) & ~(size_t)127;
   h->last_jobs = 0;
-  GLOC_TRY(ensure_pinned(h, n_jobs));
+  GLOC_TRY(ensure_pinned(h, n_jobs, sp.stamps));
+  h->prof.slots.clear();  // (a profiled batch that was never collected: its time line lay in the staging this batch takes)
+  h->prof.h_stamps = nullptr;
   h->chain_in_batch = false;
   *h->h_chain_err = 0u;
   fill(h->h_jobs, h->h_states);
+  // (the stamps start at zero: they go up with the states, in the same copy, and come down with them)
+  const size_t state_bytes = sizeof(CandState) * n_jobs + 8 * (size_t)sp.stamps;
+  if (sp.stamps) memset(h->h_states + n_jobs, 0, 8 * (size_t)sp.stamps);
   WsView& v = b.v;
   v.s = s;
   v.n_jobs = n_jobs;
   GLOC_TRY(h->jobs.ensure(sizeof(Job) * n_jobs, s));
-  GLOC_TRY(h->states.ensure(sizeof(CandState) * n_jobs, s));
+  GLOC_TRY(h->states.ensure(state_bytes, s));
   GLOC_TRY(h->partials.ensure(sizeof(double) * ACC_NV * (size_t)bd.n_part * n_jobs, s));
   v.jobs = h->jobs.as<Job>();
   v.states = h->states.as<CandState>();
@@ -510,12 +525,11 @@ int open_batch(gloc_reg* h, const BatchSpec& sp, Batch* out, Fill&& fill) {
   if (sp.pairs) {
     GLOC_TRY(h->pairs.ensure(sizeof(f32x4) * 2 * bd.ld * n_jobs, s));
     GLOC_TRY(h->Rt.ensure(sizeof(float) * 12 * sp.hyp * n_jobs, s));
-    GLOC_TRY(h->valid.ensure(sizeof(uint32_t) * sp.hyp * n_jobs, s));
-    GLOC_TRY(h->inliers.ensure(sizeof(uint32_t) * sp.hyp * n_jobs, s));
+    GLOC_TRY(h->valid.ensure(sizeof(uint32_t) * 2 * sp.hyp * n_jobs, s));
     v.pairs = h->pairs.as<f32x4>();
     v.Rt = h->Rt.as<float>();
     v.valid = h->valid.as<uint32_t>();
-    v.inliers = h->inliers.as<uint32_t>();
+    v.inliers = v.valid + sp.hyp * n_jobs;
     if (sp.alive) {
       GLOC_TRY(h->alive.ensure(sizeof(uint32_t) * (sp.hyp + 1) * n_jobs, s));
       v.a_idx = h->alive.as<uint32_t>();
@@ -523,7 +537,7 @@ int open_batch(gloc_reg* h, const BatchSpec& sp, Batch* out, Fill&& fill) {
     }
   }
   GLOC_HIP(hipMemcpyAsync(v.jobs, h->h_jobs, sizeof(Job) * n_jobs, hipMemcpyHostToDevice, s));
-  GLOC_HIP(hipMemcpyAsync(v.states, h->h_states, sizeof(CandState) * n_jobs, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(v.states, h->h_states, state_bytes, hipMemcpyHostToDevice, s));
   b.chained = batch_chains(h, bd, sp.split_hx, sp.warm_passes);
   GLOC_TRY(setup_split(h, bd, cs, sp.split_hx, b.chained));  // (no helper slots: h->split = NnSplit{})
   if (sp.search) GLOC_TRY(setup_heavy(h, bd, cs));
@@ -555,13 +569,13 @@ int enqueue_refit(gloc_reg* h, const BatchDims& bd, const WsView& v, float thr2,
   {  // (both callers come straight from their last ransac_score scope)
     ProfScope ps(h->prof, "accum", v.s, ProfScope::Joined);
     hipLaunchKernelGGL(accum_kernel<1>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, v.s, v.jobs, v.states, v.corr, v.d2, v.pairs, bd.ld, thr2,
-                       v.partials, bd.n_part);
+                       v.partials, bd.n_part, ps.stamp);
     GLOC_HIP(hipGetLastError());
   }
   {
     ProfScope ps(h->prof, "solve", v.s, ProfScope::Joined);
     hipLaunchKernelGGL(solve_kernel<1>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(v.split.hx ? SOLVE_THREADS : SOLVE_THREADS_LIGHT), 0, v.s, v.partials, bd.n_part, false, v.jobs,
-                       v.states, v.split, n_jobs);
+                       v.states, v.split, n_jobs, ps.stamp);
     GLOC_HIP(hipGetLastError());
   }
   return GLOC_OK;
@@ -584,15 +598,18 @@ int enqueue_ransac(gloc_reg* h, const BatchDims& bd, const RansacRule& r, const 
   // reference's call: confidence 0.99) and ~85 % inliers the iteration count drops to 5 - 8 at the first good
   // hypothesis, so [0, 16) settles nearly every job, [16, 64) most of the rest; a job that is done is skipped by the
   // later phases (its blocks exit at once).  The rule is sequential in h (ransac_scan_kernel), so the split does not
-  // change the result.  (Round 2 scored 64 first: 2.1 ms per step of 500 jobs, 0.6 with 16.)
+  // change the result.  (Round 2 scored 64 first: 2.1 ms per step of 500 jobs, 0.6 with 16.  A first phase of 8 takes the
+  // first score launch from 490 to 353 us, and the step nowhere: a third launch and hand-over, LAB_NOTES.md.)
   const bool adaptive = r.confidence > 0.f && r.confidence < 1.f;
   uint32_t bounds[4] = {0u, 0u, 0u, 0u};
   int n_ph = 0;
   for (uint32_t b : {adaptive ? 16u : 256u, adaptive ? 64u : H, H})
     if (b <= H && b > bounds[n_ph]) bounds[++n_ph] = b;
   if (bounds[n_ph] < H) bounds[++n_ph] = H;
-  GLOC_HIP(hipMemsetAsync(v.valid, 0, sizeof(uint32_t) * (size_t)H * n_jobs, s));  // never-generated = invalid
-  GLOC_HIP(hipMemsetAsync(v.inliers, 0, sizeof(uint32_t) * (size_t)H * n_jobs, s));
+  // never-generated = invalid, no inliers counted: one fill, the two tables lie end to end (open_batch, for both callers'
+  // batches: H hypotheses per job)
+  GLOC_REQUIRE(v.inliers == v.valid + (size_t)H * n_jobs, GLOC_ERR_STATE, "the batch was not opened for %u hypotheses per job", H);
+  GLOC_HIP(hipMemsetAsync(v.valid, 0, 2 * sizeof(uint32_t) * (size_t)H * n_jobs, s));
   const float thr2 = r.inlier_thresh * r.inlier_thresh;
   const uint32_t chunk_len = score_chunk_len(n_jobs, bd.max_src);
   const unsigned cchunks = (bd.max_src + chunk_len - 1) / chunk_len;
@@ -602,7 +619,7 @@ int enqueue_ransac(gloc_reg* h, const BatchDims& bd, const RansacRule& r, const 
     {
       ProfScope ps(h->prof, "ransac_hyp", s, ph ? ProfScope::Joined : ProfScope::Apart);  // (behind the phase before; the first behind the fills)
       hipLaunchKernelGGL(ransac_hyp_kernel, dim3((len + 127) / 128, n_jobs), dim3(128), 0, s, v.pairs, bd.ld,
-                         v.jobs, r.seed, H, h0, h1, st, v.Rt, v.valid);
+                         v.jobs, r.seed, H, h0, h1, st, v.Rt, v.valid, ps.stamp);
       GLOC_HIP(hipGetLastError());
     }
     ProfScope ps(h->prof, "ransac_score", s, ProfScope::Joined);
@@ -616,16 +633,16 @@ int enqueue_ransac(gloc_reg* h, const BatchDims& bd, const RansacRule& r, const 
       for (unsigned q = 0; q < NP; ++q) {
         const unsigned c0 = q * cchunks / NP, c1 = (q + 1) * cchunks / NP;
         hipLaunchKernelGGL(ransac_alive_kernel, dim3(n_jobs), dim3(1024), 0, s, v.inliers, v.valid,
-                           H, h0, h1, v.jobs, v.states, (uint32_t)(c0 * chunk_len), a_idx, a_cnt);
+                           H, h0, h1, v.jobs, v.states, (uint32_t)(c0 * chunk_len), a_idx, a_cnt, q ? nullptr : ps.stamp);
         hipLaunchKernelGGL(ransac_score_kernel, dim3((len + 255) / 256, c1 - c0, n_jobs), dim3(256), 0, s,
                            v.pairs, bd.ld, v.jobs, H, h0, 256u, v.Rt,
-                           v.valid, thr2, st, v.inliers, a_idx, a_cnt, (uint32_t)c0, chunk_len);
+                           v.valid, thr2, st, v.inliers, a_idx, a_cnt, (uint32_t)c0, chunk_len, (unsigned long long*)nullptr);
       }
     } else {
       hipLaunchKernelGGL(ransac_score_kernel, dim3((len + hpb - 1) / hpb, cchunks, n_jobs), dim3(256), 0, s,
                          v.pairs, bd.ld, v.jobs, H, h0, hpb, v.Rt,
                          v.valid, thr2, st, v.inliers, (const uint32_t*)nullptr,
-                         (const uint32_t*)nullptr, 0u, chunk_len);
+                         (const uint32_t*)nullptr, 0u, chunk_len, ps.stamp);
     }
     if (ph + 1 < n_ph)
       hipLaunchKernelGGL(ransac_scan_kernel<false>, dim3(n_jobs), dim3(64), 0, s, v.inliers,
@@ -662,19 +679,19 @@ int enqueue_pipeline(gloc_reg* h, const BatchDims& bd, const gloc_reg_params* pr
     }
     // (profiled scopes end to end: this pass behind the refit's or the previous pass's solve -- a batch's first launch
     // apart, behind the preamble's copies and fills -- and the solve behind its pass)
-    GLOC_TRY(launch_nn(h, bd, v, have_corr, false, gate2, have_corr ? ProfScope::Joined : ProfScope::Apart));
+    GLOC_TRY(launch_nn(h, bd, v, have_corr, false, gate2, have_corr ? ProfScope::Joined : ProfScope::Apart, it + 1 == prm->icp_iters));
     have_corr = true;
     if (!culled) {
       ProfScope ps(h->prof, "accum", s, ProfScope::Joined);
       hipLaunchKernelGGL(accum_kernel<0>, dim3(nblocks, n_jobs), dim3(ACC_THREADS), 0, s, v.jobs,
                          v.states, v.corr, v.d2,
-                         (const f32x4*)nullptr, bd.ld, gate2, v.partials, bd.n_part);
+                         (const f32x4*)nullptr, bd.ld, gate2, v.partials, bd.n_part, ps.stamp);
       GLOC_HIP(hipGetLastError());
     }
     {
       ProfScope ps(h->prof, "solve", s, ProfScope::Joined);
       hipLaunchKernelGGL(solve_kernel<0>, dim3(v.split.hx ? 2 * n_jobs : n_jobs), dim3(v.split.hx ? SOLVE_THREADS : SOLVE_THREADS_LIGHT), 0, s, v.partials,
-                         bd.n_part, culled, v.jobs, v.states, v.split, n_jobs);
+                         bd.n_part, culled, v.jobs, v.states, v.split, n_jobs, ps.stamp);
       GLOC_HIP(hipGetLastError());
     }
   }
@@ -704,6 +721,11 @@ int enqueue_jobs(gloc_reg* h, const std::vector<JobHost>& jh, const gloc_reg_par
   spec.alive = !adaptive;
   spec.split_hx = split_helpers(h, n_jobs);
   spec.warm_passes = warm_passes;
+  // Profiled: the batch's time line is stamped on the device (Profiler::open_stamps).  The scopes it can open, each a slot:
+  // per ICP pass the search and the solve -- and between them, in the exhaustive mode, accum_kernel<0>'s; RANSAC's pairs pass,
+  // its hypotheses and scores of at most three phases, the refit's accum and solve (9); and the closing stamp's word.
+  const bool stamped = h->prof.enabled;
+  if (stamped) spec.stamps = (h->nn_mode == 1 ? 3u : 2u) * prm->icp_iters + 9u + 1u;
   Batch b;
   GLOC_TRY(open_batch(h, spec, &b, [&](Job* jd, CandState* st) {
     for (uint32_t c = 0; c < n_jobs; ++c) {
@@ -714,8 +736,19 @@ int enqueue_jobs(gloc_reg* h, const std::vector<JobHost>& jh, const gloc_reg_par
     }
   }));
   hipStream_t s = h->stream;
-  GLOC_TRY(enqueue_pipeline(h, b.bd, prm, b.v, can, any_tgt, b.nblocks, b.chained));
-  GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState) * n_jobs, hipMemcpyDeviceToHost, s));
+  unsigned long long* d_stamps = reinterpret_cast<unsigned long long*>(b.v.states + n_jobs);
+  if (stamped) GLOC_TRY(h->prof.open_stamps(h->device, d_stamps, spec.stamps));
+  const int rc = enqueue_pipeline(h, b.bd, prm, b.v, can, any_tgt, b.nblocks, b.chained);
+  if (stamped) {  // (also where the pipeline failed: no scope after this takes a slot)
+    unsigned long long* last = h->prof.close_stamps(reinterpret_cast<const unsigned long long*>(h->h_states + n_jobs));
+    if (rc == GLOC_OK) hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(64), 0, s, last);
+    // (a scope without a slot would be counted with no time, and its time would go to the family of the last slot)
+    GLOC_REQUIRE(rc != GLOC_OK || h->prof.slots.size() < spec.stamps, GLOC_ERR_STATE,
+                 "the profiled batch opened %zu scopes, its time line has %u slots", h->prof.slots.size(), spec.stamps - 1u);
+  }
+  GLOC_TRY(rc);
+  GLOC_HIP(hipGetLastError());
+  GLOC_HIP(hipMemcpyAsync(h->h_states, h->states.p, sizeof(CandState) * n_jobs + 8 * (size_t)spec.stamps, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipEventRecord(h->done_ev, s));
   if (h->chain_in_batch) {  // (a small batch: a few KB)
     h->retry_jobs.resize(sizeof(JobHost) * n_jobs);
@@ -760,6 +793,7 @@ int collect_jobs(gloc_reg* h, uint32_t n_jobs, const size_t* n_src_of, float max
     }
     GLOC_HIP(hipEventSynchronize(h->done_ev));
   }
+  h->prof.fold_stamps();  // (a profiled batch: its time line came down with the states)
   for (uint32_t c = 0; c < n_jobs; ++c) {
     const CandState& st = h->h_states[c];
     const size_t n_src = n_src_of[c];
@@ -1114,7 +1148,8 @@ int enqueue_graph(gloc_reg* h, const BatchDims& bd, const gloc_fpfh_graph_params
     const uint32_t chunk_len = score_chunk_len(n_jobs, bd.max_src), hpb = score_hpb(S);
     const unsigned cchunks = (std::max<uint32_t>(m_max, 1u) + chunk_len - 1) / chunk_len;
     hipLaunchKernelGGL(ransac_score_kernel, dim3((S + hpb - 1) / hpb, cchunks, n_jobs), dim3(256), 0, s, v.pairs, bd.ld, v.jobs, S, 0u, hpb, v.Rt,
-                       v.valid, thr2, (const CandState*)nullptr, v.inliers, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, chunk_len);
+                       v.valid, thr2, (const CandState*)nullptr, v.inliers, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, chunk_len,
+                       (unsigned long long*)nullptr);
     hipLaunchKernelGGL(ransac_scan_kernel<true>, dim3(n_jobs), dim3(64), 0, s, v.inliers, v.valid, v.Rt, S, 0u, S, v.jobs, 0.f,
                        prm->min_inlier_ratio, v.states);
     GLOC_HIP(hipGetLastError());
@@ -1166,7 +1201,7 @@ int run_pair_graph(gloc_reg* h, const float* P, const float* Q, size_t m, const 
   if (out_score) GLOC_HIP(hipMemcpyAsync(out_score, w.score.p, sizeof(uint64_t) * m, hipMemcpyDeviceToHost, s));
   if (out_seeds) GLOC_HIP(hipMemcpyAsync(out_seeds, w.seeds.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, s));
   if (out_set_sizes) GLOC_HIP(hipMemcpyAsync(out_set_sizes, w.set_sizes.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, s));
-  if (out_seed_inliers) GLOC_HIP(hipMemcpyAsync(out_seed_inliers, h->inliers.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, s));
+  if (out_seed_inliers) GLOC_HIP(hipMemcpyAsync(out_seed_inliers, v.inliers, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipStreamSynchronize(s));  // (hp, too, is done with)
   const CandState& cs = h->h_states[0];
   bool found, ok;
@@ -1835,12 +1870,12 @@ int gloc_reg_ransac_hypotheses(gloc_reg* h, const float* src_xyz, const float* t
   GLOC_HIP(hipMemcpyAsync(v.pairs, hp.data(), sizeof(float) * hp.size(), hipMemcpyHostToDevice, s));
   GLOC_HIP(hipMemsetAsync(v.inliers, 0, sizeof(uint32_t) * (size_t)n_hyp, s));
   hipLaunchKernelGGL(ransac_hyp_kernel, dim3((n_hyp + 127) / 128, 1), dim3(128), 0, s, v.pairs, ld, v.jobs, seed, n_hyp, 0u, n_hyp,
-                     (const CandState*)nullptr, v.Rt, v.valid);
+                     (const CandState*)nullptr, v.Rt, v.valid, (unsigned long long*)nullptr);
   GLOC_HIP(hipGetLastError());
   dim3 grid((n_hyp + 255) / 256, (unsigned)((n + SC_CHUNK - 1) / SC_CHUNK), 1);
   hipLaunchKernelGGL(ransac_score_kernel, grid, dim3(256), 0, s, v.pairs, ld, v.jobs, n_hyp, 0u, 256u /* thread <-> hypothesis */, v.Rt,
                      v.valid, inlier_thresh * inlier_thresh, (const CandState*)nullptr, v.inliers, (const uint32_t*)nullptr,
-                     (const uint32_t*)nullptr, 0u, (uint32_t)SC_CHUNK);
+                     (const uint32_t*)nullptr, 0u, (uint32_t)SC_CHUNK, (unsigned long long*)nullptr);
   GLOC_HIP(hipGetLastError());
   GLOC_HIP(hipMemcpyAsync(out_Rt, v.Rt, sizeof(float) * 12 * (size_t)n_hyp, hipMemcpyDeviceToHost, s));
   GLOC_HIP(hipMemcpyAsync(out_valid, v.valid, sizeof(uint32_t) * (size_t)n_hyp, hipMemcpyDeviceToHost, s));

@@ -146,6 +146,20 @@ __host__ __device__ __forceinline__ uint32_t nn_parts_for(uint32_t w, uint32_t t
   return w > 4 * (unsigned long long)thresh ? 8u : (w > 2 * (unsigned long long)thresh ? 4u : 2u);
 }
 
+// A profiled batch's time line (Profiler's device stamps, common.hpp): the first work-group of a launch leaves the device's
+// constant-rate clock (s_memrealtime: 100 MHz) in the launch's slot -- one lane, one vector store.  `stamp` is null with
+// profiling off and in every launch that does not open a scope.  The test on the block is wave-uniform: scalar compares
+// and a branch that every other work-group takes, nothing in the vector pipes.
+__device__ __forceinline__ void stamp_launch(unsigned long long* stamp) {
+  if (stamp != nullptr && (blockIdx.x | blockIdx.y | blockIdx.z) == 0u) {
+    asm volatile("");  // (keeps the two tests apart: merged, every wave would pay the lane compare)
+    if (threadIdx.x == 0) *stamp = __builtin_amdgcn_s_memrealtime();
+  }
+}
+
+// The closing stamp of a profiled batch: the end of its last scope.
+__global__ void stamp_kernel(unsigned long long* stamp) { stamp_launch(stamp); }
+
 // per-candidate state, device resident
 struct CandState {
   double Td[12];      // current absolute transform (R row-major 9, t 3), fp64
@@ -171,7 +185,9 @@ constexpr int NN_TC = 256;
 __global__ __launch_bounds__(256) void nn_kernel(const Job* __restrict__ jobs,
                                                  const CandState* __restrict__ states,
                                                  uint32_t* __restrict__ corr,
-                                                 float* __restrict__ d2out, size_t ld) {
+                                                 float* __restrict__ d2out, size_t ld,
+                                                 unsigned long long* __restrict__ stamp /* profiled batches: stamp_launch */) {
+  stamp_launch(stamp);
   __shared__ f32x4 tl[2][NN_TC];
   const int tid = threadIdx.x;
   const int job = blockIdx.y;
@@ -371,7 +387,8 @@ __global__ void ransac_hyp_kernel(const f32x4* __restrict__ pairs, size_t ld,
                                   uint32_t n_hyp, uint32_t h_begin, uint32_t h_end,
                                   const CandState* __restrict__ states,
                                   float* __restrict__ Rt /* [job][n_hyp][12] */,
-                                  uint32_t* __restrict__ valid) {
+                                  uint32_t* __restrict__ valid, unsigned long long* __restrict__ stamp) {
+  stamp_launch(stamp);
   const int cand = blockIdx.y;
   const uint32_t h = h_begin + blockIdx.x * blockDim.x + threadIdx.x;
   if (h >= h_end) return;
@@ -435,7 +452,9 @@ __global__ __launch_bounds__(256) void ransac_score_kernel(const f32x4* __restri
                                                            uint32_t* __restrict__ inliers,
                                                            const uint32_t* __restrict__ alive_idx /* [cand][n_hyp] or null */,
                                                            const uint32_t* __restrict__ alive_cnt, uint32_t chunk0,
-                                                           uint32_t chunk_len /* pairs per work-group: a multiple of SC_STAGE (SC_CHUNK; less in small batches) */) {
+                                                           uint32_t chunk_len /* pairs per work-group: a multiple of SC_STAGE (SC_CHUNK; less in small batches) */,
+                                                           unsigned long long* __restrict__ stamp) {
+  stamp_launch(stamp);
   // staged pairs, two correspondences per entry, structure-of-arrays: (px0 px1 py0 py1)(pz0 pz1 qx0 qx1)(qy0 qy1 qz0 qz1)
   // so that one packed fp32 instruction moves / measures two correspondences.
   //
@@ -558,7 +577,9 @@ __global__ __launch_bounds__(1024) void ransac_alive_kernel(const uint32_t* __re
                                                             const uint32_t* __restrict__ valid, uint32_t n_hyp,
                                                             uint32_t h0, uint32_t h1, const Job* __restrict__ jobs,
                                                             const CandState* __restrict__ states, uint32_t first_pair,
-                                                            uint32_t* __restrict__ alive_idx, uint32_t* __restrict__ alive_cnt) {
+                                                            uint32_t* __restrict__ alive_idx, uint32_t* __restrict__ alive_cnt,
+                                                            unsigned long long* __restrict__ stamp) {
+  stamp_launch(stamp);
   __shared__ uint32_t wave_cnt[16], base_s;
   const int cand = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const uint32_t n = jobs[cand].n_src, best = states[cand].best_inl;
@@ -713,7 +734,8 @@ template <int MODE>
 __global__ __launch_bounds__(ACC_THREADS) void accum_kernel(
     const Job* __restrict__ jobs, const CandState* __restrict__ states, const uint32_t* __restrict__ corr,
     const float* __restrict__ d2in, const f32x4* __restrict__ pairs, size_t ld, float gate2,
-    double* __restrict__ partials /* [job][n_part][ACC_NV] */, uint32_t n_part) {
+    double* __restrict__ partials /* [job][n_part][ACC_NV] */, uint32_t n_part, unsigned long long* __restrict__ stamp) {
+  stamp_launch(stamp);
   __shared__ double red[ACC_THREADS / 64][ACC_NV];
   const int cand = blockIdx.y;
   const Job& J = jobs[cand];
@@ -950,7 +972,9 @@ template <int MODE>
 __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const double* __restrict__ partials,
                                                               uint32_t n_part, bool per_group,
                                                               const Job* __restrict__ jobs,
-                                                              CandState* __restrict__ states, NnSplit sp, uint32_t n_jobs) {
+                                                              CandState* __restrict__ states, NnSplit sp, uint32_t n_jobs,
+                                                              unsigned long long* __restrict__ stamp) {
+  stamp_launch(stamp);
   __shared__ double sub[SOLVE_R][ACC_NV];
   __shared__ double tot[ACC_NV];
   const int tid = threadIdx.x;

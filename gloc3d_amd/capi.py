@@ -133,6 +133,32 @@ class IssParams(C.Structure):
                 ("gamma_21", C.c_float), ("gamma_32", C.c_float)]
 
 
+class ClusterParams(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("min_size", C.c_uint32), ("max_size", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class ScanFilterParams(C.Structure):
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("ror_radius", C.c_float), ("ror_min_neighbors", C.c_uint32),
+                ("sor_mean_k", C.c_uint32), ("sor_std_mul", C.c_float), ("cluster", ClusterParams)]
+
+
+class ScanFilterInfo(C.Structure):
+    _fields_ = [("points_in", C.c_uint32), ("after_range", C.c_uint32), ("after_ror", C.c_uint32), ("after_sor", C.c_uint32),
+                ("after_cluster", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class Clusters:
+    """What ScanStore.cluster returns (E1 - E4 of include/gloc3d.h): root, cluster [n] uint32 in upload order (0xFFFFFFFF: a
+    non-finite point / a point of no kept cluster); size, cluster_root [n_kept] uint32, centroid [n_kept, 3] float64, lo, hi
+    [n_kept, 3] float32 in rank order; n_components, n_kept."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
 FPFH_DIM = 33          # floats per feature row
 FPFH_MATCH_TILE = 128  # target rows per tile of the matcher (csrc/fpfh.hpp MATCH_TILE_ROWS)
 
@@ -340,6 +366,11 @@ _PROTOS = [
                                            _vp, _vp, _vp, _vp]),
     ("gloc_reg_fpfh_graph_batch_ids_keypoints", _i, [_vp, _u32, _vp, _sz, C.POINTER(FpfhGraphParams), C.POINTER(FpfhRadiusParams),
                                                  C.POINTER(IssParams), _vp, _vp, _vp, _vp]),
+    ("gloc_cluster_default_params", None, [C.POINTER(ClusterParams)]),
+    ("gloc_scan_store_cluster", _i, [_vp, _u32, C.POINTER(ClusterParams), _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gloc_scan_filter_default_params", None, [C.POINTER(ScanFilterParams)]),
+    ("gloc_scan_store_add_filtered", _i, [_vp, _u32, C.POINTER(ScanFilterParams), _vp, _vp]),
+    ("gloc_scan_store_add_subset", _i, [_vp, _u32, _vp, _sz, _vp]),
     ("gloc_fgr_default_params", None, [C.POINTER(FgrParams)]),
     ("gloc_reg_fpfh_fgr_batch_ids", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FgrParams), _vp, _vp, _vp, _vp]),
     ("gloc_reg_fpfh_fgr_batch_ids_radius", _i, [_vp, _u32, _vp, _sz, _vp, C.POINTER(FgrParams), C.POINTER(FpfhRadiusParams), _vp, _vp, _vp, _vp]),
@@ -894,6 +925,28 @@ def default_iss_params(**over):
     return p
 
 
+def default_cluster_params(**over):
+    """gloc_cluster_params as gloc_cluster_default_params leaves them (tolerance 0.5 m, min_size 1, no max_size), then `over`."""
+    p = ClusterParams()
+    lib().gloc_cluster_default_params(C.byref(p))
+    for k_, v in over.items():
+        setattr(p, k_, v)
+    return p
+
+
+def default_scan_filter_params(**over):
+    """gloc_scan_filter_params as gloc_scan_filter_default_params leaves them -- every stage off --, then `over`; a key
+    cluster_<field> sets that field of the cluster block (cluster_tolerance = 0.5 switches the cluster stage on)."""
+    p = ScanFilterParams()
+    lib().gloc_scan_filter_default_params(C.byref(p))
+    for k_, v in over.items():
+        if k_.startswith("cluster_"):
+            setattr(p.cluster, k_[len("cluster_"):], v)
+        else:
+            setattr(p, k_, v)
+    return p
+
+
 class ScanStore(_Handle):
     """Resident scans + their search index, shared by any number of Registrars."""
 
@@ -1063,6 +1116,44 @@ class ScanStore(_Handle):
         """Several submaps, [(ids, T [n, 4, 4]), ...], in one batch call (gloc_scan_store_add_submaps): each equals its
         add_submap, bit for bit.  Returns the ids, with want_info (ids, [info dict])."""
         return _add_submaps(lib().gloc_scan_store_add_submaps, self._h, submaps, params, want_info)
+
+    def cluster(self, scan_id, params=None, figures=True):
+        """The Euclidean clusters of a resident scan (gloc_scan_store_cluster; default_cluster_params when None): a Clusters
+        object.  figures=False leaves out the centroids and corners (and the device work behind them)."""
+        prm = params or default_cluster_params()
+        n = self.points(scan_id)
+        root, label = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        nc, nk = C.c_uint32(), C.c_uint32()
+        # (one call: no scan has more clusters than points)
+        size, croot = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        cent, lo, hi = np.empty((n, 3), np.float64), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        f3 = [_np_ptr(cent), _np_ptr(lo), _np_ptr(hi)] if figures else [None, None, None]
+        check(lib().gloc_scan_store_cluster(self._h, int(scan_id), C.byref(prm), _np_ptr(root), _np_ptr(label), n, _np_ptr(size), _np_ptr(croot),
+                                            *f3, n, C.byref(nc), C.byref(nk)))
+        K = nk.value
+        out = Clusters(root=root, cluster=label, size=size[:K].copy(), cluster_root=croot[:K].copy(), n_components=int(nc.value), n_kept=K)
+        if figures:
+            out.centroid, out.lo, out.hi = cent[:K].copy(), lo[:K].copy(), hi[:K].copy()
+        return out
+
+    def add_filtered(self, base_id, params=None, want_info=False, **over):
+        """A new scan: what the stages of `params` (default_scan_filter_params(**over) when None) leave of scan base_id --
+        range crop, radius outlier removal, statistical outlier removal, clusters, one after the other
+        (gloc_scan_store_add_filtered).  Returns its id, with want_info (id, dict(points_in, after_range, after_ror,
+        after_sor, after_cluster))."""
+        prm = params or default_scan_filter_params(**over)
+        sid, info = C.c_uint32(), ScanFilterInfo()
+        check(lib().gloc_scan_store_add_filtered(self._h, int(base_id), C.byref(prm), C.cast(C.pointer(sid), C.c_void_p),
+                                                 C.cast(C.pointer(info), C.c_void_p)))
+        return (sid.value, info.as_dict()) if want_info else sid.value
+
+    def add_subset(self, base_id, idx):
+        """A new scan: rows idx of scan base_id in the order given, gathered on the device (gloc_scan_store_add_subset)."""
+        idx = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+        sid = C.c_uint32()
+        check(lib().gloc_scan_store_add_subset(self._h, int(base_id), _np_ptr(idx) if idx.shape[0] else None, idx.shape[0],
+                                               C.cast(C.pointer(sid), C.c_void_p)))
+        return sid.value
 
     def download(self, scan_id):
         n = self.points(scan_id)

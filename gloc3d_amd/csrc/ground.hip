@@ -103,13 +103,8 @@ int select_flagged(gloc_ground* h, uint32_t n, uint32_t* h_count) {
   hipStream_t s = h->stream;
   GLOC_TRY(h->sel.ensure(sizeof(uint32_t) * std::max<uint32_t>(n, 1), s));
   GLOC_TRY(h->count.ensure(sizeof(uint32_t), s));
-  const uint32_t n_tiles = (n + SEL_TILE - 1) / SEL_TILE;
-  GLOC_TRY(h->tile_cnt.ensure(sizeof(uint32_t) * std::max<uint32_t>(n_tiles, 1), s));
-  if (n_tiles) {
-    hipLaunchKernelGGL(flag_count_kernel, dim3(n_tiles), dim3(256), 0, s, h->flag.as<uint8_t>(), n, h->tile_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(flag_scatter_kernel, dim3(n_tiles), dim3(256), 0, s, h->flag.as<uint8_t>(), n, h->tile_cnt.as<uint32_t>(),
-                       n_tiles, h->sel.as<uint32_t>(), h->count.as<uint32_t>());
-    GLOC_HIP(hipGetLastError());
+  if (n) {
+    GLOC_TRY(gloc::ground::select_flagged(s, h->flag.as<uint8_t>(), n, h->tile_cnt, h->sel.as<uint32_t>(), h->count.as<uint32_t>()));
   } else {
     GLOC_HIP(hipMemsetAsync(h->count.p, 0, sizeof(uint32_t), s));
   }
@@ -359,6 +354,25 @@ int scan_lists(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m, 
     hipLaunchKernelGGL(knn_culled_kernel, dim3((nch + 3) / 4), dim3(256), 0, s, spts, m, w.cbox_lo.as<f32x4>(),
                        w.cbox_hi.as<f32x4>(), nch, (int)width, w.knn_idx.as<uint32_t>(), w.knn_d2.as<float>());
   }
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int select_flagged(hipStream_t s, const uint8_t* flag, uint32_t n, DevBuf& tile_cnt, uint32_t* sel, uint32_t* count) {
+  const uint32_t n_tiles = (n + SEL_TILE - 1) / SEL_TILE;
+  GLOC_TRY(tile_cnt.ensure(sizeof(uint32_t) * n_tiles, s));
+  hipLaunchKernelGGL(flag_count_kernel, dim3(n_tiles), dim3(256), 0, s, flag, n, tile_cnt.as<uint32_t>());
+  hipLaunchKernelGGL(flag_scatter_kernel, dim3(n_tiles), dim3(256), 0, s, flag, n, tile_cnt.as<uint32_t>(), n_tiles, sel, count);
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int scan_chunk_boxes(hipStream_t s, NormalsScratch& w, const f32x4* spts, uint32_t m) {
+  if (m == 0) return GLOC_OK;
+  const uint32_t nch = (m + KCH - 1) / KCH;
+  GLOC_TRY(w.cbox_lo.ensure(sizeof(f32x4) * nch, s));
+  GLOC_TRY(w.cbox_hi.ensure(sizeof(f32x4) * nch, s));
+  hipLaunchKernelGGL(kchunk_boxes_kernel, dim3(nch), dim3(64), 0, s, spts, m, w.cbox_lo.as<f32x4>(), w.cbox_hi.as<f32x4>());
   GLOC_HIP(hipGetLastError());
   return GLOC_OK;
 }

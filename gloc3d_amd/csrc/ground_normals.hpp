@@ -52,6 +52,14 @@ struct NormalsScratch {
 // and the FPFH features (fpfh.hip) both start from.  Enqueued on s; the lists take m x width x 8 bytes of w, grown on demand.
 int scan_lists(hipStream_t s, NormalsScratch& w, const reg::f32x4* spts, uint32_t m, const Support& sup);
 
+// Stable compaction of the indices whose byte flag is set (the two tiled kernels of ground_kernels.hpp): sel[0 .. *count)
+// = the i < n with flag[i] != 0, ascending; n >= 1; tile_cnt: scratch, grown on demand.  Enqueued on s.
+int select_flagged(hipStream_t s, const uint8_t* flag, uint32_t n, DevBuf& tile_cnt, uint32_t* sel, uint32_t* count);
+
+// The chunks and boxes of scan_lists alone, for a sweep that keeps no lists (cluster_kernels.hpp): w.cbox_lo / w.cbox_hi
+// of the ceil(m / LIST_CHUNK) chunks of `spts`.  Enqueued on s.
+int scan_chunk_boxes(hipStream_t s, NormalsScratch& w, const reg::f32x4* spts, uint32_t m);
+
 // Normals of the m points of `spts` from those lists, as gloc_ground_normals computes them from a list -- none (zero) where
 // a radius list holds fewer than min_nn entries; out_normals [m][3] in ORIGINAL order (device).  Enqueued on s.
 int scan_normals(hipStream_t s, NormalsScratch& w, const reg::f32x4* spts, uint32_t m, const Support& sup, float* out_normals);

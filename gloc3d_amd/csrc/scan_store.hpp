@@ -75,6 +75,10 @@ namespace submap {
 struct Ws;  // the scratch of gloc_scan_store_add_submaps (submap.hip), made on first use
 void free_ws(Ws* w);
 }  // namespace submap
+namespace cluster {
+struct Ws;  // the scratch of gloc_scan_store_cluster / _add_filtered / _add_subset (cluster.hip), made on first use
+void free_ws(Ws* w);
+}  // namespace cluster
 }  // namespace gloc
 
 struct gloc_scan_store : gloc::Handle {  // (always on its own stream; the base's profiler stays idle)
@@ -93,9 +97,11 @@ struct gloc_scan_store : gloc::Handle {  // (always on its own stream; the base'
   gloc::DevBuf fpfh_tmp, spfh_tmp;      // features in original order (as nrm_tmp) and the SPFH counts they are summed from
   gloc::DevBuf iss_sal, iss_sal_sorted, iss_eig, iss_flag, iss_list, iss_count;  // the keypoint detector's scratch (iss.hip)
   gloc::submap::Ws* submap_ws = nullptr;
+  gloc::cluster::Ws* cluster_ws = nullptr;
   std::atomic<int> attached{0};  // registration handles using this store
   ~gloc_scan_store() {
     gloc::submap::free_ws(submap_ws);
+    gloc::cluster::free_ws(cluster_ws);
     for (auto& s : scans) {
       if (s.block) (void)hipFree(s.block);
       if (s.nrm) (void)hipFree(s.nrm);

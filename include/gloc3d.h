@@ -1168,6 +1168,96 @@ int gloc_reg_fpfh_graph_batch_ids_keypoints(gloc_reg* h, uint32_t src_scan_id, c
                                             const gloc_iss_params* iss, float* out_T, uint32_t* out_inliers, uint32_t* out_n_pairs,
                                             int* out_ok);
 
+/* ---- Euclidean clusters and outlier filters of resident scans -------------------------------------------------- *
+ * What a scan is customarily prepared with before it is described or registered (pcl::EuclideanClusterExtraction,
+ * pcl::RadiusOutlierRemoval, pcl::StatisticalOutlierRemoval; Open3D's cluster_dbscan at min_points 1 and its two
+ * remove_*_outlier): the connected components of the "within `tolerance`" graph, which drop the small blobs and keep the
+ * structure, and the two neighbourhood filters.  Opt-in: nothing calls these unless asked, and a filter never changes a
+ * scan -- its survivors become a NEW resident scan.  Every integer output is exact and every float output has a stated
+ * summation order; the executable contract is tests/cluster_ref.py.  NONE below is 0xFFFFFFFF.
+ *
+ * E1  Graph.  The vertices are the points of the scan in upload order; i ~ j iff d2(i, j) <= r2, with R1's d2
+ *     ((dx dx + dy dy) + dz dz in fp32, un-fused) and r2 = tolerance * tolerance rounded to fp32.  A point with a
+ *     non-finite coordinate is a vertex of nothing, whatever r2 (an infinite r2 included): its root and cluster are NONE.
+ *     Exact duplicates are neighbours (d2 = 0).  Nothing depends on whether the scan carries a target index.
+ * E2  Components.  root(i) = the smallest upload index in i's connected component.
+ * E3  Clusters.  size(c) = the component's point count.  A component is KEPT iff size >= max(min_size, 1) and
+ *     (max_size == 0 or size <= max_size).  Kept components are ranked by descending size, ties by ascending root;
+ *     cluster(i) = that rank, or NONE where i's component is not kept.
+ * E4  Per kept cluster, in rank order: size; root; centroid = the fp64 sums of the widened fp32 coordinates divided by
+ *     (double)size; min / max corner in fp32 (of equal zeros -0 is the smaller).  An ORDERED SUM here and in E6: the
+ *     terms, in ascending upload index, are cut into runs of 64; a run's terms are added one by one from +0.0, then the
+ *     runs' sums are added one by one, in run order, from +0.0.  E4's terms are the cluster's points.
+ * E5  Radius outlier removal.  i stays iff it is finite and count(i) - 1 >= min_neighbors, count = R1's count for
+ *     `ror_radius`: the whole neighbourhood, self included, before any cap.
+ * E6  Statistical outlier removal.  The list of i is its k-NN list of mean_k + 1 entries, self included, ascending
+ *     (d2, index), mean_k in [1, 15]; only finite distances enter a list, an entry a list cannot fill counts as FLT_MAX.
+ *     m_i = (the fp64 sum of sqrt((double)d2) over the first mean_k entries of the list without i itself, in list
+ *     order) / (double)mean_k.  Over the N finite points, as ordered sums (E4) whose terms are ALL the scan's points in
+ *     upload order with +0.0 for a non-finite one: mu = sum(m_i) / N, sigma = sqrt(sum((m_i - mu) (m_i - mu)) / N) --
+ *     population, two passes, fp64, nothing fused.  i stays iff it is finite and m_i <= mu + (double)std_mul * sigma.  A
+ *     scan with fewer than mean_k + 1 finite points is refused.
+ * E7  Derived scans.  The survivors of a filter, in upload order, become a new resident scan: exactly the scan
+ *     gloc_scan_store_add_device makes of those points.  The range crop keeps i iff it is finite, not
+ *     (x x + y y) + z z > max_range^2 (max_range > 0) and not (x x + y y) + z z < min_range^2 (min_range > 0), fp32
+ *     un-fused as the submaps' max_range; the cluster stage keeps the points whose cluster is not NONE.
+ *     gloc_scan_store_add_filtered runs its stages ONE AFTER THE OTHER, each on the survivors of the one before, in the
+ *     order range crop, radius outlier removal, statistical outlier removal, clusters; a stage whose switch is zero is
+ *     skipped.  Its result equals the chain of single-stage calls bit for bit.  A call in which nothing survives a stage
+ *     is refused after that stage's device work and adds nothing. */
+typedef struct gloc_cluster_params {
+  float tolerance;     /* default 0.5 m; >= 0 and finite; 0: no cluster stage (refused by gloc_scan_store_cluster) */
+  uint32_t min_size;   /* default 1 */
+  uint32_t max_size;   /* default 0: no upper limit; else >= min_size */
+  uint32_t reserved_;  /* 0 */
+} gloc_cluster_params; /* 16 bytes */
+
+void gloc_cluster_default_params(gloc_cluster_params* p);
+
+/* E1 - E4 of a resident scan of n points, nothing is kept.  out_root / out_cluster [n] in upload order (capacity_points
+ * entries each); out_size / out_cluster_root [n_kept], out_centroid3 [n_kept][3], out_lo3 / out_hi3 [n_kept][3] in rank
+ * order (capacity_clusters rows each); n_components counts all components, n_kept the kept ones.  Every output may be
+ * NULL.  The parameter block is checked before the handle.  GLOC_ERR_INVALID before any device work and with the outputs
+ * untouched: a null block, tolerance not positive and finite, min_size > max_size != 0, reserved_ != 0, a null store, an
+ * unknown id, a scan of 2^31 points or more.  A point buffer given with capacity_points < n, or a cluster buffer with
+ * capacity_clusters < n_kept: GLOC_ERR_INVALID after the device work -- the two counts are returned, the buffers that are
+ * too small are not written. */
+int gloc_scan_store_cluster(gloc_scan_store* st, uint32_t scan_id, const gloc_cluster_params* prm, uint32_t* out_root,
+                            uint32_t* out_cluster, size_t capacity_points, uint32_t* out_size, uint32_t* out_cluster_root,
+                            double* out_centroid3, float* out_lo3, float* out_hi3, size_t capacity_clusters, uint32_t* n_components,
+                            uint32_t* n_kept);
+
+typedef struct gloc_scan_filter_params {
+  float min_range, max_range;  /* <= 0: off; both set: min_range <= max_range */
+  float ror_radius;            /* 0: off; else positive and finite */
+  uint32_t ror_min_neighbors;
+  uint32_t sor_mean_k;         /* 0: off; else 1 .. 15 */
+  float sor_std_mul;           /* finite */
+  gloc_cluster_params cluster; /* tolerance 0: off */
+} gloc_scan_filter_params;     /* 40 bytes */
+
+void gloc_scan_filter_default_params(gloc_scan_filter_params* p); /* everything off (cluster: min_size 1, max_size 0) */
+
+typedef struct gloc_scan_filter_info {
+  uint32_t points_in, after_range, after_ror, after_sor, after_cluster; /* a skipped stage repeats the count before it */
+} gloc_scan_filter_info;
+
+/* E7: *new_id is a new resident scan of what the stages of prm leave of scan base_id (all stages off: a copy).  info
+ * may be NULL; on a refusal after device work it holds the counts up to the stage that left nothing.  The base scan is
+ * only read; the call holds the store's mutex, returns when the scan is complete and has released every intermediate
+ * scan.  The parameter block is checked before the handle.  GLOC_ERR_INVALID before any device work: a null block, a
+ * radius or tolerance that is negative or not finite, min_size > max_size != 0, reserved_ != 0, sor_mean_k > 15,
+ * sor_std_mul not finite, a non-finite range, min_range > max_range with both set, a null store or new_id, an unknown
+ * id; after a stage's device work: fewer than sor_mean_k + 1 finite points at the statistical stage, no survivor.  A
+ * call that fails adds nothing. */
+int gloc_scan_store_add_filtered(gloc_scan_store* st, uint32_t base_id, const gloc_scan_filter_params* prm, uint32_t* new_id,
+                                 gloc_scan_filter_info* info);
+
+/* The primitive under E7: a new resident scan of rows idx[0 .. m) of scan base_id in the order given (indices may
+ * repeat) -- a gather on the device, then the scan gloc_scan_store_add_device makes of those rows.  GLOC_ERR_INVALID
+ * before any device work: a null argument, m = 0 or m >= 2^31, an unknown id, an index >= the scan's size. */
+int gloc_scan_store_add_subset(gloc_scan_store* st, uint32_t base_id, const uint32_t* idx, size_t m, uint32_t* new_id);
+
 /* ---- Fast Global Registration on the FPFH matches -------------------------------------------------------------- *
  * A third way from F3's match list to a pose, beside F4 and G1 - G4: Fast Global Registration (Zhou, Park, Koltun, ECCV
  * 2016; pcl and Open3D carry it beside their RANSAC routes).  A tuple test thins the matches, then ONE graduated-non-convexity

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgloc3d.so")
-SOURCES = ["common.hip", "comm.hip", "knn.hip", "scan_store.hip", "scan_features.hip", "reg.hip", "vlad.hip", "bev.hip", "ground.hip", "coarse.hip", "sc.hip", "m2dp.hip", "ndt.hip", "submap.hip", "p2l.hip", "gicp.hip", "vgicp.hip", "vmap.hip", "fpfh.hip", "iss.hip", "cluster.hip", "pairgraph.hip", "fgr.hip", "eval.hip", "pillar.hip", "vgg.hip"]
+SOURCES = ["common.hip", "comm.hip", "knn.hip", "scan_store.hip", "scan_features.hip", "reg.hip", "vlad.hip", "bev.hip", "ground.hip", "coarse.hip", "sc.hip", "m2dp.hip", "ndt.hip", "submap.hip", "p2l.hip", "gicp.hip", "vgicp.hip", "vmap.hip", "fpfh.hip", "iss.hip", "cluster.hip", "pairgraph.hip", "fgr.hip", "eval.hip", "pgo.hip", "pillar.hip", "vgg.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the exact kernels must reproduce the reference's un-fused fp32 arithmetic
 EXTRA = os.environ.get("GLOC3D_EXTRA_FLAGS", "").split()

@@ -100,6 +100,16 @@ class RobustParams(C.Structure):
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_GEMAN_MCCLURE = range(5)
 
 
+class PgoParams(C.Structure):
+    _fields_ = [("max_iters", C.c_uint32), ("pcg_max_iters", C.c_uint32), ("lambda_init", C.c_double), ("pcg_tol", C.c_double),
+                ("rot_eps", C.c_double), ("trans_eps", C.c_double), ("grad_eps", C.c_double), ("reserved_", C.c_uint32 * 2)]
+
+
+class PgoResult(C.Structure):
+    _fields_ = [("iters", C.c_uint32), ("accepted", C.c_uint32), ("pcg_iters", C.c_uint32), ("status", C.c_int32),
+                ("cost_initial", C.c_double), ("cost_final", C.c_double), ("lam", C.c_double), ("grad_inf", C.c_double)]
+
+
 class FpfhParams(C.Structure):
     _fields_ = [("normal_k", C.c_uint32), ("feature_k", C.c_uint32), ("mutual", C.c_uint32), ("ransac_iters", C.c_uint32),
                 ("inlier_thresh", C.c_float), ("min_inlier_ratio", C.c_float), ("ransac_confidence", C.c_float),
@@ -461,6 +471,18 @@ _PROTOS = [
     ("gloc_coarse_release", _i, [_vp, _u32]),
     ("gloc_coarse_cells", _i, [_vp, _u32, C.POINTER(_u32), _vp, _sz]),
     ("gloc_coarse_match", _i, [_vp, _u32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("gloc_pgo_default_params", None, [C.POINTER(PgoParams)]),
+    ("gloc_pgo_create", _i, [_i, C.POINTER(_vp)]),
+    ("gloc_pgo_destroy", _i, [_vp]),
+    ("gloc_pgo_set_stream", _i, [_vp, _vp]),
+    ("gloc_pgo_synchronize", _i, [_vp]),
+    ("gloc_pgo_set_profile", _i, [_vp, _i]),
+    ("gloc_pgo_profile", _i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
+    ("gloc_pgo_profile_reset", _i, [_vp]),
+    ("gloc_pgo_linearize", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(PgoParams), C.POINTER(RobustParams),
+                            _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    ("gloc_pgo_optimize", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(PgoParams), C.POINTER(RobustParams),
+                           _vp, _vp, _vp, C.POINTER(PgoResult)]),
     ("gloc_sc_default_params", _i, [C.POINTER(ScParams)]),
     ("gloc_sc_create", _i, [_i, C.POINTER(ScParams), C.POINTER(_vp)]),
     ("gloc_sc_destroy", _i, [_vp]),
@@ -2176,6 +2198,63 @@ class CoarseMatcher(_Handle):
         check(lib().gloc_coarse_match(self._h, int(q_grid), _np_ptr(ids), n, C.byref(self.params), _np_ptr(xyyaw),
                                       _np_ptr(ratio), _np_ptr(ok), _np_ptr(self.last_scale)))
         return xyyaw, ratio, ok.astype(bool)
+
+
+def default_pgo_params(**over):
+    """gloc_pgo_params as gloc_pgo_default_params leaves them, then `over`."""
+    p = PgoParams()
+    lib().gloc_pgo_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+class PoseGraphOptimizer(_Handle):
+    """Levenberg-Marquardt over the node poses of a pose graph on the device (gloc_pgo_* of include/gloc3d.h): poses
+    [n, 4, 4] float64 (node -> map), edges (src, tgt, Z [m, 4, 4] float32 source -> target, info [m, 6, 6] float64)."""
+
+    _C = "pgo"
+    set_stream, synchronize = _set_stream, _synchronize
+    set_profile, profile, profile_reset = _set_profile, _profile, _profile_reset
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        check(lib().gloc_pgo_create(device, C.byref(self._h)))
+
+    @staticmethod
+    def _graph(poses, fixed, src, tgt, Z, info, mask):
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 16)
+        fx = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+        s, t = np.ascontiguousarray(src, np.uint32).reshape(-1), np.ascontiguousarray(tgt, np.uint32).reshape(-1)
+        Zf = np.ascontiguousarray(Z, np.float32).reshape(-1, 16)
+        Om = np.ascontiguousarray(info, np.float64).reshape(-1, 36)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        assert fx.shape[0] == P.shape[0] and t.shape[0] == s.shape[0] == Zf.shape[0] == Om.shape[0]
+        assert mk is None or mk.shape[0] == s.shape[0]
+        return P, fx, s, t, Zf, Om, mk
+
+    def linearize(self, poses, fixed, src, tgt, Z, info, mask=None, params=None, robust=None):
+        """One linearisation at `poses`: dict(r [m, 6], s2 [m], weight [m], g [n, 6], Hdiag [n, 6, 6], cost)."""
+        P, fx, s, t, Zf, Om, mk = self._graph(poses, fixed, src, tgt, Z, info, mask)
+        prm = params or default_pgo_params()
+        n, m = P.shape[0], s.shape[0]
+        r, s2, w = np.empty((m, 6)), np.empty(m), np.empty(m)
+        g, H, cost = np.empty((n, 6)), np.empty((n, 6, 6)), C.c_double()
+        check(lib().gloc_pgo_linearize(self._h, _np_ptr(P), _np_ptr(fx), n, _np_ptr(s), _np_ptr(t), _np_ptr(Zf), _np_ptr(Om),
+                                       None if mk is None else _np_ptr(mk), m, C.byref(prm), None if robust is None else C.byref(robust),
+                                       _np_ptr(r), _np_ptr(s2), _np_ptr(w), _np_ptr(g), _np_ptr(H), C.byref(cost)))
+        return dict(r=r, s2=s2, weight=w, g=g, Hdiag=H, cost=cost.value)
+
+    def optimize(self, poses, fixed, src, tgt, Z, info, mask=None, params=None, robust=None):
+        """(poses [n, 4, 4] float64, s2 [m], weight [m], PgoResult)."""
+        P, fx, s, t, Zf, Om, mk = self._graph(poses, fixed, src, tgt, Z, info, mask)
+        prm = params or default_pgo_params()
+        n, m = P.shape[0], s.shape[0]
+        out, s2, w, res = np.empty((n, 4, 4)), np.empty(m), np.empty(m), PgoResult()
+        check(lib().gloc_pgo_optimize(self._h, _np_ptr(P), _np_ptr(fx), n, _np_ptr(s), _np_ptr(t), _np_ptr(Zf), _np_ptr(Om),
+                                      None if mk is None else _np_ptr(mk), m, C.byref(prm), None if robust is None else C.byref(robust),
+                                      _np_ptr(out), _np_ptr(s2), _np_ptr(w), C.byref(res)))
+        return out, s2, w, res
 
 
 def default_sc_params(**over):

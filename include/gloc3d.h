@@ -1840,6 +1840,106 @@ int gloc_scan_store_add_raycast_batch(gloc_scan_store* st, size_t count, const d
                                       const double* T16 /* [count][16] */, const uint64_t* seeds /* [count] */,
                                       const gloc_raycast_params* params, uint32_t* scan_ids /* [count] */);
 
+/* ---- pose-graph optimisation --------------------------------------------------------------------------- *
+ * What turns the edges the entries above produce into corrected poses: gloc_reg_<m>_pairs gives an edge's Z, and
+ * gloc_reg_evaluate_pairs its information matrix.  Levenberg-Marquardt over all node poses, block-Jacobi preconditioned
+ * conjugate gradients inside, everything fp64 on the device.  The executable contract is tests/pgo_ref.py.
+ *
+ *   G1. Node k has pose T_k = (R_k, t_k), node frame -> map frame, [n][16] row-major DOUBLES on both sides of the ABI (a
+ *       map is kilometres wide; the fp32 T16 of the per-pair entries would cap convergence at fp32 rounding).  Edge e is
+ *       (i = edge_src[e], j = edge_tgt[e], Z, Omega): Z [16] fp32 maps source -> target, Z ~ T_j^-1 T_i -- exactly an
+ *       out_T row of gloc_reg_<m>_pairs --, and Omega [36] is an out_info36 row of gloc_reg_evaluate_pairs, read from
+ *       its UPPER triangle: the Hessian for Z <- exp(xi) Z, xi = (w, v), rotation first, (exp(w) R, exp(w) t + v).
+ *   G2. The residual is the left perturbation that takes Z to the predicted relative pose, so Omega weights it as it is:
+ *         R_E = R_j^T R_i R_Z^T,  t_E = R_j^T (t_i - t_j) - R_E t_Z,  r = (log R_E, t_E),  s2 = r^T Omega r.
+ *       log R: v = vee(R - R^T) / 2, th = atan2(|v|, (tr R - 1) / 2), w = v th / |v| (v (1 + |v|^2 / 6) below |v| = 1e-8):
+ *       residual rotations up to ~3 rad are exact to rounding, pi itself is not handled.
+ *   G3. Nodes are perturbed the same way, T_k <- (exp(w_k) R_k, exp(w_k) t_k + v_k); to first order
+ *       r(delta) = r + A (delta_i - delta_j) with ONE 6 x 6 Jacobian per edge,
+ *         A = [ Jl^-1(w) R_j^T                      0     ]     Jl^-1(w) = I - [w]x / 2 + c [w]x^2,
+ *             [ [R_E t_Z]x R_j^T - R_j^T [t_i]x     R_j^T ]     c = 1 / th^2 - (1 + cos th) / (2 th sin th), 1/12 below 1e-6
+ *       (checked against central differences in tests/test_pgo_ref_cpu.py).  Per edge, with the robust weight w_e:
+ *       W_e = w_e A^T Omega A, b_e = w_e A^T Omega r;  g_k = sum +- b_e, H_kk = sum W_e, (H x)_k = sum +- W_e (x_i - x_j),
+ *       + where k is the edge's source, - where it is the target, over the edges at k in ascending edge index.
+ *   G4. Translations are taken relative to the first fixed node's translation (subtracted in fp64 on input, added back on
+ *       output): the lever arm [t_i]x has the size of the map, not of the distance to an arbitrary origin.  g and H_kk as
+ *       gloc_pgo_linearize returns them refer to that origin.
+ *   G5. Robust weighting: `robust` NULL or kind NONE is the plain sum of squares.  Otherwise w_e is gloc_robust_weight of
+ *       s2 at `scale` (dimensionless, as for generalized ICP) for the edges robust_mask selects (NULL: all; odometry
+ *       edges usually keep weight 1) and 1 for the others.  A schedule (scale_start != 0) is refused: the step control
+ *       needs one objective.  That objective is F = sum rho_e: rho = s2 for an unweighted edge and otherwise, t = s2 / c^2,
+ *         HUBER  t <= 1 ? s2 : c^2 (2 sqrt t - 1)     CAUCHY  c^2 log(1 + t)
+ *         TUKEY  t <= 1 ? (c^2 / 3)(1 - (1 - t)^3) : c^2 / 3     GEMAN_MCCLURE  s2 / (1 + t).
+ *   G6. A node is FREE if it is not fixed and has an edge.  Every other node gets no update and its pose is returned bit
+ *       for bit.  D = blockdiag(H_kk) over the free nodes; a step solves (H + lambda D) delta = -g (Marquardt scaling: the
+ *       damping does not depend on where the origin lies).  lambda starts at lambda_init; gain = (F - F_new) /
+ *       (delta^T (lambda D delta - g)); the step is accepted iff gain > 0 and F_new is finite; then lambda <- lambda
+ *       max(1/3, 1 - (2 gain - 1)^3), nu = 2 (Nielsen); otherwise lambda <- lambda nu, nu <- 2 nu.
+ *   G7. The solve: preconditioned conjugate gradients from x = 0 with M = ((1 + lambda) H_kk)^-1 from the 6 x 6 Cholesky
+ *       and pivot rule of the Gauss-Newton refinements (the factor of H_kk, scaled: the pivot rule does not see the
+ *       factor 1 + lambda), until |residual|^2 <= pcg_tol^2 |g|^2 or pcg_max_iters.  A free node whose block fails the
+ *       pivot rule ends the call with status 2 and the poses of the last accepted step.  Two limits follow from this
+ *       choice of solver, both measured.  A node perturbed about the origin couples its rotation
+ *       to its translation through the lever arm |t|: H_kk's smallest pivot is about (Omega_rot / (|t|^2 Omega_trans))^2 of
+ *       its largest, so the 1e-12 rule refuses maps wider than about 1000 sqrt(Omega_rot / Omega_trans) metres from the
+ *       first fixed node -- 20 km for the information matrices of gloc_reg_evaluate_pairs (Omega_rot / Omega_trans is the
+ *       mean squared point range, some 400 m^2), a few km for edges with weak rotations.  And block-Jacobi PCG needs
+ *       thousands of iterations per step on a loop of thousands of nodes: at the default cap every solve is cut short
+ *       (an inexact step, still a descent step) and max_iters is reached before the minimum; raise pcg_max_iters there.
+ *   G8. Stops, tested after an accepted step: max |w_k| <= rot_eps and max |v_k| <= trans_eps (both set): status 1;
+ *       max |g| <= grad_eps (set; also tested before the first step): status 3; max_iters attempts: status 0; no free
+ *       node: status 2 with zero iterations.  An eps of 0 switches its test off.
+ *   G9. Deterministic: no floating-point atomics, every sum in a fixed order (a node's edges in ascending index spread
+ *       over the 64 lanes of a wave, per-work-group partials in index order); two calls on the same input give the same bits.
+ *
+ * The checks come in this order, each refusing with GLOC_ERR_INVALID, before any device work and with the outputs
+ * untouched: a null prm; max_iters = 0; pcg_max_iters = 0; lambda_init, pcg_tol not finite and positive; rot_eps,
+ * trans_eps, grad_eps not finite or negative; reserved_ != 0; a robust block the robust entries refuse, or one with a
+ * schedule; a null array (robust_mask may be); n outside [2, 2^20]; m outside [1, 2^22]; an edge end >= n; an edge from
+ * a node to itself; no fixed node; a non-finite value in poses, Z or info; a null handle.  Duplicate edges, edges in both
+ * directions and components without a fixed node are legal (the damping keeps such a component solvable).  Calls are
+ * synchronous. */
+typedef struct gloc_pgo gloc_pgo;
+typedef struct gloc_pgo_params {
+  uint32_t max_iters;      /* 50: Levenberg-Marquardt attempts */
+  uint32_t pcg_max_iters;  /* 200 per attempt */
+  double lambda_init;      /* 1e-4 (Ceres' initial trust radius inverted) */
+  double pcg_tol;          /* 1e-8, relative to |g| */
+  double rot_eps;          /* 1e-6 rad; 0: no step test */
+  double trans_eps;        /* 1e-6 m; 0: no step test */
+  double grad_eps;         /* 1e-6; 0: no gradient test */
+  uint32_t reserved_[2];   /* 0 */
+} gloc_pgo_params;         /* 56 bytes */
+typedef struct gloc_pgo_result {
+  uint32_t iters, accepted, pcg_iters;
+  int32_t status;          /* G8 */
+  double cost_initial, cost_final, lambda, grad_inf;
+} gloc_pgo_result;         /* 48 bytes */
+
+void gloc_pgo_default_params(gloc_pgo_params* p);
+int gloc_pgo_create(int device, gloc_pgo** out);
+int gloc_pgo_destroy(gloc_pgo* h);
+int gloc_pgo_set_stream(gloc_pgo* h, void* hip_stream);
+int gloc_pgo_synchronize(gloc_pgo* h);
+/* families: pgo_setup, pgo_linearize, pgo_gather, pgo_pcg, pgo_step */
+int gloc_pgo_set_profile(gloc_pgo* h, int enable);
+int gloc_pgo_profile(gloc_pgo* h, const char* kernel, double* total_ms, uint64_t* launches);
+int gloc_pgo_profile_reset(gloc_pgo* h);
+
+/* One linearisation at the given poses (G2-G5).  Any output may be NULL, but not all of them. */
+int gloc_pgo_linearize(gloc_pgo* h, const double* poses /* [n][16] */, const uint8_t* fixed /* [n] */, size_t n,
+                       const uint32_t* edge_src, const uint32_t* edge_tgt /* [m] */, const float* Z /* [m][16] */,
+                       const double* info /* [m][36] */, const uint8_t* robust_mask /* [m], may be NULL */, size_t m,
+                       const gloc_pgo_params* prm, const gloc_robust_params* robust /* NULL: plain */,
+                       double* out_r6 /* [m][6] */, double* out_s2 /* [m] */, double* out_weight /* [m] */,
+                       double* out_g6 /* [n][6] */, double* out_Hdiag36 /* [n][36] symmetric */, double* out_cost);
+
+/* G6-G8.  out_s2 and out_weight (at the returned poses) may be NULL. */
+int gloc_pgo_optimize(gloc_pgo* h, const double* poses, const uint8_t* fixed, size_t n, const uint32_t* edge_src,
+                      const uint32_t* edge_tgt, const float* Z, const double* info, const uint8_t* robust_mask, size_t m,
+                      const gloc_pgo_params* prm, const gloc_robust_params* robust, double* out_poses /* [n][16] */,
+                      double* out_s2, double* out_weight, gloc_pgo_result* out);
+
 #ifdef __cplusplus
 }
 #endif

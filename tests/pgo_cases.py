@@ -148,3 +148,224 @@ def rel_error(A, B):
         er = max(er, np.linalg.norm(R.log_so3(D[:3, :3])))
         et = max(et, np.linalg.norm(D[:3, 3]))
     return er, et
+
+
+# ---- the cases of the sweep (tests/test_pgo_sweep_cpu.py, tests/test_pgo_sweep_gpu.py) ---------------------------------
+def tiled(g, K, layout):
+    """K copies of g with IDENTICAL pose values (a translated copy would have another [t_i]x, another computation), each
+    with its own fixed node.  "blocks": node k of copy c at c n0 + k, edge e at c m0 + e.  "interleaved": node k of copy c
+    at k K + c, edge e at e K + c.  Either way a node's incident edges keep the base's ascending order, and copy 0 holds
+    the first fixed node.  copies(x, K, layout) views a per-node or per-edge array of the tiled graph as [K, n0 or m0, ...]."""
+    n0 = len(g["init"])
+    src, tgt, c = g["src"].astype(np.int64), g["tgt"].astype(np.int64), np.arange(K, dtype=np.int64)
+    if layout == "blocks":
+        rep = lambda x: np.tile(x, (K,) + (1,) * (x.ndim - 1))
+        s, t = (src[None, :] + n0 * c[:, None]).reshape(-1), (tgt[None, :] + n0 * c[:, None]).reshape(-1)
+    else:
+        assert layout == "interleaved"
+        rep = lambda x: np.repeat(x, K, axis=0)
+        s, t = (src[:, None] * K + c[None, :]).reshape(-1), (tgt[:, None] * K + c[None, :]).reshape(-1)
+    out = {k: rep(np.asarray(g[k])) for k in ("init", "fixed", "Z", "info")}
+    out["src"], out["tgt"] = s.astype(np.uint32), t.astype(np.uint32)
+    return out
+
+
+def copies(x, K, layout):
+    x = np.asarray(x)
+    if layout == "blocks":
+        return x.reshape((K, x.shape[0] // K) + x.shape[1:])
+    return np.swapaxes(x.reshape((x.shape[0] // K, K) + x.shape[1:]), 0, 1)
+
+
+def base30():
+    return graph(30, 10, seed=21, noise=1.0)
+
+
+def base16():
+    return graph(16, 5, seed=53, noise=1.0)
+
+
+def rejecting():
+    """A start so far off (0.5 rad, 5 m of drift a step) that Levenberg-Marquardt from lambda_init = 1e-6 rejects steps.
+    Seed 66, not base16's 53: on 53 the step test before the last fails by 1.77 x only (max |v| = 1.77e-6 against 1e-6).
+    Of seeds 50-129, 66 is the first that has the margins tests/test_pgo_sweep_cpu.py asks for AND rejects after an
+    accepted step with gains off Nielsen's clamp (gains 0.51, four from -0.178 to -0.159, 0.081, 0.747 ... 1.011), so the
+    final lambda depends on the gains (seed 51's is the same to the bit in the dense and the PCG run)."""
+    return graph(16, 5, seed=66, noise=1.0, drift=(0.5, 5.0))
+
+
+def rejecting_twice():
+    """The same recipe at seed 195 (the first of seeds 50-399 with the margins and two separate runs of rejections): six
+    steps rejected, four accepted, ONE rejected -- lambda x 2 only if nu went back to 2 --, ten accepted."""
+    return graph(16, 5, seed=195, noise=1.0, drift=(0.5, 5.0))
+
+
+def with_a_leaf_of_zero_information():
+    """base30 and a node 30 hanging on node 7 by one edge whose information matrix is all zeros: H_kk = 0 at a free node."""
+    g = base30()
+    leaf = left(np.array([0.01, -0.02, 0.03, 0.1, 0.2, -0.1]), g["init"][7] @ se3([0.0, 0.0, 0.2], [1.5, 0.0, 0.0]))
+    g["init"] = np.concatenate([g["init"], [leaf]])
+    g["fixed"] = np.append(g["fixed"], 0).astype(np.uint8)
+    g["src"], g["tgt"] = np.append(g["src"], 30).astype(np.uint32), np.append(g["tgt"], 7).astype(np.uint32)
+    g["Z"] = np.concatenate([g["Z"], [se3([0.0, 0.0, 0.2], [1.5, 0.0, 0.0]).astype(np.float32)]])
+    g["info"] = np.concatenate([g["info"], np.zeros((1, 6, 6))])
+    return g
+
+
+def beyond_tukey():
+    """Every edge past Tukey's cutoff at scale 3 (s2 > 9): w = 0, g = 0, F = m c^2 / 3 = 40 x 3."""
+    return graph(30, 10, seed=24, noise=1.0, outliers=0.3, drift=(0.05, 0.5))
+
+
+def _quarter(k):
+    """One of the 24 rotations of the cube: entries 0 and +-1, exact in float32."""
+    X = np.array([[1, 0, 0], [0, 0, -1], [0, 1, 0]], np.float64)
+    Y = np.array([[0, 0, 1], [0, 1, 0], [-1, 0, 0]], np.float64)
+    Z = np.array([[0, -1, 0], [1, 0, 0], [0, 0, 1]], np.float64)
+    R_ = np.eye(3)
+    for a, M in zip((k % 4, (k // 4) % 4, (k // 16) % 4), (Z, X, Y)):
+        R_ = R_ @ np.linalg.matrix_power(M, a)
+    return np.round(R_)
+
+
+def exact(n=7, seed=61):
+    """Poses of quarter turns and small integer translations on a loop with two closures, Z cut from them: every product
+    in the residual is exact, so at init = truth the residual is 0 exactly."""
+    rng = np.random.default_rng(seed)
+    truth = np.array([np.eye(4) for _ in range(n)])
+    for k in range(n):
+        truth[k, :3, :3] = _quarter(int(rng.integers(0, 64)))
+        truth[k, :3, 3] = rng.integers(-6, 7, 3)
+    src = [k + 1 for k in range(n - 1)] + [n - 1, 0, 5]
+    tgt = [k for k in range(n - 1)] + [0, 3, 2]
+    src, tgt = np.array(src, np.uint32), np.array(tgt, np.uint32)
+    Z = np.array([np.round(np.linalg.inv(truth[j]) @ truth[i]) for i, j in zip(src, tgt)]).astype(np.float32)
+    fixed = np.zeros(n, np.uint8)
+    fixed[0] = 1
+    return dict(truth=truth, init=truth.copy(), fixed=fixed, src=src, tgt=tgt, Z=Z, info=random_info(rng, len(src)))
+
+
+def turned(g, theta, seed=62):
+    """g with every free node turned on the left by theta about an axis of its own (translations turn with it)."""
+    rng = np.random.default_rng(seed)
+    out = dict(g, init=g["init"].copy())
+    for k in np.flatnonzero(np.asarray(g["fixed"]) == 0):
+        a = rng.normal(size=3)
+        out["init"][k] = left(np.concatenate([a / np.linalg.norm(a) * theta, np.zeros(3)]), g["init"][k])
+    return out
+
+
+def large_pair(theta):
+    """Two nodes, one edge, at the truth but for node 1 turned by theta (and moved a little): residual rotation theta."""
+    g = graph(2, 0, seed=1, noise=0.0, loop=False)
+    g["init"] = g["truth"].copy()
+    a = np.array([0.6, -0.48, 0.64])
+    g["init"][1] = left(np.concatenate([a * theta, [0.05, -0.02, 0.03]]), g["init"][1])
+    return g
+
+
+def large_loop5(theta):
+    """loop5 at the truth but for node 2 turned by theta: its three edges (one of them the doubled one) carry theta."""
+    g = loop5()
+    g["init"] = g["truth"].copy()
+    a = np.array([-0.48, 0.64, 0.6])
+    g["init"][2] = left(np.concatenate([a * theta, [0.02, 0.04, -0.03]]), g["init"][2])
+    return g
+
+
+def translation_only():
+    """Two components without a rotation error anywhere, translations weighted 1000 x the rotations.  Nodes 0-6: exact()
+    with integer translation errors at three nodes.  Nodes 7-13: a second exact() at its truth, node 7 fixed: its free
+    nodes have g = 0 exactly, so x = 0 exactly in every solve and the retraction runs at theta = 0."""
+    a, b = exact(7, 61), exact(7, 63)
+    a["init"][2, :3, 3] += [1, 0, -1]
+    a["init"][4, :3, 3] += [0, 2, 0]
+    a["init"][6, :3, 3] += [-1, 1, 1]
+    g = {k: np.concatenate([a[k], b[k]]) for k in ("truth", "init", "fixed", "Z")}
+    g["src"], g["tgt"] = np.concatenate([a["src"], b["src"] + 7]).astype(np.uint32), np.concatenate([a["tgt"], b["tgt"] + 7]).astype(np.uint32)
+    rng = np.random.default_rng(64)
+    g["info"] = random_info(rng, len(g["src"]), rot=1.0, trans=1e3)
+    return g
+
+
+def last_fixed_257():
+    """n257 with only node 255 fixed (the last node that has an edge): the origin of G4 is not node 0."""
+    g = n257()
+    g["fixed"][:] = 0
+    g["fixed"][255] = 1
+    return g
+
+
+def last_fixed_30(offset=(4000.0, -3000.0, 50.0)):
+    """base30 moved 4000 m away with only node 29 fixed."""
+    g = base30()
+    g["init"] = g["init"].copy()
+    g["init"][:, :3, 3] += np.asarray(offset)
+    g["fixed"][:] = 0
+    g["fixed"][29] = 1
+    return g
+
+
+# ---- the device's summation order (G9; DESIGN.md section 14), restated for the objective --------------------------------
+THREADS, MAX_GRID = 256, 1024
+
+
+def _group_sum(v):
+    """[groups, 256] -> [groups]: each wave of 64 by the butterfly (xor 32, 16, ..., 1), then the four waves in index order."""
+    w = v.reshape(-1, 4, 64)
+    lane = np.arange(64)
+    for s in (32, 16, 8, 4, 2, 1):
+        w = w + w[..., lane ^ s]
+    w = w[..., 0]
+    return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+
+
+def _strided(x, lanes):
+    """lane l adds x[l], x[l + lanes], ... in that order, from 0."""
+    rounds = -(-len(x) // lanes)
+    pad = np.zeros(rounds * lanes, x.dtype)
+    pad[:len(x)] = x
+    acc = np.zeros(lanes, x.dtype)
+    for i in range(rounds):
+        acc = acc + pad[i * lanes:(i + 1) * lanes]
+    return acc
+
+
+def device_order_sum(x):
+    """sum(x) as linearize_kernel and finalize_kernel add the objective's terms: min(ceil(m / 256), 1024) work-groups
+    stride over the edges, a lane adds its terms in order, a work-group adds its lanes (_group_sum); one work-group then
+    adds the partials the same way."""
+    x = np.asarray(x)
+    ge = min(-(-len(x) // THREADS), MAX_GRID)
+    parts = _group_sum(_strided(x, ge * THREADS).reshape(ge, THREADS))
+    return _group_sum(_strided(parts, THREADS).reshape(1, THREADS))[0]
+
+
+def sum_depth(m):
+    """The longest chain of additions a term of the objective passes in device_order_sum: its lane's strided sum, six
+    butterfly steps and three additions of waves, then the same over the partials."""
+    ge = min(-(-m // THREADS), MAX_GRID)
+    return -(-m // (ge * THREADS)) + 9 + -(-ge // THREADS) + 9
+
+
+# ---- reference-versus-reference figures the GPU sweep's tolerances are multiples of ---------------------------------------
+# max |pose entry difference| between the reference's dense and PCG runs (test_pgo_gpu.TIGHT stops unless noted), measured
+# on the CPU and rounded up; tests/test_pgo_sweep_cpu.py::test_recorded_dense_versus_pcg re-measures each.
+RECORDED = {"base30": 1.19e-10,            # (test_pgo_gpu.DENSE_VS_PCG["plain"]: the same graph)
+            "base16_default8": 1.78e-15,   # base16() at the library's default stops, max_iters = 8
+            "rejecting": 3.56e-15,         # rejecting() at the library's default stops, lambda_init = 1e-6
+            "rejecting_twice": 3.11e-15,   # rejecting_twice(), the same
+            "translation_only": 4.45e-15, "last_fixed_30": 1.54e-10, "loop5": 5.75e-12, "hub65": 1.07e-14, "hub300": 1.43e-14}
+REJECTING_LAMBDA_REL = {"rejecting": 4.55e-8, "rejecting_twice": 7.13e-8}   # |lambda_dense - lambda_pcg| / lambda_dense at the end
+PCG_STOP_TOL = 3e-3              # the pcg_tol at which hub(65)'s solves all stop with a factor >= 2 to spare
+
+
+def recorded_case(name):
+    """(graph, stops): stops None means test_pgo_gpu.TIGHT; otherwise overrides of the library's defaults."""
+    if name == "base16_default8":
+        return base16(), dict(max_iters=8)
+    if name in ("rejecting", "rejecting_twice"):
+        return (rejecting if name == "rejecting" else rejecting_twice)(), dict(lambda_init=1e-6)
+    make = {"base30": base30, "translation_only": translation_only, "last_fixed_30": last_fixed_30, "loop5": loop5,
+            "hub65": lambda: hub(65, seed=65), "hub300": lambda: hub(300, seed=300)}
+    return make[name](), None

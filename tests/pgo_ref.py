@@ -195,9 +195,13 @@ def solve_dense(L, src, tgt, free, lam):
     return x, 0
 
 
-def solve_pcg(L, src, tgt, free, lam, tol, max_iters):
-    """Block-Jacobi preconditioned conjugate gradients from x = 0 on (H + lam D) x = -g; M = ((1 + lam) H_kk)^-1."""
+def solve_pcg(L, src, tgt, free, lam, tol, max_iters, hist=None):
+    """Block-Jacobi preconditioned conjugate gradients from x = 0 on (H + lam D) x = -g; M = ((1 + lam) H_kk)^-1.
+    hist (a dict, optional) receives rr: |residual|^2 before iteration 0 and after every iteration, g2, and breakdown:
+    whether the loop left through `not pAp > 0`."""
     n = len(free)
+    if hist is not None:
+        hist.update(rr=[], g2=0.0, breakdown=False)
     Minv = np.zeros((n, 6, 6))
     for k in np.flatnonzero(free):
         Lk = chol6(L.Hd[k])                    # (the pivot rule does not depend on the factor 1 + lam)
@@ -211,16 +215,23 @@ def solve_pcg(L, src, tgt, free, lam, tol, max_iters):
     g2 = (r * r).sum()
     z = prec(r)
     p, rz, rr, it = z.copy(), (r * z).sum(), g2, 0
+    if hist is not None:
+        hist["g2"] = float(g2)
+        hist["rr"].append(float(rr))
     while it < max_iters and not rr <= tol * tol * g2:
         Ap = matvec(L, src, tgt, free, lam, p)
         pAp = (p * Ap).sum()
         if not pAp > 0:
+            if hist is not None:
+                hist["breakdown"] = True
             break
         a = rz / pAp
         x += a * p
         r -= a * Ap
         it += 1
         rr = (r * r).sum()
+        if hist is not None:
+            hist["rr"].append(float(rr))
         z = prec(r)
         rz_new = (r * z).sum()
         p = z + (rz_new / rz) * p
@@ -238,9 +249,10 @@ def retract(P, x):
     return Q
 
 
-def optimize(poses, fixed, src, tgt, Z, info, mask=None, kind=NONE, scale=1.0, solver="dense", **over):
+def optimize(poses, fixed, src, tgt, Z, info, mask=None, kind=NONE, scale=1.0, solver="dense", trace=None, **over):
     """Levenberg-Marquardt with Marquardt scaling.  Returns dict(poses, s2, weight, iters, accepted, pcg_iters, status,
-    cost_initial, cost_final, lam, grad_inf)."""
+    cost_initial, cost_final, lam, grad_inf).  trace (a list, optional) receives one dict per attempt: gain, accepted, lam
+    (the attempt's), max_w, max_v (the step's), grad_inf (of the trial linearisation), pcg (solve_pcg's hist; PCG only)."""
     prm = dict(DEFAULTS, **over)
     poses = np.asarray(poses, np.float64)
     fixed, src, tgt = np.asarray(fixed, bool), np.asarray(src, np.int64), np.asarray(tgt, np.int64)
@@ -261,10 +273,11 @@ def optimize(poses, fixed, src, tgt, Z, info, mask=None, kind=NONE, scale=1.0, s
     else:
         for _ in range(prm["max_iters"]):
             out["iters"] += 1
+            hist = {} if trace is not None else None
             if solver == "dense":
                 x, it = solve_dense(L, src, tgt, free, lam)
             else:
-                x, it = solve_pcg(L, src, tgt, free, lam, prm["pcg_tol"], prm["pcg_max_iters"])
+                x, it = solve_pcg(L, src, tgt, free, lam, prm["pcg_tol"], prm["pcg_max_iters"], hist)
             out["pcg_iters"] += it
             if x is None:
                 out["status"] = 2
@@ -273,6 +286,9 @@ def optimize(poses, fixed, src, tgt, Z, info, mask=None, kind=NONE, scale=1.0, s
             Ln = lin(Pn)
             den = float((x * (lam * (L.Hd @ x[:, :, None])[:, :, 0] - L.g)).sum())
             gain = (L.F - Ln.F) / den if den != 0 else -1.0
+            if trace is not None:
+                trace.append(dict(gain=float(gain), accepted=bool(gain > 0 and np.isfinite(Ln.F)), lam=float(lam), pcg=hist, grad_inf=ginf(Ln),
+                                  max_w=float(np.linalg.norm(x[:, :3], axis=1).max()), max_v=float(np.linalg.norm(x[:, 3:], axis=1).max())))
             if gain > 0 and np.isfinite(Ln.F):
                 P, L = Pn, Ln
                 out["accepted"] += 1

@@ -110,6 +110,11 @@ class PgoResult(C.Structure):
                 ("cost_initial", C.c_double), ("cost_final", C.c_double), ("lam", C.c_double), ("grad_inf", C.c_double)]
 
 
+class PgoConsistencyParams(C.Structure):
+    _fields_ = [("chi2", C.c_double), ("drift_rot", C.c_double), ("drift_trans", C.c_double), ("n_seeds", C.c_uint32),
+                ("min_clique", C.c_uint32), ("reserved_", C.c_uint32 * 2)]
+
+
 class FpfhParams(C.Structure):
     _fields_ = [("normal_k", C.c_uint32), ("feature_k", C.c_uint32), ("mutual", C.c_uint32), ("ransac_iters", C.c_uint32),
                 ("inlier_thresh", C.c_float), ("min_inlier_ratio", C.c_float), ("ransac_confidence", C.c_float),
@@ -483,6 +488,9 @@ _PROTOS = [
                             _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     ("gloc_pgo_optimize", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(PgoParams), C.POINTER(RobustParams),
                            _vp, _vp, _vp, C.POINTER(PgoResult)]),
+    ("gloc_pgo_consistency_default_params", None, [C.POINTER(PgoConsistencyParams)]),
+    ("gloc_pgo_consistency", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(PgoConsistencyParams),
+                              _vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), _vp, _vp, _vp, _vp, _vp, _vp]),
     ("gloc_sc_default_params", _i, [C.POINTER(ScParams)]),
     ("gloc_sc_create", _i, [_i, C.POINTER(ScParams), C.POINTER(_vp)]),
     ("gloc_sc_destroy", _i, [_vp]),
@@ -2255,6 +2263,42 @@ class PoseGraphOptimizer(_Handle):
                                       None if mk is None else _np_ptr(mk), m, C.byref(prm), None if robust is None else C.byref(robust),
                                       _np_ptr(out), _np_ptr(s2), _np_ptr(w), C.byref(res)))
         return out, s2, w, res
+
+    def consistency(self, poses, src, tgt, Z, info, path=None, params=None, want_s2=False):
+        """The largest mutually consistent set of the L candidate closures at `poses` (gloc_pgo_consistency, C1 - C6):
+        dict(mask [L] bool, clique_size, winner_rank, ok, status [L], degree [L], score [L], seeds [n_seeds], clique_sizes
+        [n_seeds]) and, with want_s2, s2 [L, L].  path [n]: a coordinate along the trajectory, None for all zeros."""
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 16)
+        s, t = np.ascontiguousarray(src, np.uint32).reshape(-1), np.ascontiguousarray(tgt, np.uint32).reshape(-1)
+        Zf = np.ascontiguousarray(Z, np.float32).reshape(-1, 16)
+        Om = np.ascontiguousarray(info, np.float64).reshape(-1, 36)
+        pth = None if path is None else np.ascontiguousarray(path, np.float64).reshape(-1)
+        n, L = P.shape[0], s.shape[0]
+        assert t.shape[0] == L and Zf.shape[0] == L and Om.shape[0] == L and (pth is None or pth.shape[0] == n)
+        prm = params or default_pgo_consistency_params()
+        S = max(1, min(int(prm.n_seeds), 1024))          # (an n_seeds out of range is refused by the call; the arrays just exist)
+        mask, status, degree, score = np.zeros(L, np.uint8), np.zeros(L, np.uint8), np.zeros(L, np.uint32), np.zeros(L, np.uint64)
+        seeds, sizes = np.zeros(S, np.uint32), np.zeros(S, np.uint32)
+        s2 = np.empty((L, L)) if want_s2 else None
+        size, rank, ok = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib().gloc_pgo_consistency(self._h, _np_ptr(P), n, _np_ptr(s), _np_ptr(t), _np_ptr(Zf), _np_ptr(Om),
+                                         None if pth is None else _np_ptr(pth), L, C.byref(prm), _np_ptr(mask), C.byref(size), C.byref(rank),
+                                         C.byref(ok), _np_ptr(status), _np_ptr(degree), _np_ptr(score), _np_ptr(seeds), _np_ptr(sizes),
+                                         None if s2 is None else _np_ptr(s2)))
+        out = dict(mask=mask.astype(bool), clique_size=size.value, winner_rank=rank.value, ok=bool(ok.value), status=status, degree=degree,
+                   score=score, seeds=seeds, clique_sizes=sizes)
+        if want_s2:
+            out["s2"] = s2
+        return out
+
+
+def default_pgo_consistency_params(**over):
+    """gloc_pgo_consistency_params as gloc_pgo_consistency_default_params leaves them, then `over`."""
+    p = PgoConsistencyParams()
+    lib().gloc_pgo_consistency_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
 
 
 def default_sc_params(**over):

@@ -86,6 +86,23 @@ int consensus_sets(hipStream_t s, Profiler& prof, Ws& w, const Batch& b, const g
   return GLOC_OK;
 }
 
+int score_matrix(hipStream_t s, const uint32_t* count, uint32_t rows, uint32_t words, unsigned long long* bits, unsigned long long* score,
+                 uint32_t* degree) {
+  uint32_t lanes_per_row = 1;
+  while (lanes_per_row < std::min(words, 64u)) lanes_per_row <<= 1;
+  const Group g{nullptr, 0, count, 0u, rows, words, bits};  // (the score kernel reads counts, rows, words and bits only)
+  hipLaunchKernelGGL(pg_score_kernel, dim3((rows + PG_WAVES - 1) / PG_WAVES, 1), dim3(PG_THREADS), sizeof(unsigned long long) * PG_WAVES * words, s, g,
+                     lanes_per_row, score, degree);
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
+int rank_seeds(hipStream_t s, const uint32_t* count, uint32_t rows, const unsigned long long* key, uint32_t n_seeds, uint32_t* seeds) {
+  hipLaunchKernelGGL(pg_seeds_kernel, dim3(1), dim3(PG_THREADS), 0, s, count, 0u, rows, key, n_seeds, seeds);
+  GLOC_HIP(hipGetLastError());
+  return GLOC_OK;
+}
+
 }  // namespace pairgraph
 }  // namespace gloc
 

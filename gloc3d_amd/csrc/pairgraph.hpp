@@ -38,5 +38,13 @@ struct Batch {
 // budget: bytes of matrices and seed rows in flight (0: BUDGET_BYTES).
 int consensus_sets(hipStream_t s, Profiler& prof, Ws& w, const Batch& b, const gloc_fpfh_graph_params& prm, size_t budget, uint32_t* valid);
 
+// G2 and G3's ranking for ONE bit matrix another stage has made (the pose graph's consistency matrix, pgo.hip): the same
+// pg_score_kernel and pg_seeds_kernel, launched as a group of one job.  count (device, [1]): the matrix's side M <= rows;
+// bits [rows][words], the bits past M zero.  score_matrix leaves score and degree [rows]; rank_seeds the n_seeds
+// positions of largest key (any 64-bit key: the seed order is the kernel's), PG_NONE (0xFFFFFFFF) past M.
+int score_matrix(hipStream_t s, const uint32_t* count, uint32_t rows, uint32_t words, unsigned long long* bits, unsigned long long* score,
+                 uint32_t* degree);
+int rank_seeds(hipStream_t s, const uint32_t* count, uint32_t rows, const unsigned long long* key, uint32_t n_seeds, uint32_t* seeds);
+
 }  // namespace pairgraph
 }  // namespace gloc

@@ -9,12 +9,18 @@
 //
 // Memory: both the current and the trial linearisation are resident (36 doubles per edge, 48 per node, each), so a
 // rejected step costs nothing to undo.
+//
+// The closure selection (gloc_pgo_consistency, C1 - C6; pgo_consistency_kernels.hpp, tests/pcm_ref.py) is the second half
+// of this file.  Launches per call: pc_setup, pc_pair, pg_score, pc_key, pg_seeds, pc_clique, pc_choose -- seven, ordered by
+// the stream alone.  It borrows the optimiser's upload buffers (every optimiser call uploads its own graph again).
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "common.hpp"
+#include "pairgraph.hpp"
 #include "pgo.hpp"
+#include "pgo_consistency_kernels.hpp"
 #include "pgo_kernels.hpp"
 #include "seg_sort.hpp"
 
@@ -32,6 +38,8 @@ struct gloc_pgo : Handle {
   std::vector<double> hP, hOm, hd;
   std::vector<float> hZ;
   std::vector<uint8_t> hmask;
+  // the closure selection's
+  DevBuf c_ops, c_status, c_path, c_count, c_bits, c_s2, c_score, c_degree, c_key, c_seeds, c_sizes, c_members, c_counts, c_res, c_mask;
   // of the call in progress
   uint32_t n = 0, m = 0, ge = 0, gm = 0, gu = 0, kind = 0;
   double c2 = 1.0, origin[3] = {0, 0, 0};
@@ -393,6 +401,166 @@ int gloc_pgo_optimize(gloc_pgo* h, const double* poses, const uint8_t* fixed, si
   }
   GLOC_TRY(edge_outputs(h, cur, out_s2, out_weight));
   *out = res;
+  return GLOC_OK;
+}
+
+}  // extern "C"
+
+// ---- the closure selection ------------------------------------------------------------------------------------------------
+namespace {
+
+struct Closures {
+  const double* poses;
+  size_t n;
+  const uint32_t *src, *tgt;
+  const float* Z;
+  const double *info, *path;
+  size_t L;
+};
+
+int check_consistency(const gloc_pgo* h, const Closures& c, const gloc_pgo_consistency_params* p, bool outputs, bool want_s2) {
+  GLOC_REQUIRE(p, GLOC_ERR_INVALID, "params is null");
+  GLOC_REQUIRE(std::isfinite(p->chi2) && p->chi2 > 0.0, GLOC_ERR_INVALID, "chi2 = %g must be > 0 and finite", p->chi2);
+  GLOC_REQUIRE(std::isfinite(p->drift_rot) && p->drift_rot >= 0.0, GLOC_ERR_INVALID, "drift_rot = %g must be >= 0 and finite", p->drift_rot);
+  GLOC_REQUIRE(std::isfinite(p->drift_trans) && p->drift_trans >= 0.0, GLOC_ERR_INVALID, "drift_trans = %g must be >= 0 and finite", p->drift_trans);
+  GLOC_REQUIRE(p->n_seeds >= 1 && p->n_seeds <= 1024, GLOC_ERR_INVALID, "n_seeds = %u outside [1, 1024]", p->n_seeds);
+  GLOC_REQUIRE(p->reserved_[0] == 0 && p->reserved_[1] == 0, GLOC_ERR_INVALID, "reserved_ must be 0");
+  GLOC_REQUIRE(c.poses && c.src && c.tgt && c.Z && c.info && outputs, GLOC_ERR_INVALID, "null argument");
+  GLOC_REQUIRE(c.n >= 2 && c.n <= MAX_NODES, GLOC_ERR_INVALID, "n = %zu nodes outside [2, 2^20]", c.n);
+  GLOC_REQUIRE(c.L >= 1 && c.L <= PC_MAX_L, GLOC_ERR_INVALID, "L = %zu closures outside [1, 16384]", c.L);
+  GLOC_REQUIRE(!want_s2 || c.L <= PC_MAX_S2_L, GLOC_ERR_INVALID, "out_s2 is refused for L = %zu > 4096 closures", c.L);
+  for (size_t a = 0; a < c.L; ++a)
+    GLOC_REQUIRE(c.src[a] < c.n && c.tgt[a] < c.n, GLOC_ERR_INVALID, "closure %zu has an end (%u, %u) beyond the %zu nodes", a, c.src[a], c.tgt[a], c.n);
+  for (size_t a = 0; a < c.L; ++a) GLOC_REQUIRE(c.src[a] != c.tgt[a], GLOC_ERR_INVALID, "closure %zu joins node %u to itself", a, c.src[a]);
+  for (size_t i = 0; i < 16 * c.n; ++i) GLOC_REQUIRE(std::isfinite(c.poses[i]), GLOC_ERR_INVALID, "pose %zu is not finite", i / 16);
+  for (size_t i = 0; i < 16 * c.L; ++i) GLOC_REQUIRE(std::isfinite(c.Z[i]), GLOC_ERR_INVALID, "Z of closure %zu is not finite", i / 16);
+  for (size_t i = 0; i < 36 * c.L; ++i) GLOC_REQUIRE(std::isfinite(c.info[i]), GLOC_ERR_INVALID, "info of closure %zu is not finite", i / 36);
+  if (c.path)
+    for (size_t k = 0; k < c.n; ++k) GLOC_REQUIRE(std::isfinite(c.path[k]), GLOC_ERR_INVALID, "path of node %zu is not finite", k);
+  GLOC_REQUIRE(h, GLOC_ERR_INVALID, "null handle");
+  return GLOC_OK;
+}
+
+template <class T>
+int fetch(gloc_pgo* h, const DevBuf& d, T* to, size_t count) {
+  if (!to) return GLOC_OK;
+  GLOC_HIP(hipMemcpyAsync(to, d.p, sizeof(T) * count, hipMemcpyDeviceToHost, h->stream));
+  return GLOC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void gloc_pgo_consistency_default_params(gloc_pgo_consistency_params* p) {
+  if (!p) return;
+  p->chi2 = 16.8119;  // the 99 % quantile of chi-squared with 6 degrees of freedom
+  p->drift_rot = 0.0;
+  p->drift_trans = 0.0;
+  p->n_seeds = 64;
+  p->min_clique = 2;
+  p->reserved_[0] = p->reserved_[1] = 0;
+}
+
+int gloc_pgo_consistency(gloc_pgo* h, const double* poses, size_t n, const uint32_t* src, const uint32_t* tgt, const float* Z, const double* info,
+                         const double* path, size_t L, const gloc_pgo_consistency_params* prm, uint8_t* out_mask, uint32_t* out_clique_size,
+                         uint32_t* out_winner_rank, uint32_t* out_ok, uint8_t* out_status, uint32_t* out_degree, uint64_t* out_score,
+                         uint32_t* out_seeds, uint32_t* out_clique_sizes, double* out_s2) {
+  const Closures c{poses, n, src, tgt, Z, info, path, L};
+  GLOC_TRY(check_consistency(h, c, prm,
+                             out_mask || out_clique_size || out_winner_rank || out_ok || out_status || out_degree || out_score || out_seeds ||
+                                 out_clique_sizes || out_s2,
+                             out_s2 != nullptr));
+  GLOC_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const uint32_t Lu = (uint32_t)L, words = (Lu + 63u) / 64u, S = prm->n_seeds;
+  // the upload: the optimiser's layouts (prepare) for poses, Z and Omega; a closure's two path coordinates
+  h->hP.resize(12 * n), h->hZ.resize(12 * L), h->hOm.resize(21 * L), h->hd.assign(2 * L, 0.0);
+  for (size_t k = 0; k < n; ++k)
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b < 3; ++b) h->hP[12 * k + 3 * a + b] = poses[16 * k + 4 * a + b];
+      h->hP[12 * k + 9 + a] = poses[16 * k + 4 * a + 3] - poses[4 * a + 3];
+    }
+  for (size_t e = 0; e < L; ++e) {
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b < 3; ++b) h->hZ[(size_t)(3 * a + b) * L + e] = Z[16 * e + 4 * a + b];
+      h->hZ[(size_t)(9 + a) * L + e] = Z[16 * e + 4 * a + 3];
+    }
+    for (int a = 0; a < 6; ++a)
+      for (int b = a; b < 6; ++b) h->hOm[(size_t)ut(a, b) * L + e] = info[36 * e + 6 * a + b];
+    if (path) h->hd[e] = path[src[e]], h->hd[L + e] = path[tgt[e]];
+  }
+  GLOC_TRY(h->P[0].ensure(sizeof(double) * 12 * n, s));
+  GLOC_TRY(h->src.ensure(sizeof(uint32_t) * L, s));
+  GLOC_TRY(h->tgt.ensure(sizeof(uint32_t) * L, s));
+  GLOC_TRY(h->Zf.ensure(sizeof(float) * 12 * L, s));
+  GLOC_TRY(h->Om.ensure(sizeof(double) * 21 * L, s));
+  GLOC_TRY(h->c_path.ensure(sizeof(double) * 2 * L, s));
+  GLOC_TRY(h->c_ops.ensure(sizeof(double) * PC_OPS * L, s));
+  GLOC_TRY(h->c_status.ensure(L, s));
+  GLOC_TRY(h->c_count.ensure(sizeof(uint32_t), s));
+  GLOC_TRY(h->c_bits.ensure(sizeof(unsigned long long) * L * words, s));
+  if (out_s2) GLOC_TRY(h->c_s2.ensure(sizeof(double) * L * L, s));
+  GLOC_TRY(h->c_score.ensure(sizeof(unsigned long long) * L, s));
+  GLOC_TRY(h->c_degree.ensure(sizeof(uint32_t) * L, s));
+  GLOC_TRY(h->c_key.ensure(sizeof(unsigned long long) * L, s));
+  GLOC_TRY(h->c_seeds.ensure(sizeof(uint32_t) * S, s));
+  GLOC_TRY(h->c_sizes.ensure(sizeof(uint32_t) * S, s));
+  GLOC_TRY(h->c_members.ensure(sizeof(unsigned long long) * S * words, s));
+  GLOC_TRY(h->c_counts.ensure(sizeof(uint32_t) * S * L, s));
+  GLOC_TRY(h->c_res.ensure(sizeof(uint32_t) * 4, s));
+  GLOC_TRY(h->c_mask.ensure(L, s));
+  GLOC_HIP(hipMemcpyAsync(h->P[0].p, h->hP.data(), sizeof(double) * 12 * n, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->src.p, src, sizeof(uint32_t) * L, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->tgt.p, tgt, sizeof(uint32_t) * L, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->Zf.p, h->hZ.data(), sizeof(float) * 12 * L, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->Om.p, h->hOm.data(), sizeof(double) * 21 * L, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->c_path.p, h->hd.data(), sizeof(double) * 2 * L, hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipMemcpyAsync(h->c_count.p, &Lu, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  GLOC_HIP(hipStreamSynchronize(s));  // (`Lu` is on this frame, the vectors are pageable)
+  const uint32_t gl = (Lu + THREADS - 1) / THREADS;
+  unsigned long long* bits = h->c_bits.as<unsigned long long>();
+  {
+    ProfScope ps(h->prof, "pgo_consistency", s, ProfScope::Apart, "pgo_consistency_pairs");
+    hipLaunchKernelGGL(pc_setup_kernel, dim3(gl), dim3(THREADS), 0, s, Lu, h->src.as<uint32_t>(), h->tgt.as<uint32_t>(), h->Zf.as<float>(),
+                       h->Om.as<double>(), h->P[0].as<double>(), h->c_path.as<double>(), h->c_ops.as<double>(), h->c_status.as<uint8_t>());
+    GLOC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pc_pair_kernel, dim3(words, words), dim3(THREADS), 0, s, Lu, words, h->c_ops.as<double>(), h->c_status.as<uint8_t>(), prm->chi2,
+                       prm->drift_rot * prm->drift_rot, prm->drift_trans * prm->drift_trans, bits, out_s2 ? h->c_s2.as<double>() : nullptr);
+    GLOC_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(h->prof, "pgo_consistency", s, ProfScope::Apart, "pgo_consistency_score");
+    GLOC_TRY(pairgraph::score_matrix(s, h->c_count.as<uint32_t>(), Lu, words, bits, h->c_score.as<unsigned long long>(), h->c_degree.as<uint32_t>()));
+    hipLaunchKernelGGL(pc_key_kernel, dim3(gl), dim3(THREADS), 0, s, Lu, h->c_score.as<unsigned long long>(), h->c_degree.as<uint32_t>(),
+                       h->c_key.as<unsigned long long>());
+    GLOC_HIP(hipGetLastError());
+    GLOC_TRY(pairgraph::rank_seeds(s, h->c_count.as<uint32_t>(), Lu, h->c_key.as<unsigned long long>(), S, h->c_seeds.as<uint32_t>()));
+  }
+  {
+    ProfScope ps(h->prof, "pgo_consistency", s, ProfScope::Apart, "pgo_consistency_clique");
+    uint32_t lanes_per_row = 1;
+    while (lanes_per_row < std::min(words, 64u)) lanes_per_row <<= 1;
+    hipLaunchKernelGGL(pc_clique_kernel, dim3(S), dim3(THREADS), sizeof(unsigned long long) * 3 * words, s, Lu, words, lanes_per_row, bits,
+                       h->c_seeds.as<uint32_t>(), h->c_sizes.as<uint32_t>(), h->c_members.as<unsigned long long>(), h->c_counts.as<uint32_t>());
+    GLOC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pc_choose_kernel, dim3(1), dim3(THREADS), 0, s, Lu, words, S, prm->min_clique, h->c_sizes.as<uint32_t>(),
+                       h->c_members.as<unsigned long long>(), h->c_res.as<uint32_t>(), h->c_mask.as<uint8_t>());
+    GLOC_HIP(hipGetLastError());
+  }
+  uint32_t res[3] = {0, 0, 0};
+  GLOC_TRY(fetch(h, h->c_res, res, 3));
+  GLOC_TRY(fetch(h, h->c_mask, out_mask, L));
+  GLOC_TRY(fetch(h, h->c_status, out_status, L));
+  GLOC_TRY(fetch(h, h->c_degree, out_degree, L));
+  GLOC_TRY(fetch(h, h->c_score, out_score, L));
+  GLOC_TRY(fetch(h, h->c_seeds, out_seeds, S));
+  GLOC_TRY(fetch(h, h->c_sizes, out_clique_sizes, S));
+  GLOC_TRY(fetch(h, h->c_s2, out_s2, L * L));
+  GLOC_HIP(hipStreamSynchronize(s));
+  if (out_clique_size) *out_clique_size = res[0];
+  if (out_winner_rank) *out_winner_rank = res[1];
+  if (out_ok) *out_ok = res[2];
   return GLOC_OK;
 }
 

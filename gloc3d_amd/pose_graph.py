@@ -11,7 +11,7 @@ class PoseGraph:
         self.poses, self.fixed = [], []
         self.src, self.tgt, self.Z, self.info, self.robust = [], [], [], [], []
         self._device, self._opt = device, None
-        self.last_s2 = self.last_weight = None
+        self.last_s2 = self.last_weight = self.last_consistency = None
 
     def __len__(self):
         return len(self.poses)
@@ -72,6 +72,37 @@ class PoseGraph:
             setattr(self, name, [getattr(self, name)[e] for e in keep])
         self.last_s2, self.last_weight = self.last_s2[keep], self.last_weight[keep]
         return gone
+
+    def select_consistent(self, params=None, path=None, apply=True):
+        """The largest mutually consistent set of the closures -- the edges added with robust=True -- at the graph's current
+        poses (gloc_pgo_consistency; params: a capi.PgoConsistencyParams).  path [n]: a coordinate along the trajectory,
+        the node index by default.  Returns the indices of the kept closures in the graph as the call leaves it; with apply
+        the others are dropped as prune() drops edges (none is when no set reaches min_clique: then the returned list is
+        empty and the graph stays).
+        Use: select_consistent(), optimize(), and select_consistent() again with a smaller drift on the corrected poses to
+        re-admit closures the drifted start hid."""
+        if self._opt is None:
+            self._opt = capi.PoseGraphOptimizer(self._device)
+        cand = [e for e in range(len(self.src)) if self.robust[e]]
+        if not cand:
+            return []
+        pth = np.arange(len(self.poses), dtype=np.float64) if path is None else np.asarray(path, np.float64)
+        out = self._opt.consistency(np.array(self.poses), [self.src[e] for e in cand], [self.tgt[e] for e in cand],
+                                    np.array([self.Z[e] for e in cand]), np.array([self.info[e] for e in cand]), pth, params)
+        self.last_consistency = out
+        if not out["ok"]:
+            return []
+        kept = [e for e, m in zip(cand, out["mask"]) if m]
+        if apply:
+            gone = set(cand) - set(kept)
+            keep = [e for e in range(len(self.src)) if e not in gone]
+            new_index = {e: k for k, e in enumerate(keep)}
+            for name in ("src", "tgt", "Z", "info", "robust"):
+                setattr(self, name, [getattr(self, name)[e] for e in keep])
+            if self.last_weight is not None:
+                self.last_s2, self.last_weight = self.last_s2[keep], self.last_weight[keep]
+            kept = [new_index[e] for e in kept]
+        return kept
 
     def close(self):
         if self._opt is not None:

@@ -1921,7 +1921,7 @@ int gloc_pgo_create(int device, gloc_pgo** out);
 int gloc_pgo_destroy(gloc_pgo* h);
 int gloc_pgo_set_stream(gloc_pgo* h, void* hip_stream);
 int gloc_pgo_synchronize(gloc_pgo* h);
-/* families: pgo_setup, pgo_linearize, pgo_gather, pgo_pcg, pgo_step */
+/* families: pgo_setup, pgo_linearize, pgo_gather, pgo_pcg, pgo_step; pgo_consistency (gloc_pgo_consistency, below) */
 int gloc_pgo_set_profile(gloc_pgo* h, int enable);
 int gloc_pgo_profile(gloc_pgo* h, const char* kernel, double* total_ms, uint64_t* launches);
 int gloc_pgo_profile_reset(gloc_pgo* h);
@@ -1939,6 +1939,71 @@ int gloc_pgo_optimize(gloc_pgo* h, const double* poses, const uint8_t* fixed, si
                       const uint32_t* edge_tgt, const float* Z, const double* info, const uint8_t* robust_mask, size_t m,
                       const gloc_pgo_params* prm, const gloc_robust_params* robust, double* out_poses /* [n][16] */,
                       double* out_s2, double* out_weight, gloc_pgo_result* out);
+
+/* ---- mutually consistent loop closures (pairwise consistency maximisation) -------------------------------- *
+ * What stands between the closures and the optimiser: the robust kernel of gloc_pgo_optimize rejects a closure only
+ * after it has bent the solution and cannot reject a group of wrong closures that agree with each other.  Two closures are
+ * CONSISTENT when the cycle through both of them and the trajectory between their ends closes within its covariance; the
+ * largest mutually consistent set found by a greedy clique search is kept (after Mangelson et al., ICRA 2018; parity with
+ * their code is not claimed).  A stage of the gloc_pgo handle -- its stream, grow-only buffers and profile (family
+ * pgo_consistency; its parts also as pgo_consistency_pairs, _score, _clique) --, fp64 throughout, no atomics.  The
+ * executable contract is tests/pcm_ref.py.
+ *
+ * Inputs: poses [n][16] doubles, the current estimates (G1); L candidate closures src, tgt, Z [L][16] fp32, info [L][36]
+ * fp64 read from the upper triangle (G1's edges); path [n] doubles or NULL (all zeros), a coordinate along the trajectory
+ * in the caller's units (steps, metres travelled).
+ *
+ *   C1. Translations are taken relative to node 0's translation (fp64, on input).  Per closure a: Sigma_a = Omega_a^-1 by
+ *       the 6 x 6 Cholesky and pivot rule of G7 -- column b the solve of the unit vector e_b, its rows a <= b kept and
+ *       mirrored --, and B_a = (T_ja Z_a) T_ia^-1, the pose the closure predicts for the map seen from its source.  A closure
+ *       whose Omega fails the pivot rule has status 1 and is consistent with nothing.
+ *   C2. Pair statistic for a < b, with i = src, j = tgt:  X = T_ja^-1 T_jb;  r = G2's residual evaluated with
+ *       T_i := B_b T_ia, T_j := T_ja, Z := Z_a (the same log and series branch), which is (log R_E, t_E) of
+ *       E = X Z_b (T_ib^-1 T_ia) Z_a^-1;  Ad_X = [[R_X, 0], [[t_X]x R_X, R_X]], the first-order transport of the left
+ *       perturbation (w, v);  d = |path_ia - path_ib| + |path_ja - path_jb|;
+ *         M = Sigma_a + Ad_X Sigma_b Ad_X^T + diag(drift_rot^2 d (1,1,1), drift_trans^2 d (1,1,1)),  read from its upper triangle;
+ *         s2_ab = r^T M^-1 r = |L^-1 r|^2 with M = L L^T by the same Cholesky.
+ *       The drift term is isotropic and ignores the lever arm of rotation drift: a stated limit of the model.
+ *   C3. C_ab = C_ba = 1 iff both closures have status 0, M passed the pivot rule, s2_min(a,b),max(a,b) is finite and
+ *       s2 < chi2.  C_aa = 0.  Only the a < b form is ever evaluated (far from consistency the two directions differ
+ *       freely), so the matrix is symmetric by definition.  out_s2 holds +inf wherever one of the conditions before the
+ *       last fails, and on the diagonal: out_s2 < chi2 IS the matrix.
+ *   C4. degree_a = sum_b C_ab;  S_ab = C_ab |{k : C_ak and C_bk}|,  score_a = sum_b S_ab (unsigned 64-bit; the
+ *       correspondence graph's G2);  key_a = score_a + degree_a (an isolated consistent pair has score 0 but outranks an
+ *       isolated closure).  The seeds are the n_seeds closures of largest key, ties to the smaller position; ranks past L
+ *       hold 0xFFFFFFFF and a clique size of 0.
+ *   C5. Per seed s: K = {s}, cand = row_s; while cand is not empty: v = the member of cand maximising
+ *       popcount(row_v & cand), ties to the smaller position; K <- K + {v}; cand <- cand & row_v.  Integers only.
+ *   C6. The winner is the largest clique, ties to the smaller seed rank; out_mask marks its members, out_clique_size and
+ *       out_winner_rank describe it.  With fewer than min_clique members the mask is all zero and out_ok = 0.
+ *
+ * The checks come in this order, each refusing with GLOC_ERR_INVALID, before any device work and with the outputs
+ * untouched: a null prm; chi2 not finite and positive; drift_rot, drift_trans not finite or negative; n_seeds outside
+ * [1, 1024]; reserved_ != 0; a null array (path may be) or every output null; n outside [2, 2^20]; L outside
+ * [1, 16384]; out_s2 given with L > 4096; a closure end >= n; a closure from a node to itself; a non-finite value in
+ * poses, Z, info or path; a null handle.  Duplicate closures are legal (and consistent with each other).  Calls are
+ * synchronous and deterministic: no floating-point sum crosses a lane.
+ *
+ * Use: select, then optimise; then select again on the corrected poses with a smaller drift to re-admit closures the
+ * drifted start hid.  The defaults are conventions, not tuned. */
+typedef struct gloc_pgo_consistency_params {
+  double chi2;            /* 16.8119: the 99 % quantile of chi-squared with 6 degrees of freedom */
+  double drift_rot;       /* 0: rad per square root of a unit of path */
+  double drift_trans;     /* 0: m per square root of a unit of path */
+  uint32_t n_seeds;       /* 64, 1 .. 1024 */
+  uint32_t min_clique;    /* 2 */
+  uint32_t reserved_[2];  /* 0 */
+} gloc_pgo_consistency_params;   /* 40 bytes */
+
+void gloc_pgo_consistency_default_params(gloc_pgo_consistency_params* p);
+
+/* C1-C6.  Any output may be NULL, but not all of them.  out_s2 is a diagnostic of L^2 doubles. */
+int gloc_pgo_consistency(gloc_pgo* h, const double* poses /* [n][16] */, size_t n, const uint32_t* src, const uint32_t* tgt /* [L] */,
+                         const float* Z /* [L][16] */, const double* info /* [L][36] */, const double* path /* [n] or NULL */, size_t L,
+                         const gloc_pgo_consistency_params* prm, uint8_t* out_mask /* [L] */, uint32_t* out_clique_size,
+                         uint32_t* out_winner_rank, uint32_t* out_ok, uint8_t* out_status /* [L] */, uint32_t* out_degree /* [L] */,
+                         uint64_t* out_score /* [L] */, uint32_t* out_seeds /* [n_seeds] */, uint32_t* out_clique_sizes /* [n_seeds] */,
+                         double* out_s2 /* [L][L] */);
 
 #ifdef __cplusplus
 }

@@ -33,8 +33,8 @@ int forward_device(gloc_vlad* h, const float* d_feat, size_t n, size_t hw, float
   GLOC_TRY(h->nrm2.ensure(sizeof(float) * n * K, s));
   const int nslabs = (int)((KC + FC_ROWS - 1) / FC_ROWS);
   GLOC_TRY(h->fc_part.ensure(sizeof(float) * (size_t)nslabs * FC_NB * OD, s));
-  const size_t lds = sizeof(float) * ((size_t)C * VPITCH + (size_t)Kp * VPITCH + 2 * 4 * VP + VP);
-  GLOC_REQUIRE(lds <= 160 * 1024, GLOC_ERR_INVALID, "feature dim %d needs %zu B of LDS (> 160 KiB)", C, lds);
+  const size_t lds = tile_lds_bytes(h->C, h->Kp);
+  GLOC_REQUIRE(lds <= TILE_LDS_MAX, GLOC_ERR_INVALID, "feature dim %d needs %zu B of LDS (> 160 KiB)", C, lds);
   GLOC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vlad_tile_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   {
@@ -93,11 +93,14 @@ int gloc_vlad_create(int device, size_t dim, size_t clusters, size_t out_dim, co
   GLOC_REQUIRE(dim >= 1 && dim <= 560 && clusters >= 1 && clusters <= 64 && out_dim >= 1 &&
                    out_dim <= 65536,
                GLOC_ERR_INVALID, "need dim <= 560 (LDS tile), clusters <= 64, out_dim <= 65536");
+  GLOC_REQUIRE(tile_lds_bytes(dim, padded_clusters(clusters)) <= TILE_LDS_MAX, GLOC_ERR_INVALID,
+               "dim %zu with %zu clusters needs %zu B of LDS for one tile (> 160 KiB)", dim, clusters,
+               tile_lds_bytes(dim, padded_clusters(clusters)));
   gloc_vlad* h = nullptr;
   GLOC_TRY(create_handle(device, &h));
   h->C = dim;
   h->K = clusters;
-  h->Kp = (clusters + 15) / 16 * 16;
+  h->Kp = padded_clusters(clusters);
   h->out_dim = out_dim;
   h->normalize_input = normalize_input;
   h->has_bias = conv_b != nullptr;

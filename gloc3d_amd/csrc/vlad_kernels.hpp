@@ -23,6 +23,15 @@ constexpr int VP = 64;        // positions per tile
 constexpr int VPITCH = VP + 1;
 constexpr int FC_ROWS = 512;  // FC slab
 constexpr int FC_NB = 8;      // images per FC pass
+constexpr size_t TILE_LDS_MAX = 160 * 1024;  // one workgroup's LDS on gfx950
+
+// clusters padded to whole MFMA tiles of 16
+constexpr size_t padded_clusters(size_t K) { return (K + 15) / 16 * 16; }
+// bytes of dynamic LDS vlad_tile_kernel needs (the layout below): 4 (65 (C + Kp) + 576).  Kp = 64 fits up to
+// C = 557, Kp <= 48 up to the ABI's C = 560.
+constexpr size_t tile_lds_bytes(size_t C, size_t Kp) {
+  return sizeof(float) * (C * VPITCH + Kp * VPITCH + 2 * 4 * VP + VP);
+}
 
 // dynamic LDS: X [C][VPITCH] | SOFT [Kp][VPITCH] | red [4][VP] (x2) | inv [VP]
 __global__ __launch_bounds__(256) void vlad_tile_kernel(

@@ -1337,7 +1337,11 @@ int gloc_reg_fgr_pairs(gloc_reg* h, const float* P, const float* Q, size_t m, ui
  * residual aggregation to `clusters` x `dim`, intra-normalisation, L2, FC to `out_dim`.
  * conv_w [clusters][dim], conv_b [clusters] or NULL (vladv2), centroids [clusters][dim],
  * fc_w [clusters*dim][out_dim] (hidden1_weights), all row-major fp32, copied to the device.
- * feat: n feature maps in NCHW order, [n][dim][hw]; out: [n][out_dim].  fp32 throughout. */
+ * feat: n feature maps in NCHW order, [n][dim][hw]; out: [n][out_dim].  fp32 throughout.
+ * Limits, checked by gloc_vlad_create (GLOC_ERR_INVALID, *out = NULL): 1 <= clusters <= 64; 1 <= dim <= 560 and one
+ * tile of 64 positions must fit the 160 KiB of LDS, 65 * (dim + roundup16(clusters)) + 576 <= 40960 floats (more than 48
+ * clusters: dim <= 557); 1 <= out_dim <= 65536, and <= 16384 with gating (gloc_vlad_set_gating).  The forward calls refuse
+ * n = 0, hw = 0, n > 2^20 and hw > 2^24 (GLOC_ERR_INVALID). */
 typedef struct gloc_vlad gloc_vlad;
 int gloc_vlad_create(int device, size_t dim, size_t clusters, size_t out_dim, const float* conv_w,
                      const float* conv_b, const float* centroids, const float* fc_w,
